@@ -5,8 +5,8 @@ One "step" = one pass of the batch seam (gat_sample_and_count: place every isoch
 per contig, count every annotation track) over `--samples` Monte-Carlo samples per GPU, followed by the
 read-back of the count matrix to the host ("seed -> count matrix on host").  The headline line is
 BASELINE.json's config2 (10k segments x 1 annotation track x 10k intervals, hg19 workspace, 10 000 samples,
-CounterNucleotideOverlap); the same run then measures the other single-GPU shapes of BASELINE.json (config3, the
-north_star target shape; one call's worth of config5 and config4; refdata, the reference's own test data with its
+CounterNucleotideOverlap); with --full the same run then measures the other single-GPU shapes of BASELINE.json (config3,
+the north_star target shape; one call's worth of config5 and config4; refdata, the reference's own test data with its
 fragmented workspace) and reports them under "configs".  Inputs are
 resident in HBM before the timed region.  The headline shape's steps are software-pipelined one deep (--pipeline 2, the
 default; config.steps_in_flight): step i+1's kernels are enqueued before the host waits for step i, as gat_amd.run() does
@@ -25,9 +25,15 @@ process -- plus
   roofline       : the overlap-count kernel: algorithmic bytes / kernel time measured with HIP events in this run.  For
                    k_count_seg the bytes are SURVEY.md 8d's contract; k_count_merged never moves those (it looks a sample
                    segment up once in an index of all tracks): bound "l2", its L2 requests against the L2s' peak
-  cpu_baseline   : the CPU oracle (oracle/gat_oracle.c, a port of the reference) timed on this host (N = 1 only)
-and a few small extras (sustained_value, the step's HBM bytes, strong-scaling ms per job, the extra shapes' values, under N > 1
-the collective's figures).  Everything else goes to the details file (--details, default bench_details.json beside this script):
+  cpu_baseline   : the CPU oracle (oracle/gat_oracle.c, a port of the reference) timed on this host (N = 1, --full only)
+
+A plain run (no --full) does only what the headline needs: set up, W warm-up steps, the K timed steps, the count matrix of
+the last step to --dump-outputs DIR if given, the line; --details FILE writes what it has.  Everything below, and the
+roofline's fields that come from the per-kernel steps, is --full alone.
+
+--full adds a few small extras to the line (sustained_value, the step's HBM bytes, strong-scaling ms per job, the extra shapes'
+values, under N > 1 the collective's figures), and `value` may then be the sustained loop's figure (headline()).  Everything
+else goes to the details file (--details, default bench_details.json beside this script):
   kernels        : per-kernel time of the step (HIP events on the launch stream)
   sustained      : the same step repeated for at least a second behind the driver's K steps (mean, min, max over repeats)
   configs        : the same for config3 / config5 / config4 shapes (config3 with its own cpu_baseline)
@@ -84,6 +90,11 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--scale", type=float, default=1.0, help="scale interval counts (debugging only)")
     ap.add_argument("--counter", default=None, help="another counter than the configuration's (experiments only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel split, sustained loop, cpu_baseline, the --extra shapes, strong "
+                         "scaling, the gat_amd.run() block, the collective timed by itself, the details file (default: the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the count matrix of the last timed step to DIR/counts.npy (float64)")
     return ap.parse_args()
 
 
@@ -296,7 +307,7 @@ class Workload(object):
             dt = float(t.item())
         return dt
 
-    def measure(self, steps, warmup, sustain_s=0.0):
+    def measure(self, steps, warmup, sustain_s=0.0, full=True):
         import torch
         import torch.distributed as dist
         world = self.world
@@ -309,6 +320,10 @@ class Workload(object):
         # after the device was idle run 5-8 % slower than the steady state: `sustained` shows the difference.)
         acc = dict((k, 0.0) for k in self.KEYS)
         dt = self.timed(steps, warmup, acc)
+        # --dump-outputs: the matrix of the last timed step, copied before any step behind the timed region reuses its buffer
+        self.timed_counts = self.host[self.last].numpy().copy() if self.host is not None and self.args.dump_outputs else None
+        if not full:                                     # (a plain run: the headline alone)
+            return self.report(steps, warmup, dt, acc, None, None, 0)
         # the per-kernel split of the step (`kernels`, `sampler`): an event behind every kernel of the sampler costs a
         # call 50-60 us, so the library records them on request only -- here in a few steps of their own behind the timed
         # region (whose count kernel carries its two events always: `roofline`)
@@ -370,7 +385,6 @@ class Workload(object):
         # the small combining kernel
         main_ms = (acc["ms_count_main"] or acc["ms_count"]) / steps
         count_s = main_ms / 1e3
-        samp_s = acck["ms_sampler"] / 1e3
         achieved = bytes_per_sample * S / count_s / 1e9 if count_s > 0 else 0.0
         from gat_amd import _lib
         kernel = _lib.COUNT_KERNELS.get(int(acc.get("count_kernel", 1)), "k_count_seg")
@@ -381,10 +395,11 @@ class Workload(object):
                 "algorithmic_bytes_per_launch": bytes_per_sample * S,
                 "algorithmic_bytes_per_sample": bytes_per_sample,
                 "avg_launch_ms": main_ms,
-                "count_phase_ms": acck["ms_count"] / ksteps,
-                "share_of_gpu_time": acck["ms_count"] / max(1e-9, acck["ms_count"] + acck["ms_sampler"] + acck["ms_contig"]),
                 "note": "achieved/frac follow the SURVEY 8d contract (every annotation interval charged once per sample); "
                         "the kernel serves annotations from LDS / L2, so real HBM traffic is lower: see hbm_measured_GBps"}
+        if acck is not None:                             # (the per-kernel steps ran: --full)
+            roof["count_phase_ms"] = acck["ms_count"] / ksteps
+            roof["share_of_gpu_time"] = acck["ms_count"] / max(1e-9, acck["ms_count"] + acck["ms_sampler"] + acck["ms_contig"])
         if merged:
             # k_count_merged looks every sample segment up ONCE in a merged index of all tracks; the contract's bytes (every
             # annotation interval once per sample) are never moved.  Its algorithmic bytes are what the algorithm does look
@@ -481,31 +496,33 @@ class Workload(object):
                                        "all-gather and D2H run on a second stream beside the next step's kernels"
                                        % (self.host[0].numel() * 8 if self.host is not None else 0)},
             "roofline": roof,
-            "kernels": {"k_rng_ms": acck["ms_rng"] / ksteps, "k_place_ms": acck["ms_place"] / ksteps,
-                        "k_merge_ms": acck["ms_merge"] / ksteps, "k_tail_ms": acck["ms_ktail"] / ksteps,
-                        "k_finalize_ms": acck["ms_finalize"] / ksteps,
-                        "k_sampler_ms": (acck["ms_tail"] - acck["ms_ktail"] - acck["ms_finalize"]) / ksteps,
-                        "k_contig_ms": acck["ms_contig"] / ksteps, "count_main_ms": main_ms,
-                        "count_phase_ms": acck["ms_count"] / ksteps, "sampler_phase_ms": acck["ms_sampler"] / ksteps,
-                        "measured": "HIP events behind every kernel in %d steps of their own behind the timed region (the "
-                                    "events cost a call 50-60 us: gat_ctx_set_kernel_times); count_main_ms: the two events "
-                                    "around the count kernel inside the timed region" % ksteps},
-            "sampler": {"kernel": "k_rng + k_place + k_merge + k_sampler (random rows, placement, consolidation)",
-                        "avg_launch_ms": acck["ms_sampler"] / ksteps,
-                        "placements_per_s": acck["n_placed"] / samp_s if samp_s else 0.0,
-                        "mt19937_draws_per_s": acck["n_draws"] / samp_s if samp_s else 0.0,
-                        "kernel_samples_per_s": S * ksteps / samp_s if samp_s else 0.0,
-                        "contig_kernel_avg_ms": acck["ms_contig"] / ksteps,
-                        "units_retried": acc["n_retried"], "units_run_in_full": acc["n_full_units"],
-                        "units_resumed_out_of_rows": acc["n_resumed_units"],
-                        "rows_generated_per_draw_consumed": (self.P.rows_per_sample() * float(self.S) * steps / acc["n_draws"]) if acc["n_draws"] else None,
-                        "units_finished_by_k_tail": acc["n_tail_units"],
-                        "batches_per_step": acc["n_batches"] / steps,
-                        # wall time of a step against what its kernels took on the stream (HIP events around the call)
-                        "stream_ms_per_step": acc["ms_total"] / steps,
-                        "work_units": S * steps * flat["n_units"]},
-            "allgather": allgather,
         }
+        if acck is not None:                             # (the per-kernel steps ran: --full)
+            samp_s = acck["ms_sampler"] / 1e3
+            out["kernels"] = {"k_rng_ms": acck["ms_rng"] / ksteps, "k_place_ms": acck["ms_place"] / ksteps,
+                              "k_merge_ms": acck["ms_merge"] / ksteps, "k_tail_ms": acck["ms_ktail"] / ksteps,
+                              "k_finalize_ms": acck["ms_finalize"] / ksteps,
+                              "k_sampler_ms": (acck["ms_tail"] - acck["ms_ktail"] - acck["ms_finalize"]) / ksteps,
+                              "k_contig_ms": acck["ms_contig"] / ksteps, "count_main_ms": main_ms,
+                              "count_phase_ms": acck["ms_count"] / ksteps, "sampler_phase_ms": acck["ms_sampler"] / ksteps,
+                              "measured": "HIP events behind every kernel in %d steps of their own behind the timed region (the "
+                                          "events cost a call 50-60 us: gat_ctx_set_kernel_times); count_main_ms: the two events "
+                                          "around the count kernel inside the timed region" % ksteps}
+            out["sampler"] = {"kernel": "k_rng + k_place + k_merge + k_sampler (random rows, placement, consolidation)",
+                              "avg_launch_ms": acck["ms_sampler"] / ksteps,
+                              "placements_per_s": acck["n_placed"] / samp_s if samp_s else 0.0,
+                              "mt19937_draws_per_s": acck["n_draws"] / samp_s if samp_s else 0.0,
+                              "kernel_samples_per_s": S * ksteps / samp_s if samp_s else 0.0,
+                              "contig_kernel_avg_ms": acck["ms_contig"] / ksteps,
+                              "units_retried": acc["n_retried"], "units_run_in_full": acc["n_full_units"],
+                              "units_resumed_out_of_rows": acc["n_resumed_units"],
+                              "rows_generated_per_draw_consumed": (self.P.rows_per_sample() * float(self.S) * steps / acc["n_draws"]) if acc["n_draws"] else None,
+                              "units_finished_by_k_tail": acc["n_tail_units"],
+                              "batches_per_step": acc["n_batches"] / steps,
+                              # wall time of a step against what its kernels took on the stream (HIP events around the call)
+                              "stream_ms_per_step": acc["ms_total"] / steps,
+                              "work_units": S * steps * flat["n_units"]}
+        out["allgather"] = allgather
         if step_block is not None:
             out["step"] = step_block
         return out
@@ -743,6 +760,41 @@ def final_line(out, details_path=None):
     return text
 
 
+def write_details(out, path):
+    """the full report as JSON; the path written, or None if it could not be"""
+    try:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+    except OSError as e:
+        sys.stderr.write("bench.py: could not write %s: %s\n" % (path, e))
+        return None
+    return path
+
+
+DUMP_LIMIT = 64 << 20           # bytes of --dump-outputs in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (counts below 2^53 are exact).  An array that would take the
+    total past DUMP_LIMIT is written as a fixed sample instead: <name>_sample.npy, the values at the flat positions in
+    <name>_sample_index.npy (the same positions, seed 0, on every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    room = DUMP_LIMIT
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes <= room:
+            np.save(os.path.join(dirname, name + ".npy"), a)
+            room -= a.nbytes
+            continue
+        n = min(a.size, room // 16)                  # a value and its index, 8 bytes each
+        idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+        np.save(os.path.join(dirname, name + "_sample.npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(dirname, name + "_sample_index.npy"), idx.astype(np.float64))
+        room -= 16 * n
+
+
 class Guard(object):
     """N > 1: whatever happens, rank 0 leaves ONE JSON line and the job ends -- never a hang, never a run without a line.  A rank
     that fails takes the job down (the launcher terminates the others: SIGTERM; a collective that waits for a dead rank ends at
@@ -849,7 +901,7 @@ def run(args, rank, world, guard):
 
     cfg_samples = synthetic.CONFIG_SAMPLES[args.config]
     W = Workload(args.config, args.samples or cfg_samples, args, dev_index, rank, world, depth=args.pipeline)
-    main_out = W.measure(args.steps, args.warmup, args.sustain_seconds)
+    main_out = W.measure(args.steps, args.warmup, args.sustain_seconds if args.full else 0.0, full=args.full)
     out = {"metric": METRIC, "value": main_out["value"], "unit": "samples/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": main_out["ms_per_step"], "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "u32", "data": "synthetic"}
@@ -864,7 +916,10 @@ def run(args, rank, world, guard):
         torch.cuda.synchronize()
         np.savez(args.dump_counts, counts=W.host[W.last].numpy(), samples_per_rank=W.S, world=world, seed=args.seed,
                  first_sample=W.last_first)
-    cpu_leg = rank == 0 and not args.no_cpu_baseline and world == 1      # reported on rank 0 at N=1 only
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"counts": W.timed_counts})
+    # everything below the headline is --full's: a plain run closes, writes its details only if asked to, and prints its line
+    cpu_leg = args.full and rank == 0 and not args.no_cpu_baseline and world == 1      # reported on rank 0 at N=1 only
     if cpu_leg:
         out["cpu_baseline"] = cpu_baseline(W.flat, W.counters, args.seed, args.cpu_seconds)
         if args.config in REFERENCE_CYTHON:
@@ -875,7 +930,7 @@ def run(args, rank, world, guard):
     W.close()
     del W
     extras = {}
-    for name in [x for x in args.extra.split(",") if x and x != args.config]:
+    for name in [x for x in args.extra.split(",") if x and x != args.config and args.full]:
         guard.phase = "extra shape " + name
         torch.cuda.empty_cache()
         # (measured like the headline shape: these steps are 6-70 ms and gain 0-1 % from the second step in flight)
@@ -898,21 +953,16 @@ def run(args, rank, world, guard):
         del E
     if extras:
         out["configs"] = extras
-    if not args.no_strong and args.scale == 1.0:
+    if args.full and not args.no_strong and args.scale == 1.0:
         guard.phase = "strong scaling"
         out["strong_scaling"] = strong_scaling(args, dev_index, rank, world)
-    if not args.no_api and world == 1 and args.scale == 1.0:
+    if args.full and not args.no_api and world == 1 and args.scale == 1.0:
         out["api"] = api_block(args)
     if rank == 0:
         # the bulk goes to a file (and nowhere near stdout); stdout carries ONE small line, the last thing printed
-        details = args.details or os.path.join(ROOT, "bench_details.json")
-        try:
-            with open(details, "w") as f:
-                json.dump(out, f, indent=1)
-                f.write("\n")
-        except OSError as e:
-            sys.stderr.write("bench.py: could not write %s: %s\n" % (details, e))
-            details = None
+        details = None
+        if args.full or args.details:
+            details = write_details(out, args.details or os.path.join(ROOT, "bench_details.json"))
         sys.stdout.flush()
         guard.printed = True
         print(final_line(out, os.path.relpath(details, ROOT) if details else None), flush=True)

@@ -1003,8 +1003,26 @@ def g9_configs():
     config_case("config2", 4, 202, counters=list(COUNTERS), tag="config2all")
 
 
+# ------------------------------------------------------------------------------------------
+# G10 the reference's C searchsorted (utils/gat_utils.c, compiled into oracle/_ref by build()) on the inputs of
+# tests/test_oracle_golden.py::test_searchsorted_against_reference_c, so that the test runs where the reference is absent
+def g10_searchsorted():
+    from oracle import oracle as O
+    rs = numpy.random.RandomState(3)
+    base = numpy.sort(rs.randint(0, 1000, size=200)).astype(numpy.uint32)
+    targets = [int(t) for t in list(rs.randint(0, 1100, size=300)) + [0, 999, 1000, 4294967295]]
+    expect = [O.ref_searchsorted_u32(base, t) for t in targets]
+    assert None not in expect, "oracle/_ref not built: run build() where the reference tree is present"
+    with open(os.path.join(HERE, "searchsorted.json"), "w") as f:
+        json.dump({"base": [int(x) for x in base], "targets": targets, "expect": expect}, f)
+        f.write("\n")
+    print("G10 searchsorted: %d targets" % len(targets))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g5u", "g6", "g7", "g8", "g9", "g5s"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g5u", "g6", "g7", "g8", "g9", "g5s", "g10"]
+    if "g10" in which:
+        g10_searchsorted()
     if "g9" in which:
         g9_configs()
     if "g5s" in which:

@@ -102,3 +102,23 @@ def test_final_line_carries_the_target_shape_and_the_value_source():
     assert "value_source" in line and line["k_steps_value"] > 0
     c3 = line["configs"]["config3"]
     assert c3["kernel"].startswith("k_count_merged") and c3["cpu_baseline"]["kind"] == "port" and c3["cpu_baseline"]["cores"] >= 1
+
+
+def test_dump_outputs_float64_and_a_fixed_sample_past_the_limit(tmp_path):
+    """--dump-outputs: an array that fits is written whole in float64; one that would pass DUMP_LIMIT is written as a sample
+    whose positions are the same on every run"""
+    import numpy as np
+    B = _bench()
+    a = np.arange(24, dtype=np.int64).reshape(1, 2, 12) * 3
+    B.dump_outputs(str(tmp_path / "whole"), {"counts": a})
+    got = np.load(str(tmp_path / "whole" / "counts.npy"))
+    assert got.dtype == np.float64 and got.shape == a.shape and np.array_equal(got, a)
+    B.DUMP_LIMIT = 16 * 100
+    big = np.arange(5000, dtype=np.int64) * 7
+    for d in ("s1", "s2"):
+        B.dump_outputs(str(tmp_path / d), {"counts": big})
+        assert sorted(os.listdir(str(tmp_path / d))) == ["counts_sample.npy", "counts_sample_index.npy"]
+    v1, i1 = (np.load(str(tmp_path / "s1" / f)) for f in ("counts_sample.npy", "counts_sample_index.npy"))
+    v2, i2 = (np.load(str(tmp_path / "s2" / f)) for f in ("counts_sample.npy", "counts_sample_index.npy"))
+    assert v1.dtype == i1.dtype == np.float64 and len(v1) == len(i1) == 100 and len(set(i1.tolist())) == 100
+    assert np.array_equal(i1, i2) and np.array_equal(v1, v2) and np.array_equal(v1, big[i1.astype(np.int64)])

@@ -1127,7 +1127,7 @@ def test_bench_default_line_is_small_and_honest(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     details = str(tmp_path / "details.json")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--extra", "config3", "--extra-steps", "2",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--extra", "config3", "--extra-steps", "2",
            "--no-strong", "--no-api", "--sustain-seconds", "0.2", "--cpu-seconds", "2", "--details", details]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1143,13 +1143,45 @@ def test_bench_default_line_is_small_and_honest(tmp_path):
     assert full["sustained"]["seconds"] >= 0.2 and "kernels" in full and "sampler" in full
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """a run without --full: the K steps and nothing else (no cpu_baseline, no extra shapes, no sustained loop, no per-kernel
+    steps), value / ms_per_step of exactly those steps, and --dump-outputs writes the last timed step's count matrix, equal to
+    the oracle's columns for its sample ids"""
+    import subprocess
+    import sys
+    from gat_amd import problem
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    details, dump = str(tmp_path / "details.json"), str(tmp_path / "outputs")
+    S, K, W = 256, 3, 2
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--samples", str(S),
+           "--dump-outputs", dump, "--details", details]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line, out = _bench_outputs(r, details)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in line, k
+    assert line["steps"] == K and line["warmup"] == W and line["unit"] == "samples/s" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(S * 1e3 / line["ms_per_step"], rel=1e-3)
+    assert line["value_source"].startswith("the %d timed steps" % K)
+    for k in ("cpu_baseline", "configs", "strong_scaling", "api", "sustained", "kernels", "sampler"):
+        assert k not in out, k
+    assert os.listdir(dump) == ["counts.npy"]
+    got = np.load(os.path.join(dump, "counts.npy"))
+    assert got.dtype == np.float64 and got.shape == (1, 1, S)
+    cfg = synthetic.config("config2")
+    flat = problem.flatten_arrays(cfg["segments"], cfg["annotations"], cfg["workspace"], cfg["isochores"])
+    first = (W + K - 1) * S                               # the last timed step's sample ids
+    want, _ = O.run_samples(flat, [cfg["counter"]], 12345, 1, first, first + S)
+    assert np.array_equal(got[0], want[0].astype(np.float64))
+
+
 def test_bench_two_ranks_on_one_gpu(tmp_path):
     """bench.py's N > 1 path (rank-disjoint sample ranges, all-gather of the count matrix, max-over-ranks timing,
     one JSON line from rank 0) with two ranks sharing this box's GPU: GAT_BENCH_SHARE_GPU=1 swaps RCCL, which
     refuses two ranks on one device, for gloo; everything else is the code the multi-GPU launch runs."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GAT_BENCH_SHARE_GPU="1")
-    r = _torchrun(2, [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
+    r = _torchrun(2, [os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2",
                       "--warmup", "1", "--samples", "2000", "--extra", "", "--no-strong", "--sustain-seconds", "0.2",
                       "--details", str(tmp_path / "d.json")], env, root, 600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1184,7 +1216,7 @@ def test_bench_eight_ranks_on_one_gpu(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GAT_BENCH_SHARE_GPU="1")
     dump = str(tmp_path / "counts8.npz")
-    r = _torchrun(8, [os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2",
+    r = _torchrun(8, [os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--steps", "2",
                       "--warmup", "1", "--samples", "64", "--extra", "", "--sustain-seconds", "0", "--dump-counts", dump,
                       "--details", str(tmp_path / "d8.json")], env, root, 900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1214,7 +1246,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict((k, v) for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"))
     env["GAT_BENCH_SHARE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--samples",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--samples",
            "1000", "--extra", "config1", "--extra-steps", "1", "--sustain-seconds", "0", "--details", str(tmp_path / "d2.json")]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]

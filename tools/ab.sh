@@ -10,7 +10,7 @@ for LIB in "$@"; do
   for SH in $SHAPES; do
     CFG=${SH%%:*}; S=${SH##*:}
     TAG=$(basename $LIB .so)_${CFG}_${S}
-    env ${AB_ENV:-} GAT_LIB_PATH=$R/$LIB python3 bench.py --no-cpu-baseline --no-api --no-strong --sustain-seconds 0 --extra "" \
+    env ${AB_ENV:-} GAT_LIB_PATH=$R/$LIB python3 bench.py --full --no-cpu-baseline --no-api --no-strong --sustain-seconds 0 --extra "" \
         --config $CFG --samples $S --steps ${AB_STEPS:-10} --warmup 3 --details $OUT/$TAG.json > /dev/null 2> $OUT/$TAG.err || { echo "FAILED $TAG"; tail -3 $OUT/$TAG.err; }
     echo -n "$(basename $LIB .so) ${AB_ENV:-} | "; python3 tools/show_bench.py $OUT/$TAG.json
   done

@@ -13,7 +13,7 @@ SHAPES=${@:-"config2:10000 config3:10000 config5:125000 config4:12500 refdata:10
 for SH in $SHAPES; do
   CFG=${SH%%:*}; S=${SH##*:}
   OUT=$R/gpurun_out/prof_${TAG}/${CFG}; rm -rf $OUT; mkdir -p $OUT
-  ARGS="--no-cpu-baseline --no-api --no-strong --sustain-seconds 0 --extra= --config $CFG --samples $S --steps 3 --warmup 1"
+  ARGS="--full --no-cpu-baseline --no-api --no-strong --sustain-seconds 0 --extra= --config $CFG --samples $S --steps 3 --warmup 1"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $ARGS --details $OUT/bench.json > $OUT/bench_trace.log 2>&1
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 bench.py $ARGS --details /dev/null > $OUT/bench_fetch.log 2>&1
   rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 bench.py $ARGS --details /dev/null > $OUT/bench_write.log 2>&1

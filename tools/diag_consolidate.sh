@@ -14,7 +14,7 @@ LIB=$R/build/diagc/libgat_mi355_diagc.so
 for SH in $SHAPES; do
   CFG=${SH%%:*}; S=${SH##*:}
   rm -f $OUT/phases.jsonl
-  GAT_LIB_PATH=$LIB GAT_DIAG_OUT=$OUT/phases.jsonl python3 bench.py --no-cpu-baseline --no-api --no-strong --sustain-seconds 0 \
+  GAT_LIB_PATH=$LIB GAT_DIAG_OUT=$OUT/phases.jsonl python3 bench.py --full --no-cpu-baseline --no-api --no-strong --sustain-seconds 0 \
       --extra "" --config $CFG --samples $S --steps 2 --warmup 1 --details /dev/null > $OUT/bench_${CFG}_${S}.log 2>&1
   python3 - $OUT/phases.jsonl $CFG $S <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ TAG=$1; shift
 OUT=$R/gpurun_out/diag_$TAG; mkdir -p $OUT
 make -C gat_amd/csrc -s -j2 EXTRA=-DGAT_DIAG BUILD=$OUT/build OUT=$OUT/libgat_mi355_diag.so || exit 1
 rm -f $OUT/phases.jsonl
-GAT_LIB_PATH=$OUT/libgat_mi355_diag.so GAT_DIAG_OUT=$OUT/phases.jsonl python3 bench.py --no-cpu-baseline --extra "" --steps 2 --warmup 1 "$@" > $OUT/bench.log 2>&1
+GAT_LIB_PATH=$OUT/libgat_mi355_diag.so GAT_DIAG_OUT=$OUT/phases.jsonl python3 bench.py --full --no-cpu-baseline --extra "" --steps 2 --warmup 1 "$@" > $OUT/bench.log 2>&1
 python3 - $OUT/phases.jsonl <<'PY'
 import json, sys
 tot = {}; wu = 0

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/kstats; rm -rf $OUT; mkdir -p $OUT
 if [ -n "${KSTATS_SCRIPT:-}" ]; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $KSTATS_SCRIPT "$@" > $OUT/log 2>&1
 else
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --no-cpu-baseline "$@" > $OUT/log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --no-cpu-baseline "$@" > $OUT/log 2>&1
 fi
 python3 - $OUT <<'PY'
 import csv, glob, sys

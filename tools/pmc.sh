@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/pmc; rm -rf $OUT; mkdir -p $OUT
 i=0
 for G in "$@"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $G --output-format csv -d $OUT/g$i -- python3 bench.py --no-cpu-baseline $ARGS > $OUT/log$i 2>&1
+  rocprofv3 --kernel-trace --pmc $G --output-format csv -d $OUT/g$i -- python3 bench.py --full --no-cpu-baseline $ARGS > $OUT/log$i 2>&1
 done
 python3 - $OUT <<'PY'
 import csv, glob, sys, collections
