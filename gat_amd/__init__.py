@@ -10,7 +10,7 @@ import numpy as np
 from . import intervals, problem, synthetic            # noqa: F401
 from . import io as IO                                   # noqa: F401
 from . import stats as Stats                             # noqa: F401
-from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments,  # noqa: F401
+from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift,  # noqa: F401
                      Counter, computeCountsAll, overlap_sizes, CounterNucleotideOverlap, CounterNucleotideDensity, CounterSegmentOverlap,
                      CounterSegmentMidpointOverlap, CounterAnnotationOverlap, CounterAnnotationMidpointOverlap,
                      UnconditionalWorkspace, ConditionalWorkspaceCooccurance, ConditionalWorkspaceCentered,
@@ -180,6 +180,8 @@ def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, 
                                      bucket_size, nbuckets,
                                      count_workspace=None if count_workspace is None else count_workspace.asArrays())
     flat["sampler"] = getattr(sampler, "kind", 0)
+    if flat["sampler"] == SamplerShift.kind:
+        flat["shift_radius"], flat["shift_extension"] = sampler.radius, sampler.extension
     job.flat = flat
     names = job.names
     if flat["n_contigs"] == 0:
@@ -456,9 +458,11 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
             dist.broadcast_object_list(box, src=0)
             seed = int(box[0])
     conditional = getattr(workspace_generator, "is_conditional", False)
-    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments)):
-        raise NotImplementedError("only SamplerAnnotator and SamplerSegments run on the GPU path")
+    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift)):
+        raise NotImplementedError("only SamplerAnnotator, SamplerSegments and SamplerShift run on the GPU path")
     mt_state = None
+    if reference_stream and isinstance(sampler, SamplerShift):
+        raise NotImplementedError("reference_stream: SamplerShift runs on the per-unit streams only")
     if reference_stream:
         # the reference's own stream: numpy.random.seed(seed) once (scripts/gat-run.py:267-271), every work unit of every
         # segment track drawing from it in order -- an unpatched reference's table, number for number, at one stream's speed
@@ -686,7 +690,13 @@ def buildParser(usage=None):
     parser.add_option_group(g)
     g = optparse.OptionGroup(parser, "Sampling algorithm options")
     g.add_option("-c", "--counter", dest="counters", type="choice", action="append", choices=tuple(COUNTERS.keys()))
-    g.add_option("-m", "--sampler", dest="sampler", type="choice", choices=("annotator", "segments"))
+    g.add_option("-m", "--sampler", dest="sampler", type="choice", choices=("annotator", "segments", "shift"))
+    g.add_option("--shift-extension", dest="shift_extension", type="float",
+                 help="if the sampling method is 'shift', the size of the region around a segment's midpoint it is shifted "
+                      "within (0: use --shift-expansion) [default=%default]")
+    g.add_option("--shift-expansion", dest="shift_expansion", type="float",
+                 help="if the sampling method is 'shift', the region a segment is shifted within is its length times this "
+                      "[default=%default]")
     g.add_option("-n", "--num-samples", dest="num_samples", type="int")
     g.add_option("--bucket-size", dest="bucket_size", type="int")
     g.add_option("--nbuckets", dest="nbuckets", type="int")
@@ -735,6 +745,7 @@ def buildParser(usage=None):
                         overlapping_annotations=False, pseudo_count=1.0, pvalue_method="empirical", qvalue_method="BH",
                         qvalue_lambda=None, qvalue_pi0_method="smoother",
                         random_seed=None, reference_stream=False, restrict_workspace=False, sample_files=[], sampler="annotator", segment_files=[],
+                        shift_expansion=2.0, shift_extension=0,
                         truncate_segments_to_workspace=False, truncate_workspace_to_annotations=False,
                         conditional="unconditional", conditional_extension=None, conditional_expansion=None,
                         workspace_files=[], device=0, loglevel=1, stdout=None, stdlog=None)
@@ -752,6 +763,8 @@ def fromSegments(options, args=None):
         sampler = SamplerAnnotator(bucket_size=options.bucket_size, nbuckets=options.nbuckets)
     elif options.sampler == "segments":
         sampler = SamplerSegments()                      # scripts/gat-run.py:133 passes no bucket arguments
+    elif options.sampler == "shift":
+        sampler = SamplerShift(radius=options.shift_expansion, extension=options.shift_extension)   # scripts/gat-run.py:129-132
     else:
         raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
     counters = []

@@ -73,6 +73,8 @@ class ProblemDesc(C.Structure):
         ("anno_end", C.c_void_p),
         ("anno_group", C.c_void_p),
         ("annotations", C.c_void_p),
+        ("shift_radius", C.c_double),
+        ("shift_extension", C.c_int32),
     ]
 
 
@@ -122,6 +124,7 @@ class Stats(C.Structure):
         ("n_unit_overlaps", C.c_int64),
         ("kernel_times", C.c_int64),
         ("n_queued_units", C.c_int64),
+        ("n_empty_windows", C.c_int64),
     ]
 
     def asdict(self):
@@ -531,6 +534,8 @@ class Problem(object):
         d.bucket_size = int(flat.get("bucket_size", 0))
         d.nbuckets = int(flat.get("nbuckets", 100000))
         d.sampler = int(flat.get("sampler", 0))
+        d.shift_radius = float(flat.get("shift_radius", 2.0))
+        d.shift_extension = int(flat.get("shift_extension", 0))
         assert len(keep["seg_off"]) == d.n_units + 1 and len(keep["ws_off"]) == d.n_units + 1
         assert len(keep["cws_nseg"]) == d.n_contigs
         if annotations is not None:

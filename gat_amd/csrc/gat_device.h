@@ -650,8 +650,9 @@ __device__ __forceinline__ void wave_sort_fast(uint2* seg, int n, uint32_t* scra
 // SegmentList.merge(0) (gat/SegmentList.pyx:756-816) on a list already sorted by start (empty
 // segments anywhere are skipped, as the reference skips them): in place, 64 elements per step.
 // head[i] = first non-empty, or int32(start) - 0 > running max end; the previous group's end is
-// the running max seen just before the next head.  Returns the new length.
-template <bool MEM = false>
+// the running max seen just before the next head.  Returns the new length.  ADJ_APART: SegmentList.normalize
+// (gat/SegmentList.pyx:697-750) instead -- a start AT the running max end heads a group (adjacent pieces stay apart).
+template <bool MEM = false, bool ADJ_APART = false>
 __device__ __forceinline__ int wave_merge0(uint2* seg, int n, int lane) {
   int count = 0;
   int32_t carry = INT32_MIN;
@@ -671,7 +672,7 @@ __device__ __forceinline__ int wave_merge0(uint2* seg, int n, int lane) {
     const int32_t excl = __builtin_amdgcn_update_dpp(carry, incl, 0x138, 0xf, 0xf, false);   // wave_shr:1, lane 0 keeps carry
     const uint64_t vb = __ballot(valid);
     const bool prev_valid = any || (vb & lanemask_lt(lane)) != 0;
-    const bool head = valid && (!prev_valid || (int32_t)s > excl);
+    const bool head = valid && (!prev_valid || (ADJ_APART ? (int32_t)s >= excl : (int32_t)s > excl));
     const uint64_t hb = __ballot(head);
     const int pos = count + __popcll(hb & lanemask_lt(lane));
     wave_sync<MEM>();

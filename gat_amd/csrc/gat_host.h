@@ -348,6 +348,12 @@ struct gat_problem {
   DevBuf<uint4> d_ws_rec;                // per workspace segment {start, end, previous segment's end (INT32_MIN: none), cdf}: what a
                                          // position draw needs of its segment in ONE 16-byte access (k_place_grid)
   DevBuf<int64_t> d_cws_nseg;
+  // GAT_SAMPLER_SHIFT: per working segment two records {length, first window piece (index into the unit's workspace),
+  // window pieces, window bases} {first piece's clipped start, last piece's clipped end, 0, 0} -- the window
+  // (getOverlappingSegmentsWithRange + truncate, gat/Engine.pyx:1083-1084) does not depend on the stream; d_shift_off:
+  // per unit, the index of its first record pair
+  DevBuf<uint4> d_shift;
+  DevBuf<int32_t> d_shift_off;
   gat_annotations* anno = nullptr;       // the annotation tables: its own (made from the lists of its desc) or a shared object
   // per-batch scratch
   int64_t batch = 0;

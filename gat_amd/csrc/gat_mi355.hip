@@ -28,6 +28,7 @@
 #define GAT_NUM_COUNTERS_DEV 6
 #include "gat_kernels.h"
 #include "gat_tail.h"
+#include "gat_shift.h"
 #include "gat_stats.h"
 
 
@@ -482,7 +483,35 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_
     if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     const int32_t* skip_ptr = nullptr;
     int skip_stride = 0;
-    if (!P->h_order.empty()) {
+    if (!P->h_order.empty() && P->sampler == GAT_SAMPLER_SHIFT) {
+      // SamplerShift: k_shift writes the units' final (normalized) lists; no front end, no split path, no records
+      if (serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerShift has no reference-stream mode");
+      gat::ShiftArgs H;
+      memset(&H, 0, sizeof(H));
+      H.units_o = P->d_units_o.p; H.n_units = P->n_units; H.n_active = (int32_t)P->h_order.size();
+      H.rec_stride = (int32_t)P->batch;
+      // (LDS for the list a unit is expected to leave -- about one piece per segment, a quarter + 64 on top -- not for its slab
+      //  region: LDS is what bounds the waves a CU holds, and the kernel is a chain of dependent loads; a longer list is sorted
+      //  and merged in the slab)
+      uint32_t max_work = 0;
+      for (int32_t u : P->h_order) max_work = std::max(max_work, P->h_units[(size_t)u].hist_total);
+      H.lds_cap = std::min<int32_t>(std::min(P->max_unit_cap, 2048), (int32_t)(max_work + max_work / 4 + 64));
+      H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.shift = P->d_shift.p; H.shift_off = P->d_shift_off.p;
+      H.seed = seed; H.sample_begin = begin;
+      H.slab = P->d_slab.p; H.slab_stride = P->slab_stride;
+      H.unit_n = P->d_unit_n.p; H.flags = P->flags_dev(); H.stat = P->d_stat.p; H.ws_stat = P->d_ws_stat.p;
+      const unsigned n_act = (unsigned)P->h_order.size();
+      const unsigned gy = std::min(n_act, 32768u), gz = (n_act + gy - 1) / std::max(gy, 1u);
+      const size_t lds = (size_t)(gat::kMtLdsWords + 2 * (size_t)H.lds_cap) * 4;
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_shift, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(gat::k_shift, dim3((unsigned)nb, gy, gz), dim3(64), lds, ctx->stream, H);
+      HIPCHK(ctx, hipGetLastError());
+      ctx->k_recorded = false;
+      ctx->t_recorded = false;
+      P->split_ran = false;
+      P->patched_contigs = false;
+      P->patched_counts = false;
+    } else if (!P->h_order.empty()) {
       const int smode = serial_state != nullptr ? 0 : P->sampler_mode;
       gat::SamplerArgs A;
       memset(&A, 0, sizeof(A));
@@ -1053,6 +1082,7 @@ static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, int64_t nb, gat_st
       st->n_full_units += (int64_t)stat[4];
       st->n_resumed_units += (int64_t)stat[5];
       st->n_queued_units += (int64_t)(stat[9] & 0xffffffffull);
+      st->n_empty_windows += (int64_t)stat[7];
       if (timed) {
         // (a timing query that fails leaves its figure at 0: it must not turn a call that computed its counts into an error)
         auto lap = [](hipEvent_t a, hipEvent_t b) { float ms = 0; if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); ms = 0; } return ms; };
@@ -1394,6 +1424,8 @@ extern "C" int gat_sample_and_count(gat_ctx* ctx, gat_problem* P, const int32_t*
 extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, int n_counters,
                                            uint32_t* mt_state, int64_t n_samples, void* counts_dev, gat_stats* stats) {
   if (!mt_state) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: NULL state");
+  if (P->sampler == GAT_SAMPLER_SHIFT)
+    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerShift runs on the per-unit streams only");
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
   const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state);
   return rc ? rc : call_wait(ctx, P, stats);

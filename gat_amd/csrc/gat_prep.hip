@@ -746,6 +746,39 @@ static uint32_t host_overlap(const gat_segment* w, int64_t nw, uint32_t s, uint3
   return ov;
 }
 
+// SamplerShift (gat/Engine.pyx:1063-1084): the window of every working segment -- [max(0, mid - area), max(0, mid + area)]
+// in the reference's int32 lmax, the workspace segments overlapping it, truncated to it and normalized (empties dropped:
+// gat/SegmentList.pyx:1186-1203).  Those are the workspace segments with end > window start and start < window end, a
+// contiguous run [lo, hi]; only the run's first start and last end are clipped.  Two records per working segment.
+static void shift_windows(std::vector<uint4>& out, const gat_segment* us, int64_t nus, const gat_segment* uw, int64_t nuw,
+                          const std::vector<uint32_t>& cdf, double radius, int32_t extension) {
+  const double half_radius = radius / 2;
+  for (int64_t i = 0; i < nus; ++i) {
+    if (host_overlap(uw, nuw, us[i].start, us[i].end) == 0) continue;          // working = segments.filter(workspace)
+    const uint32_t length = us[i].end - us[i].start;
+    const uint32_t mid = us[i].start + length / 2u;
+    const int32_t area = extension ? extension / 2 : (int32_t)(uint32_t)(uint64_t)std::floor((double)length * half_radius);
+    const int32_t ws_start = std::max<int32_t>(0, (int32_t)(mid - (uint32_t)area));
+    const int32_t ws_end = std::max<int32_t>(0, (int32_t)(mid + (uint32_t)area));
+    const uint32_t s0 = (uint32_t)ws_start, e0 = (uint32_t)ws_end;
+    const gat_segment* lo_it = std::upper_bound(uw, uw + nuw, s0, [](uint32_t v, const gat_segment& g) { return v < g.end; });
+    const gat_segment* hi_it = std::lower_bound(uw, uw + nuw, e0, [](const gat_segment& g, uint32_t v) { return g.start < v; });
+    const int64_t lo = lo_it - uw, hi = (hi_it - uw) - 1;                     // pieces lo..hi
+    uint32_t k = 0, fs = 0, le = 0, sum = 0;
+    if (hi >= lo && s0 < e0) {
+      k = (uint32_t)(hi - lo + 1);
+      fs = std::max(uw[lo].start, s0);
+      le = std::min(uw[hi].end, e0);
+      if (k == 1) sum = le - fs;
+      else {
+        sum = (uw[lo].end - fs) + (le - uw[hi].start) + (cdf[(size_t)hi - 1] - cdf[(size_t)lo]);   // (cdf: cumulated lengths - 1)
+      }
+    }
+    out.push_back(make_uint4(length, k ? (uint32_t)lo : 0u, k, sum));
+    out.push_back(make_uint4(fs, le, 0u, 0u));
+  }
+}
+
 static int32_t cap_for(const gat_ctx* ctx, int64_t n) {
   int64_t c = n + n / 4 + 96;
   if (gat_opt(ctx, "GAT_TEST_SMALL_CAPS")) c = n / 2 + 8;      // tests: force the overflow / retry path
@@ -1031,8 +1064,12 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   P->n_contigs = d->n_contigs;
   P->n_tracks = d->n_tracks;
   P->merge_contigs = d->merge_contigs ? 1 : 0;
-  if (d->sampler != GAT_SAMPLER_ANNOTATOR && d->sampler != GAT_SAMPLER_SEGMENTS)
+  if (d->sampler != GAT_SAMPLER_ANNOTATOR && d->sampler != GAT_SAMPLER_SEGMENTS && d->sampler != GAT_SAMPLER_SHIFT)
     return set_err(ctx, GAT_ERR_ARG, "unknown sampler %d", d->sampler);
+  if (d->sampler == GAT_SAMPLER_SHIFT && !(d->shift_radius >= 0.0 && d->shift_radius <= 1e9))
+    return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: radius %g must be >= 0", d->shift_radius);
+  if (d->sampler == GAT_SAMPLER_SHIFT && d->shift_extension < 0)
+    return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: extension %d must be >= 0", (int)d->shift_extension);
   P->sampler = d->sampler;
   P->h_units.resize((size_t)d->n_units);
   P->h_base_cap.assign((size_t)d->n_units, 0);
@@ -1041,6 +1078,8 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   std::vector<uint2> h_ws;
   std::vector<uint32_t> h_ws_cdf, h_rank_len, h_ws_tree;
   std::vector<std::pair<int64_t, int32_t>> work;   // (working segments, unit)
+  std::vector<uint4> h_shift;                      // GAT_SAMPLER_SHIFT: the windows (gat_problem::d_shift)
+  std::vector<int32_t> h_shift_off((size_t)std::max(1, d->n_units), 0);
   std::vector<std::vector<int32_t>> per_contig((size_t)d->n_contigs);
   std::vector<double> len_cv2((size_t)std::max(1, d->n_units), 0.0);
 
@@ -1055,6 +1094,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     std::vector<uint2> ws;
     std::vector<uint32_t> cdf, tree_start, tree_cdf;
     std::vector<uint32_t> pgrid, cgrid;  // the grids of a fragmented workspace, header included (UnitDev::pgrid_off / cgrid_off)
+    std::vector<uint4> shift;            // GAT_SAMPLER_SHIFT: two records per working segment (gat_problem::d_shift)
     int64_t nwork = 0;
     double cv2 = 0.0;
   };
@@ -1117,7 +1157,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     R.rank.push_back(0u);                           // rank 0 is never drawn (r >= 1, gat/Engine.pyx:419-422)
     for (uint32_t l : lens) {
       const int64_t i = ((int64_t)l + bucket - 1) / bucket;
-      if (i >= d->nbuckets) {
+      if (i >= d->nbuckets && d->sampler != GAT_SAMPLER_SHIFT) {     // (SamplerShift has no length histogram)
         fail_unit(R, GAT_ERR_VALUE, "unit %d: segment of length %u too large: increase nbuckets (%d) or bucket_size (%lld)",
                   u, l, d->nbuckets, (long long)bucket);
         break;
@@ -1239,6 +1279,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     }
     U.ltotal = (int32_t)ltotal;
     U.n_target = (int32_t)nus;                       // SamplerSegments places len(segments) segments
+    if (d->sampler == GAT_SAMPLER_SHIFT) shift_windows(R.shift, us, nus, uw, nuw, R.cdf, d->shift_radius, d->shift_extension);
     R.nwork = nwork;
     R.active = true;
   }
@@ -1275,7 +1316,14 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     if (!R.pgrid.empty()) U.pgrid_off = append16(R.pgrid);
     if (!R.cgrid.empty()) U.cgrid_off = append16(R.cgrid);
     len_cv2[(size_t)u] = R.cv2;
-    P->h_base_cap[u] = cap_for(ctx, d->sampler == GAT_SAMPLER_SEGMENTS ? std::max<int64_t>(R.nwork, d->seg_off[u + 1] - d->seg_off[u]) : R.nwork);
+    // (SamplerShift: a segment gives one piece, two where it wraps round its window -- more only in fragmented windows, which
+    //  the overflow path takes)
+    P->h_base_cap[u] = cap_for(ctx, d->sampler == GAT_SAMPLER_SEGMENTS ? std::max<int64_t>(R.nwork, d->seg_off[u + 1] - d->seg_off[u])
+                                  : d->sampler == GAT_SAMPLER_SHIFT ? 2 * R.nwork : R.nwork);
+    if (d->sampler == GAT_SAMPLER_SHIFT) {
+      h_shift_off[(size_t)u] = (int32_t)(h_shift.size() / 2);
+      h_shift.insert(h_shift.end(), R.shift.begin(), R.shift.end());
+    }
     work.push_back(std::make_pair(R.nwork, (int32_t)u));
   }
   // contig -> units (reference order)
@@ -1356,6 +1404,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   {
     const char* env = gat_opt(ctx, "GAT_SAMPLER_MODE");
     if (env && !strcmp(env, "wave")) P->sampler_mode = 0;
+    if (P->sampler == GAT_SAMPLER_SHIFT) P->sampler_mode = 0;       // (k_shift: a wave per work unit, its stream in LDS)
     auto expect = [](uint64_t range) {
       if (range == 0) return 0.0;
       uint64_t m = range; m |= m >> 1; m |= m >> 2; m |= m >> 4; m |= m >> 8; m |= m >> 16; m |= m >> 32;
@@ -1429,6 +1478,11 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   HIPCHK(ctx, P->d_contig_units.upload(P->h_contig_units, ctx));
   HIPCHK(ctx, P->d_ws.upload(h_ws, ctx));
   HIPCHK(ctx, P->d_ws_cdf.upload(h_ws_cdf, ctx));
+  if (P->sampler == GAT_SAMPLER_SHIFT) {
+    if (h_shift.empty()) h_shift.push_back(make_uint4(0u, 0u, 0u, 0u));
+    HIPCHK(ctx, P->d_shift.upload(h_shift, ctx));
+    HIPCHK(ctx, P->d_shift_off.upload(h_shift_off, ctx));
+  }
   {
     // what a position draw needs of its workspace segment (gat/Engine.pyx:318-325) as one record
     std::vector<uint4> rec(std::max<size_t>(1, h_ws.size()));

@@ -1188,6 +1188,43 @@ class SamplerSegments(Sampler):
         return SegmentList(array=seg)
 
 
+class SamplerShift(Sampler):
+    """gat/Engine.pyx:998: moves every working segment by a random amount within a window around itself -- the
+    workspace within `extension // 2` of the segment's midpoint when `extension` is not 0, else within
+    floor(length * radius / 2) -- wrapping what leaves the window round to its other end.  The list is normalized
+    as the reference leaves it (overlaps united, adjacent pieces kept apart).  Same per-unit stream convention as
+    SamplerAnnotator.sample.  `extension` is truncated to an int as the reference's `cdef int` does; negative values
+    raise ValueError."""
+
+    kind = 2
+
+    def __init__(self, radius=2, extension=0):
+        radius, extension = float(radius), int(extension)
+        if not radius >= 0 or extension < 0:
+            raise ValueError("SamplerShift: radius (%r) and extension (%r) must be >= 0" % (radius, extension))
+        self.radius = radius
+        self.extension = extension
+
+    def sample(self, segments, workspace, seed=None):
+        assert workspace.isNormalized, "workspace is not normalized"
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 32))
+        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
+            return SegmentList()
+        s, w = segments.asArray(), workspace.asArray()
+        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
+                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)],
+                    sampler=self.kind, shift_radius=self.radius, shift_extension=self.extension)
+        P = _lib.Problem(get_context(), flat)
+        try:
+            seg, _ = P.sample(seed, 0, 1)
+        finally:
+            P.close()
+        r = SegmentList(array=seg)
+        r.isNormalized = 1
+        return r
+
+
 class Counter(object):
     name = None
 

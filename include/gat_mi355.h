@@ -50,6 +50,8 @@ typedef struct gat_annotations gat_annotations;
 #define GAT_SAMPLER_ANNOTATOR 0   /* SamplerAnnotator: place until the workspace overlap matches (default)   */
 #define GAT_SAMPLER_SEGMENTS 1    /* SamplerSegments: len(segments) placements, no consolidation; the lists are */
                                   /* normalized only by fromIsochores, so counters need isochore keys           */
+#define GAT_SAMPLER_SHIFT 2       /* SamplerShift(radius, extension) (gat/Engine.pyx:998-1111): every working   */
+                                  /* segment moved within a window around itself; per-unit streams only         */
 
 /*
  * Flat description of what gat.computeSample (gat/__init__.py:494-591) walks for one segment
@@ -75,7 +77,7 @@ typedef struct {
   const int64_t* cws_nseg;      /* n_contigs: len(contig_workspace[contig]) (Engine.pyx:1437)   */
   uint32_t bucket_size;         /* SamplerAnnotator(bucket_size, nbuckets): gat/Engine.pyx:498  */
   int32_t nbuckets;
-  int32_t sampler;              /* GAT_SAMPLER_ANNOTATOR (gat/Engine.pyx:445) or GAT_SAMPLER_SEGMENTS (:653) */
+  int32_t sampler;              /* GAT_SAMPLER_ANNOTATOR (gat/Engine.pyx:445), GAT_SAMPLER_SEGMENTS (:653) or GAT_SAMPLER_SHIFT (:998) */
   /* Optional (all 0 / NULL: annos / anno_off are the [track][contig] lists above).  With anno_group set, the caller hands
    * over the annotation lists as it holds them -- one per (track, isochore key), the `annotations` argument of
    * UnconditionalSampler.sample (gat/__init__.py:704) -- and the library forms computeSample's contig_annotations itself
@@ -89,6 +91,11 @@ typedef struct {
    * annotations to the sampling of every segment track (gat/__init__.py:971-1010); a host that loops over tracks builds
    * their tables once.  n_tracks / n_contigs / merge_contigs must be the object's; annos / anno_* above are ignored. */
   const gat_annotations* annotations;
+  /* GAT_SAMPLER_SHIFT only (ignored otherwise): SamplerShift(radius, extension) -- the window around a segment is
+   * extension // 2 on either side of its midpoint when extension != 0, else floor(length * radius / 2).  Both must be
+   * >= 0 (GAT_ERR_VALUE): the reference's unsigned casts give a negative value no meaning. */
+  double shift_radius;
+  int32_t shift_extension;
 } gat_problem_desc;
 
 /* The annotation side of gat_problem_desc by itself: the tracks' lists per contig -- [track][contig] CSR, or with
@@ -166,6 +173,9 @@ typedef struct {
                                 /* call was in flight (gat_amd.run() keeps two segment tracks' calls in flight): the fields read 0 */
   int64_t n_queued_units;       /* work units k_tail (lists of up to 1 024 segments) or k_resume_big (longer ones) left to     */
                                 /* k_sampler's queue: a wave each, the slow way (0 when neither ran: k_sampler took every unit)  */
+  int64_t n_empty_windows;      /* GAT_SAMPLER_SHIFT: segments whose window held no workspace base -- the reference's         */
+                                /* randint(0, 0) raises inside getRandomPosition, which returns 0; the direction is still     */
+                                /* drawn and the segment contributes nothing (gat/SegmentList.pyx:902-917)                     */
 } gat_stats;
 
 #define GAT_COUNT_KERNEL_NONE 0
