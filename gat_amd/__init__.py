@@ -10,7 +10,7 @@ import numpy as np
 from . import intervals, problem, synthetic            # noqa: F401
 from . import io as IO                                   # noqa: F401
 from . import stats as Stats                             # noqa: F401
-from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift,  # noqa: F401
+from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation,  # noqa: F401
                      Counter, computeCountsAll, overlap_sizes, CounterNucleotideOverlap, CounterNucleotideDensity, CounterSegmentOverlap,
                      CounterSegmentMidpointOverlap, CounterAnnotationOverlap, CounterAnnotationMidpointOverlap,
                      UnconditionalWorkspace, ConditionalWorkspaceCooccurance, ConditionalWorkspaceCentered,
@@ -458,11 +458,14 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
             dist.broadcast_object_list(box, src=0)
             seed = int(box[0])
     conditional = getattr(workspace_generator, "is_conditional", False)
-    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift)):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments and SamplerShift run on the GPU path")
+    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation)):
+        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift and SamplerGlobalPermutation run on "
+                                  "the GPU path")
     mt_state = None
     if reference_stream and isinstance(sampler, SamplerShift):
         raise NotImplementedError("reference_stream: SamplerShift runs on the per-unit streams only")
+    if reference_stream and isinstance(sampler, SamplerGlobalPermutation):
+        raise NotImplementedError("reference_stream: SamplerGlobalPermutation runs on the per-unit streams only")
     if reference_stream:
         # the reference's own stream: numpy.random.seed(seed) once (scripts/gat-run.py:267-271), every work unit of every
         # segment track drawing from it in order -- an unpatched reference's table, number for number, at one stream's speed
@@ -690,7 +693,7 @@ def buildParser(usage=None):
     parser.add_option_group(g)
     g = optparse.OptionGroup(parser, "Sampling algorithm options")
     g.add_option("-c", "--counter", dest="counters", type="choice", action="append", choices=tuple(COUNTERS.keys()))
-    g.add_option("-m", "--sampler", dest="sampler", type="choice", choices=("annotator", "segments", "shift"))
+    g.add_option("-m", "--sampler", dest="sampler", type="choice", choices=("annotator", "segments", "shift", "global-permutation"))
     g.add_option("--shift-extension", dest="shift_extension", type="float",
                  help="if the sampling method is 'shift', the size of the region around a segment's midpoint it is shifted "
                       "within (0: use --shift-expansion) [default=%default]")
@@ -765,6 +768,8 @@ def fromSegments(options, args=None):
         sampler = SamplerSegments()                      # scripts/gat-run.py:133 passes no bucket arguments
     elif options.sampler == "shift":
         sampler = SamplerShift(radius=options.shift_expansion, extension=options.shift_extension)   # scripts/gat-run.py:129-132
+    elif options.sampler == "global-permutation":
+        sampler = SamplerGlobalPermutation()             # scripts/gat-run.py:137-138
     else:
         raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
     counters = []

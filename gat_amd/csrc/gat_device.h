@@ -188,6 +188,142 @@ __device__ __forceinline__ uint32_t rng_range(WaveRng& r, uint32_t range, int la
   return v;
 }
 
+// ------------------------------------------------------------------------------------------
+// CPython's random.Random on the same wave generator (SamplerGlobalPermutation draws from Python's random,
+// gat/Engine.pyx:1300-1312).  The twist and tempering are numpy's; the seeding and the integer draw differ.
+//
+// random.seed(v), 0 <= v < 2^32: init_by_array with the one-word key [v] -- init_genrand(19650218) (the same for every
+// stream: a constant table), then 624 steps mt[i] = (mt[i] ^ ((mt[i-1] ^ (mt[i-1] >> 30)) * 1664525)) + v over
+// i = 1..623, 1 (mt[0] = mt[623] at the wrap), then 623 steps with 1566083941 and "- i" over i = 2..623, 1, then
+// mt[0] = 0x80000000.  Both chains run on scalar registers, scattered to the lanes with v_writelane as SeedStep does.
+struct MtInitTable {
+  uint32_t w[kMtN];
+  constexpr MtInitTable() : w() {
+    w[0] = 19650218u;
+    for (int i = 1; i < kMtN; ++i) w[i] = 1812433253u * (w[i - 1] ^ (w[i - 1] >> 30)) + (uint32_t)i;
+  }
+};
+__constant__ constexpr MtInitTable kMtInit{};
+
+template <int J, bool SECOND>
+struct ArrayStep {
+  // word base + J of the block: src holds its old value in lane J; p carries the new value of the word before it
+  static __device__ __forceinline__ void run(uint32_t& buf, uint32_t src, uint32_t& p, uint32_t key, uint32_t base, int cnt) {
+    if (J < cnt) {
+      const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)src, J);
+      p = SECOND ? (m ^ ((p ^ (p >> 30)) * 1566083941u)) - (base + (uint32_t)J) : (m ^ ((p ^ (p >> 30)) * 1664525u)) + key;
+      asm("v_writelane_b32 %0, %1, %2" : "+v"(buf) : "s"(p), "n"(J));
+    }
+    ArrayStep<J + 1, SECOND>::run(buf, src, p, key, base, cnt);
+  }
+};
+template <bool SECOND>
+struct ArrayStep<kWave, SECOND> {
+  static __device__ __forceinline__ void run(uint32_t&, uint32_t, uint32_t&, uint32_t, uint32_t, int) {}
+};
+
+__device__ __forceinline__ void rng_seed_by_array(WaveRng& r, uint32_t key, int lane) {
+  // first pass over i = 1..623, reading init_genrand(19650218) from the table
+  uint32_t p = kMtInit.w[0];
+  for (int base = 1; base < kMtN; base += kWave) {
+    const int i = base + lane;
+    const uint32_t src = i < kMtN ? kMtInit.w[i] : 0u;
+    uint32_t buf = src;
+    ArrayStep<0, false>::run(buf, src, p, key, (uint32_t)base, kMtN - base);
+    if (i < kMtN) r.mt[i] = buf;
+  }
+  wave_sync();
+  uint32_t m1 = r.mt[1];
+  p = (m1 ^ ((p ^ (p >> 30)) * 1664525u)) + key;     // the wrap: mt[0] = mt[623], then i = 1 once more
+  wave_sync();
+  if (lane == 0) r.mt[1] = p;
+  wave_sync();
+  // second pass over i = 2..623
+  for (int base = 2; base < kMtN; base += kWave) {
+    const int i = base + lane;
+    const uint32_t src = r.mt[i < kMtN ? i : kMtN - 1];
+    uint32_t buf = src;
+    ArrayStep<0, true>::run(buf, src, p, key, (uint32_t)base, kMtN - base);
+    wave_sync();
+    if (i < kMtN) r.mt[i] = buf;
+    wave_sync();
+  }
+  m1 = r.mt[1];
+  p = (m1 ^ ((p ^ (p >> 30)) * 1566083941u)) - 1u;   // the wrap, then i = 1
+  wave_sync();
+  if (lane == 0) { r.mt[1] = p; r.mt[0] = 0x80000000u; }
+  r.pos = kMtN;
+  r.rbuf = 0;
+  r.ndraws = 0;
+  r.use_pre = false;
+  r.exhausted = false;
+  r.can_switch = false;
+  wave_sync();
+}
+
+// The Python draws keep r.rbuf = the tempered words of the block of 64 that holds r.pos (twisting at 624).  Reloading
+// a block already held gives the same words, so a block start always reloads.
+__device__ __forceinline__ void py_window(WaveRng& r, int lane) {
+  if (r.pos == kMtN) { rng_twist(r, lane); r.pos = 0; }
+  if ((r.pos & (kWave - 1)) == 0) {
+    const int i = r.pos + lane;
+    uint32_t y = r.mt[i < kMtN ? i : kMtN - 1];
+    y ^= (y >> 11);
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    y ^= (y >> 18);
+    r.rbuf = y;
+  }
+}
+
+// random._randbelow(n), 1 <= n < 2^32: k = n.bit_length() (of n, not n - 1), r = getrandbits(k) = word >> (32 - k),
+// redrawn while r >= n.  The rejection test runs on the block's words at once; the first accepted word is the draw.
+__device__ __forceinline__ uint32_t py_randbelow(WaveRng& r, uint32_t n, int lane) {
+  const uint32_t sh = (uint32_t)__builtin_clz(n);
+  for (;;) {
+    py_window(r, lane);
+    const int base = r.pos & ~(kWave - 1), off = r.pos - base, lim = kMtN - base < kWave ? kMtN - base : kWave;
+    const uint32_t v = r.rbuf >> sh;
+    const uint64_t m = __ballot(lane >= off && lane < lim && v < n);
+    if (m) {
+      const int f = (int)__builtin_ctzll(m);
+      r.ndraws += (uint32_t)(f + 1 - off);
+      r.pos = base + f + 1;
+      return (uint32_t)__builtin_amdgcn_readlane((int)v, f);
+    }
+    r.ndraws += (uint32_t)(lim - off);
+    r.pos = base + lim;
+  }
+}
+
+// `count` draws of random._randbelow(n) with one bound: rejection does not depend on the draw's index, so the k-th
+// accepted word is the k-th draw -- a ballot of the accepted words and a prefix popcount place a block's draws at once.
+// store(i, value) runs in the lane that holds draw i.
+template <typename Store>
+__device__ __forceinline__ void py_randbelow_batch(WaveRng& r, uint32_t n, int count, int lane, Store store) {
+  const uint32_t sh = (uint32_t)__builtin_clz(n);
+  int done = 0;
+  while (done < count) {
+    py_window(r, lane);
+    const int base = r.pos & ~(kWave - 1), off = r.pos - base, lim = kMtN - base < kWave ? kMtN - base : kWave;
+    const uint32_t v = r.rbuf >> sh;
+    const bool ok = lane >= off && lane < lim && v < n;
+    const uint64_t m = __ballot(ok);
+    const int c = __popcll(m), rank = __popcll(m & lanemask_lt(lane)), need = count - done;
+    if (ok && rank < need) store(done + rank, v);
+    if (c >= need) {
+      const int f = (int)__builtin_ctzll(__ballot(ok && rank == need - 1));
+      r.ndraws += (uint32_t)(f + 1 - off);
+      r.pos = base + f + 1;
+      done = count;
+    } else {
+      r.ndraws += (uint32_t)(lim - off);
+      r.pos = base + lim;
+      done += c;
+    }
+  }
+}
+
 // utils/gat_utils.c:36-60 searchsorted with cmpPosition (gat/Engine.pyx:119): leftmost i with
 // (int)(a[i]-t) >= 0.  All operands wave-uniform: runs on the scalar unit / scalar cache.
 __device__ __forceinline__ int bisect_u32(const uint32_t* __restrict__ a, int n, uint32_t t) {

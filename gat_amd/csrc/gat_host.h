@@ -354,6 +354,13 @@ struct gat_problem {
   // per unit, the index of its first record pair
   DevBuf<uint4> d_shift;
   DevBuf<int32_t> d_shift_off;
+  // GAT_SAMPLER_GLOBAL_PERMUTATION: per unit {offset into d_perm_len, offset into d_perm_w / d_perm_cum, |W|, free}; the
+  // working segments' lengths in list order; W (the unit's workspace extended by its working segments, merge(0)ed) and its
+  // cumulated lengths (entry j: bases of pieces 0..j)
+  DevBuf<uint4> d_perm_unit;
+  DevBuf<uint32_t> d_perm_len;
+  DevBuf<uint2> d_perm_w;
+  DevBuf<uint32_t> d_perm_cum;
   gat_annotations* anno = nullptr;       // the annotation tables: its own (made from the lists of its desc) or a shared object
   // per-batch scratch
   int64_t batch = 0;

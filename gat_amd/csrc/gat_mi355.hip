@@ -29,6 +29,7 @@
 #include "gat_kernels.h"
 #include "gat_tail.h"
 #include "gat_shift.h"
+#include "gat_permute.h"
 #include "gat_stats.h"
 
 
@@ -505,6 +506,33 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_
       const size_t lds = (size_t)(gat::kMtLdsWords + 2 * (size_t)H.lds_cap) * 4;
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_shift, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(gat::k_shift, dim3((unsigned)nb, gy, gz), dim3(64), lds, ctx->stream, H);
+      HIPCHK(ctx, hipGetLastError());
+      ctx->k_recorded = false;
+      ctx->t_recorded = false;
+      P->split_ran = false;
+      P->patched_contigs = false;
+      P->patched_counts = false;
+    } else if (!P->h_order.empty() && P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
+      // SamplerGlobalPermutation: k_permute writes the units' final (normalized) lists, as k_shift does
+      if (serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerGlobalPermutation has no reference-stream mode");
+      gat::PermuteArgs H;
+      memset(&H, 0, sizeof(H));
+      H.units_o = P->d_units_o.p; H.n_units = P->n_units; H.n_active = (int32_t)P->h_order.size();
+      H.rec_stride = (int32_t)P->batch;
+      // (LDS for the lengths and the points of the longest unit, up to 2 048 working segments -- 24 KB with the generator's
+      //  state; a longer unit keeps them in its slab region)
+      uint32_t max_work = 0;
+      for (int32_t u : P->h_order) max_work = std::max(max_work, P->h_units[(size_t)u].hist_total);
+      H.lds_cap = (int32_t)std::min<uint32_t>(max_work, 2048u);
+      H.perm_unit = P->d_perm_unit.p; H.perm_len = P->d_perm_len.p; H.perm_w = P->d_perm_w.p; H.perm_cum = P->d_perm_cum.p;
+      H.seed = seed; H.sample_begin = begin;
+      H.slab = P->d_slab.p; H.slab_stride = P->slab_stride;
+      H.unit_n = P->d_unit_n.p; H.flags = P->flags_dev(); H.ws_stat = P->d_ws_stat.p;
+      const unsigned n_act = (unsigned)P->h_order.size();
+      const unsigned gy = std::min(n_act, 32768u), gz = (n_act + gy - 1) / std::max(gy, 1u);
+      const size_t lds = (size_t)(gat::kMtLdsWords + ((H.lds_cap + 1) & ~1) + 2 * (size_t)H.lds_cap) * 4;
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_permute, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(gat::k_permute, dim3((unsigned)nb, gy, gz), dim3(64), lds, ctx->stream, H);
       HIPCHK(ctx, hipGetLastError());
       ctx->k_recorded = false;
       ctx->t_recorded = false;
@@ -1426,6 +1454,8 @@ extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const i
   if (!mt_state) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: NULL state");
   if (P->sampler == GAT_SAMPLER_SHIFT)
     return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerShift runs on the per-unit streams only");
+  if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION)
+    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerGlobalPermutation runs on the per-unit streams only");
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
   const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state);
   return rc ? rc : call_wait(ctx, P, stats);

@@ -779,6 +779,30 @@ static void shift_windows(std::vector<uint4>& out, const gat_segment* us, int64_
   }
 }
 
+// SamplerGlobalPermutation (gat/Engine.pyx:1284-1299): working = segments.filter(workspace) (kept whole), W = the workspace
+// extended by them and merge(0)ed (adjacent pieces united), free = W.sum() - sum(lengths).  Appends W and its cumulated
+// lengths; returns free (negative: the reference's randint(0, free) raises).
+static int64_t permute_tables(std::vector<uint2>& w, std::vector<uint32_t>& cum, const gat_segment* us, int64_t nus,
+                              const gat_segment* uw, int64_t nuw) {
+  std::vector<uint2> all;
+  int64_t total = 0;
+  all.reserve((size_t)(nus + nuw));
+  for (int64_t i = 0; i < nuw; ++i) all.push_back(make_uint2(uw[i].start, uw[i].end));
+  for (int64_t i = 0; i < nus; ++i) {
+    if (host_overlap(uw, nuw, us[i].start, us[i].end) == 0) continue;
+    all.push_back(make_uint2(us[i].start, us[i].end));
+    total += us[i].end - us[i].start;
+  }
+  std::stable_sort(all.begin(), all.end(), [](const uint2& a, const uint2& b) { return a.x < b.x; });
+  for (const uint2& p : all) {
+    if (!w.empty() && p.x <= w.back().y) w.back().y = std::max(w.back().y, p.y);
+    else w.push_back(p);
+  }
+  int64_t sum = 0;
+  for (const uint2& p : w) { sum += p.y - p.x; cum.push_back((uint32_t)sum); }
+  return sum - total;
+}
+
 static int32_t cap_for(const gat_ctx* ctx, int64_t n) {
   int64_t c = n + n / 4 + 96;
   if (gat_opt(ctx, "GAT_TEST_SMALL_CAPS")) c = n / 2 + 8;      // tests: force the overflow / retry path
@@ -1064,7 +1088,8 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   P->n_contigs = d->n_contigs;
   P->n_tracks = d->n_tracks;
   P->merge_contigs = d->merge_contigs ? 1 : 0;
-  if (d->sampler != GAT_SAMPLER_ANNOTATOR && d->sampler != GAT_SAMPLER_SEGMENTS && d->sampler != GAT_SAMPLER_SHIFT)
+  if (d->sampler != GAT_SAMPLER_ANNOTATOR && d->sampler != GAT_SAMPLER_SEGMENTS && d->sampler != GAT_SAMPLER_SHIFT &&
+      d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION)
     return set_err(ctx, GAT_ERR_ARG, "unknown sampler %d", d->sampler);
   if (d->sampler == GAT_SAMPLER_SHIFT && !(d->shift_radius >= 0.0 && d->shift_radius <= 1e9))
     return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: radius %g must be >= 0", d->shift_radius);
@@ -1080,6 +1105,10 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   std::vector<std::pair<int64_t, int32_t>> work;   // (working segments, unit)
   std::vector<uint4> h_shift;                      // GAT_SAMPLER_SHIFT: the windows (gat_problem::d_shift)
   std::vector<int32_t> h_shift_off((size_t)std::max(1, d->n_units), 0);
+  // GAT_SAMPLER_GLOBAL_PERMUTATION: gat_problem::d_perm_*
+  std::vector<uint4> h_perm_unit((size_t)std::max(1, d->n_units), make_uint4(0u, 0u, 0u, 0u));
+  std::vector<uint32_t> h_perm_len, h_perm_cum;
+  std::vector<uint2> h_perm_w;
   std::vector<std::vector<int32_t>> per_contig((size_t)d->n_contigs);
   std::vector<double> len_cv2((size_t)std::max(1, d->n_units), 0.0);
 
@@ -1095,6 +1124,10 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     std::vector<uint32_t> cdf, tree_start, tree_cdf;
     std::vector<uint32_t> pgrid, cgrid;  // the grids of a fragmented workspace, header included (UnitDev::pgrid_off / cgrid_off)
     std::vector<uint4> shift;            // GAT_SAMPLER_SHIFT: two records per working segment (gat_problem::d_shift)
+    std::vector<uint32_t> lens;          // GAT_SAMPLER_GLOBAL_PERMUTATION: the working lengths, W, its cumulated lengths, free
+    std::vector<uint2> perm_w;
+    std::vector<uint32_t> perm_cum;
+    int64_t perm_free = 0;
     int64_t nwork = 0;
     double cv2 = 0.0;
   };
@@ -1157,7 +1190,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     R.rank.push_back(0u);                           // rank 0 is never drawn (r >= 1, gat/Engine.pyx:419-422)
     for (uint32_t l : lens) {
       const int64_t i = ((int64_t)l + bucket - 1) / bucket;
-      if (i >= d->nbuckets && d->sampler != GAT_SAMPLER_SHIFT) {     // (SamplerShift has no length histogram)
+      if (i >= d->nbuckets && d->sampler != GAT_SAMPLER_SHIFT && d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION) {   // (no length histogram)
         fail_unit(R, GAT_ERR_VALUE, "unit %d: segment of length %u too large: increase nbuckets (%d) or bucket_size (%lld)",
                   u, l, d->nbuckets, (long long)bucket);
         break;
@@ -1280,6 +1313,15 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     U.ltotal = (int32_t)ltotal;
     U.n_target = (int32_t)nus;                       // SamplerSegments places len(segments) segments
     if (d->sampler == GAT_SAMPLER_SHIFT) shift_windows(R.shift, us, nus, uw, nuw, R.cdf, d->shift_radius, d->shift_extension);
+    if (d->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
+      R.perm_free = permute_tables(R.perm_w, R.perm_cum, us, nus, uw, nuw);
+      if (R.perm_free < 0) {
+        fail_unit(R, GAT_ERR_VALUE, "unit %d: SamplerGlobalPermutation: the working segments overlap (free length %lld < 0)",
+                  u, (long long)R.perm_free);
+        continue;
+      }
+      R.lens = lens;
+    }
     R.nwork = nwork;
     R.active = true;
   }
@@ -1320,6 +1362,16 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     //  the overflow path takes)
     P->h_base_cap[u] = cap_for(ctx, d->sampler == GAT_SAMPLER_SEGMENTS ? std::max<int64_t>(R.nwork, d->seg_off[u + 1] - d->seg_off[u])
                                   : d->sampler == GAT_SAMPLER_SHIFT ? 2 * R.nwork : R.nwork);
+    if (d->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
+      // (exact: the lengths and the sorted points at the top of the region when the unit is too long for LDS, the pieces --
+      //  at most n + |W| -- below them)
+      P->h_base_cap[u] = (int32_t)(2 * R.nwork + (int64_t)R.perm_w.size());
+      h_perm_unit[(size_t)u] = make_uint4((uint32_t)h_perm_len.size(), (uint32_t)h_perm_w.size(), (uint32_t)R.perm_w.size(),
+                                          (uint32_t)R.perm_free);
+      h_perm_len.insert(h_perm_len.end(), R.lens.begin(), R.lens.end());
+      h_perm_w.insert(h_perm_w.end(), R.perm_w.begin(), R.perm_w.end());
+      h_perm_cum.insert(h_perm_cum.end(), R.perm_cum.begin(), R.perm_cum.end());
+    }
     if (d->sampler == GAT_SAMPLER_SHIFT) {
       h_shift_off[(size_t)u] = (int32_t)(h_shift.size() / 2);
       h_shift.insert(h_shift.end(), R.shift.begin(), R.shift.end());
@@ -1405,6 +1457,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     const char* env = gat_opt(ctx, "GAT_SAMPLER_MODE");
     if (env && !strcmp(env, "wave")) P->sampler_mode = 0;
     if (P->sampler == GAT_SAMPLER_SHIFT) P->sampler_mode = 0;       // (k_shift: a wave per work unit, its stream in LDS)
+    if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) P->sampler_mode = 0;    // (k_permute: the same)
     auto expect = [](uint64_t range) {
       if (range == 0) return 0.0;
       uint64_t m = range; m |= m >> 1; m |= m >> 2; m |= m >> 4; m |= m >> 8; m |= m >> 16; m |= m >> 32;
@@ -1482,6 +1535,14 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     if (h_shift.empty()) h_shift.push_back(make_uint4(0u, 0u, 0u, 0u));
     HIPCHK(ctx, P->d_shift.upload(h_shift, ctx));
     HIPCHK(ctx, P->d_shift_off.upload(h_shift_off, ctx));
+  }
+  if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
+    if (h_perm_len.empty()) h_perm_len.push_back(0u);
+    if (h_perm_w.empty()) { h_perm_w.push_back(make_uint2(0u, 0u)); h_perm_cum.push_back(0u); }
+    HIPCHK(ctx, P->d_perm_unit.upload(h_perm_unit, ctx));
+    HIPCHK(ctx, P->d_perm_len.upload(h_perm_len, ctx));
+    HIPCHK(ctx, P->d_perm_w.upload(h_perm_w, ctx));
+    HIPCHK(ctx, P->d_perm_cum.upload(h_perm_cum, ctx));
   }
   {
     // what a position draw needs of its workspace segment (gat/Engine.pyx:318-325) as one record

@@ -9,6 +9,7 @@ libgat_mi355.so -- see gat_amd/__init__.py:run and gat_amd/_lib.py.  There is no
 import collections
 import math
 import operator
+import random
 
 import numpy as np
 
@@ -1215,6 +1216,37 @@ class SamplerShift(Sampler):
         flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
                     merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)],
                     sampler=self.kind, shift_radius=self.radius, shift_extension=self.extension)
+        P = _lib.Problem(get_context(), flat)
+        try:
+            seg, _ = P.sample(seed, 0, 1)
+        finally:
+            P.close()
+        r = SegmentList(array=seg)
+        r.isNormalized = 1
+        return r
+
+
+class SamplerGlobalPermutation(Sampler):
+    """gat/Engine.pyx:1234: keeps the lengths of the working segments (those overlapping the workspace, kept whole),
+    shuffles their order and the gaps between them, and lays them into the workspace extended by them (merge(0):
+    adjacent pieces united) from a random shift, wrapping round its end and splitting at its gaps.  The list is
+    normalized as the reference leaves it (adjacent pieces kept apart).  The reference draws from Python's random: the
+    stream of a call is random.seed(seed), `seed` by default a draw of Python's random.  No parameters."""
+
+    kind = 3
+
+    def __init__(self):
+        pass
+
+    def sample(self, segments, workspace, seed=None):
+        assert workspace.isNormalized, "workspace is not normalized"
+        if seed is None:
+            seed = random.getrandbits(32)
+        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
+            return SegmentList()
+        s, w = segments.asArray(), workspace.asArray()
+        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
+                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], sampler=self.kind)
         P = _lib.Problem(get_context(), flat)
         try:
             seg, _ = P.sample(seed, 0, 1)
