@@ -40,8 +40,9 @@ def unit_tables(segments, workspace):
     return lengths, W, wsum - sum(lengths)
 
 
-def sample(rng, segments, workspace):
-    """SamplerGlobalPermutation().sample(segments, workspace) drawing from rng (a random.Random)."""
+def sample(rng, segments, workspace, stats=None):
+    """SamplerGlobalPermutation().sample(segments, workspace) drawing from rng (a random.Random).  stats, when given,
+    gathers the segments whose range straddles the wrap (linear position Wsum) and the pieces before and after it."""
     t = unit_tables(segments, workspace)
     if t is None:
         return []
@@ -63,6 +64,8 @@ def sample(rng, segments, workspace):
         q = shift + points[x] + before
         before += length
         p, end = q, q + length
+        if stats is not None and p < wsum < end:
+            stats["straddles"] = stats.get("straddles", 0) + 1
         while p < end:
             turn, lp = divmod(p, wsum)
             j = _piece(cum, lp)
@@ -71,6 +74,9 @@ def sample(rng, segments, workspace):
             (head if turn else tail).append(piece)
             p = stop
         assert j < nw
+    if stats is not None:
+        stats["head"] = stats.get("head", 0) + len(head)
+        stats["tail"] = stats.get("tail", 0) + len(tail)
     return head + tail
 
 

@@ -138,6 +138,13 @@ def filled_from_end(ws, end, remainder):
     return out
 
 
+def _fill(fill, ws, x, remainder, stats):
+    """one fill, noting in stats how many pieces the widest window taken whole (the remainder beyond its bases) had."""
+    if u32(remainder) > _sum(ws):
+        stats["fill_all_max"] = max(stats.get("fill_all_max", 0), len(ws))
+    return fill(ws, x, remainder)
+
+
 def random_position(rng, ws, stats):
     """SegmentList.getRandomPosition (:902-917); randint(0, 0) raises ValueError, which the cpdef's C return type turns
     into a printed warning and 0 -- no draw."""
@@ -156,7 +163,9 @@ def random_position(rng, ws, stats):
 
 
 def sample(rng, segments, workspace, radius=2.0, extension=0, stats=None):
-    """SamplerShift(radius, extension).sample(segments, workspace) drawing from rng (an oracle RandomState)."""
+    """SamplerShift(radius, extension).sample(segments, workspace) drawing from rng (an oracle RandomState).  stats
+    gathers the empty windows, the widest window a fill took whole (fill_all_max) and the most pieces a call put down
+    before its normalize (raw_pieces_max)."""
     if stats is None:
         stats = {}
     extension = int(extension)
@@ -177,14 +186,15 @@ def sample(rng, segments, workspace, radius=2.0, extension=0, stats=None):
         ws_end = i32(ws[-1][1]) if ws else 0
         if start < ws_start:
             remainder = lmin(ws_start - start, length)
-            out += filled_from_start(ws, start, u32(length - remainder))
-            out += filled_from_end(ws, ws_end, remainder)
+            out += _fill(filled_from_start, ws, start, u32(length - remainder), stats)
+            out += _fill(filled_from_end, ws, ws_end, remainder, stats)
         elif end > ws_end:
             remainder = lmin(end - ws_end, length)
-            out += filled_from_end(ws, end, u32(length - remainder))
-            out += filled_from_start(ws, ws_start, remainder)
+            out += _fill(filled_from_end, ws, end, u32(length - remainder), stats)
+            out += _fill(filled_from_start, ws, ws_start, remainder, stats)
         else:
-            out += filled_from_start(ws, start, length)
+            out += _fill(filled_from_start, ws, start, length, stats)
+    stats["raw_pieces_max"] = max(stats.get("raw_pieces_max", 0), len(out))
     if not out:
         return []
     return [tuple(x) for x in O.aslist(O.normalize(out))]

@@ -11,12 +11,12 @@ import pytest
 
 import gat_amd
 import permutation_model as M
+import sampler_edges as E
 from gat_amd import _lib, problem, synthetic
-from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 INT_COUNTERS = ["nucleotide-overlap", "segment-overlap", "segment-midoverlap", "annotation-overlap"]
-KIND = 3
+KIND = E.PERM
 
 
 @pytest.fixture(scope="module")
@@ -26,88 +26,21 @@ def ctx():
     c.close()
 
 
-def _rand_norm(r, n, span, maxlen, start=0):
-    pts = sorted(r.sample(range(start, span), 2 * n))
-    out = []
-    for i in range(n):
-        s, e = pts[2 * i], min(pts[2 * i + 1], pts[2 * i] + maxlen)
-        if e > s:
-            out.append((s, e))
-    return out
+_rand_norm, _as_lists, _model_counts = E.rand_norm, E.as_lists, E.model_counts
 
 
 def _units_flat(units):
-    """one contig per unit, no isochores, no annotations: the sampler alone."""
-    segs = [np.array(s, dtype=np.int64).reshape(-1, 2) for s, _ in units]
-    ws = [np.array(w, dtype=np.int64).reshape(-1, 2) for _, w in units]
-
-    def cat(lst):
-        a = np.concatenate(lst) if lst else np.zeros((0, 2), np.int64)
-        out = np.empty(len(a), dtype=O.SEG)
-        out["start"], out["end"] = a[:, 0], a[:, 1]
-        return out
-
-    def off(lst):
-        return np.concatenate([[0], np.cumsum([len(x) for x in lst])]).astype(np.int64)
-
-    n = len(units)
-    return dict(n_units=n, segs=cat(segs), seg_off=off(segs), ws=cat(ws), ws_off=off(ws),
-                unit_contig=np.arange(n, dtype=np.int32), n_contigs=n, merge_contigs=0, n_tracks=0,
-                annos=np.zeros(0, dtype=O.SEG), anno_off=np.zeros(1, np.int64), cws_nseg=np.array([len(w) for w in ws], np.int64),
-                sampler=KIND)
+    return E.units_flat(units, KIND)
 
 
 def _model_units(flat, seed, s0, s1):
     """the model's (sample, unit) lists in gat_sample_units' order: unit u of sample s draws from
     random.seed((seed + s * n_units + u) mod 2^32)."""
-    n = int(flat["n_units"])
-    segs, ws = O.aslist(flat["segs"]), O.aslist(flat["ws"])
-    so, wo = flat["seg_off"], flat["ws_off"]
-    lists = []
-    for s in range(s0, s1):
-        for u in range(n):
-            us, uw = segs[so[u]:so[u + 1]], ws[wo[u]:wo[u + 1]]
-            if not us or not uw:
-                lists.append([])
-                continue
-            lists.append(M.sample(random.Random((seed + s * n + u) & 0xFFFFFFFF), us, uw))
-    return lists
-
-
-def _as_lists(seg, off):
-    return [[(int(a), int(b)) for a, b in zip(seg["start"][off[i]:off[i + 1]], seg["end"][off[i]:off[i + 1]])]
-            for i in range(len(off) - 1)]
+    return E.model_units(flat, seed, s0, s1)[0]
 
 
 def _device_units(ctx, flat, seed, s0, s1):
-    P = _lib.Problem(ctx, flat)
-    try:
-        seg, off = P.sample(seed, s0, s1, unit_level=True)
-        return _as_lists(seg, off), P.last_stats
-    finally:
-        P.close()
-
-
-def _model_counts(flat, unit_lists, counters, S):
-    """the counters over the contig lists (fromIsochores: the units of a contig concatenated and merge(0)d when keys
-    carry isochores), summed over contigs."""
-    n, nc, nt = int(flat["n_units"]), int(flat["n_contigs"]), int(flat["n_tracks"])
-    annos, ao = O.aslist(flat["annos"]), flat["anno_off"]
-    out = [np.zeros((nt, S), np.int64) for _ in counters]
-    for s in range(S):
-        contig = [[] for _ in range(nc)]
-        for u in range(n):
-            c = int(flat["unit_contig"][u])
-            if c >= 0:
-                contig[c] += unit_lists[s * n + u]
-        if int(flat["merge_contigs"]):
-            contig = [O.aslist(O.merge(sorted(x), 0)) if x else [] for x in contig]
-        for k, name in enumerate(counters):
-            for t in range(nt):
-                out[k][t, s] = sum(int(O.counter(name, contig[c], annos[ao[t * nc + c]:ao[t * nc + c + 1]],
-                                                 int(flat["cws_nseg"][c])))
-                                   for c in range(nc) if contig[c])
-    return out
+    return E.device_units(ctx, flat, seed, s0, s1)
 
 
 def _random_units(r, n, fragmented=0.3):

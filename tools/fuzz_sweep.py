@@ -1,11 +1,16 @@
-"""one-off sweep of the fuzz generator of tests/test_hip_parity.py over many seeds (GPU vs oracle, bit-exact);
-usage: tools/fuzz_sweep.py first_seed n_seeds [edge|merged|long|scan|frag|units]"""
+"""one-off sweep of the fuzz generator of tests/test_hip_parity.py over many seeds (GPU vs oracle, bit-exact), or of the
+shift / global permutation edge cases of tests/test_sampler_edges_gpu.py (GPU vs tests/shift_model.py, permutation_model.py);
+usage: tools/fuzz_sweep.py first_seed n_seeds [edge|merged|long|scan|frag|units|shift|perm]"""
 import importlib.util, os, sys, time
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, root)
+sys.path.insert(0, os.path.join(root, "tests"))
 spec = importlib.util.spec_from_file_location("thp", os.path.join(root, "tests", "test_hip_parity.py"))
 m = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(m)
+spec = importlib.util.spec_from_file_location("tse", os.path.join(root, "tests", "test_sampler_edges_gpu.py"))
+se = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(se)
 from gat_amd import _lib
 
 
@@ -31,6 +36,8 @@ long_lists = len(sys.argv) > 3 and sys.argv[3] == "long"
 scan = len(sys.argv) > 3 and sys.argv[3] == "scan"
 frag = len(sys.argv) > 3 and sys.argv[3] == "frag"
 units = len(sys.argv) > 3 and sys.argv[3] == "units"
+shift = len(sys.argv) > 3 and sys.argv[3] == "shift"
+perm = len(sys.argv) > 3 and sys.argv[3] == "perm"
 uo = [0, 0, 0]
 handed = 0
 bad = 0
@@ -43,7 +50,11 @@ for seed in range(first, first + n):
     if (merged or long_lists or edge) and seed % 4 >= 2:
         ctx.options["GAT_PLACE_NO_CM"] = "1"           # k_place's steps as the compiler writes them (the shapes test picks by itself)
     try:
-        if units:
+        if shift:
+            se.shift_case(ctx, seed)
+        elif perm:
+            se.perm_case(ctx, seed)
+        elif units:
             r = m._units_direct_case(ctx, seed)
             uo = [uo[0] + r[0], uo[1] + r[1], uo[2] + (1 if r[2] else 0)]
         elif frag:
@@ -64,6 +75,6 @@ for seed in range(first, first + n):
     except Exception as e:             # noqa: BLE001
         bad += 1
         print("seed %d: %s: %s" % (seed, type(e).__name__, str(e)[:300]), flush=True)
-    if (seed - first + 1) % 2000 == 0:  # (a sweep cut short by `timeout` still says how far it came)
+    if (seed - first + 1) % (100 if shift or perm else 2000) == 0:  # (a sweep cut short by `timeout` still says how far it came)
         print("... %d seeds, %d failures, %.0f s" % (seed - first + 1, bad, time.time() - t0), flush=True)
 print("%d seeds, %d failures, %.1f s %s" % (n, bad, time.time() - t0, outcomes if edge else ("units through k_tail_big: %d" % handed if long_lists else ("units finished by k_tail: %d" % handed if frag else ("candidates %d, overlaps taken off %d, problems repeated through k_contig %d" % tuple(uo) if units else "")))))
