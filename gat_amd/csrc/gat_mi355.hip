@@ -278,6 +278,12 @@ struct CountLaunch {
   const uint32_t* ws_tree = nullptr;
   int max_units = 1;          // ... the most units a contig has
 };
+// n launch positions spread over grid y and z (each <= 65535) behind the x the kernel asks for
+static inline dim3 grid_yz(unsigned x, unsigned n) {
+  const unsigned gy = std::min(n, 32768u);
+  return dim3(x, gy, (n + gy - 1) / std::max(gy, 1u));
+}
+
 static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, gat::CountArgs A, DevBuf<uint32_t>& part,
                         int swap_capx, int list_cap, CountLaunch& L) {
   L.main_recorded = false;
@@ -321,7 +327,6 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
     const unsigned gpy = (unsigned)std::min<int64_t>(n_pairs, 32768), gpz = (unsigned)((n_pairs + gpy - 1) / gpy);
     if (gpz > 65535) return set_err(ctx, GAT_ERR_CAPACITY, "more than 2^31 (track tile, contig) pairs");
     dim3 grid((unsigned)((A.n_samples + SC - 1) / SC), gpy, gpz);
-    const unsigned gcy = (unsigned)std::min(std::max(1, A.n_contigs), 32768), gcz = ((unsigned)std::max(1, A.n_contigs) + gcy - 1) / gcy;
     const size_t lds_merged = (size_t)A.n_tracks * 4 * (gat::kMergedThreads / gat::kWave);
     const int route = count_route(ctx, annos.has_merged, C, A.n_contigs, A.n_tracks, swap_capx, !annos.per_track);
     if (route == GAT_COUNT_KERNEL_MERGED) {
@@ -386,7 +391,7 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
       const size_t lds_swap = (size_t)3 * swap_capx * 4 + ((size_t)(1 << lcells) + 1) * 4;
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_count_swap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_swap));
       HIPCHK(ctx, hipEventRecord(L.ev_main[0], ctx->stream));
-      hipLaunchKernelGGL(gat::k_count_swap, dim3((unsigned)A.n_samples, gcy, gcz), dim3(gat::kSwapThreads), lds_swap, ctx->stream, B);
+      hipLaunchKernelGGL(gat::k_count_swap, grid_yz((unsigned)A.n_samples, (unsigned)std::max(1, A.n_contigs)), dim3(gat::kSwapThreads), lds_swap, ctx->stream, B);
       HIPCHK(ctx, hipGetLastError());
       HIPCHK(ctx, hipEventRecord(L.ev_main[1], ctx->stream));
       L.main_recorded = true;
@@ -396,21 +401,13 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
     const bool hits = C.slot[GAT_COUNTER_SEGMENT_OVERLAP] >= 0 || C.slot[GAT_COUNTER_SEGMENT_MIDOVERLAP] >= 0;
     HIPCHK(ctx, hipEventRecord(L.ev_main[0], ctx->stream));
     const int kv = (staged ? 4 : 0) + (hits ? 2 : 0) + (A.seg_merged != nullptr ? 1 : 0);
-    const void* fn = kv == 7 ? (const void*)gat::k_count_seg<true, true, true> : kv == 6 ? (const void*)gat::k_count_seg<true, true, false>
-                   : kv == 5 ? (const void*)gat::k_count_seg<true, false, true> : kv == 4 ? (const void*)gat::k_count_seg<true, false, false>
-                   : kv == 3 ? (const void*)gat::k_count_seg<false, true, true> : kv == 2 ? (const void*)gat::k_count_seg<false, true, false>
-                   : kv == 1 ? (const void*)gat::k_count_seg<false, false, true> : (const void*)gat::k_count_seg<false, false, false>;
-    if (staged) HIPCHK(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    switch (kv) {
-      case 7: hipLaunchKernelGGL((gat::k_count_seg<true, true, true>), grid, dim3(256), lds, ctx->stream, A); break;
-      case 6: hipLaunchKernelGGL((gat::k_count_seg<true, true, false>), grid, dim3(256), lds, ctx->stream, A); break;
-      case 5: hipLaunchKernelGGL((gat::k_count_seg<true, false, true>), grid, dim3(256), lds, ctx->stream, A); break;
-      case 4: hipLaunchKernelGGL((gat::k_count_seg<true, false, false>), grid, dim3(256), lds, ctx->stream, A); break;
-      case 3: hipLaunchKernelGGL((gat::k_count_seg<false, true, true>), grid, dim3(256), lds, ctx->stream, A); break;
-      case 2: hipLaunchKernelGGL((gat::k_count_seg<false, true, false>), grid, dim3(256), lds, ctx->stream, A); break;
-      case 1: hipLaunchKernelGGL((gat::k_count_seg<false, false, true>), grid, dim3(256), lds, ctx->stream, A); break;
-      default: hipLaunchKernelGGL((gat::k_count_seg<false, false, false>), grid, dim3(256), lds, ctx->stream, A); break;
-    }
+    typedef void (*count_fn)(gat::CountArgs);
+    static const count_fn kCountSegFns[8] = {
+        gat::k_count_seg<false, false, false>, gat::k_count_seg<false, false, true>, gat::k_count_seg<false, true, false>,
+        gat::k_count_seg<false, true, true>, gat::k_count_seg<true, false, false>, gat::k_count_seg<true, false, true>,
+        gat::k_count_seg<true, true, false>, gat::k_count_seg<true, true, true>};
+    if (staged) HIPCHK(ctx, hipFuncSetAttribute((const void*)kCountSegFns[kv], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kCountSegFns[kv], grid, dim3(256), lds, ctx->stream, A);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(L.ev_main[1], ctx->stream));
     L.main_recorded = true;
@@ -436,9 +433,8 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
       const size_t need = (size_t)A.n_contigs * 2 * (size_t)A.n_tracks * (size_t)A.n_samples;
       if (part.n < need) HIPCHK(ctx, part.alloc(need));
       B.part = part.p;
-      const unsigned gcy = (unsigned)std::min(A.n_contigs, 32768), gcz = ((unsigned)A.n_contigs + gcy - 1) / gcy;
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_count_anno_idx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
-      hipLaunchKernelGGL(gat::k_count_anno_idx, dim3((unsigned)A.n_samples, gcy, gcz), dim3(gat::kAnnoThreads), lds_a, ctx->stream, B);
+      hipLaunchKernelGGL(gat::k_count_anno_idx, grid_yz((unsigned)A.n_samples, (unsigned)A.n_contigs), dim3(gat::kAnnoThreads), lds_a, ctx->stream, B);
       HIPCHK(ctx, hipGetLastError());
       const int64_t nfin = (int64_t)A.n_tracks * A.n_samples;
       hipLaunchKernelGGL(gat::k_count_anno_finish, dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, ctx->stream, B);
@@ -458,531 +454,556 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
 // the caller sizes the batch again and repeats it (results do not depend on the batching: streams are per unit).
 constexpr int kRelayout = 1;
 static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, int64_t nb, gat_stats* st, bool timed, const unsigned long long* h_stat);
-// defer: only enqueue (the caller adds the count kernels behind, synchronises once and calls finish_sampler_batch)
-// records_ok: the consumer is k_count_seg alone, which reads (merged list, k_tail's record): no k_finalize
-// serial_state: the run's ONE MT19937 state on the device (k_serial: the reference's own stream) instead of the per-unit streams
-// units_direct: an isochore problem whose counters (the nucleotide counters, through the merged index) take the units' lists as
-// the sampler leaves them: no k_contig (k_count_merged<2, .> + k_units_overlap; P->units_direct says whether the batch took it)
-static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t begin, int64_t nb,
-                             gat_stats* st, bool timed, bool need_unit_lists = false, bool defer = false, bool records_ok = false,
-                             uint32_t* serial_state = nullptr, bool loose_ok = false, unsigned long long* h_stat = nullptr,
-                             bool units_direct = false) {
-  if (h_stat == nullptr) h_stat = ctx->h_stat;
-  P->units_direct = false;
-  {
-    int rc = ensure_scratch(ctx, P, nb);
-    if (rc) return rc;
-    if (P->batch < nb) return set_err(ctx, GAT_ERR_MEMORY, "internal: batch %lld > scratch %lld", (long long)nb, (long long)P->batch);
-    // (unit_n, contig_n and ws_stat are zeroed once when allocated: the kernels rewrite every entry of the active units
-    //  in every batch and never touch the others)
-#ifdef GAT_DBG_QUEUE
-    HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 16 * 8, ctx->stream));
-#else
-    HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 10 * 8, ctx->stream));
-#endif         // (statistics, status word, k_tail's queue length)
-    if (units_direct && P->d_cand_count.n) HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, P->d_cand_count.n * 4, ctx->stream));
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    const int32_t* skip_ptr = nullptr;
-    int skip_stride = 0;
-    if (!P->h_order.empty() && P->sampler == GAT_SAMPLER_SHIFT) {
-      // SamplerShift: k_shift writes the units' final (normalized) lists; no front end, no split path, no records
-      if (serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerShift has no reference-stream mode");
-      gat::ShiftArgs H;
-      memset(&H, 0, sizeof(H));
-      H.units_o = P->d_units_o.p; H.n_units = P->n_units; H.n_active = (int32_t)P->h_order.size();
-      H.rec_stride = (int32_t)P->batch;
-      // (LDS for the list a unit is expected to leave -- about one piece per segment, a quarter + 64 on top -- not for its slab
-      //  region: LDS is what bounds the waves a CU holds, and the kernel is a chain of dependent loads; a longer list is sorted
-      //  and merged in the slab)
-      uint32_t max_work = 0;
-      for (int32_t u : P->h_order) max_work = std::max(max_work, P->h_units[(size_t)u].hist_total);
-      H.lds_cap = std::min<int32_t>(std::min(P->max_unit_cap, 2048), (int32_t)(max_work + max_work / 4 + 64));
-      H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.shift = P->d_shift.p; H.shift_off = P->d_shift_off.p;
-      H.seed = seed; H.sample_begin = begin;
-      H.slab = P->d_slab.p; H.slab_stride = P->slab_stride;
-      H.unit_n = P->d_unit_n.p; H.flags = P->flags_dev(); H.stat = P->d_stat.p; H.ws_stat = P->d_ws_stat.p;
-      const unsigned n_act = (unsigned)P->h_order.size();
-      const unsigned gy = std::min(n_act, 32768u), gz = (n_act + gy - 1) / std::max(gy, 1u);
-      const size_t lds = (size_t)(gat::kMtLdsWords + 2 * (size_t)H.lds_cap) * 4;
-      HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_shift, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(gat::k_shift, dim3((unsigned)nb, gy, gz), dim3(64), lds, ctx->stream, H);
-      HIPCHK(ctx, hipGetLastError());
-      ctx->k_recorded = false;
-      ctx->t_recorded = false;
-      P->split_ran = false;
-      P->patched_contigs = false;
-      P->patched_counts = false;
-    } else if (!P->h_order.empty() && P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
-      // SamplerGlobalPermutation: k_permute writes the units' final (normalized) lists, as k_shift does
-      if (serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerGlobalPermutation has no reference-stream mode");
-      gat::PermuteArgs H;
-      memset(&H, 0, sizeof(H));
-      H.units_o = P->d_units_o.p; H.n_units = P->n_units; H.n_active = (int32_t)P->h_order.size();
-      H.rec_stride = (int32_t)P->batch;
-      // (LDS for the lengths and the points of the longest unit, up to 2 048 working segments -- 24 KB with the generator's
-      //  state; a longer unit keeps them in its slab region)
-      uint32_t max_work = 0;
-      for (int32_t u : P->h_order) max_work = std::max(max_work, P->h_units[(size_t)u].hist_total);
-      H.lds_cap = (int32_t)std::min<uint32_t>(max_work, 2048u);
-      H.perm_unit = P->d_perm_unit.p; H.perm_len = P->d_perm_len.p; H.perm_w = P->d_perm_w.p; H.perm_cum = P->d_perm_cum.p;
-      H.seed = seed; H.sample_begin = begin;
-      H.slab = P->d_slab.p; H.slab_stride = P->slab_stride;
-      H.unit_n = P->d_unit_n.p; H.flags = P->flags_dev(); H.ws_stat = P->d_ws_stat.p;
-      const unsigned n_act = (unsigned)P->h_order.size();
-      const unsigned gy = std::min(n_act, 32768u), gz = (n_act + gy - 1) / std::max(gy, 1u);
-      const size_t lds = (size_t)(gat::kMtLdsWords + ((H.lds_cap + 1) & ~1) + 2 * (size_t)H.lds_cap) * 4;
-      HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_permute, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(gat::k_permute, dim3((unsigned)nb, gy, gz), dim3(64), lds, ctx->stream, H);
-      HIPCHK(ctx, hipGetLastError());
-      ctx->k_recorded = false;
-      ctx->t_recorded = false;
-      P->split_ran = false;
-      P->patched_contigs = false;
-      P->patched_counts = false;
-    } else if (!P->h_order.empty()) {
-      const int smode = serial_state != nullptr ? 0 : P->sampler_mode;
-      gat::SamplerArgs A;
-      memset(&A, 0, sizeof(A));
-      A.units = P->d_units.p; A.units_o = P->d_units_o.p; A.order = P->d_order.p; A.n_units = P->n_units; A.batch = (int32_t)nb;
-      A.rec_stride = (int32_t)P->batch;                  // (the scratch's size in samples: the records' row length in every batch)
-      A.ws = P->d_ws.p; A.ws_cdf = P->d_ws_cdf.p; A.rank_len = P->d_rank_len.p; A.ws_tree = P->d_ws_tree.p;
-      A.ws_rec = P->d_ws_rec.p;
-      A.seed = seed; A.sample_begin = begin; A.sampler_kind = P->sampler;
-      A.place_plain_step = gat_opt(ctx, "GAT_PLACE_NO_CM") ? 1 : 0;
-      A.slab = P->d_slab.p; A.slab_stride = P->slab_stride;
-      A.unit_n = P->d_unit_n.p; A.flags = P->flags_dev(); A.stat = P->d_stat.p; A.ws_stat = P->d_ws_stat.p;
+
+// what a caller of run_sampler_batch asks for beyond the defaults
+struct BatchOpts {
+  bool need_unit_lists = false;          // somebody reads the units' final lists (gat_sample_units): written whoever counts
+  bool defer = false;                    // only enqueue (the caller adds the count kernels behind, synchronises once and calls finish_sampler_batch)
+  bool records_ok = false;               // the consumer is k_count_seg alone, which reads (merged list, k_tail's record): no k_finalize
+  uint32_t* serial_state = nullptr;      // the run's ONE MT19937 state on the device (k_serial: the reference's own stream) instead of the per-unit streams
+  bool loose_ok = false;                 // the consumer skips empty segments (k_count_merged): long lists may keep what a trim emptied
+  unsigned long long* h_stat = nullptr;  // the pinned words the batch's statistics are copied to (nullptr: the context's)
+  // an isochore problem whose counters (the nucleotide counters, through the merged index) take the units' lists as the sampler
+  // leaves them: no k_contig (k_count_merged<2, .> + k_units_overlap; P->units_direct says whether the batch took it)
+  bool units_direct = false;
+};
+
+// One batch's decisions -- which stages run, and the sizes they share -- made once (plan_batch) from the problem, the context's
+// knobs and the caller's options; read-only for the stages.  What a stage leaves for the kernels behind it, it adds to the
+// batch's SamplerArgs.
+struct BatchPlan {
+  BatchOpts o;
+  int64_t nb; bool timed;
+  unsigned n_act;          // active units: the launch positions
+  uint32_t max_work;       // the largest hist_total of the active units
+  int smode;               // 0: the reference's own stream (k_serial), no front end
+  bool huge;               // a SamplerAnnotator list beyond LDS is worked on in the slab (HUGE variant); SamplerSegments never holds a list
+  bool tree;               // workspaces beyond the register loop: search trees
+  bool split;              // the split path (k_consolidate / k_merge_big + k_tail + k_finalize in front of k_sampler); lists beyond LDS: old path
+  bool long_lists;         // k_sampler<BIG>: the code for lists beyond the bucket sorts
+  unsigned n_long;         // the long units, which come first in the launch order
+  int nbk;                 // histogram buckets for the longest list (a power of two, 1 024 .. 8 192)
+  size_t lds_merge;        // the most k_merge_big takes: its LDS holds one list and the counting sort's histogram
+  bool merge_big;          // the first consolidation of the long lists by whole workgroups, launched over the n_long units
+  bool tail_big;           // ... the placement rounds behind it, one stream per lane (k_tail_big)
+  bool resume_big;         // ... and the rest of the unit with the list where it is (k_resume_big)
+  bool long_queue;         // ... with k_sampler working off a queue (k_queue_rest)
+  int big_buckets;         // no workgroup pass: the wave's own counting sort, its scratch behind k_sampler's segment buffer (0: none)
+  size_t lds;              // k_sampler's LDS for the longest list
+};
+
+static BatchPlan plan_batch(const gat_ctx* ctx, const gat_problem* P, int64_t nb, bool timed, const BatchOpts& o) {
+  BatchPlan B = {};
+  B.o = o; B.nb = nb; B.timed = timed;
+  B.n_act = (unsigned)P->h_order.size();
+  for (int32_t u : P->h_order) B.max_work = std::max(B.max_work, P->h_units[(size_t)u].hist_total);
+  B.smode = o.serial_state != nullptr ? 0 : P->sampler_mode;
+  B.lds = (size_t)(gat::kMtLdsWords + 2 * (size_t)P->max_unit_cap) * 4;
+  B.huge = P->sampler != GAT_SAMPLER_SEGMENTS && ((int64_t)B.lds > ctx->max_lds || gat_opt(ctx, "GAT_TEST_HUGE") != nullptr);
+  if (B.huge || P->sampler == GAT_SAMPLER_SEGMENTS) B.lds = (size_t)gat::kMtLdsWords * 4;
+  B.tree = P->max_nws > gat::kWsTreeMin;
+  B.split = P->split_path && B.smode && !B.huge;
+  B.long_lists = !B.huge && B.max_work + B.max_work / 8 > 1024;
+  if (!B.long_lists) return B;
+  B.nbk = 1024;
+  while (B.nbk < P->max_unit_cap && B.nbk < 8192) B.nbk <<= 1;
+  B.lds_merge = (size_t)2 * P->max_unit_cap * 4 + (size_t)(B.nbk + 1) * 4;
+  for (int32_t u : P->h_order) { const uint32_t w = P->h_units[(size_t)u].hist_total; if (w + w / 8 > 1024) ++B.n_long; else break; }
+  B.merge_big = B.smode && P->sampler != GAT_SAMPLER_SEGMENTS && (int64_t)B.lds_merge + 1024 <= ctx->max_lds && B.n_long > 0 &&
+                !gat_opt(ctx, "GAT_NO_MERGE_BIG");
+  if (B.merge_big) {
+    B.tail_big = !B.split && P->d_patch.p != nullptr && P->max_nws <= gat::kTailMaxWs && !gat_opt(ctx, "GAT_NO_TAIL_BIG");
+    B.resume_big = B.tail_big && !gat_opt(ctx, "GAT_NO_RESUME_BIG");
+    B.long_queue = B.resume_big && !gat_opt(ctx, "GAT_NO_LONG_QUEUE");
+  } else {
+    // no workgroup pass: the wave's own counting sort, scratch behind the segment buffer if it fits
+    int nbk = B.nbk;
+    while (nbk >= 1024 && (int64_t)(B.lds + (size_t)(nbk + 1) * 4) > ctx->max_lds) nbk >>= 1;
+    if (nbk >= 1024) { B.big_buckets = nbk; B.lds += (size_t)(nbk + 1) * 4; }
+  }
+  return B;
+}
+
+// The wave-per-unit samplers that write the units' final (normalized) lists -- no front end, no split path, no records: what
+// their argument structs share, the grid and the launch.  H comes with the sampler's own tables and lds_cap.
+template <typename Args>
+static int enqueue_list_sampler(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin,
+                                void (*kernel)(Args), Args& H, size_t lds) {
+  H.units_o = P->d_units_o.p; H.n_units = P->n_units; H.n_active = (int32_t)B.n_act;
+  H.rec_stride = (int32_t)P->batch;
+  H.seed = seed; H.sample_begin = begin;
+  H.slab = P->d_slab.p; H.slab_stride = P->slab_stride;
+  H.unit_n = P->d_unit_n.p; H.flags = P->flags_dev(); H.ws_stat = P->d_ws_stat.p;
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid_yz((unsigned)B.nb, B.n_act), dim3(64), lds, ctx->stream, H);
+  HIPCHK(ctx, hipGetLastError());
+  return GAT_OK;
+}
+
+// SamplerShift: k_shift
+static int enqueue_shift(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
+  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerShift has no reference-stream mode");
+  gat::ShiftArgs H;
+  memset(&H, 0, sizeof(H));
+  // (LDS for the list a unit is expected to leave -- about one piece per segment, a quarter + 64 on top -- not for its slab
+  //  region: LDS is what bounds the waves a CU holds, and the kernel is a chain of dependent loads; a longer list is sorted
+  //  and merged in the slab)
+  H.lds_cap = std::min<int32_t>(std::min(P->max_unit_cap, 2048), (int32_t)(B.max_work + B.max_work / 4 + 64));
+  H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.shift = P->d_shift.p; H.shift_off = P->d_shift_off.p;
+  H.stat = P->d_stat.p;
+  return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_shift, H, (size_t)(gat::kMtLdsWords + 2 * (size_t)H.lds_cap) * 4);
+}
+
+// SamplerGlobalPermutation: k_permute
+static int enqueue_permute(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
+  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerGlobalPermutation has no reference-stream mode");
+  gat::PermuteArgs H;
+  memset(&H, 0, sizeof(H));
+  // (LDS for the lengths and the points of the longest unit, up to 2 048 working segments -- 24 KB with the generator's
+  //  state; a longer unit keeps them in its slab region)
+  H.lds_cap = (int32_t)std::min<uint32_t>(B.max_work, 2048u);
+  H.perm_unit = P->d_perm_unit.p; H.perm_len = P->d_perm_len.p; H.perm_w = P->d_perm_w.p; H.perm_cum = P->d_perm_cum.p;
+  return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_permute, H,
+                              (size_t)(gat::kMtLdsWords + ((H.lds_cap + 1) & ~1) + 2 * (size_t)H.lds_cap) * 4);
+}
+
+// the arguments every kernel of SamplerAnnotator / SamplerSegments starts from
+static int base_sampler_args(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin, gat::SamplerArgs& A) {
+  memset(&A, 0, sizeof(A));
+  A.units = P->d_units.p; A.units_o = P->d_units_o.p; A.order = P->d_order.p; A.n_units = P->n_units; A.batch = (int32_t)B.nb;
+  A.rec_stride = (int32_t)P->batch;                  // (the scratch's size in samples: the records' row length in every batch)
+  A.ws = P->d_ws.p; A.ws_cdf = P->d_ws_cdf.p; A.rank_len = P->d_rank_len.p; A.ws_tree = P->d_ws_tree.p;
+  A.ws_rec = P->d_ws_rec.p;
+  A.seed = seed; A.sample_begin = begin; A.sampler_kind = P->sampler;
+  A.place_plain_step = gat_opt(ctx, "GAT_PLACE_NO_CM") ? 1 : 0;
+  A.slab = P->d_slab.p; A.slab_stride = P->slab_stride;
+  A.unit_n = P->d_unit_n.p; A.flags = P->flags_dev(); A.stat = P->d_stat.p; A.ws_stat = P->d_ws_stat.p;
 #if defined(GAT_DIAG) || defined(GAT_DIAG_CONS)
-      {
-        const size_t nd = (size_t)nb * std::max(1, P->n_units) * 8;
-        if (P->d_diag.n < nd) HIPCHK(ctx, P->d_diag.alloc(nd));
-        HIPCHK(ctx, hipMemsetAsync(P->d_diag.p, 0, nd * 8, ctx->stream));
-        A.diag = P->d_diag.p;
-      }
+  {
+    const size_t nd = (size_t)B.nb * std::max(1, P->n_units) * 8;
+    if (P->d_diag.n < nd) HIPCHK(ctx, P->d_diag.alloc(nd));
+    HIPCHK(ctx, hipMemsetAsync(P->d_diag.p, 0, nd * 8, ctx->stream));
+    A.diag = P->d_diag.p;
+  }
 #endif
 #ifdef GAT_DIAG
-      {
-        const size_t np = std::max<size_t>(1, P->h_order.size()) * 8;
-        if (P->d_diag_place.n < np) HIPCHK(ctx, P->d_diag_place.alloc(np));
-        HIPCHK(ctx, hipMemsetAsync(P->d_diag_place.p, 0, np * 8, ctx->stream));
-        A.diag_place = P->d_diag_place.p;
-        const size_t nt = std::max<size_t>(1, P->h_order.size()) * (size_t)((nb + 63) / 64) * 2;
-        if (P->d_diag_tiles.n < nt) HIPCHK(ctx, P->d_diag_tiles.alloc(nt));
-        HIPCHK(ctx, hipMemsetAsync(P->d_diag_tiles.p, 0, nt * 8, ctx->stream));
-        A.diag_tiles = P->d_diag_tiles.p;
-      }
-#endif
-      // the units' launch positions are spread over grid y and z (each <= 65535)
-      const unsigned n_act = (unsigned)P->h_order.size();
-      const unsigned gy = std::min(n_act, 32768u), gz = (n_act + gy - 1) / std::max(gy, 1u);
-      A.n_active = (int32_t)n_act;
-      if (smode) {
-        // lane-parallel front end: the scratch was sized for P->batch samples, tiles are laid out for that
-        const int64_t nsb_alloc = (P->batch + 63) / 64;
-        const unsigned nsb = (unsigned)((nb + 63) / 64);
-        (void)nsb_alloc;
-        A.rng_off = P->d_rng_off.p; A.rng_rows = P->d_rng_rows.p; A.rng_out = P->d_rng_out.p;
-        A.rng_ckpt = P->d_rng_ckpt.p;
-        A.st = P->d_st.p;
-        {
-          // the streams' seeding chains at full occupancy, 16 checkpoints each; k_rng's waves regenerate the rest
-          const int64_t n_tiles = (int64_t)nsb * n_act, per_block = gat::kSeedThreads / gat::kWave;
-          hipLaunchKernelGGL(gat::k_seed, dim3((unsigned)((n_tiles + per_block - 1) / per_block)), dim3(gat::kSeedThreads), 0, ctx->stream,
-                             A, (int)nsb);
-          HIPCHK(ctx, hipGetLastError());
-        }
-        const size_t lds_rng = (size_t)gat::kMtN * 64 * 4;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_rng, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rng));
-        hipLaunchKernelGGL(gat::k_rng, dim3(nsb, gy, gz), dim3(gat::kRngThreads), lds_rng, ctx->stream, A);
-        HIPCHK(ctx, hipGetLastError());
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[0], ctx->stream));
-        const dim3 gp(nsb, gy, gz);
-        // (small calls of a problem of simple units -- about a wave per SIMD or less, e.g. the metric's 10 000 samples cut over
-        //  eight GPUs -- take the wide kernel as well: its loop stores unconditionally and four tiles share a rank table; config 2,
-        //  k_place at 1 250 / 2 500 / 5 000 samples: 0.46 / 0.47 / 0.56 ms against the lean kernel's 0.52 / 0.53 / 0.57, at 10 000
-        //  1.05 against 0.92)
-        const bool small_call = (int64_t)nsb * (int64_t)n_act <= 1536 && !gat_opt(ctx, "GAT_PLACE_NO_WIDE");
-        const int mode = P->all_simple ? ((gat_opt(ctx, "GAT_PLACE_WIDE") || small_call) ? 3 : 1)
-                                       : (P->all_one_ws && !gat_opt(ctx, "GAT_PLACE_NO_WIDE") ? 3 : (P->max_nws > gat::kPlaceWsLds ? 2 : 0));
-        // (k_place_wide: kPlaceWide tiles per workgroup, the largest unit's rank table beside their rings)
-        const dim3 gw((nsb + gat::kPlaceWide - 1) / gat::kPlaceWide, gy, gz);
-        const size_t lds_wide = (size_t)P->max_hist * 4;
-        // calls of a few hundred tiles of a problem of simple units: one stream walked by the 64 lanes of a wave (k_place_scan:
-        // a stream's states as a prefix scan over its rows) instead of one lane walking it row by row -- the chain of the longest
-        // unit's tile, 0.37 ms on config 2 whatever the sample count, is what such a call waited for
-        const char* env_scan = gat_opt(ctx, "GAT_PLACE_SCAN_TILES");
-        const int64_t scan_tiles = env_scan ? atoll(env_scan) : 768;      // (config 2: faster up to ~2 300 samples x 24 units per call)
-        const bool scan = P->sampler == GAT_SAMPLER_ANNOTATOR && P->all_simple && P->all_cm_ok && A.place_plain_step == 0 &&
-                          (int64_t)nsb * (int64_t)n_act <= scan_tiles;
-        if (scan) {
-          const int64_t n_tiles = (int64_t)nsb * n_act;
-          const unsigned nblocks = (unsigned)(((n_tiles + 7) / 8) * 8 * 4);
-          hipLaunchKernelGGL(gat::k_place_scan, dim3(nblocks), dim3(gat::kScanWaves * 64), 0, ctx->stream, A, (int)nsb,
-                             gat_opt(ctx, "GAT_PLACE_SCAN_SEQ") ? 1 : 0);
-        } else
-        if (P->sampler == GAT_SAMPLER_SEGMENTS) {
-          if (mode == 3) {
-            HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_wide<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide));
-            hipLaunchKernelGGL((gat::k_place_wide<1>), gw, dim3(gat::kPlaceWide * 64), lds_wide, ctx->stream, A);
-          } else if (mode == 1) hipLaunchKernelGGL((gat::k_place<1, 1>), gp, dim3(64), 0, ctx->stream, A);
-          else if (mode == 0) hipLaunchKernelGGL((gat::k_place<1, 0>), gp, dim3(64), 0, ctx->stream, A);
-          else hipLaunchKernelGGL((gat::k_place<1, 2>), gp, dim3(64), 0, ctx->stream, A);
-        } else {
-          // (k_place_pipe: the rows of the single-workspace-segment units prefetched by hand, see GAT_PLACE_LOOP_PIPE)
-          const bool pipe = P->pipe_pays && !gat_opt(ctx, "GAT_PLACE_NO_PIPE");
-          const bool rank_fits = P->max_hist < (uint32_t)gat::kPlaceRankLds;
-          // fragmented workspaces: the cdf grids of the long workspaces in LDS, eight tiles of a unit per workgroup (k_place_grid);
-          // static LDS: the workspace and rank tables (4 KB each) and an 8 KB ring per tile
-          const size_t lds_grid = (size_t)P->grid_lds_words * 4 + 16;
-          const bool grid_k = mode == 2 && P->grid_place && (int64_t)lds_grid + 8192 + 1024 + (int64_t)gat::kPlaceGridTiles * 8192 <= ctx->max_lds;
-          if (grid_k) {
-            HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_grid));
-            hipLaunchKernelGGL(gat::k_place_grid, dim3((nsb + gat::kPlaceGridTiles - 1) / gat::kPlaceGridTiles, gy, gz),
-                               dim3(gat::kPlaceGridTiles * 64), lds_grid, ctx->stream, A);
-          } else
-          if (mode == 3) {
-            HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_wide<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide));
-            hipLaunchKernelGGL((gat::k_place_wide<0>), gw, dim3(gat::kPlaceWide * 64), lds_wide, ctx->stream, A);
-          } else if (mode == 1 && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 1>), gp, dim3(64), 0, ctx->stream, A);
-          else if (mode == 1) hipLaunchKernelGGL((gat::k_place<0, 1>), gp, dim3(64), 0, ctx->stream, A);
-          else if (mode == 0 && P->small_tables && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0, 1>), gp, dim3(64), 0, ctx->stream, A);
-          else if (mode == 0 && P->small_tables) hipLaunchKernelGGL((gat::k_place<0, 0, 1>), gp, dim3(64), 0, ctx->stream, A);
-          else if (mode == 0 && P->max_nws <= 64 && rank_fits && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0, 2>), gp, dim3(64), 0, ctx->stream, A);
-          else if (mode == 0 && P->max_nws <= 64) hipLaunchKernelGGL((gat::k_place<0, 0, 2>), gp, dim3(64), 0, ctx->stream, A);
-          else if (mode == 0 && rank_fits && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0>), gp, dim3(64), 0, ctx->stream, A);
-          else if (mode == 0) hipLaunchKernelGGL((gat::k_place<0, 0>), gp, dim3(64), 0, ctx->stream, A);
-          else hipLaunchKernelGGL((gat::k_place<0, 2>), gp, dim3(64), 0, ctx->stream, A);
-        }
-        HIPCHK(ctx, hipGetLastError());
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[1], ctx->stream));
-      }
-      ctx->k_recorded = timed && smode;
-      size_t lds = (size_t)(gat::kMtLdsWords + 2 * (size_t)P->max_unit_cap) * 4;
-      // SamplerSegments never holds a list; a SamplerAnnotator list beyond LDS is worked on in the slab (HUGE variant)
-      const bool huge = P->sampler != GAT_SAMPLER_SEGMENTS && ((int64_t)lds > ctx->max_lds || gat_opt(ctx, "GAT_TEST_HUGE") != nullptr);
-      if (huge || P->sampler == GAT_SAMPLER_SEGMENTS) lds = (size_t)gat::kMtLdsWords * 4;
-      A.lds_cap = P->max_unit_cap;
-      A.big_buckets = 0;
-      uint32_t max_work = 0;
-      for (int32_t u : P->h_order) max_work = std::max(max_work, P->h_units[u].hist_total);
-      A.st2 = nullptr;
-      // the split path (k_consolidate / k_merge_big + k_tail + k_finalize in front of k_sampler); lists beyond LDS: old path
-      const bool split = P->split_path && smode && !huge;
-      unsigned n_long_big = 0;                  // launch positions k_merge_big was given
-      bool long_lists = false;                  // k_sampler<BIG>: the code for lists beyond the bucket sorts
-      if (!huge && max_work + max_work / 8 > 1024) {
-        long_lists = true;
-        int nbk = 1024;
-        while (nbk < P->max_unit_cap && nbk < 8192) nbk <<= 1;
-        // the first consolidation of the long lists by whole workgroups (k_merge_big): its LDS holds one list and the
-        // counting sort's histogram; launched over the long units, which come first in the launch order
-        const size_t lds_m = (size_t)2 * P->max_unit_cap * 4 + (size_t)(nbk + 1) * 4;
-        unsigned n_long = 0;
-        for (int32_t u : P->h_order) { const uint32_t w = P->h_units[u].hist_total; if (w + w / 8 > 1024) ++n_long; else break; }
-        if (smode && P->sampler != GAT_SAMPLER_SEGMENTS && (int64_t)lds_m + 1024 <= ctx->max_lds && n_long > 0 &&
-            !gat_opt(ctx, "GAT_NO_MERGE_BIG")) {
-          gat::SamplerArgs M = A;
-          M.st2 = P->d_st2.p;
-          M.big_buckets = nbk;
-          M.cum = split ? P->d_cum.p : nullptr;
-          n_long_big = n_long;
-          const bool tree_m = P->max_nws > gat::kWsTreeMin;
-          // (the form by the class's longest list: 8, 16 or 24 elements of it in every thread's registers; 0 = round 3's form,
-          //  the list read twice and sorted bucket by bucket)
-          typedef void (*merge_fn)(gat::SamplerArgs);
-          static const merge_fn kMergeFns[2][4] = {
-              {gat::k_merge_big<false, 0>, gat::k_merge_big<false, 8>, gat::k_merge_big<false, 16>, gat::k_merge_big<false, gat::kMergeRegs>},
-              {gat::k_merge_big<true, 0>, gat::k_merge_big<true, 8>, gat::k_merge_big<true, 16>, gat::k_merge_big<true, gat::kMergeRegs>}};
-          const bool merge_old = gat_opt(ctx, "GAT_MERGE_OLD") != nullptr;
-          for (int f = 0; f < 4; ++f)
-            HIPCHK(ctx, hipFuncSetAttribute((const void*)kMergeFns[tree_m ? 1 : 0][f], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
-          M.n_long = (int32_t)n_long;
-          for (size_t c = 0; c + 1 < P->h_class_start.size() && (unsigned)P->h_class_start[c] < n_long; ++c) {
-            // one launch per size class: LDS for the class's longest list and its histogram
-            const int a0 = P->h_class_start[c], a1 = std::min<int>(P->h_class_start[c + 1], (int)n_long);
-            // LDS for what the class's longest unit is EXPECTED to have placed at its first consolidation, not for its slab
-            // region (a quarter + 96 above the unit's segments): the count of placements is the unit's segments +- a
-            // renewal count's spread, cv(length) x sqrt(n) -- 90 for 8 000 segments -- so a twelfth + 64 on top is seven of
-            // those; a list beyond it takes k_sampler's own (slow) way.  And as many histogram buckets (a power of two, at
-            // least 1 024: a few elements per bucket sort as fast as one) as leave the number of workgroups a CU can hold
-            // at its maximum: this kernel is a chain of dependent passes, and chr1's 8 000 segments with 8 192 buckets were
-            // 113 KB -- ONE workgroup per CU for the classes that take most of its time (config-4 shape: 22.9 of 27.4 ms)
-            const int n0 = (int)P->h_units[(size_t)P->h_order[(size_t)a0]].hist_total;
-            const int ccap = std::min<int>(P->h_units[(size_t)P->h_order[(size_t)a0]].slab_cap, (n0 + n0 / 12 + 64 + 63) / 64 * 64);
-            auto wgs_at = [&](int nbk_) { return (int)(((size_t)ctx->max_lds) / ((size_t)2 * ccap * 4 + (size_t)(nbk_ + 1) * 4 + 1024)); };
-            int cnbk = 8192;
-            while (cnbk > 1024 && (cnbk / 2 >= ccap || wgs_at(cnbk) < wgs_at(1024))) cnbk >>= 1;
-            const size_t lds_c = (size_t)2 * ccap * 4 + (size_t)(cnbk + 1) * 4;
-            const int per = (ccap + gat::kMergeThreads - 1) / gat::kMergeThreads;
-            const int form = merge_old || per > gat::kMergeRegs ? 0 : (per <= 8 ? 1 : (per <= 16 ? 2 : 3));
-            size_t lds_k = lds_c;
-            if (form > 0) {
-              // (the register forms: the histogram shares the list's LDS -- up to about a bucket per element)
-              int maxb = 8192;
-              if (const char* e = gat_opt(ctx, "GAT_MERGE_BUCKETS")) maxb = std::max(1024, atoi(e));
-              cnbk = 1024;
-              while (2 * cnbk + gat::kMergeThreads + 1 <= ccap && 2 * cnbk <= maxb) cnbk <<= 1;     // (+ a word of padding per thread)
-              lds_k = ((size_t)ccap + (size_t)std::max(ccap, cnbk + gat::kMergeThreads + 1)) * 4;   // (short lists: the 1 024 buckets and their padding need their own words)
-            }
-            M.a_base = a0; M.a_end = a1; M.lds_cap = ccap; M.big_buckets = cnbk;
-            const unsigned cnt = (unsigned)(a1 - a0), gmy = std::min(cnt, 32768u);
-            const dim3 gm((unsigned)nb, gmy, (cnt + gmy - 1) / gmy);
-            hipLaunchKernelGGL(kMergeFns[tree_m ? 1 : 0][form], gm, dim3(gat::kMergeThreads), lds_k, ctx->stream, M);
-            HIPCHK(ctx, hipGetLastError());
-          }
-          A.st2 = P->d_st2.p;                    // (k_sampler reads it for those units only: see n_long below)
-          A.n_long = (int32_t)n_long;
-          if (!split && P->d_patch.p != nullptr && P->max_nws <= gat::kTailMaxWs && !gat_opt(ctx, "GAT_NO_TAIL_BIG")) {
-            // the placement rounds behind that consolidation, one stream per lane; k_sampler resumes at the trim
-            gat::TailArgs TB;
-            TB.S = A;
-            TB.cum = nullptr; TB.patch = P->d_patch.p; TB.todo = nullptr; TB.todo_count = nullptr;
-            // (counts alone, by k_count_merged -- or through k_contig, which merge(0)s the lists again: what a trim emptied may
-            //  stay in the list as [0, 0))
-            TB.loose_ok = (loose_ok && !need_unit_lists && !gat_opt(ctx, "GAT_RESUME_COMPACT")) ? 1 : 0;
-            // (bit 0: no bridge between two neighbours, bit 1: none over two segments on the right; "1" or anything else: both off)
-            TB.no_bridge = 0;
-            if (const char* e = gat_opt(ctx, "GAT_TB_NO_BRIDGE")) { const int v = atoi(e); TB.no_bridge = (v == 2 || v == 5) ? (v == 2 ? 2 : 1) : 3; }
-            TB.no_log_map = gat_opt(ctx, "GAT_TB_NO_LOG_MAP") ? 1 : 0;
-            const unsigned gby = std::min(n_long, 32768u);
-            hipLaunchKernelGGL(gat::k_tail_big, dim3((unsigned)((nb + 63) / 64), gby, (n_long + gby - 1) / gby), dim3(64), 0,
-                               ctx->stream, TB);
-            HIPCHK(ctx, hipGetLastError());
-            if (!gat_opt(ctx, "GAT_NO_RESUME_BIG")) {
-              // ... and the rest of the unit -- log inserted, trim, final filter -- with the list where it is
-              // (a reader that takes the segments one by one in any order -- k_count_merged on the units' lists, no contig lists
-              //  in between --: the log stays behind the merged list, the trim works on virtual indices)
-              const dim3 gr((unsigned)nb, gby, (n_long + gby - 1) / gby);
-              if (TB.loose_ok && !P->merge_contigs && !gat_opt(ctx, "GAT_RESUME_INSERT"))
-                hipLaunchKernelGGL(gat::k_resume_big<true>, gr, dim3(64), 0, ctx->stream, TB);
-              else
-                hipLaunchKernelGGL(gat::k_resume_big<false>, gr, dim3(64), 0, ctx->stream, TB);
-              HIPCHK(ctx, hipGetLastError());
-            }
-            A.tb = reinterpret_cast<const int32_t*>(P->d_patch.p);
-            A.skip_stride = (int32_t)(sizeof(gat::TailPatch) / 4);
-            if (!gat_opt(ctx, "GAT_NO_RESUME_BIG") && !gat_opt(ctx, "GAT_NO_LONG_QUEUE")) {
-              // k_sampler behind them works off a queue: launched over every (sample, unit) -- one or two waves a CU with such
-              // lists in LDS -- it took 3.1 ms per 12 500 samples of the config-4 shape to find every unit finished
-              TB.todo = P->d_todo.p; TB.todo_count = P->todo_count_dev();
-              const int64_t tot = (int64_t)nb * n_act;
-              hipLaunchKernelGGL(gat::k_queue_rest, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, TB, (int)n_act);
-              HIPCHK(ctx, hipGetLastError());
-              A.todo = P->d_todo.p;
-              A.todo_count = P->todo_count_dev();
-            }
-          }
-        } else {
-          // no workgroup pass: the wave's own counting sort, scratch behind the segment buffer if it fits
-          while (nbk >= 1024 && (int64_t)(lds + (size_t)(nbk + 1) * 4) > ctx->max_lds) nbk >>= 1;
-          if (nbk >= 1024) { A.big_buckets = nbk; lds += (size_t)(nbk + 1) * 4; }
-        }
-      }
-      const bool tree = P->max_nws > gat::kWsTreeMin;
-      ctx->t_recorded = false;
-      P->split_ran = split;
-      P->patched_contigs = false;
-      P->patched_counts = false;
-      if (split) {
-        // the split path: first consolidation (wave per unit), the loop's tail (lane per unit), the final list (wave per
-        // unit); k_sampler below then only resumes -- from the merged list -- the units k_tail left alone
-        gat::TailArgs T;
-        T.S = A;
-        T.loose_ok = 0; T.no_bridge = 0; T.no_log_map = 0;
-        T.S.st2 = P->d_st2.p;
-        T.S.n_long = (int32_t)n_long_big;                           // (whose verdict k_consolidate respects)
-        T.S.lds_cap = std::min(P->max_unit_cap, 1280);              // k_consolidate: the lists the wave bucket sorts take
-        T.S.slab_final = P->d_fslab.p;
-        T.cum = P->d_cum.p;
-        T.patch = P->d_patch.p;
-        T.todo = P->d_todo.p;
-        T.todo_count = P->todo_count_dev();                         // (zeroed with the statistics at the batch's start)
-        const size_t lds_max = (size_t)(gat::kSortScratchWords + 2 * (size_t)T.S.lds_cap) * 4;
-        const dim3 gu((unsigned)nb, gy, gz), gt((unsigned)((nb + 63) / 64), gy, gz);
-        if (tree) HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_consolidate<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        else HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_consolidate<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        // (a call of a few hundred tiles does not fill the chip whatever the LDS of a workgroup: one launch for all classes,
-        //  each launch less is a tail less -- config 2 at 1 250 samples: k_consolidate 0.121 -> 0.101 ms)
-        const bool one_class = (int64_t)((nb + 63) / 64) * (int64_t)n_act <= 1024 && !gat_opt(ctx, "GAT_SIZE_CLASSES");
-        for (size_t c = 0; c + 1 < P->h_class_start.size(); ++c) {
-          // one launch per size class, its LDS sized for the class's longest list
-          if (one_class && c > 0) break;
-          const int a0 = P->h_class_start[c], a1 = one_class ? P->h_class_start.back() : P->h_class_start[c + 1];
-          // (as for k_merge_big: LDS for what the class's longest unit is expected to have placed -- its segments +- a renewal
-          //  count's spread -- not for its slab region; the rare list beyond it is k_sampler's.  GAT_CONSOLIDATE_SLAB_LDS: the old size)
-          const int n0 = (int)P->h_units[(size_t)P->h_order[(size_t)a0]].hist_total;
-          const int tight = gat_opt(ctx, "GAT_CONSOLIDATE_SLAB_LDS") ? INT32_MAX : (n0 + n0 / 12 + 64 + 31) / 32 * 32;
-          const int ccap = std::min(std::min(P->h_units[(size_t)P->h_order[(size_t)a0]].slab_cap, T.S.lds_cap), tight);
-          gat::TailArgs C = T;
-          C.S.a_base = a0; C.S.a_end = a1; C.S.lds_cap = ccap;
-          const size_t lds_c = (size_t)(gat::kSortScratchWords + 2 * (size_t)ccap) * 4;
-          const unsigned cnt = (unsigned)(a1 - a0), cy = std::min(cnt, 32768u);
-          const dim3 gc((unsigned)nb, cy, (cnt + cy - 1) / cy);
-          if (tree) hipLaunchKernelGGL(gat::k_consolidate<true>, gc, dim3(64), lds_c, ctx->stream, C);
-          else hipLaunchKernelGGL(gat::k_consolidate<false>, gc, dim3(64), lds_c, ctx->stream, C);
-          HIPCHK(ctx, hipGetLastError());
-        }
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], ctx->stream));
-        if (P->tail_long_ws && P->max_nws > gat::kTailMaxWs) hipLaunchKernelGGL(gat::k_tail<true>, gt, dim3(64), 0, ctx->stream, T);
-        else hipLaunchKernelGGL(gat::k_tail<false>, gt, dim3(64), 0, ctx->stream, T);
-        HIPCHK(ctx, hipGetLastError());
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_t[0], ctx->stream));
-        // isochore problems: k_contig re-sorts the units of a contig anyway and takes (merged list, k_tail's record) as
-        // it is -- no final unit lists unless somebody asked for them (gat_sample_units)
-        P->patched_contigs = P->merge_contigs && P->n_contigs > 0 && !need_unit_lists && !gat_opt(ctx, "GAT_CONTIG_FINAL_LISTS");
-        P->units_direct = units_direct && P->patched_contigs && P->units_direct_ok && serial_state == nullptr;
-        P->patched_counts = !P->merge_contigs && records_ok && !need_unit_lists;
-        if (!P->patched_contigs && !P->patched_counts) hipLaunchKernelGGL(gat::k_finalize, gu, dim3(64), 0, ctx->stream, T);
-        HIPCHK(ctx, hipGetLastError());
-        if (timed) { HIPCHK(ctx, hipEventRecord(ctx->ev_t[1], ctx->stream)); ctx->t_recorded = true; }
-        A.st2 = P->d_st2.p;
-        A.n_long = (int32_t)n_act;
-        A.slab_final = P->d_fslab.p;
-        A.skip = &P->d_patch.p->state;
-        A.skip_stride = (int32_t)(sizeof(gat::TailPatch) / 4);
-        A.todo = P->d_todo.p;
-        A.todo_count = P->todo_count_dev();
-      } else if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], ctx->stream));
-      // variant: sampler kind x (long lists: counting-sort scratch) x (workspaces beyond the register loop: search trees)
-      int variant = P->sampler == GAT_SAMPLER_SEGMENTS ? (tree ? 5 : 4)
-                  : huge ? (tree ? 7 : 6) : (long_lists ? 2 : 0) + (tree ? 1 : 0);
-      // short lists only (20 waves of this kernel fit a CU's LDS): the instantiation with registers for 5 waves per SIMD
-      if (variant == 0 && (int64_t)lds * 20 <= ctx->max_lds && !gat_opt(ctx, "GAT_NO_WPE5")) variant = 8;
-      const void* ks = variant == 0 ? (const void*)gat::k_sampler<0, false, false, false>
-                     : variant == 1 ? (const void*)gat::k_sampler<0, false, true, false>
-                     : variant == 2 ? (const void*)gat::k_sampler<0, true, false, false>
-                     : variant == 3 ? (const void*)gat::k_sampler<0, true, true, false>
-                     : variant == 4 ? (const void*)gat::k_sampler<1, false, false, false>
-                     : variant == 5 ? (const void*)gat::k_sampler<1, false, true, false>
-                     : variant == 6 ? (const void*)gat::k_sampler<0, false, false, true>
-                     : variant == 7 ? (const void*)gat::k_sampler<0, false, true, true>
-                                    : (const void*)gat::k_sampler<0, false, false, false, 5>;
-      HIPCHK(ctx, hipFuncSetAttribute(ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      auto launch_sampler = [&](const dim3& gs, size_t lds_, const gat::SamplerArgs& K) {
-        switch (variant) {
-          case 0: hipLaunchKernelGGL((gat::k_sampler<0, false, false, false>), gs, dim3(64), lds_, ctx->stream, K); break;
-          case 1: hipLaunchKernelGGL((gat::k_sampler<0, false, true, false>), gs, dim3(64), lds_, ctx->stream, K); break;
-          case 2: hipLaunchKernelGGL((gat::k_sampler<0, true, false, false>), gs, dim3(64), lds_, ctx->stream, K); break;
-          case 3: hipLaunchKernelGGL((gat::k_sampler<0, true, true, false>), gs, dim3(64), lds_, ctx->stream, K); break;
-          case 4: hipLaunchKernelGGL((gat::k_sampler<1, false, false, false>), gs, dim3(64), lds_, ctx->stream, K); break;
-          case 5: hipLaunchKernelGGL((gat::k_sampler<1, false, true, false>), gs, dim3(64), lds_, ctx->stream, K); break;
-          case 6: hipLaunchKernelGGL((gat::k_sampler<0, false, false, true>), gs, dim3(64), lds_, ctx->stream, K); break;
-          case 7: hipLaunchKernelGGL((gat::k_sampler<0, false, true, true>), gs, dim3(64), lds_, ctx->stream, K); break;
-          default: hipLaunchKernelGGL((gat::k_sampler<0, false, false, false, 5>), gs, dim3(64), lds_, ctx->stream, K); break;
-        }
-      };
-      const bool list_in_lds = !huge && P->sampler != GAT_SAMPLER_SEGMENTS;
-      if (serial_state != nullptr) {
-        // the reference's own stream: one wave, every (sample, unit) of the batch in order
-        gat::SamplerArgs K = A;
-        K.serial_state = serial_state;
-        K.unit_pos = P->d_unit_pos.p;
-        const int sv = variant == 8 ? 0 : variant;
-        const void* kf = sv == 0 ? (const void*)gat::k_serial<0, false, false, false> : sv == 1 ? (const void*)gat::k_serial<0, false, true, false>
-                       : sv == 2 ? (const void*)gat::k_serial<0, true, false, false> : sv == 3 ? (const void*)gat::k_serial<0, true, true, false>
-                       : sv == 4 ? (const void*)gat::k_serial<1, false, false, false> : sv == 5 ? (const void*)gat::k_serial<1, false, true, false>
-                       : sv == 6 ? (const void*)gat::k_serial<0, false, false, true> : (const void*)gat::k_serial<0, false, true, true>;
-        HIPCHK(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        switch (sv) {
-          case 0: hipLaunchKernelGGL((gat::k_serial<0, false, false, false>), dim3(1), dim3(64), lds, ctx->stream, K); break;
-          case 1: hipLaunchKernelGGL((gat::k_serial<0, false, true, false>), dim3(1), dim3(64), lds, ctx->stream, K); break;
-          case 2: hipLaunchKernelGGL((gat::k_serial<0, true, false, false>), dim3(1), dim3(64), lds, ctx->stream, K); break;
-          case 3: hipLaunchKernelGGL((gat::k_serial<0, true, true, false>), dim3(1), dim3(64), lds, ctx->stream, K); break;
-          case 4: hipLaunchKernelGGL((gat::k_serial<1, false, false, false>), dim3(1), dim3(64), lds, ctx->stream, K); break;
-          case 5: hipLaunchKernelGGL((gat::k_serial<1, false, true, false>), dim3(1), dim3(64), lds, ctx->stream, K); break;
-          case 6: hipLaunchKernelGGL((gat::k_serial<0, false, false, true>), dim3(1), dim3(64), lds, ctx->stream, K); break;
-          default: hipLaunchKernelGGL((gat::k_serial<0, false, true, true>), dim3(1), dim3(64), lds, ctx->stream, K); break;
-        }
-      } else if (split) {
-        launch_sampler(dim3((unsigned)std::min<int64_t>((int64_t)nb * n_act, 8192)), lds, A);      // off the queue
-      } else if (list_in_lds && A.big_buckets == 0 && P->h_class_start.size() > 2 &&
-                 !(A.todo_count != nullptr && P->max_nws <= gat::kWsTreeMin && !gat_opt(ctx, "GAT_SIZE_CLASSES"))) {
-        // (not behind k_resume_big where it takes every unit -- workspaces of up to 32 segments --: the queue then holds the
-        //  per cent of units it declined, and one launch runs them side by side where five ran them class after class)
-        // one launch per size class: LDS for the class's longest list
-        for (size_t c = 0; c + 1 < P->h_class_start.size(); ++c) {
-          const int a0 = P->h_class_start[c], a1 = P->h_class_start[c + 1];
-          const int ccap = P->h_units[(size_t)P->h_order[(size_t)a0]].slab_cap;
-          gat::SamplerArgs K = A;
-          K.a_base = a0; K.a_end = a1;
-          const unsigned cnt = (unsigned)(a1 - a0), cy = std::min(cnt, 32768u);
-          // (off the queue -- long lists behind k_resume_big --: a one-dimensional launch, every class takes its own entries)
-          const dim3 gc = A.todo_count != nullptr ? dim3((unsigned)std::min<int64_t>((int64_t)nb * cnt, 8192)) : dim3((unsigned)nb, cy, (cnt + cy - 1) / cy);   // (8 192: what is left is a few long units, one to a workgroup)
-          launch_sampler(gc, (size_t)(gat::kMtLdsWords + 2 * (size_t)ccap) * 4, K);
-        }
-      } else if (A.todo_count != nullptr) {
-        launch_sampler(dim3((unsigned)std::min<int64_t>((int64_t)nb * n_act, 8192)), lds, A);      // off the queue
-      } else {
-        launch_sampler(dim3((unsigned)nb, gy, gz), lds, A);
-      }
-      HIPCHK(ctx, hipGetLastError());
-      if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[3], ctx->stream));
-      skip_ptr = A.skip != nullptr ? A.skip : (A.tb != nullptr ? A.tb : nullptr);     // (n_tail_units: finished by k_tail / carried on by k_tail_big)
-      skip_stride = A.skip_stride;
-    }
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    if (P->merge_contigs && P->n_contigs > 0) {
-      gat::ContigArgs B;
-      B.contig_unit_off = P->d_contig_unit_off.p; B.contig_units = P->d_contig_units.p; B.units = P->d_units.p;
-      B.cu_rec = P->d_cu_rec.p;
-      B.contig_slab_off = P->d_contig_slab_off.p; B.n_units = P->n_units; B.n_contigs = P->n_contigs;
-      B.slab_in = P->final_slab(); B.slab_out = P->d_cslab.p; B.slab_stride = P->slab_stride;
-      B.unit_n = P->d_unit_n.p; B.contig_n = P->d_contig_n.p; B.stat = P->d_stat.p;
-      B.slab_merged = nullptr; B.unit_pos = P->d_unit_pos.p; B.st2 = nullptr; B.patch = nullptr; B.patch_stride = 0;
-      B.ws_stat = P->d_ws_stat.p;
-      B.rec_stride = (int32_t)P->batch;
-      if (P->split_ran && P->patched_contigs) {
-        B.slab_merged = P->d_slab.p;
-        B.st2 = P->d_st2.p;
-        B.patch = reinterpret_cast<const int32_t*>(P->d_patch.p);
-        B.patch_stride = (int32_t)(sizeof(gat::TailPatch) / 4);
-      }
-      const int need_max = P->h_contig_order.empty() ? 64 : P->h_contig_need[(size_t)P->h_contig_order[0]];
-      size_t lds = (size_t)std::max(64, need_max) * 8 + gat::kSortScratchWords * 4;
-      const bool huge_c = (int64_t)lds > ctx->max_lds || gat_opt(ctx, "GAT_TEST_HUGE") != nullptr;   // list stays in the output slab
-      if (huge_c) lds = gat::kSortScratchWords * 4;
-      // (units_direct: the lists only concatenated, the candidates for k_units_overlap noted: k_contig<., true>)
-      const bool nosort = P->units_direct;
-      B.bmap = P->d_bmap.p; B.bmap_off = P->d_bmap_off.p; B.bshift = P->bshift;
-      B.cand = P->d_cand.p; B.cand_cap = (uint32_t)(P->d_cand.n / gat::kCandSlots); B.cand_count = P->d_cand_count.p;
-      const void* kc = nosort ? (huge_c ? (const void*)gat::k_contig<true, true> : (const void*)gat::k_contig<false, true>)
-                              : (huge_c ? (const void*)gat::k_contig<true> : (const void*)gat::k_contig<false>);
-      HIPCHK(ctx, hipFuncSetAttribute(kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      B.order = P->d_contig_order.p;
-      B.flags = P->flags_dev();
-      // one launch per size class: LDS for the class's longest expected list (more waves per CU for the short contigs)
-      for (size_t k = 0; k + 1 < P->h_contig_class_start.size(); ++k) {
-        const int c0 = P->h_contig_class_start[k], c1 = P->h_contig_class_start[k + 1];
-        // (one launch where the list is put together in place: beyond LDS, or only concatenated)
-        const bool one = huge_c || nosort;
-        if (one && k > 0) break;
-        B.base = one ? 0 : c0;
-        B.count = one ? P->n_contigs : c1 - c0;
-        B.lds_cap = one ? 0 : std::max(64, P->h_contig_need[(size_t)P->h_contig_order[(size_t)c0]]);
-        const size_t lds_k = nosort ? 64 : (huge_c ? lds : (size_t)B.lds_cap * 8 + gat::kSortScratchWords * 4);
-        const unsigned gcy = (unsigned)std::min(B.count, 32768), gcz = ((unsigned)B.count + gcy - 1) / gcy;
-        if (nosort && huge_c) hipLaunchKernelGGL((gat::k_contig<true, true>), dim3((unsigned)nb, gcy, gcz), dim3(64), lds_k, ctx->stream, B);
-        else if (nosort) hipLaunchKernelGGL((gat::k_contig<false, true>), dim3((unsigned)nb, gcy, gcz), dim3(64), lds_k, ctx->stream, B);
-        else if (huge_c) hipLaunchKernelGGL(gat::k_contig<true>, dim3((unsigned)nb, gcy, gcz), dim3(64), lds_k, ctx->stream, B);
-        else hipLaunchKernelGGL(gat::k_contig<false>, dim3((unsigned)nb, gcy, gcz), dim3(64), lds_k, ctx->stream, B);
-        HIPCHK(ctx, hipGetLastError());
-      }
-    }
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    if (!P->h_order.empty()) {
-      // (behind k_contig: on isochore problems it is k_contig that writes the statistics of the units k_tail finished)
-      hipLaunchKernelGGL(gat::k_reduce_stats, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)P->d_ws_stat.p,
-                         (int64_t)nb, (int64_t)P->n_units, (int64_t)P->batch, P->d_stat.p, skip_ptr, skip_stride);
-      HIPCHK(ctx, hipGetLastError());
-    }
-#ifdef GAT_DBG_QUEUE
-    { unsigned long long w[16]; hipStreamSynchronize(ctx->stream); hipMemcpy(w, P->d_stat.p, 16 * 8, hipMemcpyDeviceToHost);
-      fprintf(stderr, "round broken by: empty segment %llu, placeholder neighbour %llu, both neighbours and more %llu, two on the right %llu, two logged %llu, logged + neighbour %llu\n", w[10], w[11], w[12], w[13], w[14], w[15]); }
-#endif
-    HIPCHK(ctx, hipMemcpyAsync(h_stat, P->d_stat.p, 10 * 8, hipMemcpyDeviceToHost, ctx->stream));   // (word 9: the queue's length)
-    if (defer) return GAT_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return finish_sampler_batch(ctx, P, nb, st, timed, h_stat);
+  {
+    const size_t np = std::max<size_t>(1, P->h_order.size()) * 8;
+    if (P->d_diag_place.n < np) HIPCHK(ctx, P->d_diag_place.alloc(np));
+    HIPCHK(ctx, hipMemsetAsync(P->d_diag_place.p, 0, np * 8, ctx->stream));
+    A.diag_place = P->d_diag_place.p;
+    const size_t nt = std::max<size_t>(1, P->h_order.size()) * (size_t)((B.nb + 63) / 64) * 2;
+    if (P->d_diag_tiles.n < nt) HIPCHK(ctx, P->d_diag_tiles.alloc(nt));
+    HIPCHK(ctx, hipMemsetAsync(P->d_diag_tiles.p, 0, nt * 8, ctx->stream));
+    A.diag_tiles = P->d_diag_tiles.p;
   }
+#endif
+  A.n_active = (int32_t)B.n_act;
+  if (B.smode) {
+    A.rng_off = P->d_rng_off.p; A.rng_rows = P->d_rng_rows.p; A.rng_out = P->d_rng_out.p;
+    A.rng_ckpt = P->d_rng_ckpt.p;
+    A.st = P->d_st.p;
+  }
+  return GAT_OK;
+}
+
+// the one k_place* kernel of a batch: nsb tiles of 64 samples per unit
+static int launch_place(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B, const gat::SamplerArgs& A, unsigned nsb) {
+  const dim3 gp = grid_yz(nsb, B.n_act);
+  // (small calls of a problem of simple units -- about a wave per SIMD or less, e.g. the metric's 10 000 samples cut over
+  //  eight GPUs -- take the wide kernel as well: its loop stores unconditionally and four tiles share a rank table; config 2,
+  //  k_place at 1 250 / 2 500 / 5 000 samples: 0.46 / 0.47 / 0.56 ms against the lean kernel's 0.52 / 0.53 / 0.57, at 10 000
+  //  1.05 against 0.92)
+  const bool small_call = (int64_t)nsb * (int64_t)B.n_act <= 1536 && !gat_opt(ctx, "GAT_PLACE_NO_WIDE");
+  const int mode = P->all_simple ? ((gat_opt(ctx, "GAT_PLACE_WIDE") || small_call) ? 3 : 1)
+                                 : (P->all_one_ws && !gat_opt(ctx, "GAT_PLACE_NO_WIDE") ? 3 : (P->max_nws > gat::kPlaceWsLds ? 2 : 0));
+  // (k_place_wide: kPlaceWide tiles per workgroup, the largest unit's rank table beside their rings)
+  const dim3 gw = grid_yz((nsb + gat::kPlaceWide - 1) / gat::kPlaceWide, B.n_act);
+  const size_t lds_wide = (size_t)P->max_hist * 4;
+  // calls of a few hundred tiles of a problem of simple units: one stream walked by the 64 lanes of a wave (k_place_scan:
+  // a stream's states as a prefix scan over its rows) instead of one lane walking it row by row -- the chain of the longest
+  // unit's tile, 0.37 ms on config 2 whatever the sample count, is what such a call waited for
+  const char* env_scan = gat_opt(ctx, "GAT_PLACE_SCAN_TILES");
+  const int64_t scan_tiles = env_scan ? atoll(env_scan) : 768;      // (config 2: faster up to ~2 300 samples x 24 units per call)
+  const bool scan = P->sampler == GAT_SAMPLER_ANNOTATOR && P->all_simple && P->all_cm_ok && A.place_plain_step == 0 &&
+                    (int64_t)nsb * (int64_t)B.n_act <= scan_tiles;
+  if (scan) {
+    const int64_t n_tiles = (int64_t)nsb * B.n_act;
+    const unsigned nblocks = (unsigned)(((n_tiles + 7) / 8) * 8 * 4);
+    hipLaunchKernelGGL(gat::k_place_scan, dim3(nblocks), dim3(gat::kScanWaves * 64), 0, ctx->stream, A, (int)nsb,
+                       gat_opt(ctx, "GAT_PLACE_SCAN_SEQ") ? 1 : 0);
+  } else if (P->sampler == GAT_SAMPLER_SEGMENTS) {
+    if (mode == 3) {
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_wide<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide));
+      hipLaunchKernelGGL((gat::k_place_wide<1>), gw, dim3(gat::kPlaceWide * 64), lds_wide, ctx->stream, A);
+    } else if (mode == 1) hipLaunchKernelGGL((gat::k_place<1, 1>), gp, dim3(64), 0, ctx->stream, A);
+    else if (mode == 0) hipLaunchKernelGGL((gat::k_place<1, 0>), gp, dim3(64), 0, ctx->stream, A);
+    else hipLaunchKernelGGL((gat::k_place<1, 2>), gp, dim3(64), 0, ctx->stream, A);
+  } else {
+    // (k_place_pipe: the rows of the single-workspace-segment units prefetched by hand, see GAT_PLACE_LOOP_PIPE)
+    const bool pipe = P->pipe_pays && !gat_opt(ctx, "GAT_PLACE_NO_PIPE");
+    const bool rank_fits = P->max_hist < (uint32_t)gat::kPlaceRankLds;
+    // fragmented workspaces: the cdf grids of the long workspaces in LDS, eight tiles of a unit per workgroup (k_place_grid);
+    // static LDS: the workspace and rank tables (4 KB each) and an 8 KB ring per tile
+    const size_t lds_grid = (size_t)P->grid_lds_words * 4 + 16;
+    const bool grid_k = mode == 2 && P->grid_place && (int64_t)lds_grid + 8192 + 1024 + (int64_t)gat::kPlaceGridTiles * 8192 <= ctx->max_lds;
+    if (grid_k) {
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_grid));
+      hipLaunchKernelGGL(gat::k_place_grid, grid_yz((nsb + gat::kPlaceGridTiles - 1) / gat::kPlaceGridTiles, B.n_act),
+                         dim3(gat::kPlaceGridTiles * 64), lds_grid, ctx->stream, A);
+    } else if (mode == 3) {
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_wide<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide));
+      hipLaunchKernelGGL((gat::k_place_wide<0>), gw, dim3(gat::kPlaceWide * 64), lds_wide, ctx->stream, A);
+    } else if (mode == 1 && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 1>), gp, dim3(64), 0, ctx->stream, A);
+    else if (mode == 1) hipLaunchKernelGGL((gat::k_place<0, 1>), gp, dim3(64), 0, ctx->stream, A);
+    else if (mode == 0 && P->small_tables && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0, 1>), gp, dim3(64), 0, ctx->stream, A);
+    else if (mode == 0 && P->small_tables) hipLaunchKernelGGL((gat::k_place<0, 0, 1>), gp, dim3(64), 0, ctx->stream, A);
+    else if (mode == 0 && P->max_nws <= 64 && rank_fits && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0, 2>), gp, dim3(64), 0, ctx->stream, A);
+    else if (mode == 0 && P->max_nws <= 64) hipLaunchKernelGGL((gat::k_place<0, 0, 2>), gp, dim3(64), 0, ctx->stream, A);
+    else if (mode == 0 && rank_fits && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0>), gp, dim3(64), 0, ctx->stream, A);
+    else if (mode == 0) hipLaunchKernelGGL((gat::k_place<0, 0>), gp, dim3(64), 0, ctx->stream, A);
+    else hipLaunchKernelGGL((gat::k_place<0, 2>), gp, dim3(64), 0, ctx->stream, A);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return GAT_OK;
+}
+
+// The lane-parallel front end: the streams (k_seed, k_rng) and every placement up to the first consolidation (k_place*).  The
+// scratch was sized for P->batch samples, tiles are laid out for that.
+static int enqueue_front_end(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B, const gat::SamplerArgs& A) {
+  const unsigned nsb = (unsigned)((B.nb + 63) / 64);
+  // the streams' seeding chains at full occupancy, 16 checkpoints each; k_rng's waves regenerate the rest
+  const int64_t n_tiles = (int64_t)nsb * B.n_act, per_block = gat::kSeedThreads / gat::kWave;
+  hipLaunchKernelGGL(gat::k_seed, dim3((unsigned)((n_tiles + per_block - 1) / per_block)), dim3(gat::kSeedThreads), 0, ctx->stream,
+                     A, (int)nsb);
+  HIPCHK(ctx, hipGetLastError());
+  const size_t lds_rng = (size_t)gat::kMtN * 64 * 4;
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_rng, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rng));
+  hipLaunchKernelGGL(gat::k_rng, grid_yz(nsb, B.n_act), dim3(gat::kRngThreads), lds_rng, ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[0], ctx->stream));
+  const int rc = launch_place(ctx, P, B, A, nsb);
+  if (rc) return rc;
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[1], ctx->stream));
+  return GAT_OK;
+}
+
+// The long-list chain (B.merge_big): k_merge_big per size class, then -- without the split path -- k_tail_big, k_resume_big and
+// k_queue_rest.  Adds to A what k_sampler (and the split path) read of it: st2 / n_long, k_tail_big's records, the queue.
+static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, gat::SamplerArgs& A) {
+  const unsigned n_long = B.n_long;
+  gat::SamplerArgs M = A;
+  M.st2 = P->d_st2.p; M.n_long = (int32_t)n_long;
+  M.big_buckets = B.nbk;
+  M.cum = B.split ? P->d_cum.p : nullptr;
+  // (the form by the class's longest list: 8, 16 or 24 elements of it in every thread's registers; 0 = round 3's form,
+  //  the list read twice and sorted bucket by bucket)
+  typedef void (*merge_fn)(gat::SamplerArgs);
+  static const merge_fn kMergeFns[2][4] = {
+      {gat::k_merge_big<false, 0>, gat::k_merge_big<false, 8>, gat::k_merge_big<false, 16>, gat::k_merge_big<false, gat::kMergeRegs>},
+      {gat::k_merge_big<true, 0>, gat::k_merge_big<true, 8>, gat::k_merge_big<true, 16>, gat::k_merge_big<true, gat::kMergeRegs>}};
+  const merge_fn* fns = kMergeFns[B.tree ? 1 : 0];
+  const bool merge_old = gat_opt(ctx, "GAT_MERGE_OLD") != nullptr;
+  for (int f = 0; f < 4; ++f)
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)fns[f], hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.lds_merge));
+  for (size_t c = 0; c + 1 < P->h_class_start.size() && (unsigned)P->h_class_start[c] < n_long; ++c) {
+    // one launch per size class: LDS for the class's longest list and its histogram
+    const int a0 = P->h_class_start[c], a1 = std::min<int>(P->h_class_start[c + 1], (int)n_long);
+    // LDS for what the class's longest unit is EXPECTED to have placed at its first consolidation, not for its slab
+    // region (a quarter + 96 above the unit's segments): the count of placements is the unit's segments +- a
+    // renewal count's spread, cv(length) x sqrt(n) -- 90 for 8 000 segments -- so a twelfth + 64 on top is seven of
+    // those; a list beyond it takes k_sampler's own (slow) way.  And as many histogram buckets (a power of two, at
+    // least 1 024: a few elements per bucket sort as fast as one) as leave the number of workgroups a CU can hold
+    // at its maximum: this kernel is a chain of dependent passes, and chr1's 8 000 segments with 8 192 buckets were
+    // 113 KB -- ONE workgroup per CU for the classes that take most of its time (config-4 shape: 22.9 of 27.4 ms)
+    const int n0 = (int)P->h_units[(size_t)P->h_order[(size_t)a0]].hist_total;
+    const int ccap = std::min<int>(P->h_units[(size_t)P->h_order[(size_t)a0]].slab_cap, (n0 + n0 / 12 + 64 + 63) / 64 * 64);
+    auto wgs_at = [&](int nbk_) { return (int)(((size_t)ctx->max_lds) / ((size_t)2 * ccap * 4 + (size_t)(nbk_ + 1) * 4 + 1024)); };
+    int cnbk = 8192;
+    while (cnbk > 1024 && (cnbk / 2 >= ccap || wgs_at(cnbk) < wgs_at(1024))) cnbk >>= 1;
+    size_t lds_k = (size_t)2 * ccap * 4 + (size_t)(cnbk + 1) * 4;
+    const int per = (ccap + gat::kMergeThreads - 1) / gat::kMergeThreads;
+    const int form = merge_old || per > gat::kMergeRegs ? 0 : (per <= 8 ? 1 : (per <= 16 ? 2 : 3));
+    if (form > 0) {
+      // (the register forms: the histogram shares the list's LDS -- up to about a bucket per element)
+      int maxb = 8192;
+      if (const char* e = gat_opt(ctx, "GAT_MERGE_BUCKETS")) maxb = std::max(1024, atoi(e));
+      cnbk = 1024;
+      while (2 * cnbk + gat::kMergeThreads + 1 <= ccap && 2 * cnbk <= maxb) cnbk <<= 1;     // (+ a word of padding per thread)
+      lds_k = ((size_t)ccap + (size_t)std::max(ccap, cnbk + gat::kMergeThreads + 1)) * 4;   // (short lists: the 1 024 buckets and their padding need their own words)
+    }
+    M.a_base = a0; M.a_end = a1; M.lds_cap = ccap; M.big_buckets = cnbk;
+    hipLaunchKernelGGL(fns[form], grid_yz((unsigned)B.nb, (unsigned)(a1 - a0)), dim3(gat::kMergeThreads), lds_k, ctx->stream, M);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  A.st2 = P->d_st2.p; A.n_long = (int32_t)n_long;       // (k_sampler reads st2 for those units only)
+  if (!B.tail_big) return GAT_OK;
+  // the placement rounds behind that consolidation, one stream per lane; k_sampler resumes at the trim
+  gat::TailArgs TB;
+  TB.S = A;
+  TB.cum = nullptr; TB.patch = P->d_patch.p; TB.todo = nullptr; TB.todo_count = nullptr;
+  // (counts alone, by k_count_merged -- or through k_contig, which merge(0)s the lists again: what a trim emptied may
+  //  stay in the list as [0, 0))
+  TB.loose_ok = (B.o.loose_ok && !B.o.need_unit_lists && !gat_opt(ctx, "GAT_RESUME_COMPACT")) ? 1 : 0;
+  // (bit 0: no bridge between two neighbours, bit 1: none over two segments on the right; "1" or anything else: both off)
+  TB.no_bridge = 0;
+  if (const char* e = gat_opt(ctx, "GAT_TB_NO_BRIDGE")) { const int v = atoi(e); TB.no_bridge = (v == 2 || v == 5) ? (v == 2 ? 2 : 1) : 3; }
+  TB.no_log_map = gat_opt(ctx, "GAT_TB_NO_LOG_MAP") ? 1 : 0;
+  hipLaunchKernelGGL(gat::k_tail_big, grid_yz((unsigned)((B.nb + 63) / 64), n_long), dim3(64), 0, ctx->stream, TB);
+  HIPCHK(ctx, hipGetLastError());
+  if (B.resume_big) {
+    // ... and the rest of the unit -- log inserted, trim, final filter -- with the list where it is
+    // (a reader that takes the segments one by one in any order -- k_count_merged on the units' lists, no contig lists
+    //  in between --: the log stays behind the merged list, the trim works on virtual indices)
+    const bool virt = TB.loose_ok && !P->merge_contigs && !gat_opt(ctx, "GAT_RESUME_INSERT");
+    hipLaunchKernelGGL(virt ? gat::k_resume_big<true> : gat::k_resume_big<false>, grid_yz((unsigned)B.nb, n_long), dim3(64), 0, ctx->stream, TB);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  A.tb = reinterpret_cast<const int32_t*>(P->d_patch.p);
+  A.skip_stride = (int32_t)(sizeof(gat::TailPatch) / 4);
+  if (B.long_queue) {
+    // k_sampler behind them works off a queue: launched over every (sample, unit) -- one or two waves a CU with such
+    // lists in LDS -- it took 3.1 ms per 12 500 samples of the config-4 shape to find every unit finished
+    TB.todo = P->d_todo.p; TB.todo_count = P->todo_count_dev();
+    const int64_t tot = (int64_t)B.nb * B.n_act;
+    hipLaunchKernelGGL(gat::k_queue_rest, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, TB, (int)B.n_act);
+    HIPCHK(ctx, hipGetLastError());
+    A.todo = P->d_todo.p; A.todo_count = P->todo_count_dev();
+  }
+  return GAT_OK;
+}
+
+// The split path: first consolidation (k_consolidate, wave per unit), the loop's tail (k_tail, lane per unit), the final list
+// (k_finalize, wave per unit) unless the batch's consumer takes (merged list, k_tail's record) -- decided here, for k_contig and
+// the count kernels: P->patched_contigs / units_direct / patched_counts.  k_sampler then only resumes -- from the merged list,
+// off the queue added to A -- the units k_tail left alone.
+static int enqueue_split_path(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, gat::SamplerArgs& A) {
+  const int64_t nb = B.nb;
+  gat::TailArgs T;
+  T.S = A;
+  T.loose_ok = 0; T.no_bridge = 0; T.no_log_map = 0;
+  T.S.st2 = P->d_st2.p;
+  T.S.n_long = (int32_t)(B.merge_big ? B.n_long : 0);         // (the launch positions k_merge_big was given, whose verdict k_consolidate respects)
+  T.S.lds_cap = std::min(P->max_unit_cap, 1280);              // k_consolidate: the lists the wave bucket sorts take
+  T.S.slab_final = P->d_fslab.p;
+  T.cum = P->d_cum.p; T.patch = P->d_patch.p;
+  T.todo = P->d_todo.p;
+  T.todo_count = P->todo_count_dev();                         // (zeroed with the statistics at the batch's start)
+  const size_t lds_max = (size_t)(gat::kSortScratchWords + 2 * (size_t)T.S.lds_cap) * 4;
+  void (*const consolidate)(gat::TailArgs) = B.tree ? gat::k_consolidate<true> : gat::k_consolidate<false>;
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)consolidate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+  // (a call of a few hundred tiles does not fill the chip whatever the LDS of a workgroup: one launch for all classes,
+  //  each launch less is a tail less -- config 2 at 1 250 samples: k_consolidate 0.121 -> 0.101 ms)
+  const bool one_class = (int64_t)((nb + 63) / 64) * (int64_t)B.n_act <= 1024 && !gat_opt(ctx, "GAT_SIZE_CLASSES");
+  for (size_t c = 0; c + 1 < P->h_class_start.size(); ++c) {
+    // one launch per size class, its LDS sized for the class's longest list
+    if (one_class && c > 0) break;
+    const int a0 = P->h_class_start[c], a1 = one_class ? P->h_class_start.back() : P->h_class_start[c + 1];
+    // (as for k_merge_big: LDS for what the class's longest unit is expected to have placed -- its segments +- a renewal
+    //  count's spread -- not for its slab region; the rare list beyond it is k_sampler's.  GAT_CONSOLIDATE_SLAB_LDS: the old size)
+    const int n0 = (int)P->h_units[(size_t)P->h_order[(size_t)a0]].hist_total;
+    const int tight = gat_opt(ctx, "GAT_CONSOLIDATE_SLAB_LDS") ? INT32_MAX : (n0 + n0 / 12 + 64 + 31) / 32 * 32;
+    const int ccap = std::min(std::min(P->h_units[(size_t)P->h_order[(size_t)a0]].slab_cap, T.S.lds_cap), tight);
+    gat::TailArgs C = T;
+    C.S.a_base = a0; C.S.a_end = a1; C.S.lds_cap = ccap;
+    const size_t lds_c = (size_t)(gat::kSortScratchWords + 2 * (size_t)ccap) * 4;
+    hipLaunchKernelGGL(consolidate, grid_yz((unsigned)nb, (unsigned)(a1 - a0)), dim3(64), lds_c, ctx->stream, C);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], ctx->stream));
+  const bool long_ws = P->tail_long_ws && P->max_nws > gat::kTailMaxWs;
+  hipLaunchKernelGGL(long_ws ? gat::k_tail<true> : gat::k_tail<false>, grid_yz((unsigned)((nb + 63) / 64), B.n_act), dim3(64), 0, ctx->stream, T);
+  HIPCHK(ctx, hipGetLastError());
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_t[0], ctx->stream));
+  // isochore problems: k_contig re-sorts the units of a contig anyway and takes (merged list, k_tail's record) as
+  // it is -- no final unit lists unless somebody asked for them (gat_sample_units)
+  P->patched_contigs = P->merge_contigs && P->n_contigs > 0 && !B.o.need_unit_lists && !gat_opt(ctx, "GAT_CONTIG_FINAL_LISTS");
+  P->units_direct = B.o.units_direct && P->patched_contigs && P->units_direct_ok && B.o.serial_state == nullptr;
+  P->patched_counts = !P->merge_contigs && B.o.records_ok && !B.o.need_unit_lists;
+  if (!P->patched_contigs && !P->patched_counts) hipLaunchKernelGGL(gat::k_finalize, grid_yz((unsigned)nb, B.n_act), dim3(64), 0, ctx->stream, T);
+  HIPCHK(ctx, hipGetLastError());
+  if (B.timed) { HIPCHK(ctx, hipEventRecord(ctx->ev_t[1], ctx->stream)); ctx->t_recorded = true; }
+  A.st2 = P->d_st2.p; A.n_long = (int32_t)B.n_act;
+  A.slab_final = P->d_fslab.p;
+  A.skip = &P->d_patch.p->state;
+  A.skip_stride = (int32_t)(sizeof(gat::TailPatch) / 4);
+  A.todo = P->d_todo.p; A.todo_count = P->todo_count_dev();
+  return GAT_OK;
+}
+
+// k_sampler / k_serial by variant: sampler kind x (long lists: counting-sort scratch) x (workspaces beyond the register loop:
+// search trees) -- 0..3 SamplerAnnotator, 4 / 5 SamplerSegments, 6 / 7 lists beyond LDS -- and 8, k_sampler's alone: variant 0
+// with registers for 5 waves per SIMD
+typedef void (*sampler_fn)(gat::SamplerArgs);
+static const sampler_fn kSamplerFns[9] = {
+    gat::k_sampler<0, false, false, false>, gat::k_sampler<0, false, true, false>, gat::k_sampler<0, true, false, false>,
+    gat::k_sampler<0, true, true, false>, gat::k_sampler<1, false, false, false>, gat::k_sampler<1, false, true, false>,
+    gat::k_sampler<0, false, false, true>, gat::k_sampler<0, false, true, true>, gat::k_sampler<0, false, false, false, 5>};
+static const sampler_fn kSerialFns[8] = {
+    gat::k_serial<0, false, false, false>, gat::k_serial<0, false, true, false>, gat::k_serial<0, true, false, false>,
+    gat::k_serial<0, true, true, false>, gat::k_serial<1, false, false, false>, gat::k_serial<1, false, true, false>,
+    gat::k_serial<0, false, false, true>, gat::k_serial<0, false, true, true>};
+
+// k_sampler over what the stages in front of it left it (everything, without them) -- or k_serial: the reference's own stream
+static int enqueue_sampler(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B, const gat::SamplerArgs& A) {
+  const int64_t nb = B.nb;
+  int variant = P->sampler == GAT_SAMPLER_SEGMENTS ? (B.tree ? 5 : 4)
+              : B.huge ? (B.tree ? 7 : 6) : (B.long_lists ? 2 : 0) + (B.tree ? 1 : 0);
+  // short lists only (20 waves of this kernel fit a CU's LDS): the instantiation with registers for 5 waves per SIMD
+  if (variant == 0 && (int64_t)B.lds * 20 <= ctx->max_lds && !gat_opt(ctx, "GAT_NO_WPE5")) variant = 8;
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)kSamplerFns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.lds));
+  auto launch_sampler = [&](const dim3& gs, size_t lds_, const gat::SamplerArgs& K) {
+    hipLaunchKernelGGL(kSamplerFns[variant], gs, dim3(64), lds_, ctx->stream, K);
+  };
+  const dim3 off_queue((unsigned)std::min<int64_t>((int64_t)nb * B.n_act, 8192));
+  const bool list_in_lds = !B.huge && P->sampler != GAT_SAMPLER_SEGMENTS;
+  if (B.o.serial_state != nullptr) {
+    // the reference's own stream: one wave, every (sample, unit) of the batch in order
+    gat::SamplerArgs K = A;
+    K.serial_state = B.o.serial_state; K.unit_pos = P->d_unit_pos.p;
+    const sampler_fn serial = kSerialFns[variant == 8 ? 0 : variant];
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)serial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.lds));
+    hipLaunchKernelGGL(serial, dim3(1), dim3(64), B.lds, ctx->stream, K);
+  } else if (B.split) {
+    launch_sampler(off_queue, B.lds, A);
+  } else if (list_in_lds && A.big_buckets == 0 && P->h_class_start.size() > 2 &&
+             !(A.todo_count != nullptr && P->max_nws <= gat::kWsTreeMin && !gat_opt(ctx, "GAT_SIZE_CLASSES"))) {
+    // (not behind k_resume_big where it takes every unit -- workspaces of up to 32 segments --: the queue then holds the
+    //  per cent of units it declined, and one launch runs them side by side where five ran them class after class)
+    // one launch per size class: LDS for the class's longest list
+    for (size_t c = 0; c + 1 < P->h_class_start.size(); ++c) {
+      const int a0 = P->h_class_start[c], a1 = P->h_class_start[c + 1];
+      const int ccap = P->h_units[(size_t)P->h_order[(size_t)a0]].slab_cap;
+      gat::SamplerArgs K = A;
+      K.a_base = a0; K.a_end = a1;
+      const unsigned cnt = (unsigned)(a1 - a0);
+      // (off the queue -- long lists behind k_resume_big --: a one-dimensional launch, every class takes its own entries)
+      const dim3 gc = A.todo_count != nullptr ? dim3((unsigned)std::min<int64_t>((int64_t)nb * cnt, 8192)) : grid_yz((unsigned)nb, cnt);   // (8 192: what is left is a few long units, one to a workgroup)
+      launch_sampler(gc, (size_t)(gat::kMtLdsWords + 2 * (size_t)ccap) * 4, K);
+    }
+  } else if (A.todo_count != nullptr) {
+    launch_sampler(off_queue, B.lds, A);
+  } else {
+    launch_sampler(grid_yz((unsigned)nb, B.n_act), B.lds, A);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return GAT_OK;
+}
+
+// SamplerAnnotator / SamplerSegments: the stages the plan names in front of k_sampler, then k_sampler (or k_serial).  A is left
+// as k_sampler saw it: k_reduce_stats reads from it which units k_tail finished / k_tail_big carried on.
+static int enqueue_placement_sampler(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin, gat::SamplerArgs& A) {
+  int rc = base_sampler_args(ctx, P, B, seed, begin, A);
+  if (!rc && B.smode) rc = enqueue_front_end(ctx, P, B, A);
+  if (rc) return rc;
+  ctx->k_recorded = B.timed && B.smode;
+  A.lds_cap = P->max_unit_cap;           // (the list kernels' fields: the front end reads neither)
+  A.big_buckets = B.big_buckets;
+  if (B.merge_big && (rc = enqueue_long_lists(ctx, P, B, A))) return rc;
+  P->split_ran = B.split;
+  if (B.split) rc = enqueue_split_path(ctx, P, B, A);
+  else if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], ctx->stream));
+  if (!rc) rc = enqueue_sampler(ctx, P, B, A);
+  if (rc) return rc;
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[3], ctx->stream));
+  return GAT_OK;
+}
+
+// fromIsochores: the units' lists of a contig united into the contig's list (k_contig<HUGE, NOSORT>), one launch per size class
+typedef void (*contig_fn)(gat::ContigArgs);
+static const contig_fn kContigFns[2][2] = {{gat::k_contig<false>, gat::k_contig<true>},                 // [nosort][huge]
+                                           {gat::k_contig<false, true>, gat::k_contig<true, true>}};
+static int enqueue_contigs(gat_ctx* ctx, gat_problem* P, int64_t nb) {
+  gat::ContigArgs B;
+  B.contig_unit_off = P->d_contig_unit_off.p; B.contig_units = P->d_contig_units.p; B.units = P->d_units.p;
+  B.cu_rec = P->d_cu_rec.p;
+  B.contig_slab_off = P->d_contig_slab_off.p; B.n_units = P->n_units; B.n_contigs = P->n_contigs;
+  B.slab_in = P->final_slab(); B.slab_out = P->d_cslab.p; B.slab_stride = P->slab_stride;
+  B.unit_n = P->d_unit_n.p; B.contig_n = P->d_contig_n.p; B.stat = P->d_stat.p;
+  B.slab_merged = nullptr; B.unit_pos = P->d_unit_pos.p; B.st2 = nullptr; B.patch = nullptr; B.patch_stride = 0;
+  B.ws_stat = P->d_ws_stat.p;
+  B.rec_stride = (int32_t)P->batch;
+  if (P->split_ran && P->patched_contigs) {
+    B.slab_merged = P->d_slab.p;
+    B.st2 = P->d_st2.p;
+    B.patch = reinterpret_cast<const int32_t*>(P->d_patch.p);
+    B.patch_stride = (int32_t)(sizeof(gat::TailPatch) / 4);
+  }
+  const int need_max = P->h_contig_order.empty() ? 64 : P->h_contig_need[(size_t)P->h_contig_order[0]];
+  size_t lds = (size_t)std::max(64, need_max) * 8 + gat::kSortScratchWords * 4;
+  const bool huge_c = (int64_t)lds > ctx->max_lds || gat_opt(ctx, "GAT_TEST_HUGE") != nullptr;   // list stays in the output slab
+  if (huge_c) lds = gat::kSortScratchWords * 4;
+  // (units_direct: the lists only concatenated, the candidates for k_units_overlap noted: k_contig<., true>)
+  const bool nosort = P->units_direct;
+  B.bmap = P->d_bmap.p; B.bmap_off = P->d_bmap_off.p; B.bshift = P->bshift;
+  B.cand = P->d_cand.p; B.cand_cap = (uint32_t)(P->d_cand.n / gat::kCandSlots); B.cand_count = P->d_cand_count.p;
+  const contig_fn kc = kContigFns[nosort ? 1 : 0][huge_c ? 1 : 0];
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  B.order = P->d_contig_order.p;
+  B.flags = P->flags_dev();
+  // one launch per size class: LDS for the class's longest expected list (more waves per CU for the short contigs)
+  for (size_t k = 0; k + 1 < P->h_contig_class_start.size(); ++k) {
+    const int c0 = P->h_contig_class_start[k], c1 = P->h_contig_class_start[k + 1];
+    // (one launch where the list is put together in place: beyond LDS, or only concatenated)
+    const bool one = huge_c || nosort;
+    if (one && k > 0) break;
+    B.base = one ? 0 : c0;
+    B.count = one ? P->n_contigs : c1 - c0;
+    B.lds_cap = one ? 0 : std::max(64, P->h_contig_need[(size_t)P->h_contig_order[(size_t)c0]]);
+    const size_t lds_k = nosort ? 64 : (huge_c ? lds : (size_t)B.lds_cap * 8 + gat::kSortScratchWords * 4);
+    hipLaunchKernelGGL(kc, grid_yz((unsigned)nb, (unsigned)B.count), dim3(64), lds_k, ctx->stream, B);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  return GAT_OK;
+}
+
+// One batch as the sequence of its stages: scratch and statistics reset, the units' sampler, fromIsochores, the statistics and
+// -- unless deferred -- the synchronisation and the batch's checks.
+static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t begin, int64_t nb,
+                             gat_stats* st, bool timed, const BatchOpts& o = BatchOpts()) {
+  unsigned long long* h_stat = o.h_stat != nullptr ? o.h_stat : ctx->h_stat;
+  P->units_direct = false;
+  int rc = ensure_scratch(ctx, P, nb);
+  if (rc) return rc;
+  if (P->batch < nb) return set_err(ctx, GAT_ERR_MEMORY, "internal: batch %lld > scratch %lld", (long long)nb, (long long)P->batch);
+  // (unit_n, contig_n and ws_stat are zeroed once when allocated: the kernels rewrite every entry of the active units
+  //  in every batch and never touch the others)
+#ifdef GAT_DBG_QUEUE
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 16 * 8, ctx->stream));
+#else
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 10 * 8, ctx->stream));
+#endif         // (statistics, status word, k_tail's queue length)
+  if (o.units_direct && P->d_cand_count.n) HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, P->d_cand_count.n * 4, ctx->stream));
+  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+  gat::SamplerArgs A = {};                 // (SamplerAnnotator / SamplerSegments: what k_sampler saw)
+  if (!P->h_order.empty()) {
+    // (what a stage records or leaves in place of final lists, it says itself)
+    ctx->k_recorded = ctx->t_recorded = false;
+    P->split_ran = P->patched_contigs = P->patched_counts = false;
+    const BatchPlan B = plan_batch(ctx, P, nb, timed, o);
+    if (P->sampler == GAT_SAMPLER_SHIFT) rc = enqueue_shift(ctx, P, B, seed, begin);
+    else if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) rc = enqueue_permute(ctx, P, B, seed, begin);
+    else rc = enqueue_placement_sampler(ctx, P, B, seed, begin, A);
+    if (rc) return rc;
+  }
+  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+  if (P->merge_contigs && P->n_contigs > 0 && (rc = enqueue_contigs(ctx, P, nb))) return rc;
+  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  if (!P->h_order.empty()) {
+    // (behind k_contig: on isochore problems it is k_contig that writes the statistics of the units k_tail finished)
+    const int32_t* skip_ptr = A.skip != nullptr ? A.skip : A.tb;     // (n_tail_units: finished by k_tail / carried on by k_tail_big)
+    hipLaunchKernelGGL(gat::k_reduce_stats, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)P->d_ws_stat.p,
+                       (int64_t)nb, (int64_t)P->n_units, (int64_t)P->batch, P->d_stat.p, skip_ptr, A.skip_stride);
+    HIPCHK(ctx, hipGetLastError());
+  }
+#ifdef GAT_DBG_QUEUE
+  { unsigned long long w[16]; hipStreamSynchronize(ctx->stream); hipMemcpy(w, P->d_stat.p, 16 * 8, hipMemcpyDeviceToHost);
+    fprintf(stderr, "round broken by: empty segment %llu, placeholder neighbour %llu, both neighbours and more %llu, two on the right %llu, two logged %llu, logged + neighbour %llu\n", w[10], w[11], w[12], w[13], w[14], w[15]); }
+#endif
+  HIPCHK(ctx, hipMemcpyAsync(h_stat, P->d_stat.p, 10 * 8, hipMemcpyDeviceToHost, ctx->stream));   // (word 9: the queue's length)
+  if (o.defer) return GAT_OK;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return finish_sampler_batch(ctx, P, nb, st, timed, h_stat);
 }
 
 // the checks and statistics of a sampler batch whose kernels have completed (the stream has been synchronised)
@@ -1303,8 +1324,12 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
         HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, (gat::kCandSlots + 4) * 4, ctx->stream));
       }
     }
-    if ((rc = run_sampler_batch(ctx, P, K.seed, K.begin + K.enq, nb, &K.local, K.timed, false, true, records_ok, d_state, loose_ok,
-                                K.blk->h_stat + (size_t)slot * 16, units_direct))) return rc;   // (enqueued only)
+    BatchOpts o;
+    o.defer = true;                      // (enqueued only)
+    o.records_ok = records_ok; o.loose_ok = loose_ok; o.units_direct = units_direct;
+    o.serial_state = d_state;
+    o.h_stat = K.blk->h_stat + (size_t)slot * 16;
+    if ((rc = run_sampler_batch(ctx, P, K.seed, K.begin + K.enq, nb, &K.local, K.timed, o))) return rc;
     K.nb[slot] = nb;
     K.main_rec[slot] = false;
     K.count_kernel[slot] = GAT_COUNT_KERNEL_NONE;
@@ -1503,7 +1528,9 @@ static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sam
     if ((rc = ensure_scratch(ctx, P, S - done))) return rc;
     const int64_t nb = std::min<int64_t>(P->batch, S - done);
     // (timed unless another problem's call in flight owns the context's per-kernel events)
-    if ((rc = run_sampler_batch(ctx, P, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr, unit_level)) == kRelayout) continue;
+    BatchOpts o;
+    o.need_unit_lists = unit_level;
+    if ((rc = run_sampler_batch(ctx, P, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr, o)) == kRelayout) continue;
     if (rc) return rc;
     const bool from_contigs = P->merge_contigs && !unit_level;
     const uint2* src = from_contigs ? P->d_cslab.p : P->final_slab();
