@@ -10,7 +10,7 @@ import numpy as np
 from . import intervals, problem, synthetic            # noqa: F401
 from . import io as IO                                   # noqa: F401
 from . import stats as Stats                             # noqa: F401
-from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation,  # noqa: F401
+from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation,  # noqa: F401
                      Counter, computeCountsAll, overlap_sizes, CounterNucleotideOverlap, CounterNucleotideDensity, CounterSegmentOverlap,
                      CounterSegmentMidpointOverlap, CounterAnnotationOverlap, CounterAnnotationMidpointOverlap,
                      UnconditionalWorkspace, ConditionalWorkspaceCooccurance, ConditionalWorkspaceCentered,
@@ -458,14 +458,16 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
             dist.broadcast_object_list(box, src=0)
             seed = int(box[0])
     conditional = getattr(workspace_generator, "is_conditional", False)
-    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation)):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift and SamplerGlobalPermutation run on "
-                                  "the GPU path")
+    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation)):
+        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation and "
+                                  "SamplerLocalPermutation run on the GPU path")
     mt_state = None
     if reference_stream and isinstance(sampler, SamplerShift):
         raise NotImplementedError("reference_stream: SamplerShift runs on the per-unit streams only")
     if reference_stream and isinstance(sampler, SamplerGlobalPermutation):
         raise NotImplementedError("reference_stream: SamplerGlobalPermutation runs on the per-unit streams only")
+    if reference_stream and isinstance(sampler, SamplerLocalPermutation):
+        raise NotImplementedError("reference_stream: SamplerLocalPermutation runs on the per-unit streams only")
     if reference_stream:
         # the reference's own stream: numpy.random.seed(seed) once (scripts/gat-run.py:267-271), every work unit of every
         # segment track drawing from it in order -- an unpatched reference's table, number for number, at one stream's speed
@@ -644,9 +646,18 @@ def fromCounts(filename):
     return annotator_results
 
 
-def buildParser(usage=None):
+# --sampler choices.  SAMPLERS is what buildParser() offers when it is not told otherwise, and stays as it was: callers and
+# tests rely on a bare buildParser() refusing everything else.  ALL_SAMPLERS adds local-permutation, which reproduces
+# what the reference computes rather than what its docstring describes (DESIGN §5 "k_permute_local"); scripts/gat-run.py
+# asks for it, so the command line takes --sampler=local-permutation.
+SAMPLERS = ("annotator", "segments", "shift", "global-permutation")
+ALL_SAMPLERS = SAMPLERS + ("local-permutation",)
+
+
+def buildParser(usage=None, samplers=SAMPLERS):
     """gat command line parser: the options of the reference's buildParser (gat/__init__.py:54-429)
-    that concern the accelerated path, with the same names, destinations and defaults."""
+    that concern the accelerated path, with the same names, destinations and defaults.  `samplers`: the choices of
+    --sampler (SAMPLERS, or ALL_SAMPLERS as scripts/gat-run.py passes)."""
     import optparse
     parser = optparse.OptionParser(version="%prog (gat_amd " + __version__ + ")", usage=usage)
     g = optparse.OptionGroup(parser, "Input options")
@@ -693,7 +704,7 @@ def buildParser(usage=None):
     parser.add_option_group(g)
     g = optparse.OptionGroup(parser, "Sampling algorithm options")
     g.add_option("-c", "--counter", dest="counters", type="choice", action="append", choices=tuple(COUNTERS.keys()))
-    g.add_option("-m", "--sampler", dest="sampler", type="choice", choices=("annotator", "segments", "shift", "global-permutation"))
+    g.add_option("-m", "--sampler", dest="sampler", type="choice", choices=tuple(samplers))
     g.add_option("--shift-extension", dest="shift_extension", type="float",
                  help="if the sampling method is 'shift', the size of the region around a segment's midpoint it is shifted "
                       "within (0: use --shift-expansion) [default=%default]")
@@ -770,6 +781,8 @@ def fromSegments(options, args=None):
         sampler = SamplerShift(radius=options.shift_expansion, extension=options.shift_extension)   # scripts/gat-run.py:129-132
     elif options.sampler == "global-permutation":
         sampler = SamplerGlobalPermutation()             # scripts/gat-run.py:137-138
+    elif options.sampler == "local-permutation":
+        sampler = SamplerLocalPermutation()              # scripts/gat-run.py:135-136
     else:
         raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
     counters = []

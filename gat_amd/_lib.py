@@ -37,7 +37,7 @@ SYMBOLS = [
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
 # gat_problem_desc::sampler (GAT_SAMPLER_*)
-SAMPLER_ANNOTATOR, SAMPLER_SEGMENTS, SAMPLER_SHIFT, SAMPLER_GLOBAL_PERMUTATION = 0, 1, 2, 3
+SAMPLER_ANNOTATOR, SAMPLER_SEGMENTS, SAMPLER_SHIFT, SAMPLER_GLOBAL_PERMUTATION, SAMPLER_LOCAL_PERMUTATION = 0, 1, 2, 3, 4
 
 
 def mt19937_seed(seed):

@@ -361,6 +361,15 @@ struct gat_problem {
   DevBuf<uint32_t> d_perm_len;
   DevBuf<uint2> d_perm_w;
   DevBuf<uint32_t> d_perm_cum;
+  // GAT_SAMPLER_LOCAL_PERMUTATION: per unit {offset into d_lperm_piece, active pieces, offset into d_lperm_len, sum of the
+  // pieces' n (draw groups)}; per active workspace piece, in order, {first working segment (index into the unit's list), n,
+  // work_end, free} (work_start is 0: gat_local_permute.h); the lengths of the unit's segments, unfiltered, in list order --
+  // a piece's working segments are a contiguous run of them
+  DevBuf<uint4> d_lperm_unit;
+  DevBuf<uint4> d_lperm_piece;
+  DevBuf<uint32_t> d_lperm_len;
+  int32_t lperm_max_n = 0;               // ... the most working segments of one piece, the longest raw list (sum of 2n) of a unit
+  int64_t lperm_max_out = 0;
   gat_annotations* anno = nullptr;       // the annotation tables: its own (made from the lists of its desc) or a shared object
   // per-batch scratch
   int64_t batch = 0;

@@ -30,6 +30,7 @@
 #include "gat_tail.h"
 #include "gat_shift.h"
 #include "gat_permute.h"
+#include "gat_local_permute.h"
 #include "gat_stats.h"
 
 
@@ -567,6 +568,27 @@ static int enqueue_permute(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uin
                               (size_t)(gat::kMtLdsWords + ((H.lds_cap + 1) & ~1) + 2 * (size_t)H.lds_cap) * 4);
 }
 
+// SamplerLocalPermutation: k_permute_local
+static int enqueue_permute_local(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
+  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerLocalPermutation has no reference-stream mode");
+  gat::LocalPermuteArgs H;
+  memset(&H, 0, sizeof(H));
+  // (LDS for the lengths and points of the largest piece, up to 2 048 working segments, and -- the same words -- for the final
+  //  list of up to 2 048 pieces: 3 KB for a fragmented workspace of one or two segments per piece, where the kernel is the
+  //  chain of the pieces' draws and the waves a CU holds are what hides it; 27 KB at most.  A larger piece keeps its arrays
+  //  in the slab, a longer list is sorted and merged there)
+  H.lds_cap = std::max(64, std::min(P->lperm_max_n, 2048));
+  const int32_t words = std::max<int32_t>(((H.lds_cap + 1) & ~1) + 2 * H.lds_cap, 2 * (int32_t)std::min<int64_t>(P->lperm_max_out, 2048));
+  H.list_cap = words / 2;
+  H.lp_unit = P->d_lperm_unit.p; H.lp_piece = P->d_lperm_piece.p; H.lp_len = P->d_lperm_len.p;
+  // (GAT_LPERM_SIMPLE: one piece per wave step throughout, the A/B of the batched small-piece path;
+  //  GAT_EXP_LPERM_NO_NORMALIZE: a timing experiment with wrong results -- no final sort and merge, empty lists)
+  H.simple = gat_opt(ctx, "GAT_LPERM_SIMPLE") ? 1 : 0;
+  H.no_normalize = gat_opt(ctx, "GAT_EXP_LPERM_NO_NORMALIZE") ? 1 : 0;
+  return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_permute_local, H,
+                              (size_t)(gat::kMtLdsWords + 2 * gat::kLpBatchDraws + words) * 4);
+}
+
 // the arguments every kernel of SamplerAnnotator / SamplerSegments starts from
 static int base_sampler_args(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin, gat::SamplerArgs& A) {
   memset(&A, 0, sizeof(A));
@@ -983,6 +1005,7 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_
     const BatchPlan B = plan_batch(ctx, P, nb, timed, o);
     if (P->sampler == GAT_SAMPLER_SHIFT) rc = enqueue_shift(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) rc = enqueue_permute(ctx, P, B, seed, begin);
+    else if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) rc = enqueue_permute_local(ctx, P, B, seed, begin);
     else rc = enqueue_placement_sampler(ctx, P, B, seed, begin, A);
     if (rc) return rc;
   }
@@ -1012,6 +1035,9 @@ static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, int64_t nb, gat_st
     int rc;
     const int32_t flags = *reinterpret_cast<const int32_t*>(h_stat + 8);
     const unsigned long long* stat = h_stat;
+    if (flags & gat::kStatusCoordRange)
+      return set_err(ctx, GAT_ERR_ASSERT, "SamplerLocalPermutation: a sampled coordinate exceeds 2^31 - 1 before it wraps (flags=%d): the reference "
+                                          "raises OverflowError (gat/Engine.pyx:1208, :1212)", flags);
     if (flags & (gat::kStatusAssert | gat::kStatusTrimAssert))
       return set_err(ctx, GAT_ERR_ASSERT, "sampler assertion failed on device (flags=%d): %s", flags,
                      (flags & gat::kStatusAssert) ? "sampled list has no overlap with the workspace (gat/Engine.pyx:645)"
@@ -1481,6 +1507,8 @@ extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const i
     return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerShift runs on the per-unit streams only");
   if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION)
     return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerGlobalPermutation runs on the per-unit streams only");
+  if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION)
+    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerLocalPermutation runs on the per-unit streams only");
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
   const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state);
   return rc ? rc : call_wait(ctx, P, stats);

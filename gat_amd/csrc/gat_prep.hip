@@ -803,6 +803,36 @@ static int64_t permute_tables(std::vector<uint2>& w, std::vector<uint32_t>& cum,
   return sum - total;
 }
 
+// SamplerLocalPermutation (gat/Engine.pyx:1174-1188): per workspace piece (ws, we) the working segments are
+// getOverlappingSegments' set (gat/SegmentList.pyx:952-983) -- from the last segment with start <= ws (the first one when
+// there is none) on, every segment with start <= we, whether or not it reaches the piece --, a contiguous run of the
+// unit's list.  work_start / work_end come out as 0 / we: min() and max() of the run's list (built with _add, normalized
+// flag 0) fail their assertion inside a cpdef that cannot raise and return 0.  free = we - sum(lengths).  Appends one
+// record {first, n, we, free} per piece with n > 0; returns the index of the first piece with free < 0 (the reference's
+// randint(0, free) raises), -1 when there is none.  sum_n / max_n: the run lengths' sum and maximum.
+static int64_t local_permute_tables(std::vector<uint4>& pieces, int64_t& sum_n, int64_t& max_n, const gat_segment* us, int64_t nus,
+                                    const gat_segment* uw, int64_t nuw) {
+  std::vector<uint64_t> cum((size_t)nus + 1, 0);
+  for (int64_t i = 0; i < nus; ++i) cum[(size_t)i + 1] = cum[(size_t)i] + (us[i].end - us[i].start);
+  auto starts_le = [&](uint32_t x) {                       // segments with start <= x
+    int64_t lo = 0, hi = nus;
+    while (lo < hi) { const int64_t m = (lo + hi) >> 1; if (us[m].start <= x) lo = m + 1; else hi = m; }
+    return lo;
+  };
+  int64_t bad = -1;
+  sum_n = max_n = 0;
+  for (int64_t k = 0; k < nuw; ++k) {
+    const int64_t first = std::max<int64_t>(0, starts_le(uw[k].start) - 1), n = starts_le(uw[k].end) - first;
+    if (n <= 0) continue;
+    const int64_t free_len = (int64_t)uw[k].end - (int64_t)(cum[(size_t)(first + n)] - cum[(size_t)first]);
+    if (free_len < 0 && bad < 0) bad = k;
+    pieces.push_back(make_uint4((uint32_t)first, (uint32_t)n, uw[k].end, (uint32_t)std::max<int64_t>(free_len, 0)));
+    sum_n += n;
+    max_n = std::max(max_n, n);
+  }
+  return bad;
+}
+
 static int32_t cap_for(const gat_ctx* ctx, int64_t n) {
   int64_t c = n + n / 4 + 96;
   if (gat_opt(ctx, "GAT_TEST_SMALL_CAPS")) c = n / 2 + 8;      // tests: force the overflow / retry path
@@ -1089,7 +1119,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   P->n_tracks = d->n_tracks;
   P->merge_contigs = d->merge_contigs ? 1 : 0;
   if (d->sampler != GAT_SAMPLER_ANNOTATOR && d->sampler != GAT_SAMPLER_SEGMENTS && d->sampler != GAT_SAMPLER_SHIFT &&
-      d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION)
+      d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION && d->sampler != GAT_SAMPLER_LOCAL_PERMUTATION)
     return set_err(ctx, GAT_ERR_ARG, "unknown sampler %d", d->sampler);
   if (d->sampler == GAT_SAMPLER_SHIFT && !(d->shift_radius >= 0.0 && d->shift_radius <= 1e9))
     return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: radius %g must be >= 0", d->shift_radius);
@@ -1109,6 +1139,10 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   std::vector<uint4> h_perm_unit((size_t)std::max(1, d->n_units), make_uint4(0u, 0u, 0u, 0u));
   std::vector<uint32_t> h_perm_len, h_perm_cum;
   std::vector<uint2> h_perm_w;
+  // GAT_SAMPLER_LOCAL_PERMUTATION: gat_problem::d_lperm_*
+  std::vector<uint4> h_lperm_unit((size_t)std::max(1, d->n_units), make_uint4(0u, 0u, 0u, 0u));
+  std::vector<uint4> h_lperm_piece;
+  std::vector<uint32_t> h_lperm_len;
   std::vector<std::vector<int32_t>> per_contig((size_t)d->n_contigs);
   std::vector<double> len_cv2((size_t)std::max(1, d->n_units), 0.0);
 
@@ -1128,6 +1162,8 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     std::vector<uint2> perm_w;
     std::vector<uint32_t> perm_cum;
     int64_t perm_free = 0;
+    std::vector<uint4> lperm;            // GAT_SAMPLER_LOCAL_PERMUTATION: the active pieces, the sum and maximum of their n
+    int64_t lperm_sum_n = 0, lperm_max_n = 0;
     int64_t nwork = 0;
     double cv2 = 0.0;
   };
@@ -1166,14 +1202,26 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
         if (l[i].start >= l[i].end || l[i].end >= 0x80000000u || (i > 0 && l[i - 1].end > l[i].start)) { R.rc = GAT_ERR_ASSERT; R.err = pass ? "workspace" : "segment"; break; }
     }
     if (R.rc) continue;                                              // (the message comes from check_list below, in unit order)
+    const bool local = d->sampler == GAT_SAMPLER_LOCAL_PERMUTATION;
+    if (local) {
+      // the unit is active when some piece has a working segment (the segment in front of a piece counts): not filter()'s rule
+      const int64_t bad = local_permute_tables(R.lperm, R.lperm_sum_n, R.lperm_max_n, us, nus, uw, nuw);
+      if (bad >= 0) {
+        fail_unit(R, GAT_ERR_ASSERT, "unit %d: SamplerLocalPermutation: the working segments of workspace piece %lld [%u, %u) are longer "
+                  "than [0, %u) (free length < 0): the reference's randint raises ValueError", u, (long long)bad, uw[bad].start, uw[bad].end, uw[bad].end);
+        continue;
+      }
+      if (R.lperm.empty()) continue;     // no piece draws: an empty list, no RNG use
+    }
     // working = segments.filter(workspace); ltotal = working.intersect(workspace).sum()
     uint32_t ltotal = 0, maxlen = 0;
     int64_t nwork = 0;
     std::vector<uint32_t> lens;
     lens.reserve((size_t)nus);
     for (int64_t i = 0; i < nus; ++i) {
-      const uint32_t ov = host_overlap(uw, nuw, us[i].start, us[i].end);
-      if (ov == 0) continue;
+      // (SamplerLocalPermutation: the unit's list as it is, no overlap asked)
+      const uint32_t ov = local ? 0u : host_overlap(uw, nuw, us[i].start, us[i].end);
+      if (ov == 0 && !local) continue;
       ltotal += ov;
       const uint32_t l = us[i].end - us[i].start;
       lens.push_back(l);
@@ -1190,7 +1238,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     R.rank.push_back(0u);                           // rank 0 is never drawn (r >= 1, gat/Engine.pyx:419-422)
     for (uint32_t l : lens) {
       const int64_t i = ((int64_t)l + bucket - 1) / bucket;
-      if (i >= d->nbuckets && d->sampler != GAT_SAMPLER_SHIFT && d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION) {   // (no length histogram)
+      if (i >= d->nbuckets && d->sampler != GAT_SAMPLER_SHIFT && d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION && !local) {   // (no length histogram)
         fail_unit(R, GAT_ERR_VALUE, "unit %d: segment of length %u too large: increase nbuckets (%d) or bucket_size (%lld)",
                   u, l, d->nbuckets, (long long)bucket);
         break;
@@ -1224,7 +1272,8 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
       fail_unit(R, GAT_ERR_CAPACITY, "unit %d: %lld workspace segments (> %lld)", u, (long long)nuw, (long long)((int64_t)1 << (4 * gat::kWsTreeLevels)));
       continue;
     }
-    if (nuw > gat::kWsTreeMin || (d->merge_contigs && nuw > 2)) {   // (isochore problems: k_units_overlap asks every candidate's unit)
+    // (k_permute_local reads its own tables: no grids, no trees)
+    if (!local && (nuw > gat::kWsTreeMin || (d->merge_contigs && nuw > 2))) {   // (isochore problems: k_units_overlap asks every candidate's unit)
       // Round 6, fragmented workspaces (the reference's own test data: 6 600 - 21 000 workspace segments per contig).  A tree
       // search is four dependent 64-byte node reads; the two questions asked of a workspace have cheaper answers:
       // (a) "how many bases of [s, e) lie inside?" (SegmentList.intersect(workspace).sum(), gat/Engine.pyx:596-598): a grid over
@@ -1253,7 +1302,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
         R.pgrid[2] = span;
       }
     }
-    if (nuw > gat::kWsTreeMin) {
+    if (!local && nuw > gat::kWsTreeMin) {
       auto build = [&](std::vector<uint32_t>& tree, auto key, uint32_t pad) {
         std::vector<uint32_t> level((size_t)nuw);
         for (int64_t i = 0; i < nuw; ++i) level[(size_t)i] = key(i);
@@ -1322,7 +1371,8 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
       }
       R.lens = lens;
     }
-    R.nwork = nwork;
+    R.nwork = local ? R.lperm_sum_n : nwork;       // (the launch order: the longest draw chain first)
+    if (local) R.lens = lens;
     R.active = true;
   }
   });
@@ -1371,6 +1421,19 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
       h_perm_len.insert(h_perm_len.end(), R.lens.begin(), R.lens.end());
       h_perm_w.insert(h_perm_w.end(), R.perm_w.begin(), R.perm_w.end());
       h_perm_cum.insert(h_perm_cum.end(), R.perm_cum.begin(), R.perm_cum.end());
+    }
+    if (d->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) {
+      // (exact: two slots per working segment of every piece -- a segment gives one piece, two where it wraps; a piece of
+      //  more working segments than LDS holds keeps its lengths and points at the top of the region)
+      const int64_t cap = 2 * R.lperm_sum_n + (R.lperm_max_n > 2048 ? 2 * R.lperm_max_n : 0);
+      if (cap > INT32_MAX / 2) return set_err(ctx, GAT_ERR_CAPACITY, "unit %d: SamplerLocalPermutation: %lld working segments over its pieces", u, (long long)R.lperm_sum_n);
+      P->h_base_cap[u] = (int32_t)cap;
+      h_lperm_unit[(size_t)u] = make_uint4((uint32_t)h_lperm_piece.size(), (uint32_t)R.lperm.size(), (uint32_t)h_lperm_len.size(),
+                                           (uint32_t)R.lperm_sum_n);
+      h_lperm_piece.insert(h_lperm_piece.end(), R.lperm.begin(), R.lperm.end());
+      h_lperm_len.insert(h_lperm_len.end(), R.lens.begin(), R.lens.end());
+      P->lperm_max_n = std::max<int32_t>(P->lperm_max_n, (int32_t)R.lperm_max_n);
+      P->lperm_max_out = std::max<int64_t>(P->lperm_max_out, 2 * R.lperm_sum_n);
     }
     if (d->sampler == GAT_SAMPLER_SHIFT) {
       h_shift_off[(size_t)u] = (int32_t)(h_shift.size() / 2);
@@ -1458,6 +1521,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     if (env && !strcmp(env, "wave")) P->sampler_mode = 0;
     if (P->sampler == GAT_SAMPLER_SHIFT) P->sampler_mode = 0;       // (k_shift: a wave per work unit, its stream in LDS)
     if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) P->sampler_mode = 0;    // (k_permute: the same)
+    if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) P->sampler_mode = 0;     // (k_permute_local: the same)
     auto expect = [](uint64_t range) {
       if (range == 0) return 0.0;
       uint64_t m = range; m |= m >> 1; m |= m >> 2; m |= m >> 4; m |= m >> 8; m |= m >> 16; m |= m >> 32;
@@ -1543,6 +1607,13 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     HIPCHK(ctx, P->d_perm_len.upload(h_perm_len, ctx));
     HIPCHK(ctx, P->d_perm_w.upload(h_perm_w, ctx));
     HIPCHK(ctx, P->d_perm_cum.upload(h_perm_cum, ctx));
+  }
+  if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) {
+    if (h_lperm_piece.empty()) h_lperm_piece.push_back(make_uint4(0u, 0u, 0u, 0u));
+    if (h_lperm_len.empty()) h_lperm_len.push_back(0u);
+    HIPCHK(ctx, P->d_lperm_unit.upload(h_lperm_unit, ctx));
+    HIPCHK(ctx, P->d_lperm_piece.upload(h_lperm_piece, ctx));
+    HIPCHK(ctx, P->d_lperm_len.upload(h_lperm_len, ctx));
   }
   {
     // what a position draw needs of its workspace segment (gat/Engine.pyx:318-325) as one record

@@ -59,6 +59,8 @@ enum : int32_t {
   kStatusTrimAssert = 4, // gat/SegmentList.pyx:560 sum() > size
   kStatusUnitsOverlap = 16, // k_units_overlap: overlaps between the units' lists that are not pairwise (or more candidates than the
                          // buffer holds): host repeats the batch through k_contig and keeps to it for the problem
+  kStatusCoordRange = 32, // k_permute_local: a start or end of the walk beyond 2^31 - 1, where the reference's assignment to its C int
+                         // raises OverflowError (gat/Engine.pyx:1208, :1212)
   kStatusContigLds = 8,  // k_contig: a contig's lists exceed the LDS the launch was given (sized for what is expected,
                          // not for every unit at its capacity): host repeats the batch with the full size
 };

@@ -1257,6 +1257,41 @@ class SamplerGlobalPermutation(Sampler):
         return r
 
 
+class SamplerLocalPermutation(Sampler):
+    """gat/Engine.pyx:1117: for every workspace piece in turn, the lengths of its working segments -- the segment in
+    front of the piece and every segment starting up to the piece's end (SegmentList.getOverlappingSegments), kept
+    whole -- are shuffled, random gaps drawn, and the segments laid down from a random shift, wrapping at the end.  As
+    the reference computes it the span of a piece is [0, piece end), not the piece extended by its segments (its min()
+    / max() of the working list return 0), and so does this class.  The pieces' outputs are united (normalize:
+    adjacent pieces kept apart).  A unit samples whenever some piece has a working segment, whether or not a segment
+    overlaps the workspace.  Where the reference raises -- working segments longer than [0, piece end): ValueError; a
+    coordinate beyond 2^31 - 1 before it wraps: OverflowError -- sample() raises AssertionError (GAT_ERR_ASSERT).
+    Python's random: the stream of a call is random.seed(seed), `seed` by default a draw of Python's random."""
+
+    kind = 4
+
+    def __init__(self):
+        pass
+
+    def sample(self, segments, workspace, seed=None):
+        assert workspace.isNormalized, "workspace is not normalized"
+        if seed is None:
+            seed = random.getrandbits(32)
+        if len(segments) == 0 or len(workspace) == 0:
+            return SegmentList()
+        s, w = segments.asArray(), workspace.asArray()
+        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
+                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], sampler=self.kind)
+        P = _lib.Problem(get_context(), flat)
+        try:
+            seg, _ = P.sample(seed, 0, 1)
+        finally:
+            P.close()
+        r = SegmentList(array=seg)
+        r.isNormalized = 1
+        return r
+
+
 class Counter(object):
     name = None
 

@@ -55,6 +55,13 @@ typedef struct gat_annotations gat_annotations;
 #define GAT_SAMPLER_GLOBAL_PERMUTATION 3  /* SamplerGlobalPermutation (gat/Engine.pyx:1234-1386): the working       */
                                   /* segments' lengths shuffled, random gaps, laid into the workspace extended  */
                                   /* by them from a random shift; Python's random; per-unit streams only        */
+#define GAT_SAMPLER_LOCAL_PERMUTATION 4   /* SamplerLocalPermutation (gat/Engine.pyx:1117-1229): per workspace piece,   */
+                                  /* the lengths of getOverlappingSegments' set shuffled, random gaps, laid over */
+                                  /* [0, piece end) from a random shift (what the reference computes: its        */
+                                  /* min() / max() return 0); the pieces' outputs united by normalize(); a unit  */
+                                  /* is active when some piece has a working segment; free < 0 in a piece or a   */
+                                  /* coordinate beyond 2^31 - 1 (where the reference raises): GAT_ERR_ASSERT;    */
+                                  /* Python's random; per-unit streams only                                     */
 
 /*
  * Flat description of what gat.computeSample (gat/__init__.py:494-591) walks for one segment
@@ -80,7 +87,7 @@ typedef struct {
   const int64_t* cws_nseg;      /* n_contigs: len(contig_workspace[contig]) (Engine.pyx:1437)   */
   uint32_t bucket_size;         /* SamplerAnnotator(bucket_size, nbuckets): gat/Engine.pyx:498  */
   int32_t nbuckets;
-  int32_t sampler;              /* GAT_SAMPLER_ANNOTATOR (gat/Engine.pyx:445), GAT_SAMPLER_SEGMENTS (:653), GAT_SAMPLER_SHIFT (:998) or GAT_SAMPLER_GLOBAL_PERMUTATION (:1234) */
+  int32_t sampler;              /* GAT_SAMPLER_ANNOTATOR (gat/Engine.pyx:445), GAT_SAMPLER_SEGMENTS (:653), GAT_SAMPLER_SHIFT (:998), GAT_SAMPLER_GLOBAL_PERMUTATION (:1234) or GAT_SAMPLER_LOCAL_PERMUTATION (:1117) */
   /* Optional (all 0 / NULL: annos / anno_off are the [track][contig] lists above).  With anno_group set, the caller hands
    * over the annotation lists as it holds them -- one per (track, isochore key), the `annotations` argument of
    * UnconditionalSampler.sample (gat/__init__.py:704) -- and the library forms computeSample's contig_annotations itself
