@@ -21,6 +21,7 @@
 
 #include "../../include/gat_mi355.h"
 #include "gat_types.h"
+#include "gat_knobs.h"
 
 namespace gat { struct TailPatch; }
 
@@ -52,6 +53,7 @@ struct CallState {
   int n_flight = 0;                           // batches enqueued and not yet checked
   int64_t nb[kMaxInflight] = {};
   int count_kernel[kMaxInflight] = {};
+  Knobs knobs;                                // the knobs as they were at the top of the call: every batch of it, repeated ones too
   bool main_rec[kMaxInflight] = {};
   bool timed = false, mstat_on = false;
   int times_state = 0;             // gat_stats::kernel_times of the call
@@ -92,22 +94,16 @@ struct gat_ctx {
   std::string err;
   int max_lds = 65536;
   // gat_ctx_set_option: the context's own values of the tuning / testing knobs (GAT_*), in front of the process's -- the
-  // environment as it was when the library was first asked (gat_opt); aux_ctx / build_ctx read their owner's
+  // environment as it was when the library was first asked.  Only read_knobs (gat_knobs.h) and the two option calls touch the
+  // map, under the mutex; aux_ctx / build_ctx have none of their own: their work is handed its owner's snapshot
   std::map<std::string, std::string> options;
   mutable std::mutex options_mutex;
-  const gat_ctx* options_owner = nullptr;
 };
-
-// The knobs are no longer read from the environment where they act: gat_opt answers from the context's
-// options (gat_ctx_set_option), else from a snapshot of the process's GAT_* variables taken ONCE -- no getenv on a call's path,
-// and two host threads with a context each no longer share what a test sets.  nullptr: not set (or set to the empty string).
-const char* gat_opt(const gat_ctx* ctx, const char* key);
 
 // k_count_seg stages a track tile's lists in LDS: a list of max_m intervals takes max_m + 4 entries (one in front of its first
 // interval, three sentinels behind the last: segs_vs_pairs).  ONE condition for the launch (launch_count) and for the build
 // (build_annos: lists beyond it get the merged index) -- they had drifted apart by three entries
-inline int64_t count_lds_entries(const gat_ctx* ctx) { const char* e = gat_opt(ctx, "GAT_COUNT_LDS_ENTRIES"); return e ? atoll(e) : 1024; }
-inline bool count_lists_staged(const gat_ctx* ctx, int64_t max_m) { return max_m > 0 && max_m + 4 <= count_lds_entries(ctx); }
+inline bool count_lists_staged(const Knobs& kn, int64_t max_m) { return max_m > 0 && max_m + 4 <= kn.count_lds_entries; }
 
 void ctx_release(gat_ctx* ctx);     // gat_mi355.hip: drops one reference, frees the context with the last
 
@@ -285,6 +281,7 @@ struct gat_annotations {
   // known before the build (shape_known): whether the merged index will exist and how many intervals the tables will hold --
   // what decides the count kernel's route, and with it the sampler's last steps.  With four tracks or more the index exists
   // whatever the lists hold; lists that pass through ungrouped (no fromIsochores merge) have their sizes in the desc
+  Knobs knobs;                     // as they were when gat_annotations_create was called: all the build reads
   bool shape_known = false, will_merge = false;
   int64_t total_known = -1;        // intervals of the tables, or -1 (merged groups: known when built)
 };
@@ -296,7 +293,7 @@ int annotations_wait(gat_ctx* ctx, gat_annotations* a);   // joins the build; re
 struct PrepTimer {
   bool on;
   std::chrono::steady_clock::time_point t;
-  PrepTimer() : on(gat_opt(nullptr, "GAT_TIME_CREATE") != nullptr), t(std::chrono::steady_clock::now()) {}
+  PrepTimer() : on(process_knobs().time_create), t(std::chrono::steady_clock::now()) {}
   void lap(const char* what) {
     if (!on) return;
     const auto n = std::chrono::steady_clock::now();
@@ -438,7 +435,7 @@ struct gat_problem {
 };
 
 // gat_prep.hip
-int build_annos(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, const int64_t* lbeg, const int64_t* lend, int64_t n_lists,
+int build_annos(gat_ctx* ctx, const Knobs& kn, AnnoDev& A, const gat_segment* annos, const int64_t* lbeg, const int64_t* lend, int64_t n_lists,
                 int32_t n_groups, bool want_merged, bool checked, double mean_seg_len = 0.0, bool nucleotide_only = false);
-int layout_slab(gat_problem* P);
-int upload_layout(gat_ctx* ctx, gat_problem* P);
+int layout_slab(gat_problem* P, const Knobs& kn);
+int upload_layout(gat_ctx* ctx, gat_problem* P, const Knobs& kn);

@@ -179,17 +179,16 @@ extern "C" int gat_memcpy_h2d(gat_ctx* ctx, void* dst, const void* src, size_t b
 }
 
 // ------------------------------------------------------------------------------------------
-static int ensure_scratch(gat_ctx* ctx, gat_problem* P, int64_t want) {
+static int ensure_scratch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t want) {
   if (P->batch >= want) return GAT_OK;
   PrepTimer tm;
-  const char* env = gat_opt(ctx, "GAT_SLAB_BYTES");
   // a batch as large as a quarter of the 288 GB takes: the lane-per-stream kernels have a fixed floor per launch (the serial
   // chain of the longest unit's tile) and the wave-per-unit kernels of long-list problems fill the chip only with
   // thousands of samples in flight, so fewer, larger batches are faster (config 3, 10 000 samples: 9.7 ms in two batches
   // under 12 GB, 9.3 ms in one; config-4 shape: a rank's shard of 12 500 samples in one batch of 40 GB instead of two);
   // capped by what the device has free
-  double budget = env ? atof(env) : 72.0 * 1024 * 1024 * 1024;
-  if (!env) {
+  double budget = kn.slab_bytes;
+  if (!kn.slab_bytes_set) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
       budget = std::min(std::min(budget, 0.25 * (double)total_b), 0.6 * (double)(free_b + dev_pool_held()));
@@ -256,14 +255,14 @@ static_assert(gat::kMergedThreads / gat::kWave == kMergedWavesHost, "gat_host.h:
 // which kernel serves the segment-side counters (the choice launch_count makes)
 // merged_only: the tables were BUILT for that route alone (AnnoDev::per_track false -- decided from the knobs as they were then):
 // the route stands whatever the knobs say now (a knob flipped between the build and the call was GAT_ERR_ARG)
-static int count_route(const gat_ctx* ctx, bool has_merged, const Counters& C, int n_contigs, int n_tracks, int swap_capx,
+static int count_route(const gat_ctx* ctx, const Knobs& kn, bool has_merged, const Counters& C, int n_contigs, int n_tracks, int swap_capx,
                        bool merged_only = false) {
   if (!C.any_seg || n_contigs <= 0) return GAT_COUNT_KERNEL_NONE;
   const bool only_overlap = C.slot[GAT_COUNTER_SEGMENT_OVERLAP] < 0 && C.slot[GAT_COUNTER_SEGMENT_MIDOVERLAP] < 0;
   const size_t lds_merged = (size_t)n_tracks * 4 * (gat::kMergedThreads / gat::kWave);
-  if (only_overlap && has_merged && (int64_t)lds_merged + 1024 <= ctx->max_lds && (merged_only || !gat_opt(ctx, "GAT_COUNT_NO_MERGED")))
+  if (only_overlap && has_merged && (int64_t)lds_merged + 1024 <= ctx->max_lds && (merged_only || !kn.count_no_merged))
     return GAT_COUNT_KERNEL_MERGED;
-  if (swap_capx > 0 && only_overlap && !gat_opt(ctx, "GAT_COUNT_NO_SWAP")) return GAT_COUNT_KERNEL_SWAP;
+  if (swap_capx > 0 && only_overlap && !kn.count_no_swap) return GAT_COUNT_KERNEL_SWAP;
   return GAT_COUNT_KERNEL_SEG;
 }
 
@@ -285,7 +284,7 @@ static inline dim3 grid_yz(unsigned x, unsigned n) {
   return dim3(x, gy, (n + gy - 1) / std::max(gy, 1u));
 }
 
-static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, gat::CountArgs A, DevBuf<uint32_t>& part,
+static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, const Counters& C, gat::CountArgs A, DevBuf<uint32_t>& part,
                         int swap_capx, int list_cap, CountLaunch& L) {
   L.main_recorded = false;
   L.count_kernel = GAT_COUNT_KERNEL_NONE;
@@ -293,25 +292,22 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
   A.a_start = annos.start.p; A.a_end = annos.end.p; A.a_cumx = annos.cumx.p; A.a_off = annos.off.p;
   A.a_grid = annos.grid.p; A.g_off = annos.goff.p; A.c_shift = annos.shift.p; A.c_cells = annos.cells.p;
   if (A.n_samples <= 0 || A.n_tracks <= 0) return GAT_OK;
-  if (!annos.per_track && (C.any_anno || (C.any_seg && count_route(ctx, annos.has_merged, C, A.n_contigs, A.n_tracks, swap_capx, true) != GAT_COUNT_KERNEL_MERGED)))
+  if (!annos.per_track && (C.any_anno || (C.any_seg && count_route(ctx, kn, annos.has_merged, C, A.n_contigs, A.n_tracks, swap_capx, true) != GAT_COUNT_KERNEL_MERGED)))
     return set_err(ctx, GAT_ERR_ARG, "the annotation tables were made for the nucleotide counters only (GAT_ANNOTATIONS_NUCLEOTIDE_ONLY): "
                                      "no per-track tables for the counters asked for");
   if (C.any_seg) {
-    const int E_max = (int)count_lds_entries(ctx);
-    const char* env_sc = gat_opt(ctx, "GAT_COUNT_SAMPLES_PER_BLOCK");
-    int SC = env_sc ? atoi(env_sc) : 32;
-    if (!env_sc) {   // enough blocks to fill 256 CUs several times over, large enough to amortise the staging
+    const int E_max = (int)kn.count_lds_entries;
+    int SC = (int)kn.count_samples_per_block;
+    if (!kn.count_samples_per_block_set) {   // enough blocks to fill 256 CUs several times over, large enough to amortise the staging
       const int64_t tiles0 = (A.n_tracks + 0) , work = (int64_t)A.n_samples * tiles0 * std::max(1, A.n_contigs) / 8192;
       SC = 8;
       while (SC < 128 && SC * 2 <= work) SC *= 2;
     }
     SC = std::max(1, std::min(SC, 256));
-    const char* env_tt = gat_opt(ctx, "GAT_COUNT_TRACKS_PER_BLOCK");
-    const int TT_max = env_tt ? atoi(env_tt) : 16;
+    const int TT_max = (int)kn.count_tracks_per_block;
     int TT;
-    const char* env_st = gat_opt(ctx, "GAT_COUNT_STAGED");
     // (+4: a staged list has an entry in front of its first interval and three sentinels behind the last: segs_vs_pairs)
-    bool staged = count_lists_staged(ctx, annos.max_m) && !(env_st && atoi(env_st) == 0);
+    bool staged = count_lists_staged(kn, annos.max_m) && (int)kn.count_staged != 0;
     if (staged) TT = (int)std::min<int64_t>(std::min<int64_t>(A.n_tracks, TT_max), E_max / (annos.max_m + 4));
     else TT = (int)std::min<int64_t>(A.n_tracks, TT_max);
     TT = std::max(1, TT);
@@ -329,16 +325,15 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
     if (gpz > 65535) return set_err(ctx, GAT_ERR_CAPACITY, "more than 2^31 (track tile, contig) pairs");
     dim3 grid((unsigned)((A.n_samples + SC - 1) / SC), gpy, gpz);
     const size_t lds_merged = (size_t)A.n_tracks * 4 * (gat::kMergedThreads / gat::kWave);
-    const int route = count_route(ctx, annos.has_merged, C, A.n_contigs, A.n_tracks, swap_capx, !annos.per_track);
+    const int route = count_route(ctx, kn, annos.has_merged, C, A.n_contigs, A.n_tracks, swap_capx, !annos.per_track);
     if (route == GAT_COUNT_KERNEL_MERGED) {
       // several tracks: one look-up per sample segment in the merged index of all tracks
       A.mz = annos.mz.p; A.mz_off = annos.mz_off.p; A.mfirst = annos.mfirst.p; A.mf_off = annos.mf_off.p;
       A.m_shift = annos.m_shift.p; A.m_cells = annos.m_cells.p;
       A.m_slot_off = annos.m_slot_off.p; A.m_slot_contigs = annos.m_slot_contigs.p;
-      const char* env_sg = gat_opt(ctx, "GAT_MERGED_SAMPLES_PER_BLOCK");
       // samples per workgroup: one per wave.  (Larger groups were meant to keep the contig's index hot; measured on config 3,
       // main kernel per 10 000 samples: 4 -> 1.60 ms, 8 -> 1.69, 16 -> 1.73, 32 -> 1.83, 64 -> 2.1: the finer deal wins.)
-      int SG = env_sg ? atoi(env_sg) : 4;
+      int SG = (int)kn.merged_samples_per_block;
       SG = std::max(1, std::min(SG, std::max(1, A.n_samples)));
       A.samples_per_block = SG;
       const int64_t n_sgroups = (A.n_samples + SG - 1) / SG;
@@ -427,7 +422,7 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
     int lcells = 4;
     while ((1 << lcells) < list_cap + 1 && lcells < 13) ++lcells;
     const size_t lds_a = (size_t)2 * (list_cap + 1) * 4 + ((size_t)(1 << lcells) + 1) * 4;
-    if (list_cap > 0 && A.n_contigs > 0 && (int64_t)lds_a + 1024 <= ctx->max_lds && !gat_opt(ctx, "GAT_COUNT_NO_SWAP")) {
+    if (list_cap > 0 && A.n_contigs > 0 && (int64_t)lds_a + 1024 <= ctx->max_lds && !kn.count_no_swap) {
       gat::CountArgs B = A;
       B.lds_entries = list_cap + 1;
       B.lds_grid = lcells;
@@ -454,7 +449,7 @@ static int launch_count(gat_ctx* ctx, const AnnoDev& annos, const Counters& C, g
 // capacities (scratch released: the batch that fits the budget may now be smaller) and nothing of this batch is valid;
 // the caller sizes the batch again and repeats it (results do not depend on the batching: streams are per unit).
 constexpr int kRelayout = 1;
-static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, int64_t nb, gat_stats* st, bool timed, const unsigned long long* h_stat);
+static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb, gat_stats* st, bool timed, const unsigned long long* h_stat);
 
 // what a caller of run_sampler_batch asks for beyond the defaults
 struct BatchOpts {
@@ -473,6 +468,7 @@ struct BatchOpts {
 // knobs and the caller's options; read-only for the stages.  What a stage leaves for the kernels behind it, it adds to the
 // batch's SamplerArgs.
 struct BatchPlan {
+  const Knobs& kn;         // the call's snapshot of the knobs
   BatchOpts o;
   int64_t nb; bool timed;
   unsigned n_act;          // active units: the launch positions
@@ -493,14 +489,14 @@ struct BatchPlan {
   size_t lds;              // k_sampler's LDS for the longest list
 };
 
-static BatchPlan plan_batch(const gat_ctx* ctx, const gat_problem* P, int64_t nb, bool timed, const BatchOpts& o) {
-  BatchPlan B = {};
+static BatchPlan plan_batch(const gat_ctx* ctx, const Knobs& kn, const gat_problem* P, int64_t nb, bool timed, const BatchOpts& o) {
+  BatchPlan B = {kn};
   B.o = o; B.nb = nb; B.timed = timed;
   B.n_act = (unsigned)P->h_order.size();
   for (int32_t u : P->h_order) B.max_work = std::max(B.max_work, P->h_units[(size_t)u].hist_total);
   B.smode = o.serial_state != nullptr ? 0 : P->sampler_mode;
   B.lds = (size_t)(gat::kMtLdsWords + 2 * (size_t)P->max_unit_cap) * 4;
-  B.huge = P->sampler != GAT_SAMPLER_SEGMENTS && ((int64_t)B.lds > ctx->max_lds || gat_opt(ctx, "GAT_TEST_HUGE") != nullptr);
+  B.huge = P->sampler != GAT_SAMPLER_SEGMENTS && ((int64_t)B.lds > ctx->max_lds || kn.test_huge);
   if (B.huge || P->sampler == GAT_SAMPLER_SEGMENTS) B.lds = (size_t)gat::kMtLdsWords * 4;
   B.tree = P->max_nws > gat::kWsTreeMin;
   B.split = P->split_path && B.smode && !B.huge;
@@ -511,11 +507,11 @@ static BatchPlan plan_batch(const gat_ctx* ctx, const gat_problem* P, int64_t nb
   B.lds_merge = (size_t)2 * P->max_unit_cap * 4 + (size_t)(B.nbk + 1) * 4;
   for (int32_t u : P->h_order) { const uint32_t w = P->h_units[(size_t)u].hist_total; if (w + w / 8 > 1024) ++B.n_long; else break; }
   B.merge_big = B.smode && P->sampler != GAT_SAMPLER_SEGMENTS && (int64_t)B.lds_merge + 1024 <= ctx->max_lds && B.n_long > 0 &&
-                !gat_opt(ctx, "GAT_NO_MERGE_BIG");
+                !kn.no_merge_big;
   if (B.merge_big) {
-    B.tail_big = !B.split && P->d_patch.p != nullptr && P->max_nws <= gat::kTailMaxWs && !gat_opt(ctx, "GAT_NO_TAIL_BIG");
-    B.resume_big = B.tail_big && !gat_opt(ctx, "GAT_NO_RESUME_BIG");
-    B.long_queue = B.resume_big && !gat_opt(ctx, "GAT_NO_LONG_QUEUE");
+    B.tail_big = !B.split && P->d_patch.p != nullptr && P->max_nws <= gat::kTailMaxWs && !kn.no_tail_big;
+    B.resume_big = B.tail_big && !kn.no_resume_big;
+    B.long_queue = B.resume_big && !kn.no_long_queue;
   } else {
     // no workgroup pass: the wave's own counting sort, scratch behind the segment buffer if it fits
     int nbk = B.nbk;
@@ -583,8 +579,8 @@ static int enqueue_permute_local(gat_ctx* ctx, gat_problem* P, const BatchPlan& 
   H.lp_unit = P->d_lperm_unit.p; H.lp_piece = P->d_lperm_piece.p; H.lp_len = P->d_lperm_len.p;
   // (GAT_LPERM_SIMPLE: one piece per wave step throughout, the A/B of the batched small-piece path;
   //  GAT_EXP_LPERM_NO_NORMALIZE: a timing experiment with wrong results -- no final sort and merge, empty lists)
-  H.simple = gat_opt(ctx, "GAT_LPERM_SIMPLE") ? 1 : 0;
-  H.no_normalize = gat_opt(ctx, "GAT_EXP_LPERM_NO_NORMALIZE") ? 1 : 0;
+  H.simple = B.kn.lperm_simple ? 1 : 0;
+  H.no_normalize = B.kn.exp_lperm_no_normalize ? 1 : 0;
   return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_permute_local, H,
                               (size_t)(gat::kMtLdsWords + 2 * gat::kLpBatchDraws + words) * 4);
 }
@@ -597,7 +593,7 @@ static int base_sampler_args(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, u
   A.ws = P->d_ws.p; A.ws_cdf = P->d_ws_cdf.p; A.rank_len = P->d_rank_len.p; A.ws_tree = P->d_ws_tree.p;
   A.ws_rec = P->d_ws_rec.p;
   A.seed = seed; A.sample_begin = begin; A.sampler_kind = P->sampler;
-  A.place_plain_step = gat_opt(ctx, "GAT_PLACE_NO_CM") ? 1 : 0;
+  A.place_plain_step = B.kn.place_no_cm ? 1 : 0;
   A.slab = P->d_slab.p; A.slab_stride = P->slab_stride;
   A.unit_n = P->d_unit_n.p; A.flags = P->flags_dev(); A.stat = P->d_stat.p; A.ws_stat = P->d_ws_stat.p;
 #if defined(GAT_DIAG) || defined(GAT_DIAG_CONS)
@@ -636,24 +632,23 @@ static int launch_place(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B, 
   //  eight GPUs -- take the wide kernel as well: its loop stores unconditionally and four tiles share a rank table; config 2,
   //  k_place at 1 250 / 2 500 / 5 000 samples: 0.46 / 0.47 / 0.56 ms against the lean kernel's 0.52 / 0.53 / 0.57, at 10 000
   //  1.05 against 0.92)
-  const bool small_call = (int64_t)nsb * (int64_t)B.n_act <= 1536 && !gat_opt(ctx, "GAT_PLACE_NO_WIDE");
-  const int mode = P->all_simple ? ((gat_opt(ctx, "GAT_PLACE_WIDE") || small_call) ? 3 : 1)
-                                 : (P->all_one_ws && !gat_opt(ctx, "GAT_PLACE_NO_WIDE") ? 3 : (P->max_nws > gat::kPlaceWsLds ? 2 : 0));
+  const bool small_call = (int64_t)nsb * (int64_t)B.n_act <= 1536 && !B.kn.place_no_wide;
+  const int mode = P->all_simple ? ((B.kn.place_wide || small_call) ? 3 : 1)
+                                 : (P->all_one_ws && !B.kn.place_no_wide ? 3 : (P->max_nws > gat::kPlaceWsLds ? 2 : 0));
   // (k_place_wide: kPlaceWide tiles per workgroup, the largest unit's rank table beside their rings)
   const dim3 gw = grid_yz((nsb + gat::kPlaceWide - 1) / gat::kPlaceWide, B.n_act);
   const size_t lds_wide = (size_t)P->max_hist * 4;
   // calls of a few hundred tiles of a problem of simple units: one stream walked by the 64 lanes of a wave (k_place_scan:
   // a stream's states as a prefix scan over its rows) instead of one lane walking it row by row -- the chain of the longest
   // unit's tile, 0.37 ms on config 2 whatever the sample count, is what such a call waited for
-  const char* env_scan = gat_opt(ctx, "GAT_PLACE_SCAN_TILES");
-  const int64_t scan_tiles = env_scan ? atoll(env_scan) : 768;      // (config 2: faster up to ~2 300 samples x 24 units per call)
+  const int64_t scan_tiles = B.kn.place_scan_tiles;                 // (config 2: faster up to ~2 300 samples x 24 units per call)
   const bool scan = P->sampler == GAT_SAMPLER_ANNOTATOR && P->all_simple && P->all_cm_ok && A.place_plain_step == 0 &&
                     (int64_t)nsb * (int64_t)B.n_act <= scan_tiles;
   if (scan) {
     const int64_t n_tiles = (int64_t)nsb * B.n_act;
     const unsigned nblocks = (unsigned)(((n_tiles + 7) / 8) * 8 * 4);
     hipLaunchKernelGGL(gat::k_place_scan, dim3(nblocks), dim3(gat::kScanWaves * 64), 0, ctx->stream, A, (int)nsb,
-                       gat_opt(ctx, "GAT_PLACE_SCAN_SEQ") ? 1 : 0);
+                       B.kn.place_scan_seq ? 1 : 0);
   } else if (P->sampler == GAT_SAMPLER_SEGMENTS) {
     if (mode == 3) {
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_wide<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide));
@@ -663,7 +658,7 @@ static int launch_place(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B, 
     else hipLaunchKernelGGL((gat::k_place<1, 2>), gp, dim3(64), 0, ctx->stream, A);
   } else {
     // (k_place_pipe: the rows of the single-workspace-segment units prefetched by hand, see GAT_PLACE_LOOP_PIPE)
-    const bool pipe = P->pipe_pays && !gat_opt(ctx, "GAT_PLACE_NO_PIPE");
+    const bool pipe = P->pipe_pays && !B.kn.place_no_pipe;
     const bool rank_fits = P->max_hist < (uint32_t)gat::kPlaceRankLds;
     // fragmented workspaces: the cdf grids of the long workspaces in LDS, eight tiles of a unit per workgroup (k_place_grid);
     // static LDS: the workspace and rank tables (4 KB each) and an 8 KB ring per tile
@@ -725,7 +720,7 @@ static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
       {gat::k_merge_big<false, 0>, gat::k_merge_big<false, 8>, gat::k_merge_big<false, 16>, gat::k_merge_big<false, gat::kMergeRegs>},
       {gat::k_merge_big<true, 0>, gat::k_merge_big<true, 8>, gat::k_merge_big<true, 16>, gat::k_merge_big<true, gat::kMergeRegs>}};
   const merge_fn* fns = kMergeFns[B.tree ? 1 : 0];
-  const bool merge_old = gat_opt(ctx, "GAT_MERGE_OLD") != nullptr;
+  const bool merge_old = B.kn.merge_old;
   for (int f = 0; f < 4; ++f)
     HIPCHK(ctx, hipFuncSetAttribute((const void*)fns[f], hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.lds_merge));
   for (size_t c = 0; c + 1 < P->h_class_start.size() && (unsigned)P->h_class_start[c] < n_long; ++c) {
@@ -748,8 +743,7 @@ static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
     const int form = merge_old || per > gat::kMergeRegs ? 0 : (per <= 8 ? 1 : (per <= 16 ? 2 : 3));
     if (form > 0) {
       // (the register forms: the histogram shares the list's LDS -- up to about a bucket per element)
-      int maxb = 8192;
-      if (const char* e = gat_opt(ctx, "GAT_MERGE_BUCKETS")) maxb = std::max(1024, atoi(e));
+      const int maxb = B.kn.merge_buckets_set ? std::max(1024, (int)B.kn.merge_buckets) : 8192;
       cnbk = 1024;
       while (2 * cnbk + gat::kMergeThreads + 1 <= ccap && 2 * cnbk <= maxb) cnbk <<= 1;     // (+ a word of padding per thread)
       lds_k = ((size_t)ccap + (size_t)std::max(ccap, cnbk + gat::kMergeThreads + 1)) * 4;   // (short lists: the 1 024 buckets and their padding need their own words)
@@ -766,18 +760,18 @@ static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
   TB.cum = nullptr; TB.patch = P->d_patch.p; TB.todo = nullptr; TB.todo_count = nullptr;
   // (counts alone, by k_count_merged -- or through k_contig, which merge(0)s the lists again: what a trim emptied may
   //  stay in the list as [0, 0))
-  TB.loose_ok = (B.o.loose_ok && !B.o.need_unit_lists && !gat_opt(ctx, "GAT_RESUME_COMPACT")) ? 1 : 0;
+  TB.loose_ok = (B.o.loose_ok && !B.o.need_unit_lists && !B.kn.resume_compact) ? 1 : 0;
   // (bit 0: no bridge between two neighbours, bit 1: none over two segments on the right; "1" or anything else: both off)
   TB.no_bridge = 0;
-  if (const char* e = gat_opt(ctx, "GAT_TB_NO_BRIDGE")) { const int v = atoi(e); TB.no_bridge = (v == 2 || v == 5) ? (v == 2 ? 2 : 1) : 3; }
-  TB.no_log_map = gat_opt(ctx, "GAT_TB_NO_LOG_MAP") ? 1 : 0;
+  if (B.kn.tb_no_bridge_set) { const int v = (int)B.kn.tb_no_bridge; TB.no_bridge = (v == 2 || v == 5) ? (v == 2 ? 2 : 1) : 3; }
+  TB.no_log_map = B.kn.tb_no_log_map ? 1 : 0;
   hipLaunchKernelGGL(gat::k_tail_big, grid_yz((unsigned)((B.nb + 63) / 64), n_long), dim3(64), 0, ctx->stream, TB);
   HIPCHK(ctx, hipGetLastError());
   if (B.resume_big) {
     // ... and the rest of the unit -- log inserted, trim, final filter -- with the list where it is
     // (a reader that takes the segments one by one in any order -- k_count_merged on the units' lists, no contig lists
     //  in between --: the log stays behind the merged list, the trim works on virtual indices)
-    const bool virt = TB.loose_ok && !P->merge_contigs && !gat_opt(ctx, "GAT_RESUME_INSERT");
+    const bool virt = TB.loose_ok && !P->merge_contigs && !B.kn.resume_insert;
     hipLaunchKernelGGL(virt ? gat::k_resume_big<true> : gat::k_resume_big<false>, grid_yz((unsigned)B.nb, n_long), dim3(64), 0, ctx->stream, TB);
     HIPCHK(ctx, hipGetLastError());
   }
@@ -816,7 +810,7 @@ static int enqueue_split_path(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
   HIPCHK(ctx, hipFuncSetAttribute((const void*)consolidate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
   // (a call of a few hundred tiles does not fill the chip whatever the LDS of a workgroup: one launch for all classes,
   //  each launch less is a tail less -- config 2 at 1 250 samples: k_consolidate 0.121 -> 0.101 ms)
-  const bool one_class = (int64_t)((nb + 63) / 64) * (int64_t)B.n_act <= 1024 && !gat_opt(ctx, "GAT_SIZE_CLASSES");
+  const bool one_class = (int64_t)((nb + 63) / 64) * (int64_t)B.n_act <= 1024 && !B.kn.size_classes_set;
   for (size_t c = 0; c + 1 < P->h_class_start.size(); ++c) {
     // one launch per size class, its LDS sized for the class's longest list
     if (one_class && c > 0) break;
@@ -824,7 +818,7 @@ static int enqueue_split_path(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
     // (as for k_merge_big: LDS for what the class's longest unit is expected to have placed -- its segments +- a renewal
     //  count's spread -- not for its slab region; the rare list beyond it is k_sampler's.  GAT_CONSOLIDATE_SLAB_LDS: the old size)
     const int n0 = (int)P->h_units[(size_t)P->h_order[(size_t)a0]].hist_total;
-    const int tight = gat_opt(ctx, "GAT_CONSOLIDATE_SLAB_LDS") ? INT32_MAX : (n0 + n0 / 12 + 64 + 31) / 32 * 32;
+    const int tight = B.kn.consolidate_slab_lds ? INT32_MAX : (n0 + n0 / 12 + 64 + 31) / 32 * 32;
     const int ccap = std::min(std::min(P->h_units[(size_t)P->h_order[(size_t)a0]].slab_cap, T.S.lds_cap), tight);
     gat::TailArgs C = T;
     C.S.a_base = a0; C.S.a_end = a1; C.S.lds_cap = ccap;
@@ -839,7 +833,7 @@ static int enqueue_split_path(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
   if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_t[0], ctx->stream));
   // isochore problems: k_contig re-sorts the units of a contig anyway and takes (merged list, k_tail's record) as
   // it is -- no final unit lists unless somebody asked for them (gat_sample_units)
-  P->patched_contigs = P->merge_contigs && P->n_contigs > 0 && !B.o.need_unit_lists && !gat_opt(ctx, "GAT_CONTIG_FINAL_LISTS");
+  P->patched_contigs = P->merge_contigs && P->n_contigs > 0 && !B.o.need_unit_lists && !B.kn.contig_final_lists;
   P->units_direct = B.o.units_direct && P->patched_contigs && P->units_direct_ok && B.o.serial_state == nullptr;
   P->patched_counts = !P->merge_contigs && B.o.records_ok && !B.o.need_unit_lists;
   if (!P->patched_contigs && !P->patched_counts) hipLaunchKernelGGL(gat::k_finalize, grid_yz((unsigned)nb, B.n_act), dim3(64), 0, ctx->stream, T);
@@ -872,7 +866,7 @@ static int enqueue_sampler(gat_ctx* ctx, const gat_problem* P, const BatchPlan& 
   int variant = P->sampler == GAT_SAMPLER_SEGMENTS ? (B.tree ? 5 : 4)
               : B.huge ? (B.tree ? 7 : 6) : (B.long_lists ? 2 : 0) + (B.tree ? 1 : 0);
   // short lists only (20 waves of this kernel fit a CU's LDS): the instantiation with registers for 5 waves per SIMD
-  if (variant == 0 && (int64_t)B.lds * 20 <= ctx->max_lds && !gat_opt(ctx, "GAT_NO_WPE5")) variant = 8;
+  if (variant == 0 && (int64_t)B.lds * 20 <= ctx->max_lds && !B.kn.no_wpe5) variant = 8;
   HIPCHK(ctx, hipFuncSetAttribute((const void*)kSamplerFns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.lds));
   auto launch_sampler = [&](const dim3& gs, size_t lds_, const gat::SamplerArgs& K) {
     hipLaunchKernelGGL(kSamplerFns[variant], gs, dim3(64), lds_, ctx->stream, K);
@@ -889,7 +883,7 @@ static int enqueue_sampler(gat_ctx* ctx, const gat_problem* P, const BatchPlan& 
   } else if (B.split) {
     launch_sampler(off_queue, B.lds, A);
   } else if (list_in_lds && A.big_buckets == 0 && P->h_class_start.size() > 2 &&
-             !(A.todo_count != nullptr && P->max_nws <= gat::kWsTreeMin && !gat_opt(ctx, "GAT_SIZE_CLASSES"))) {
+             !(A.todo_count != nullptr && P->max_nws <= gat::kWsTreeMin && !B.kn.size_classes_set)) {
     // (not behind k_resume_big where it takes every unit -- workspaces of up to 32 segments --: the queue then holds the
     //  per cent of units it declined, and one launch runs them side by side where five ran them class after class)
     // one launch per size class: LDS for the class's longest list
@@ -935,7 +929,7 @@ static int enqueue_placement_sampler(gat_ctx* ctx, gat_problem* P, const BatchPl
 typedef void (*contig_fn)(gat::ContigArgs);
 static const contig_fn kContigFns[2][2] = {{gat::k_contig<false>, gat::k_contig<true>},                 // [nosort][huge]
                                            {gat::k_contig<false, true>, gat::k_contig<true, true>}};
-static int enqueue_contigs(gat_ctx* ctx, gat_problem* P, int64_t nb) {
+static int enqueue_contigs(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb) {
   gat::ContigArgs B;
   B.contig_unit_off = P->d_contig_unit_off.p; B.contig_units = P->d_contig_units.p; B.units = P->d_units.p;
   B.cu_rec = P->d_cu_rec.p;
@@ -953,7 +947,7 @@ static int enqueue_contigs(gat_ctx* ctx, gat_problem* P, int64_t nb) {
   }
   const int need_max = P->h_contig_order.empty() ? 64 : P->h_contig_need[(size_t)P->h_contig_order[0]];
   size_t lds = (size_t)std::max(64, need_max) * 8 + gat::kSortScratchWords * 4;
-  const bool huge_c = (int64_t)lds > ctx->max_lds || gat_opt(ctx, "GAT_TEST_HUGE") != nullptr;   // list stays in the output slab
+  const bool huge_c = (int64_t)lds > ctx->max_lds || kn.test_huge;   // list stays in the output slab
   if (huge_c) lds = gat::kSortScratchWords * 4;
   // (units_direct: the lists only concatenated, the candidates for k_units_overlap noted: k_contig<., true>)
   const bool nosort = P->units_direct;
@@ -981,11 +975,11 @@ static int enqueue_contigs(gat_ctx* ctx, gat_problem* P, int64_t nb) {
 
 // One batch as the sequence of its stages: scratch and statistics reset, the units' sampler, fromIsochores, the statistics and
 // -- unless deferred -- the synchronisation and the batch's checks.
-static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t begin, int64_t nb,
+static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t begin, int64_t nb,
                              gat_stats* st, bool timed, const BatchOpts& o = BatchOpts()) {
   unsigned long long* h_stat = o.h_stat != nullptr ? o.h_stat : ctx->h_stat;
   P->units_direct = false;
-  int rc = ensure_scratch(ctx, P, nb);
+  int rc = ensure_scratch(ctx, P, kn, nb);
   if (rc) return rc;
   if (P->batch < nb) return set_err(ctx, GAT_ERR_MEMORY, "internal: batch %lld > scratch %lld", (long long)nb, (long long)P->batch);
   // (unit_n, contig_n and ws_stat are zeroed once when allocated: the kernels rewrite every entry of the active units
@@ -1002,7 +996,7 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_
     // (what a stage records or leaves in place of final lists, it says itself)
     ctx->k_recorded = ctx->t_recorded = false;
     P->split_ran = P->patched_contigs = P->patched_counts = false;
-    const BatchPlan B = plan_batch(ctx, P, nb, timed, o);
+    const BatchPlan B = plan_batch(ctx, kn, P, nb, timed, o);
     if (P->sampler == GAT_SAMPLER_SHIFT) rc = enqueue_shift(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) rc = enqueue_permute(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) rc = enqueue_permute_local(ctx, P, B, seed, begin);
@@ -1010,7 +1004,7 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_
     if (rc) return rc;
   }
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-  if (P->merge_contigs && P->n_contigs > 0 && (rc = enqueue_contigs(ctx, P, nb))) return rc;
+  if (P->merge_contigs && P->n_contigs > 0 && (rc = enqueue_contigs(ctx, P, kn, nb))) return rc;
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
   if (!P->h_order.empty()) {
     // (behind k_contig: on isochore problems it is k_contig that writes the statistics of the units k_tail finished)
@@ -1026,11 +1020,11 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_
   HIPCHK(ctx, hipMemcpyAsync(h_stat, P->d_stat.p, 10 * 8, hipMemcpyDeviceToHost, ctx->stream));   // (word 9: the queue's length)
   if (o.defer) return GAT_OK;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return finish_sampler_batch(ctx, P, nb, st, timed, h_stat);
+  return finish_sampler_batch(ctx, P, kn, nb, st, timed, h_stat);
 }
 
 // the checks and statistics of a sampler batch whose kernels have completed (the stream has been synchronised)
-static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, int64_t nb, gat_stats* st, bool timed, const unsigned long long* h_stat) {
+static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb, gat_stats* st, bool timed, const unsigned long long* h_stat) {
   {
     int rc;
     const int32_t flags = *reinterpret_cast<const int32_t*>(h_stat + 8);
@@ -1045,8 +1039,8 @@ static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, int64_t nb, gat_st
     if ((flags & gat::kStatusContigLds) && !(flags & gat::kStatusOverflow)) {
       // a contig's lists were longer than expected: LDS for every unit at its capacity from now on, batch repeated
       P->contig_tight = false;
-      if (layout_slab(P)) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments");
-      if ((rc = upload_layout(ctx, P))) return rc;
+      if (layout_slab(P, kn)) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments");
+      if ((rc = upload_layout(ctx, P, kn))) return rc;
       if (st) st->n_retried += nb * (int64_t)P->h_order.size();
       return kRelayout;
     }
@@ -1056,8 +1050,8 @@ static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, int64_t nb, gat_st
       //  which the reference's lists simply grow to (round 6); the per-sample slab's 2^31 segments and the device's memory end it)
       if (P->cap_scale >= (1 << 20)) return set_err(ctx, GAT_ERR_CAPACITY, "sampler slab overflow even at 2^20 x capacity");
       P->cap_scale *= 2;
-      if (layout_slab(P)) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments after growth");
-      if ((rc = upload_layout(ctx, P))) return rc;
+      if (layout_slab(P, kn)) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments after growth");
+      if ((rc = upload_layout(ctx, P, kn))) return rc;
       if (st) st->n_retried += nb * (int64_t)P->h_order.size();
       return kRelayout;
     }
@@ -1074,7 +1068,7 @@ static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, int64_t nb, gat_st
       if (st && P->units_direct) { st->n_straddle_candidates += (int64_t)uw[2]; st->n_unit_overlaps += (int64_t)uw[1]; }
     }
 #if defined(GAT_DIAG) || defined(GAT_DIAG_CONS)
-    if (const char* fn = gat_opt(ctx, "GAT_DIAG_OUT")) {
+    if (const char* fn = kn.diag_out.empty() ? nullptr : kn.diag_out.c_str()) {
       // shares of a k_sampler work unit's life per phase, summed over the batch (tools/diag_sampler.sh)
       const size_t nd = (size_t)nb * std::max(1, P->n_units) * 8;
       std::vector<unsigned long long> h(nd);
@@ -1242,6 +1236,7 @@ static int call_swap_capx(const gat_ctx* ctx, const gat_problem* P) {
 // kernels still to come (gat_sample_and_count_enqueue: the host goes on, the device samples)
 static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
   CallState& K = P->call;
+  const Knobs& kn = K.knobs;
   Counters C;
   int rc = parse_counters(ctx, K.ids, K.n_counters, C);
   if (rc) return rc;
@@ -1278,7 +1273,7 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
       L.ev_main = K.blk->ev_main[slot];
       L.units = P->d_units.p; L.ws = P->d_ws.p; L.ws_tree = P->d_ws_tree.p;
       for (int c = 0; c < P->n_contigs; ++c) L.max_units = std::max(L.max_units, P->h_contig_unit_off[(size_t)c + 1] - P->h_contig_unit_off[(size_t)c]);
-      if ((rc = launch_count(ctx, P->anno->dev, C, A, P->d_part, swap_capx,
+      if ((rc = launch_count(ctx, kn, P->anno->dev, C, A, P->d_part, swap_capx,
                              P->merge_contigs ? P->max_contig_cap : P->max_unit_cap, L))) return rc;
       if (A.cu_rec != nullptr)       // k_units_overlap's words (candidates, "not pairwise", overlaps taken off) into the batch's slot
         HIPCHK(ctx, hipMemcpyAsync(K.blk->h_stat + (size_t)slot * 16 + 10, P->d_cand_count.p + gat::kCandSlots, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -1303,35 +1298,35 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
     if (annotations_ready(P->anno)) {
       if ((rc = annotations_wait(ctx, P->anno))) return rc;
       decide_swap(P);
-      route = count_route(ctx, P->anno->dev.has_merged, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P), !P->anno->dev.per_track);
+      route = count_route(ctx, kn, P->anno->dev.has_merged, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P), !P->anno->dev.per_track);
     } else {
       const bool only_overlap = C.slot[GAT_COUNTER_SEGMENT_OVERLAP] < 0 && C.slot[GAT_COUNTER_SEGMENT_MIDOVERLAP] < 0;
       const size_t lds_merged = (size_t)P->n_tracks * 4 * (gat::kMergedThreads / gat::kWave);
       if (C.any_seg && P->n_contigs > 0 && only_overlap && P->anno->will_merge && (int64_t)lds_merged + 1024 <= ctx->max_lds &&
-          !gat_opt(ctx, "GAT_COUNT_NO_MERGED")) {
+          !kn.count_no_merged) {
         route = GAT_COUNT_KERNEL_MERGED;                       // (whatever the swap decision would be)
       } else if (P->anno->shape_known && P->anno->total_known >= 0) {
         decide_swap(P);                                        // (from the sizes announced before the build)
-        route = count_route(ctx, P->anno->will_merge, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P));
+        route = count_route(ctx, kn, P->anno->will_merge, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P));
       } else {
         if ((rc = annotations_wait(ctx, P->anno))) return rc;
         decide_swap(P);
-        route = count_route(ctx, P->anno->dev.has_merged, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P), !P->anno->dev.per_track);
+        route = count_route(ctx, kn, P->anno->dev.has_merged, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P), !P->anno->dev.per_track);
       }
     }
     // the scratch is sized while nothing of this problem is in flight; batches behind the first fit by construction
-    if (K.n_flight == 0 && (rc = ensure_scratch(ctx, P, K.S - K.enq))) return rc;
+    if (K.n_flight == 0 && (rc = ensure_scratch(ctx, P, kn, K.S - K.enq))) return rc;
     const int64_t nb = std::min<int64_t>(P->batch, K.S - K.enq);
     const int slot = K.n_flight;
     if (d_state != nullptr)
       HIPCHK(ctx, hipMemcpyAsync(d_state + GAT_MT_STATE_WORDS, d_state, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream));
     // counts alone, all of them k_count_seg's: it reads the units as k_tail left them (no final lists are written)
-    const bool records_ok = !C.any_anno && !gat_opt(ctx, "GAT_COUNT_FINAL_LISTS") &&
+    const bool records_ok = !C.any_anno && !kn.count_final_lists &&
                             (route == GAT_COUNT_KERNEL_SEG || route == GAT_COUNT_KERNEL_MERGED);
     // (k_count_merged skips empty segments: long lists may keep what a trim emptied, no compaction pass in k_resume_big)
     const bool loose_ok = records_ok && route == GAT_COUNT_KERNEL_MERGED;
     // isochore problems: the merged index takes the units' lists as they are, no k_contig (round 6)
-    const bool units_direct = loose_ok && P->merge_contigs && P->units_direct_ok && !gat_opt(ctx, "GAT_COUNT_VIA_CONTIGS");
+    const bool units_direct = loose_ok && P->merge_contigs && P->units_direct_ok && !kn.count_via_contigs;
     if (units_direct) {
       // candidates: segments with a workspace boundary in their cells, of units that have a segment reaching out of their workspace
       // -- a fraction of a per cent of a batch's segments on isochore blocks much longer than the segments --, dealt to kCandSlots
@@ -1339,7 +1334,7 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
       // anew while nothing of the problem is in flight); a region that overflows anyway has the batch repeated with four
       // times the buffer (cand_scale), and beyond 64 times through the sorted contig lists
       double est = 0.006 * (double)nb * (double)std::max<int64_t>(1, P->n_seg_total) / gat::kCandSlots + 512.0;
-      if (gat_opt(ctx, "GAT_TEST_SMALL_CAPS")) est = 1.0;        // (tests: regions that overflow, the batch repeated with larger ones)
+      if (kn.test_small_caps) est = 1.0;        // (tests: regions that overflow, the batch repeated with larger ones)
       const size_t want = (size_t)std::min(est * P->cand_scale, 1024.0 * 1024) * gat::kCandSlots;
       if (P->d_cand.n < want && K.n_flight == 0) {
         if (P->d_cand.n > 0) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier call's kernels may still read the old buffer)
@@ -1355,7 +1350,7 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
     o.records_ok = records_ok; o.loose_ok = loose_ok; o.units_direct = units_direct;
     o.serial_state = d_state;
     o.h_stat = K.blk->h_stat + (size_t)slot * 16;
-    if ((rc = run_sampler_batch(ctx, P, K.seed, K.begin + K.enq, nb, &K.local, K.timed, o))) return rc;
+    if ((rc = run_sampler_batch(ctx, P, kn, K.seed, K.begin + K.enq, nb, &K.local, K.timed, o))) return rc;
     K.nb[slot] = nb;
     K.main_rec[slot] = false;
     K.count_kernel[slot] = GAT_COUNT_KERNEL_NONE;
@@ -1392,6 +1387,7 @@ static int call_begin(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, 
                    "(keys without isochores): the counters assert (gat/SegmentList.pyx:1031)");
   if ((rc = call_block_get(ctx, &K.blk))) return rc;
   K.active = true;
+  K.knobs = read_knobs(ctx);                       // the call's: every batch of it, the ones gat_wait enqueues too
   for (int i = 0; i < n_counters; ++i) K.ids[i] = counter_ids[i];
   K.n_counters = n_counters;
   K.seed = seed; K.begin = sample_begin; K.S = sample_end - sample_begin;
@@ -1399,7 +1395,7 @@ static int call_begin(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, 
   K.done = K.enq = 0; K.n_flight = 0;
   memset(&K.local, 0, sizeof(K.local));
   // (an event behind every kernel of the sampler costs 50-60 us of a call: 2 % at 10 000 samples of config 2, 6 % at 1 250)
-  const bool times_wanted = ctx->kernel_times || gat_opt(ctx, "GAT_KERNEL_TIMES") != nullptr;
+  const bool times_wanted = ctx->kernel_times || K.knobs.kernel_times;
   K.timed = times_wanted && ctx->timed_owner == nullptr;
   if (K.timed) ctx->timed_owner = (const void*)P;
   // (the per-kernel events exist once per context: a call enqueued while another problem's timed call is in flight runs
@@ -1450,7 +1446,7 @@ static int call_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) {
     K.end_recorded = false;
     tm.lap("batches synchronised");
     for (int slot = 0; slot < K.n_flight; ++slot) {
-      rc = finish_sampler_batch(ctx, P, K.nb[slot], &K.local, K.timed, K.blk->h_stat + (size_t)slot * 16);
+      rc = finish_sampler_batch(ctx, P, K.knobs, K.nb[slot], &K.local, K.timed, K.blk->h_stat + (size_t)slot * 16);
       if (rc == kRelayout) {
         if (K.state_host != nullptr)        // (the repeated batch draws from where this one began)
           if (hipMemcpyAsync(P->d_serial.p, P->d_serial.p + GAT_MT_STATE_WORDS, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
@@ -1542,6 +1538,7 @@ static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sam
   if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
   if (P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  const Knobs kn = read_knobs(ctx);
   gat_stats local;
   memset(&local, 0, sizeof(local));
   const int64_t S = sample_end - sample_begin;
@@ -1553,12 +1550,12 @@ static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sam
   std::vector<uint2> h_slab;
   std::vector<int32_t> h_n;
   while (done < S) {
-    if ((rc = ensure_scratch(ctx, P, S - done))) return rc;
+    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
     const int64_t nb = std::min<int64_t>(P->batch, S - done);
     // (timed unless another problem's call in flight owns the context's per-kernel events)
     BatchOpts o;
     o.need_unit_lists = unit_level;
-    if ((rc = run_sampler_batch(ctx, P, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr, o)) == kRelayout) continue;
+    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr, o)) == kRelayout) continue;
     if (rc) return rc;
     const bool from_contigs = P->merge_contigs && !unit_level;
     const uint2* src = from_contigs ? P->d_cslab.p : P->final_slab();
@@ -1588,7 +1585,7 @@ static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sam
   return GAT_OK;
 }
 
-static int count_lists_on(gat_ctx* ctx, const int32_t* counter_ids, int n_counters,
+static int count_lists_on(gat_ctx* ctx, const Knobs& kn, const int32_t* counter_ids, int n_counters,
                           const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
                           const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
                           const int64_t* ws_nseg, int32_t n_groups, void* counts_host);
@@ -1605,11 +1602,11 @@ static int count_lists_impl(gat_ctx* ctx, const int32_t* counter_ids, int n_coun
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->aux_ctx == nullptr) {
     int rc = gat_ctx_create(&ctx->aux_ctx, ctx->device, nullptr);
-    if (rc == GAT_OK) ctx->aux_ctx->options_owner = ctx;              // (the knobs are its owner's)
     if (rc) return rc;
   }
   gat_ctx* x = ctx->aux_ctx;
-  const int rc = count_lists_on(x, counter_ids, n_counters, lists, list_off, n_lists, annos, anno_begin, anno_end, n_tracks, ws_nseg,
+  const Knobs kn = read_knobs(ctx);                 // (the caller's: the auxiliary context has no options of its own)
+  const int rc = count_lists_on(x, kn, counter_ids, n_counters, lists, list_off, n_lists, annos, anno_begin, anno_end, n_tracks, ws_nseg,
                                 n_groups, counts_host);
   x->stage_used = 0;                                // (count_lists_on has drained the stream before its buffers went back to the pool)
   if (rc) return set_err(ctx, rc, "%s", x->err.c_str());
@@ -1626,21 +1623,21 @@ struct CountListBufs {
   DevBuf<int64_t> d_nseg, d_out;
   DevBuf<uint32_t> d_part;
 };
-static int count_lists_body(gat_ctx* ctx, const int32_t* counter_ids, int n_counters,
+static int count_lists_body(gat_ctx* ctx, const Knobs& kn, const int32_t* counter_ids, int n_counters,
                             const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
                             const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
                             const int64_t* ws_nseg, int32_t n_groups, void* counts_host, CountListBufs& B);
-static int count_lists_on(gat_ctx* ctx, const int32_t* counter_ids, int n_counters,
+static int count_lists_on(gat_ctx* ctx, const Knobs& kn, const int32_t* counter_ids, int n_counters,
                           const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
                           const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
                           const int64_t* ws_nseg, int32_t n_groups, void* counts_host) {
   CountListBufs B;
-  const int rc = count_lists_body(ctx, counter_ids, n_counters, lists, list_off, n_lists, annos, anno_begin, anno_end, n_tracks,
+  const int rc = count_lists_body(ctx, kn, counter_ids, n_counters, lists, list_off, n_lists, annos, anno_begin, anno_end, n_tracks,
                                   ws_nseg, n_groups, counts_host, B);
   (void)hipStreamSynchronize(ctx->stream);
   return rc;
 }
-static int count_lists_body(gat_ctx* ctx, const int32_t* counter_ids, int n_counters,
+static int count_lists_body(gat_ctx* ctx, const Knobs& kn, const int32_t* counter_ids, int n_counters,
                             const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
                             const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
                             const int64_t* ws_nseg, int32_t n_groups, void* counts_host, CountListBufs& B) {
@@ -1650,8 +1647,8 @@ static int count_lists_body(gat_ctx* ctx, const int32_t* counter_ids, int n_coun
   AnnoDev& A = B.A;
   // (the merged index pays when many lists are counted against it; for a handful -- the observed counts of a run's
   //  segment tracks -- building it costs more than the per-track kernel's extra look-ups)
-  const bool want_merged = n_lists >= 16 || gat_opt(ctx, "GAT_COUNT_LISTS_MERGED") != nullptr;
-  if ((rc = build_annos(ctx, A, annos, anno_begin, anno_end, (int64_t)n_tracks * n_groups, n_groups, want_merged, false))) return rc;
+  const bool want_merged = n_lists >= 16 || kn.count_lists_merged;
+  if ((rc = build_annos(ctx, kn, A, annos, anno_begin, anno_end, (int64_t)n_tracks * n_groups, n_groups, want_merged, false))) return rc;
   for (int64_t l = 0; l < n_lists * n_groups; ++l)
     if ((rc = check_list(ctx, lists + list_off[l], list_off[l + 1] - list_off[l], "segment", l))) return rc;
   const int64_t total = list_off[n_lists * n_groups];
@@ -1693,7 +1690,7 @@ static int count_lists_body(gat_ctx* ctx, const int32_t* counter_ids, int n_coun
     for (int g = 0; g < n_groups; ++g) longest = std::max(longest, h_n[(size_t)(l * n_groups + g)]);
     CountLaunch L;
     L.ev_main = ctx->ev_main;
-    if ((rc = launch_count(ctx, A, C, K, d_part, 0, longest, L))) return rc;
+    if ((rc = launch_count(ctx, kn, A, C, K, d_part, 0, longest, L))) return rc;
   }
   HIPCHK(ctx, staged_d2h(ctx, counts_host, d_out.p, nslots * 8));
   return GAT_OK;
@@ -1739,8 +1736,8 @@ static RcclApi* rccl_api() {
     // RTLD_NOLOAD returns a handle only for a library that is loaded, by soname or by the path it was loaded from.  Failing
     // that, any object of the process that exports the entry points (RTLD_DEFAULT: a host that linked RCCL itself); only then
     // is a library loaded afresh.  GAT_RCCL_LIB names one explicitly.
-    const char* env_lib = gat_opt(nullptr, "GAT_RCCL_LIB");
-    if (env_lib && *env_lib) api.handle = dlopen(env_lib, RTLD_NOW | RTLD_LOCAL);
+    const std::string& env_lib = process_knobs().rccl_lib;
+    if (!env_lib.empty()) api.handle = dlopen(env_lib.c_str(), RTLD_NOW | RTLD_LOCAL);
     if (!api.handle)
       for (const char* name : {"librccl.so", "librccl.so.1"}) {
         api.handle = dlopen(name, RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);

@@ -25,10 +25,7 @@ std::mutex g_pool_mutex;
 std::map<int, DevPool> g_pools;
 constexpr size_t kPoolMinBytes = (size_t)1 << 20;
 size_t pool_limit() {
-  static const size_t limit = [] {
-    const char* env = gat_opt(nullptr, "GAT_POOL_BYTES");
-    return env ? (size_t)atof(env) : (size_t)96 << 30;
-  }();
+  static const size_t limit = (size_t)process_knobs().pool_bytes;
   return limit;
 }
 }  // namespace
@@ -52,16 +49,34 @@ static const std::map<std::string, std::string>& env_snapshot() {
   }();
   return snap;
 }
-const char* gat_opt(const gat_ctx* ctx, const char* key) {
+// one name: the context's value (the caller holds its options_mutex), else the process's; nullptr: not set (or set to "")
+static const char* gat_opt(const gat_ctx* ctx, const char* key) {
   if (ctx != nullptr) {
-    const gat_ctx* own = ctx->options_owner ? ctx->options_owner : ctx;
-    std::lock_guard<std::mutex> lock(own->options_mutex);
-    auto it = own->options.find(key);
-    if (it != own->options.end()) return it->second.empty() ? nullptr : it->second.c_str();   // (values live as long as the entry:
-  }                                                                                             //  set_option between calls only)
+    auto it = ctx->options.find(key);
+    if (it != ctx->options.end()) return it->second.empty() ? nullptr : it->second.c_str();
+  }
   const auto& snap = env_snapshot();
   auto it = snap.find(key);
   return it != snap.end() && !it->second.empty() ? it->second.c_str() : nullptr;
+}
+Knobs read_knobs(const gat_ctx* ctx) {
+  Knobs k;
+  std::unique_lock<std::mutex> lock;
+  if (ctx != nullptr) lock = std::unique_lock<std::mutex>(ctx->options_mutex);
+#define GAT_KNOB_FLAG(field, name) k.field = gat_opt(ctx, name) != nullptr;
+#define GAT_KNOB_INT(field, name, dflt) if (const char* v = gat_opt(ctx, name)) { k.field = atoll(v); k.field##_set = true; }
+#define GAT_KNOB_REAL(field, name, dflt) if (const char* v = gat_opt(ctx, name)) { k.field = atof(v); k.field##_set = true; }
+#define GAT_KNOB_TEXT(field, name) if (const char* v = gat_opt(ctx, name)) k.field = v;
+  GAT_KNOBS(GAT_KNOB_FLAG, GAT_KNOB_INT, GAT_KNOB_REAL, GAT_KNOB_TEXT)
+#undef GAT_KNOB_FLAG
+#undef GAT_KNOB_INT
+#undef GAT_KNOB_REAL
+#undef GAT_KNOB_TEXT
+  return k;
+}
+const Knobs& process_knobs() {
+  static const Knobs k = read_knobs(nullptr);
+  return k;
 }
 extern "C" int gat_ctx_set_option(gat_ctx* ctx, const char* key, const char* value) {
   if (!ctx || !key || strncmp(key, "GAT_", 4) != 0) return set_err(ctx, GAT_ERR_ARG, "gat_ctx_set_option: a context and a key GAT_* are needed");
@@ -71,7 +86,14 @@ extern "C" int gat_ctx_set_option(gat_ctx* ctx, const char* key, const char* val
   return GAT_OK;
 }
 extern "C" const char* gat_ctx_get_option(const gat_ctx* ctx, const char* key) {
-  return key ? gat_opt(ctx, key) : nullptr;
+  static thread_local std::string value;              // (a copy: the map's entry may go while the caller still reads)
+  if (!key) return nullptr;
+  std::unique_lock<std::mutex> lock;
+  if (ctx != nullptr) lock = std::unique_lock<std::mutex>(ctx->options_mutex);
+  const char* v = gat_opt(ctx, key);
+  if (!v) return nullptr;
+  value = v;
+  return value.c_str();
 }
 
 static size_t pool_class(size_t bytes) {
@@ -232,12 +254,11 @@ void run_with_own_threads(int64_t n, void (*fn)(void*, int64_t), void* arg, unsi
 void host_pool_select(int pool) { t_pool = pool == 1 ? 1 : 0; }
 
 void host_pool_run(int64_t n, void (*fn)(void*, int64_t), void* arg) {
-  const char* env_t = gat_opt(nullptr, "GAT_HOST_THREADS");
-  unsigned nthreads = env_t ? (unsigned)std::max(1, atoi(env_t)) : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  const Knobs& kn = process_knobs();
+  unsigned nthreads = kn.host_threads_set ? (unsigned)std::max(1, (int)kn.host_threads) : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
   nthreads = (unsigned)std::min<int64_t>(nthreads, std::max<int64_t>(1, n));
   if (nthreads <= 1 || t_in_pool_job) { for (int64_t i = 0; i < n; ++i) fn(arg, i); return; }
-  const char* env_p = gat_opt(nullptr, "GAT_HOST_POOL");
-  if (env_p && atoi(env_p) == 0) { run_with_own_threads(n, fn, arg, nthreads); return; }
+  if ((int)kn.host_pool == 0) { run_with_own_threads(n, fn, arg, nthreads); return; }
   HostPool* P;
   {
     std::lock_guard<std::mutex> lock(g_host_pool_mutex);
@@ -324,7 +345,7 @@ static void radix_sort_hi32(std::vector<uint64_t>& v, std::vector<uint64_t>& tmp
 // cut into pieces -- an overlap sum does not change -- so that no entry keeps a scan alive over more
 // than `bound` bases; first[g] is the first entry with end > g << shift or start >= g << shift, i.e. where a scan for a
 // segment starting in cell g begins.
-static int build_merged(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, const int64_t* lbeg, const int64_t* lend,
+static int build_merged(gat_ctx* ctx, const Knobs& kn, AnnoDev& A, const gat_segment* annos, const int64_t* lbeg, const int64_t* lend,
                         int64_t n_tracks, int32_t n_groups, double mean_seg_len) {
   if (n_tracks > 65535) return GAT_OK;                              // (track ids are 16 bits: such problems keep the per-track kernel)
   PrepTimer tm;
@@ -338,8 +359,7 @@ static int build_merged(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, cons
   std::vector<std::vector<uint32_t>> cf((size_t)n_groups);
   std::vector<int> c_err((size_t)n_groups, 0);
   std::vector<double> c_scan((size_t)n_groups, 0.0);                 // entries a scan is expected to pass, x the contig's entries
-  const char* env_bf = gat_opt(ctx, "GAT_MERGED_BOUND");
-  const uint64_t bfac = env_bf ? (uint64_t)std::max(1, atoi(env_bf)) : 2;
+  const uint64_t bfac = (uint64_t)std::max(1, (int)kn.merged_bound);
   auto build_one = [&](int c) {
     std::vector<uint64_t>& e = ck[(size_t)c];
     std::vector<uint64_t> tmp;
@@ -459,11 +479,10 @@ static int build_merged(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, cons
     // entries per step of a scan (k_count_merged<.., BLK>): blocks of eight where a scan passes six or more on average
     double num = 0, den = 0;
     for (int c = 0; c < n_groups; ++c) { num += c_scan[(size_t)c]; den += (double)(hz_off[(size_t)c + 1] - hz_off[(size_t)c]); }
-    const char* env_b = gat_opt(ctx, "GAT_MERGED_BLOCK");
     // short scans: the first two entries ride in the grid cell's own record (32 bytes per cell: where the cells are few
     // enough -- the records of the config-4 shape would be 160 MB, but its scans are long and take the blocks anyway)
     const int by_length = den > 0 && num / den >= 6.0 ? 8 : (n_hf <= ((size_t)64 << 20) / 32 ? 1 : 2);
-    A.merged_block = env_b ? (atoi(env_b) == 8 ? 8 : atoi(env_b) == 1 ? 1 : 2) : by_length;
+    A.merged_block = kn.merged_block_set ? ((int)kn.merged_block == 8 ? 8 : (int)kn.merged_block == 1 ? 1 : 2) : by_length;
   }
   if (A.merged_block == 1) {
     HIPCHK(ctx, A.mcell.upload_built(n_hf * 2, ctx, [&](uint4* hc) {
@@ -489,7 +508,7 @@ static int build_merged(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, cons
 // The annotation tables of the count kernels.  n_lists = n_tracks * n_groups lists, list l = annos[lbeg[l] .. lend[l])
 // (a CSR array passes off and off + 1); checked: whether the lists have to be verified normalized (the ones the library
 // merged itself are).  want_merged: build the merged index when the problem's shape asks for it (see below).
-int build_annos(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, const int64_t* lbeg, const int64_t* lend, int64_t n_lists,
+int build_annos(gat_ctx* ctx, const Knobs& kn, AnnoDev& A, const gat_segment* annos, const int64_t* lbeg, const int64_t* lend, int64_t n_lists,
                 int32_t n_groups, bool want_merged, bool checked, double mean_seg_len, bool nucleotide_only) {
   PrepTimer tm;
   A.h_off.assign((size_t)n_lists + 1, 0);
@@ -526,16 +545,13 @@ int build_annos(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, const int64_
   // would read them from global memory with four look-ups per sample segment; the index needs two: config-5 shape,
   // one track of a million intervals, count 2.86 -> 1.74 ms per 16 384 samples)
   const int64_t n_tracks = n_groups > 0 ? n_lists / n_groups : 0;
-  const char* env_mm = gat_opt(ctx, "GAT_MERGED_MIN_TRACKS");
-  const char* env_e = gat_opt(ctx, "GAT_COUNT_LDS_ENTRIES");
-  (void)env_e;
-  const bool unstaged = !count_lists_staged(ctx, A.max_m) && A.max_m > 0 && !env_mm;
-  const bool do_merged = want_merged && n_groups > 0 && (n_tracks >= (env_mm ? atoi(env_mm) : 4) || unstaged);
+  const bool unstaged = !count_lists_staged(kn, A.max_m) && A.max_m > 0 && !kn.merged_min_tracks_set;
+  const bool do_merged = want_merged && n_groups > 0 && (n_tracks >= (int)kn.merged_min_tracks || unstaged);
   // GAT_ANNOTATIONS_NUCLEOTIDE_ONLY: the per-track tables are k_count_seg's / k_count_anno's; a caller that will only ask for the
   // nucleotide counters never reaches them once the merged index exists (config 3: 2.0 of the build's 5.3 ms)
   // (... and the count launch would take it: count_route's conditions, gat_mi355.hip)
   A.per_track = !(nucleotide_only && do_merged && n_tracks * 4 * kMergedWavesHost + 1024 <= (int64_t)ctx->max_lds &&
-                  !gat_opt(ctx, "GAT_COUNT_NO_MERGED"));
+                  !kn.count_no_merged);
   if (A.per_track) {
   {
     // starts / ends / running lengths: one pass over the lists, written straight into the pinned staging buffer (three
@@ -583,8 +599,7 @@ int build_annos(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, const int64_
   std::vector<int32_t> h_shift((size_t)std::max(1, n_groups), 0), h_cells((size_t)std::max(1, n_groups), 1);
   std::vector<int64_t> h_goff((size_t)n_lists + 1, 0);
   A.max_cells = 1;
-  const char* env_g = gat_opt(ctx, "GAT_GRID_FACTOR");
-  const int gfac = env_g ? atoi(env_g) : 2;                        // about one start per two cells (measured best of 1, 2, 4, 8)
+  const int gfac = (int)kn.grid_factor;                             // about one start per two cells (measured best of 1, 2, 4, 8)
   for (int c = 0; c < n_groups; ++c) {
     uint32_t max_start = 0;
     int64_t mc = 0;
@@ -629,7 +644,7 @@ int build_annos(gat_ctx* ctx, AnnoDev& A, const gat_segment* annos, const int64_
   HIPCHK(ctx, A.off.upload(A.h_off, ctx));
   tm.lap("  annotation tables: offsets sent");
   if (do_merged) {
-    int rc = build_merged(ctx, A, annos, lbeg, lend, n_tracks, n_groups, mean_seg_len);
+    int rc = build_merged(ctx, kn, A, annos, lbeg, lend, n_tracks, n_groups, mean_seg_len);
     if (rc) return rc;
   }
   return GAT_OK;
@@ -833,14 +848,14 @@ static int64_t local_permute_tables(std::vector<uint4>& pieces, int64_t& sum_n, 
   return bad;
 }
 
-static int32_t cap_for(const gat_ctx* ctx, int64_t n) {
+static int32_t cap_for(const Knobs& kn, int64_t n) {
   int64_t c = n + n / 4 + 96;
-  if (gat_opt(ctx, "GAT_TEST_SMALL_CAPS")) c = n / 2 + 8;      // tests: force the overflow / retry path
+  if (kn.test_small_caps) c = n / 2 + 8;      // tests: force the overflow / retry path
   c = (c + 63) / 64 * 64;
   return (int32_t)c;
 }
 
-int layout_slab(gat_problem* P) {
+int layout_slab(gat_problem* P, const Knobs& kn) {
   // regions in contig-major order so that a contig's units are adjacent (k_contig output region)
   int64_t off = 0;
   P->max_unit_cap = 0;
@@ -883,7 +898,7 @@ int layout_slab(gat_problem* P) {
         ccap += P->h_units[u].slab_cap;
       }
       need = (need + 64 + 63) / 64 * 64;
-      if (gat_opt(P->ctx, "GAT_TEST_SMALL_CAPS")) need = std::max<int64_t>(64, need / 4 / 64 * 64);      // tests: force the repeat
+      if (kn.test_small_caps) need = std::max<int64_t>(64, need / 4 / 64 * 64);      // tests: force the repeat
       P->h_contig_need[c] = (int32_t)std::min<int64_t>(P->contig_tight ? need : ccap, std::max<int64_t>(64, ccap));
     }
     P->h_contig_order.resize((size_t)P->n_contigs);
@@ -904,7 +919,7 @@ int layout_slab(gat_problem* P) {
   return GAT_OK;
 }
 
-int upload_layout(gat_ctx* ctx, gat_problem* P) {
+int upload_layout(gat_ctx* ctx, gat_problem* P, const Knobs& kn) {
   HIPCHK(ctx, P->d_units.upload(P->h_units, ctx));
   {
     // a wave finds its unit with one load (units_o[blockIdx.y]) instead of order[] -> units[]
@@ -922,8 +937,7 @@ int upload_layout(gat_ctx* ctx, gat_problem* P) {
     P->h_class_start.clear();
     const int N = (int)P->h_order.size();
     int32_t first_cap = 0;
-    const char* env_c = gat_opt(ctx, "GAT_SIZE_CLASSES");
-    const int max_classes = env_c ? std::max(1, atoi(env_c)) : 6;
+    const int max_classes = std::max(1, (int)kn.size_classes);
     for (int i = 0; i < N; ++i) {
       const int32_t cap = P->h_units[(size_t)P->h_order[(size_t)i]].slab_cap;
       if (i == 0 || ((int64_t)cap * 10 <= (int64_t)first_cap * 7 && (int)P->h_class_start.size() < max_classes)) {
@@ -971,14 +985,14 @@ static int annotations_build(gat_ctx* ctx, gat_annotations* A, const gat_annotat
     std::vector<int64_t> gbeg, gend;
     if ((rc = group_annotations(ctx, &pd, buf, gbeg, gend))) return rc;
     tm.lap("annotations grouped by contig");
-    rc = build_annos(ctx, A->dev, buf.data(), gbeg.data(), gend.data(), (int64_t)d->n_tracks * d->n_contigs, d->n_contigs, true,
+    rc = build_annos(ctx, A->knobs, A->dev, buf.data(), gbeg.data(), gend.data(), (int64_t)d->n_tracks * d->n_contigs, d->n_contigs, true,
                      d->merge_contigs != 0, d->mean_segment_length, (d->flags & GAT_ANNOTATIONS_NUCLEOTIDE_ONLY) != 0);
   } else {
     if ((int64_t)d->n_tracks * d->n_contigs > 0 && (!d->anno_off || (!d->annos && d->anno_off[(int64_t)d->n_tracks * d->n_contigs] > 0)))
       return set_err(ctx, GAT_ERR_ARG, "gat_annotations_create: NULL lists");
     static const int64_t kZero[2] = {0, 0};
     const int64_t* off = d->anno_off ? d->anno_off : kZero;
-    rc = build_annos(ctx, A->dev, d->annos, off, off + 1, (int64_t)d->n_tracks * d->n_contigs, d->n_contigs, true, false,
+    rc = build_annos(ctx, A->knobs, A->dev, d->annos, off, off + 1, (int64_t)d->n_tracks * d->n_contigs, d->n_contigs, true, false,
                      d->mean_segment_length, (d->flags & GAT_ANNOTATIONS_NUCLEOTIDE_ONLY) != 0);
   }
   if (rc) return rc;
@@ -1031,9 +1045,10 @@ extern "C" int gat_annotations_create(gat_ctx* ctx, const gat_annotations_desc* 
   A->merge_groups = d->merge_contigs ? 1 : 0;
   // whether the merged index will exist is known from the shape alone when there are enough tracks (build_annos): only then
   // may a problem sample before the tables are there (the sampler's last steps depend on the count kernel that follows)
-  const char* env_mm = gat_opt(ctx, "GAT_MERGED_MIN_TRACKS");
+  A->knobs = read_knobs(ctx);
+  const Knobs& kn = A->knobs;
   const int64_t n_groups_all = (int64_t)d->n_tracks * d->n_contigs;
-  A->will_merge = d->n_contigs > 0 && d->n_tracks >= (env_mm ? atoi(env_mm) : 4) && d->n_tracks <= 65535;
+  A->will_merge = d->n_contigs > 0 && d->n_tracks >= (int)kn.merged_min_tracks && d->n_tracks <= 65535;
   A->shape_known = A->will_merge;
   if (!d->merge_contigs && d->anno_off != nullptr && n_groups_all > 0) {
     // the lists pass through as they are (a key is its contig; of several lists of a group the last one stays): their
@@ -1052,17 +1067,14 @@ extern "C" int gat_annotations_create(gat_ctx* ctx, const gat_annotations_desc* 
       int64_t total = 0, max_m = 0;
       for (int64_t g = 0; g < n_groups_all; ++g) { if (len[(size_t)g] < 0) ok = false; total += len[(size_t)g]; max_m = std::max(max_m, len[(size_t)g]); }
       if (ok) {
-        const char* env_e = gat_opt(ctx, "GAT_COUNT_LDS_ENTRIES");
-        (void)env_e;
-        const bool unstaged = !count_lists_staged(ctx, max_m) && max_m > 0 && !env_mm;
-        A->will_merge = d->n_contigs > 0 && d->n_tracks <= 65535 && (d->n_tracks >= (env_mm ? atoi(env_mm) : 4) || unstaged);
+        const bool unstaged = !count_lists_staged(kn, max_m) && max_m > 0 && !kn.merged_min_tracks_set;
+        A->will_merge = d->n_contigs > 0 && d->n_tracks <= 65535 && (d->n_tracks >= (int)kn.merged_min_tracks || unstaged);
         A->total_known = total;
         A->shape_known = true;
       }
     }
   }
-  const char* env_a = gat_opt(ctx, "GAT_ANNOTATIONS_SYNC");
-  const bool async = (d->flags & GAT_ANNOTATIONS_ASYNC) != 0 && A->shape_known && !(env_a && atoi(env_a) != 0);
+  const bool async = (d->flags & GAT_ANNOTATIONS_ASYNC) != 0 && A->shape_known && (int)kn.annotations_sync == 0;
   if (!async) {
     int rc = annotations_build(ctx, A.get(), d);
     if (rc) return rc;
@@ -1070,7 +1082,6 @@ extern "C" int gat_annotations_create(gat_ctx* ctx, const gat_annotations_desc* 
     if (ctx->building != nullptr) (void)annotations_wait(ctx, ctx->building);     // (one build at a time has the build context)
     if (ctx->build_ctx == nullptr) {
       int rc = gat_ctx_create(&ctx->build_ctx, ctx->device, nullptr);
-      if (rc == GAT_OK) ctx->build_ctx->options_owner = ctx;          // (the knobs are its owner's)
       if (rc) return rc;
     }
     ctx->build_ctx->err.clear();
@@ -1109,6 +1120,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   if (d->n_units < 0 || d->n_contigs < 0 || d->n_tracks < 0 || d->nbuckets <= 0)
     return set_err(ctx, GAT_ERR_ARG, "gat_problem_create: negative size / nbuckets <= 0");
   PrepTimer tm;
+  const Knobs kn = read_knobs(ctx);                   // the knobs of this problem's creation
   std::unique_ptr<gat_problem> P(new gat_problem());
   // (declared behind P, so it runs first on every return: the small tables' copies in flight -- stage_push_h2d -- have
   //  landed before a half-built problem's buffers go back to the pool)
@@ -1328,8 +1340,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
         const uint32_t topc = tot - 1u;                             // the largest p
         // (one cell per two segments -- GAT_GRID_CELL_SEGS -- to begin with; refdata, k_place_grid with eight tiles: 2.2 ms at
         //  two, 2.6 at eight: the halving search over a cell's span is LDS round trips on the lane's chain)
-        const char* env_cs = gat_opt(ctx, "GAT_GRID_CELL_SEGS");
-        const int64_t cell_segs = env_cs ? std::max<int64_t>(1, atoll(env_cs)) : 2;
+        const int64_t cell_segs = std::max<int64_t>(1, kn.grid_cell_segs);
         int shift = 16;
         while (shift > 0 && ((int64_t)topc >> shift) + 1 < nuw / cell_segs) --shift;
         for (;;) {
@@ -1410,7 +1421,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     len_cv2[(size_t)u] = R.cv2;
     // (SamplerShift: a segment gives one piece, two where it wraps round its window -- more only in fragmented windows, which
     //  the overflow path takes)
-    P->h_base_cap[u] = cap_for(ctx, d->sampler == GAT_SAMPLER_SEGMENTS ? std::max<int64_t>(R.nwork, d->seg_off[u + 1] - d->seg_off[u])
+    P->h_base_cap[u] = cap_for(kn, d->sampler == GAT_SAMPLER_SEGMENTS ? std::max<int64_t>(R.nwork, d->seg_off[u + 1] - d->seg_off[u])
                                   : d->sampler == GAT_SAMPLER_SHIFT ? 2 * R.nwork : R.nwork);
     if (d->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
       // (exact: the lengths and the sorted points at the top of the region when the unit is too long for LDS, the pieces --
@@ -1493,7 +1504,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
       if (U.cgrid_off < 0) { all = false; break; }
       words = std::max(words, (int32_t)h_ws_tree[(size_t)U.cgrid_off + 3]);
     }
-    P->grid_place = any && all && !gat_opt(ctx, "GAT_PLACE_NO_GRID");
+    P->grid_place = any && all && !kn.place_no_grid;
     P->grid_lds_words = words;
   }
   P->pipe_pays = 2 * work_simple >= work_all;
@@ -1506,19 +1517,18 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     size_t small_ws = 0;
     // (round 6: k_tail takes the longer workspaces too -- their position draw through the tree over the cumulated lengths, their
     //  overlaps through the position grid; GAT_TAIL_NO_LONG_WS: as before, such units are k_sampler's)
-    P->tail_long_ws = !gat_opt(ctx, "GAT_TAIL_NO_LONG_WS");
+    P->tail_long_ws = !kn.tail_no_long_ws;
     for (int32_t u : P->h_order) if (P->h_units[(size_t)u].n_ws <= gat::kTailMaxWs || P->tail_long_ws) ++small_ws;
     // (long lists: their tail places dozens of segments, not the handful k_tail keeps aside -- 0.2 % finished there on the
     //  config-4 shape -- so those problems stay with k_merge_big + k_sampler)
     P->split_path = P->sampler == GAT_SAMPLER_ANNOTATOR && !P->h_order.empty() && 2 * small_ws >= P->h_order.size() &&
-                    max_hist + max_hist / 8 <= 1024 && !gat_opt(ctx, "GAT_NO_SPLIT");
+                    max_hist + max_hist / 8 <= 1024 && !kn.no_split;
   }
   // expected raw MT19937 outputs per placement under masked rejection (mask+1)/(range+1) per draw;
   // rows = that x working segments + slack, in whole 624-word blocks.  Streams that still run out
   // are redone by k_sampler from their seed.
   {
-    const char* env = gat_opt(ctx, "GAT_SAMPLER_MODE");
-    if (env && !strcmp(env, "wave")) P->sampler_mode = 0;
+    if (kn.sampler_mode == "wave") P->sampler_mode = 0;
     if (P->sampler == GAT_SAMPLER_SHIFT) P->sampler_mode = 0;       // (k_shift: a wave per work unit, its stream in LDS)
     if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) P->sampler_mode = 0;    // (k_permute: the same)
     if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) P->sampler_mode = 0;     // (k_permute_local: the same)
@@ -1545,8 +1555,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
       if (U.hist_total > 2) { const double x = expect((uint64_t)U.hist_total - 2); e += x; addvar(x); }
       if (U.bucket > 1) { const double x = expect((uint64_t)U.bucket - 1); e += x; addvar(x); }
       if (U.ws_total > 1) { const double x = expect((uint64_t)U.ws_total - 1); e += x; addvar(x); }
-      const char* env_sl = gat_opt(ctx, "GAT_RNG_SLACK");
-      const double slack = env_sl ? atof(env_sl) : 1.0;
+      const double slack = kn.rng_slack;
       // Spread of the raw-output count of a stream: the NUMBER of placements until the unit's bases are reproduced varies
       // by cv(length) x sqrt(n) (a renewal count) and every placement costs e outputs -- that term dominates (measured on
       // config 2: 97 / 116 / 58 outputs for units of 778 / 444 / 166 segments = e x cv x sqrt(n)) -- plus the rejection
@@ -1561,16 +1570,13 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
       // out; round 3's 5-7.5 sigma + 96, sized for a redo of every placement from the seed at 0.5 ms, generated 1.4x the rows
       // that were consumed: k_rng 0.48 -> 0.43 ms on config 2, 1.07 -> 0.92 on config 3).  A long list that runs out behind
       // k_tail_big's in-place unions is still redone from its seed -- milliseconds for thousands of placements: 7.5 sigma + 96.
-      const char* env_s0 = gat_opt(ctx, "GAT_RNG_SIGMA_MIN");
-      const char* env_s1 = gat_opt(ctx, "GAT_RNG_SIGMA_MAX");
-      const char* env_tr = gat_opt(ctx, "GAT_RNG_TAIL_ROWS");
-      const double s_min = env_s0 ? atof(env_s0) : 3.5, s_max = env_s1 ? atof(env_s1) : 7.5;
+      const double s_min = kn.rng_sigma_min, s_max = kn.rng_sigma_max;
       const bool long_list = U.hist_total + U.hist_total / 8 > 1024 || P->sampler == GAT_SAMPLER_SEGMENTS;
       // (a resumed unit goes through k_sampler's wave-per-unit consolidation and tail: tens of microseconds for hundreds of
       //  segments, a few for fifty -- up to five sigma for the larger units of the split path: config 2, k_rng + k_sampler
       //  0.55 -> 0.51 ms, where 3.5 sigma throughout gave back in k_sampler what it saved in k_rng)
       const double sigmas = long_list ? s_max : std::min(std::max(s_min, 5.0), std::max(s_min, s_min - 0.5 + nplace / 130.0));
-      const double tail_rows = env_tr ? atof(env_tr) : (long_list ? 96.0 : (nplace < 128 ? 32.0 : 48.0));
+      const double tail_rows = kn.rng_tail_rows_set ? kn.rng_tail_rows : (long_list ? 96.0 : (nplace < 128 ? 32.0 : 48.0));
       const double need = e * nplace * slack + sigmas * std::sqrt(nplace * (v + 0.5 + var_n)) + tail_rows;
       int64_t rows = ((int64_t)std::ceil(need / 16.0)) * 16;        // whole k_place chunks (8) and k_rng read groups (16)
       rows = std::min<int64_t>(rows, (int64_t)gat::kMtN * 2048);
@@ -1581,7 +1587,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   P->h_contig_slab_off.assign((size_t)d->n_contigs, 0);
   P->h_count_c_off.assign((size_t)d->n_contigs, 0);
   P->h_count_n_index.assign((size_t)d->n_contigs, 0);
-  if (layout_slab(P.get())) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments");
+  if (layout_slab(P.get(), kn)) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments");
 
   HIPCHK(ctx, P->d_order.upload(P->h_order, ctx));
   {
@@ -1628,7 +1634,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     HIPCHK(ctx, P->d_ws_rec.upload(rec, ctx));
   }
   P->units_direct_ok = false;
-  if (P->merge_contigs && P->n_contigs > 0 && P->split_path && !gat_opt(ctx, "GAT_COUNT_VIA_CONTIGS")) {
+  if (P->merge_contigs && P->n_contigs > 0 && P->split_path && !kn.count_via_contigs) {
     // counting an isochore problem from the units' lists: where a segment could reach over the end of its workspace piece.
     // One bit per cell of 2^bshift bases (about two mean segment lengths): a boundary of some unit's workspace piece lies in the
     // cell -- a segment whose cells hold no boundary lies inside one piece (k_count_merged<2, .> tests the bits from its first
@@ -1661,7 +1667,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   HIPCHK(ctx, P->d_ws_tree.upload(h_ws_tree, ctx));
   HIPCHK(ctx, P->d_rank_len.upload(h_rank_len, ctx));
   HIPCHK(ctx, P->d_cws_nseg.upload(P->h_cws_nseg, ctx));
-  int rc = upload_layout(ctx, P.get());
+  int rc = upload_layout(ctx, P.get(), kn);
   if (rc) return rc;
   tm.lap("units, layout, their uploads");
   double mean_seg_len = 0.0;                         // of the segments that are placed (for the merged index's scan estimate)

@@ -204,8 +204,12 @@ int gat_ctx_synchronize(gat_ctx* ctx);
 /* The tuning / testing knobs (GAT_*) of a context.  None is needed for normal use.  A knob's value is the
  * context's own (set here: value "" = not set, whatever the environment says; NULL = back to the process's), else the process's
  * environment variable of that name AS IT WAS when the library first looked (one snapshot: nothing reads the environment on a
- * call's path, and two host threads with a context each do not see each other's settings).  Values are read where they act:
- * a knob that shapes a problem or the annotation tables at their creation, one that picks a kernel at the call. */
+ * call's path, and two host threads with a context each do not see each other's settings).  All of them are read at once, at
+ * three moments: when a problem is created, when annotation tables are created (an asynchronous build works under the values
+ * of its creation), and at the top of a call (every batch of the call, the ones gat_wait enqueues too).  A set_option acts on
+ * the problems, tables and calls started after it; it is safe at any time from the thread that owns the context.
+ * gat_ctx_get_option returns a copy kept per calling thread: the pointer is valid until that thread's next gat_ctx_get_option,
+ * whatever is set meanwhile. */
 int gat_ctx_set_option(gat_ctx* ctx, const char* key, const char* value);
 const char* gat_ctx_get_option(const gat_ctx* ctx, const char* key);   /* NULL: not set */
 /* the hipStream_t the context's work is enqueued on (the one given to gat_ctx_create, or its private stream): a host that

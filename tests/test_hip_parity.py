@@ -1078,6 +1078,77 @@ def test_knobs_are_options_of_a_context_not_the_environment(ctx):
         P.close()
 
 
+def test_a_knob_acts_on_what_starts_after_it_was_set(ctx):
+    """The knobs are read into one snapshot per problem, per annotation object and per call (gat_knobs.h): a set_option acts on
+    what is created or called after it.  The annotation tables -- built by a thread of the library while the caller goes on --
+    are those of the knobs as they were when gat_annotations_create was called, whatever the caller sets meanwhile; a problem
+    keeps the path it was created for; a knob of the call acts on the next call."""
+    from gat_amd import problem
+    _, cfg = synthetic.small_genome()
+    flat = problem.flatten_arrays(cfg["segments"], cfg["annotations"][:2], cfg["workspace"], None)
+    counters, seed, S = ["nucleotide-overlap"], 5, 16
+    want, _ = O.run_samples(flat, counters, seed, 1, 0, S)
+
+    def count(P):
+        got = P.sample_and_count(counters, seed, 0, S)
+        assert np.array_equal(got[0], want[0])
+        return P.last_stats
+
+    # two tracks take the per-track kernel; "from one track up" set for the length of the create call alone: the merged index
+    ctx.options["GAT_MERGED_MIN_TRACKS"] = "1"
+    try:
+        A = _lib.Annotations(ctx, flat, asynchronous=True)
+    finally:
+        del ctx.options["GAT_MERGED_MIN_TRACKS"]              # (back to 4 while the tables are being built)
+    P = _lib.Problem(ctx, flat, annotations=A)
+    try:
+        A.wait()
+        assert _lib.COUNT_KERNELS[count(P)["count_kernel"]] == "k_count_merged"
+    finally:
+        P.close()
+        A.close()
+    # ... and set only after the create call: no index
+    A = _lib.Annotations(ctx, flat, asynchronous=True)
+    ctx.options["GAT_MERGED_MIN_TRACKS"] = "1"
+    try:
+        P = _lib.Problem(ctx, flat, annotations=A)
+        try:
+            A.wait()
+            assert _lib.COUNT_KERNELS[count(P)["count_kernel"]] == "k_count_seg"
+        finally:
+            P.close()
+            A.close()
+    finally:
+        del ctx.options["GAT_MERGED_MIN_TRACKS"]
+    # a knob of the creation: a problem made under GAT_NO_SPLIT keeps k_sampler behind k_place (k_tail finishes no unit) when the
+    # option is gone, one made without it keeps the split path when the option comes
+    ctx.options["GAT_NO_SPLIT"] = "1"
+    try:
+        P_plain = _lib.Problem(ctx, flat)
+    finally:
+        del ctx.options["GAT_NO_SPLIT"]
+    P_split = _lib.Problem(ctx, flat)
+    try:
+        st = count(P_plain)
+        assert st["n_tail_units"] == 0 and st["lists_from_records"] == 0
+        ctx.options["GAT_NO_SPLIT"] = "1"
+        try:
+            st = count(P_split)
+        finally:
+            del ctx.options["GAT_NO_SPLIT"]
+        assert st["n_tail_units"] > 0 and st["lists_from_records"] > 0
+        # a knob of the call: set after the creation, it acts on the next call
+        ctx.options["GAT_COUNT_FINAL_LISTS"] = "1"
+        try:
+            assert count(P_split)["lists_from_records"] == 0
+        finally:
+            del ctx.options["GAT_COUNT_FINAL_LISTS"]
+        assert count(P_split)["lists_from_records"] > 0
+    finally:
+        P_plain.close()
+        P_split.close()
+
+
 def test_wave_only_sampler_mode(ctx, monkeypatch):
     """GAT_SAMPLER_MODE=wave: the stand-alone wave-per-unit sampler (own MT19937 in LDS, no k_rng / k_place),
     which is also the fallback path of the default pipeline, gives the same bits."""

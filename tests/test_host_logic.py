@@ -899,3 +899,30 @@ def test_device_counts_rows_fetch_once():
     assert np.array_equal(np.array(rows[2], dtype=np.float64), m[1, 2].astype(np.float64))
     assert counts.host is not None and counts.tensor is None
     assert np.array_equal(counts.rows(0, 3, False)[1], m[0, 1]) and list(rows[0]) == m[1, 0].tolist() and rows[1][3] == m[1, 1, 3]
+
+
+def test_knob_names_agree_between_the_table_the_design_and_the_tests():
+    """The run-time knobs are declared once (gat_amd/csrc/gat_knobs.h).  Every name of that table is described in DESIGN.md
+    section 8b, and every GAT_* name the tests set is in the table (or one of the few the Python side reads from the
+    environment): a typo in a knob's name, on either side, fails here instead of being a silent no-op."""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "gat_amd", "csrc", "gat_knobs.h")) as f:
+        table = set(re.findall(r'"(GAT_[A-Z0-9_]+)"', f.read()))
+    assert len(table) >= 50                                  # (the table was found and parsed)
+    with open(os.path.join(root, "DESIGN.md")) as f:
+        design = f.read()
+    section = design[design.index("\n## 8b."):design.index("\n## 9.")]
+    documented = set(re.findall(r"GAT_[A-Z0-9_]+", section))
+    assert sorted(table - documented) == []
+    # not in the C++ table: read by gat_amd / bench.py from the process's environment
+    python_side = {"GAT_DEVICE_STATS", "GAT_BED_TABLE_MIN_BYTES", "GAT_BED_LINE_READER", "GAT_FORCE_COLLECTIVE_PATH", "GAT_LIB_PATH",
+                   "GAT_BENCH_SHARE_GPU", "GAT_BENCH_DIST_TIMEOUT", "GAT_BENCH_DEADLINE", "GAT_BENCH_FAIL_RANK"}
+    assert sorted(python_side - documented) == []
+    used = set()
+    for path in glob.glob(os.path.join(root, "tests", "*.py")):
+        with open(path) as f:
+            used.update(re.findall(r"""["'](GAT_[A-Z0-9_]+)["']""", f.read()))
+    assert len(used & table) >= 20                           # (the tests do set knobs)
+    assert sorted(used - table - python_side) == []
