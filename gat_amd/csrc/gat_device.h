@@ -768,6 +768,125 @@ __device__ __forceinline__ bool wave_sort_bucket_regs(uint2* dst, const uint2 (&
   return true;
 }
 
+// k_consolidate's bucket sort for a list of 65..512 segments (its only caller; ONE wave per workgroup): wave_sort_bucket with
+// what the result does not need taken out.  The list comes from the registers it was loaded into (v: E rounds of 64), every
+// element is written ONCE, to base + its arrival slot -- an element alone in its bucket is final there -- and only the buckets
+// with two or more members are looked at again: the element that arrived first in such a bucket hands (base, count) to a dense
+// list (ballot + popcount), and one lane per listed bucket insertion-sorts its two to four members in place (stable: equal starts
+// stay in arrival order, as wave_sort_bucket's rank leaves them).  The cost behind the scatter follows the number of collided
+// buckets (one or two rounds of 64), not E x the wave's largest bucket.  The counters are packed two to a word (an LDS atomic adds
+// 1 or 1 << 16 and returns the slot), so NB = 1 024 buckets fit the 512 words that held 512: a third of the elements of a list of
+// 400 share a bucket instead of half, the largest bucket is ~4 instead of ~6, and a workgroup's LDS does not grow.  After the
+// prefix a bucket's halfword is base | count << 9 (base < 512, count <= 16): one 16-bit read per element gives both.
+// Returns false, seg untouched, where wave_sort_bucket does (all starts equal, a bucket beyond 16): the caller takes the network.
+template <int E, int NB, int EV>
+__device__ __forceinline__ bool wave_sort_bucket_sparse(uint2* seg, const uint2 (&v)[EV], int n, uint32_t* scratch, int lane) {
+  static_assert(E <= EV && E * kWave <= 512 && NB % (8 * kWave) == 0 && NB / 2 <= 512, "base in 9 bits, the packed counters in 512 words");
+  constexpr int Q = NB / 2 / kWave / 4;                           // 16-byte pieces of the packed histogram per lane
+  uint32_t lo = 0xffffffffu, hi = 0u;
+#pragma unroll
+  for (int r = 0; r < E; ++r)
+    if (r * kWave + lane < n) { lo = v[r].x < lo ? v[r].x : lo; hi = v[r].x > hi ? v[r].x : hi; }
+  lo = wave_min_u32(lo); hi = wave_max_u32(hi);
+  const uint32_t span = hi - lo;
+  if (span == 0) return false;
+  const bool direct = span < (uint32_t)NB;                       // fewer positions than buckets
+  // bucket = umulhi(start - lo, scale): any scale below NB 2^32 / span keeps it monotone and below NB.  A float
+  // quotient taken down by 2^-20 is below it (the conversions and the division are off by 2^-23 each at the most) and is a
+  // dozen instructions where the 64-bit division is a hundred; span >= NB here, so the quotient is below 2^32
+  const uint32_t scale = direct ? 0u : (uint32_t)((float)NB * 4294967296.0f / (float)span * (1.0f - 0x1p-20f));
+  uint4* hist4 = reinterpret_cast<uint4*>(scratch);
+#pragma unroll
+  for (int q = 0; q < Q; ++q) hist4[q * kWave + lane] = make_uint4(0u, 0u, 0u, 0u);
+  wave_sync();
+  uint32_t aux[E];                                               // the arrival slot, then what a bucket's first arrival hands on
+#pragma unroll
+  for (int r = 0; r < E; ++r) {
+    aux[r] = 0;
+    if (r * kWave + lane < n) {
+      const uint32_t d = v[r].x - lo, bk = direct ? d : __umulhi(d, scale), sh = (bk & 1u) << 4;
+      aux[r] = (atomicAdd(&scratch[bk >> 1], 1u << sh) >> sh) & 0xffffu;
+    }
+  }
+  wave_sync();
+  // exclusive prefix over the bucket counts: lane owns 8 Q consecutive buckets (4 Q words)
+  uint32_t w[4 * Q], acc = 0, over = 0;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const uint4 x = hist4[lane * Q + q];
+    w[4 * q] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w;
+  }
+#pragma unroll
+  for (int q = 0; q < 4 * Q; ++q) { acc += w[q]; over |= w[q] + 0x7fef7fefu; }   // (a count of 17 or more carries into its half's top bit)
+  const uint32_t sum = (acc & 0xffffu) + (acc >> 16);
+  uint32_t run = wave_incl_sum_u32(sum, lane) - sum;
+  if (__ballot((over & 0x80008000u) != 0u) != 0ull) return false;
+#pragma unroll
+  for (int q = 0; q < 4 * Q; ++q) {
+    const uint32_t c0 = w[q] & 0xffffu, c1 = w[q] >> 16;
+    uint32_t o = run | (c0 << 9);
+    run += c0;
+    o |= (run | (c1 << 9)) << 16;
+    run += c1;
+    w[q] = o;
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) hist4[lane * Q + q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  wave_sync();
+  const uint16_t* __restrict__ hist16 = reinterpret_cast<const uint16_t*>(scratch);
+#pragma unroll
+  for (int r = 0; r < E; ++r) {
+    if (r * kWave + lane < n) {
+      const uint32_t d = v[r].x - lo, bk = direct ? d : __umulhi(d, scale);
+      const uint32_t h = hist16[bk], slot = aux[r];
+      seg[(h & 511u) + slot] = v[r];
+      aux[r] = (slot == 0u && h >= (2u << 9)) ? h : 0u;          // first arrival of a bucket of two or more
+    }
+  }
+  wave_sync();                                                   // (the histogram has been read: its words take the list)
+  int nl = 0;
+#pragma unroll
+  for (int r = 0; r < E; ++r) {
+    const uint64_t b = __ballot(aux[r] != 0u);
+    if (aux[r] != 0u) scratch[nl + __popcll(b & lanemask_lt(lane))] = aux[r];
+    nl += __popcll(b);
+  }
+  wave_sync();
+  for (int t0 = 0; t0 < nl; t0 += kWave) {                        // (wave-uniform: one or two rounds)
+    const uint32_t h = t0 + lane < nl ? scratch[t0 + lane] : 0u;
+    const int s0 = (int)(h & 511u), cnt = (int)(h >> 9);
+    if (cnt > 4) {                                                // rare (one list in ten has such a bucket): insertion in place
+      for (int i = s0 + 1; i < s0 + cnt; ++i) {
+        const uint2 x = seg[i];
+        int j = i - 1;
+        while (j >= s0) {
+          const uint2 y = seg[j];
+          if (!(y.x > x.x)) break;
+          seg[j + 1] = y;
+          --j;
+        }
+        if (j != i - 1) seg[j + 1] = x;
+      }
+    } else {
+      // two to four members: all read together (one LDS round trip, not one per compare), ordered in registers -- adjacent
+      // exchanges on a strictly greater start, so equal starts keep their arrival order; a pad sorts behind every member
+      uint2 a[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] = k < cnt ? seg[s0 + k] : make_uint2(0xffffffffu, 0u);
+      auto cx = [&](int i) {
+        const bool sw = a[i].x > a[i + 1].x;
+        const uint2 p = a[i], q = a[i + 1];
+        a[i] = sw ? q : p; a[i + 1] = sw ? p : q;
+      };
+      cx(0); cx(1); cx(2); cx(0); cx(1); cx(0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) if (k < cnt) seg[s0 + k] = a[k];
+    }
+  }
+  wave_sync();
+  return true;
+}
+
 // bucket sort when possible (scratch available, list short enough), else the sorting network
 template <int MAXE = 8, bool MEM = false>
 __device__ __forceinline__ void wave_sort_fast(uint2* seg, int n, uint32_t* scratch, int lane) {

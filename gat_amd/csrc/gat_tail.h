@@ -40,6 +40,11 @@ constexpr int kTailMaxWalkLong = GAT_TAIL_LONG_WALK;   // ... in a fragmented wo
                                       // the CHOSEN workspace segment only (gat/Engine.pyx:331-343), what it covers of the neighbouring pieces
                                       // shows at the consolidation -- the overshoot, and with it the trim's walk, is dozens of segments there
 constexpr int kTailRows = 8;          // random rows fetched at a time
+#ifndef GAT_CONS_BUCKETS
+#define GAT_CONS_BUCKETS 1024
+#endif
+constexpr int kConsBuckets = GAT_CONS_BUCKETS;   // k_consolidate's bucket sort of 257..512 segments (packed counters: 512 words either way)
+static_assert(kConsBuckets / 2 <= kSortScratchWords, "the packed histogram lives in the sort scratch");
 
 // what k_tail hands on, per (sample, unit) by launch position.  A finished unit (state 1) is: its merged list in the
 // slab -- the overshoot trim already applied to it in place, emptied segments left as [0, 0) -- plus these extras.
@@ -184,15 +189,17 @@ __global__ __launch_bounds__(64) void k_consolidate(TailArgs T) {
     uint2 v[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) { const int i = r * kWave + lane; v[r] = i < n ? out[i] : make_uint2(0u, 0u); }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { const int i = r * kWave + lane; if (i < n) seg[i] = v[r]; }
     GAT_CPHASE(1)
-    // (round 5, measured and dropped: the bucket sort taking the list from these registers instead of from LDS, and in
-    //  straight-line form -- pads instead of `if (i < n)` around every LDS operation, selects instead of branches: the dynamic
-    //  instruction count did not fall (selects for branches, one for one), config 2 0.69 -> 0.68 ms, and the arrays that
-    //  form keeps alive took the kernel from 54 to 80 registers and k_contig from 99 to 132: config 3 1.52 -> 1.87 and
-    //  0.99 -> 1.13 ms)
-    wave_sort_fast<8>(seg, n, scratch, lane);
+    // (the bucket sort takes the list from these registers and writes every element to LDS once; only buckets with two or more
+    //  members are looked at again: wave_sort_bucket_sparse.  Round 5's straight-line form of the old sort -- pads and selects
+    //  instead of branches -- did not lower the dynamic instruction count and cost registers: DESIGN §5)
+    const bool sorted = n <= 256 ? wave_sort_bucket_sparse<4, 512>(seg, v, n, scratch, lane)
+                                 : wave_sort_bucket_sparse<8, kConsBuckets>(seg, v, n, scratch, lane);
+    if (!sorted) {                                                  // all starts equal / a crowded bucket: the network, as before
+#pragma unroll
+      for (int r = 0; r < 8; ++r) { const int i = r * kWave + lane; if (i < n) seg[i] = v[r]; }
+      wave_sort_auto(seg, n, lane);
+    }
   }
   GAT_CPHASE(2)
   const int nU = wave_merge0(seg, n, lane);
