@@ -32,7 +32,7 @@ SYMBOLS = [
     "gat_comm_unique_id", "gat_comm_create", "gat_comm_destroy", "gat_allgather_counts", "gat_null_stats",
     "gat_sample_and_count_serial", "gat_mt19937_seed", "gat_sample_and_count_enqueue", "gat_wait",
     "gat_annotations_create", "gat_annotations_destroy", "gat_annotations_wait", "gat_list_sums", "gat_problem_rng_rows",
-    "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option",
+    "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -133,6 +133,11 @@ class Stats(C.Structure):
         return dict((f, getattr(self, f)) for f, _ in self._fields_)
 
 
+# gat_compare_stats(ctx, a_dev, n_rows_a, b_dev, n_rows_b, n_samples, ia, ib, n_pairs, obs_a, obs_b, delta, pseudo_count,
+#                   lo_index, hi_index, out): include/gat_mi355.h
+COMPARE_STATS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_void_p]
+
 _LIB = None
 
 
@@ -208,6 +213,8 @@ def lib():
     L.gat_problem_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.gat_null_stats.restype = C.c_int
     L.gat_null_stats.argtypes = [vp, vp, i64, i64, vp, vp, i64, i64, vp]
+    L.gat_compare_stats.restype = C.c_int
+    L.gat_compare_stats.argtypes = COMPARE_STATS_ARGTYPES
     L.gat_comm_unique_id.restype = C.c_int
     L.gat_comm_unique_id.argtypes = [vp]
     L.gat_comm_library_preloaded.restype = C.c_int
@@ -344,6 +351,31 @@ class Context(object):
         _check(lib().gat_null_stats(self._h, C.c_void_p(counts_dev_ptr), int(n_rows), l, _p(is_double), _p(vals), lo_i, hi_i,
                                     _p(out)), self._h)
         out[:, 1] = np.sqrt(out[:, 1] / l)                # numpy.std's last two steps (sum of squares from the device)
+        return out
+
+    def h2d(self, dev_ptr, host_array):
+        host_array = np.ascontiguousarray(host_array)
+        _check(lib().gat_memcpy_h2d(self._h, C.c_void_p(dev_ptr), _p(host_array), host_array.nbytes), self._h)
+
+    def compare_stats(self, a_dev_ptr, n_rows_a, b_dev_ptr, n_rows_b, n_samples, ia, ib, obs_a, obs_b, delta, pseudo_count):
+        """per pair (ia[p], ib[p]) of rows of two device float64 matrices: null_stats' row of the pair's transformed samples
+        log((obs_a / (a + pseudo_count) + 0.0001) / (obs_b / (b + pseudo_count) + 0.0001)) + delta with val = delta, and in
+        column 6 how many of those samples are not finite (gat_compare_stats; the rows stay on the device)."""
+        l = int(n_samples)  # noqa: E741
+        offset = int(0.05 * l)
+        lo_i, hi_i = (min(offset, l - 1), max(l - offset, 0)) if offset > 0 else (0, l - 1)      # gat/Engine.pyx:1689-1696
+        hi_i = min(hi_i, l - 1)
+        ia = np.ascontiguousarray(ia, dtype=np.int32)
+        ib = np.ascontiguousarray(ib, dtype=np.int32)
+        obs_a, obs_b, delta = (np.ascontiguousarray(x, dtype=np.float64) for x in (obs_a, obs_b, delta))
+        n = len(ia)
+        assert len(ib) == len(obs_a) == len(obs_b) == len(delta) == n
+        out = np.zeros((n, 8), dtype=np.float64)
+        _check(lib().gat_compare_stats(self._h, C.c_void_p(a_dev_ptr), int(n_rows_a), C.c_void_p(b_dev_ptr), int(n_rows_b), l,
+                                       _p(ia), _p(ib), n, _p(obs_a), _p(obs_b), _p(delta), float(pseudo_count), lo_i, hi_i,
+                                       _p(out)), self._h)
+        with np.errstate(invalid="ignore"):
+            out[:, 1] = np.sqrt(out[:, 1] / l)                # numpy.std's last two steps
         return out
 
     def count_lists(self, counters, lists, list_off, n_lists, annos, anno_off, n_tracks, ws_nseg, n_groups, anno_end=None):

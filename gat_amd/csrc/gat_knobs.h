@@ -74,7 +74,8 @@ struct gat_ctx;
   INT(count_tracks_per_block, "GAT_COUNT_TRACKS_PER_BLOCK", 16)                                                              \
   INT(count_staged, "GAT_COUNT_STAGED", 1)                                                                                   \
   INT(merged_samples_per_block, "GAT_MERGED_SAMPLES_PER_BLOCK", 4)                                                           \
-  FLAG(count_lists_merged, "GAT_COUNT_LISTS_MERGED")
+  FLAG(count_lists_merged, "GAT_COUNT_LISTS_MERGED")                                                                         \
+  REAL(compare_scratch_mb, "GAT_COMPARE_SCRATCH_MB", 1024.0) /* gat_compare_stats: megabytes of transformed rows per batch */
 
 struct Knobs {
 #define GAT_KNOB_FLAG(field, name) bool field = false;

@@ -32,6 +32,7 @@
 #include "gat_permute.h"
 #include "gat_local_permute.h"
 #include "gat_stats.h"
+#include "gat_compare.h"
 
 
 #include "gat_host.h"
@@ -1848,6 +1849,30 @@ static void np_pairwise_plan(int off, int n, std::vector<int32_t>& leaf_off, std
   prog.push_back(-1);
 }
 
+// what a launch of k_null_stats over rows of n_samples needs beside the rows: the plan of the last, partial chunk on the
+// device, the dynamic LDS, the kernel's attribute set.  `who`: the entry's name for the message
+struct StatsPlan {
+  DevBuf<int32_t> d_off, d_len, d_prog;
+  int32_t n_leaves = 0, n_prog = 0;
+  size_t lds = 0;
+  void fill(gat::StatsArgs& A) const { A.leaf_off = d_off.p; A.leaf_len = d_len.p; A.n_leaves = n_leaves; A.prog = d_prog.p; A.n_prog = n_prog; }
+};
+static int stats_plan(gat_ctx* ctx, int64_t n_samples, StatsPlan& P, const char* who) {
+  std::vector<int32_t> leaf_off, leaf_len, prog;
+  const int rest = (int)(n_samples % gat::kNpChunk);
+  if (rest > 0) np_pairwise_plan(0, rest, leaf_off, leaf_len, prog);
+  if (leaf_off.empty()) { leaf_off.push_back(0); leaf_len.push_back(0); prog.push_back(0); }
+  HIPCHK(ctx, P.d_off.upload(leaf_off, ctx));
+  HIPCHK(ctx, P.d_len.upload(leaf_len, ctx));
+  HIPCHK(ctx, P.d_prog.upload(prog, ctx));
+  P.n_leaves = rest > 0 ? (int32_t)leaf_off.size() : 0;
+  P.n_prog = rest > 0 ? (int32_t)prog.size() : 0;
+  P.lds = (size_t)(n_samples / gat::kNpChunk + 1 + leaf_off.size()) * 8;
+  if ((int64_t)P.lds > ctx->max_lds - 4096) return set_err(ctx, GAT_ERR_CAPACITY, "%s: %lld samples per row", who, (long long)n_samples);
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_null_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+  return GAT_OK;
+}
+
 extern "C" int gat_null_stats(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t n_samples,
                               const uint8_t* is_double_host, const double* vals_host, int64_t lo_index, int64_t hi_index,
                               double* out_host) {
@@ -1856,34 +1881,86 @@ extern "C" int gat_null_stats(gat_ctx* ctx, const void* counts_dev, int64_t n_ro
   if (n_samples < 1 || n_samples >= ((int64_t)1 << 31) || lo_index < 0 || hi_index < 0 || lo_index >= n_samples || hi_index >= n_samples)
     return set_err(ctx, GAT_ERR_ARG, "gat_null_stats: bad sample count / positions");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::vector<int32_t> leaf_off, leaf_len, prog;
-  const int rest = (int)(n_samples % gat::kNpChunk);
-  if (rest > 0) np_pairwise_plan(0, rest, leaf_off, leaf_len, prog);
-  DevBuf<int32_t> d_off, d_len, d_prog;
+  StatsPlan plan;
   DevBuf<uint8_t> d_dbl;
   DevBuf<double> d_vals, d_out;
-  if (leaf_off.empty()) { leaf_off.push_back(0); leaf_len.push_back(0); prog.push_back(0); }
-  HIPCHK(ctx, d_off.upload(leaf_off, ctx));
-  HIPCHK(ctx, d_len.upload(leaf_len, ctx));
-  HIPCHK(ctx, d_prog.upload(prog, ctx));
+  { const int rc = stats_plan(ctx, n_samples, plan, "gat_null_stats"); if (rc != GAT_OK) return rc; }
   HIPCHK(ctx, d_dbl.upload(std::vector<uint8_t>(is_double_host, is_double_host + n_rows), ctx));
   HIPCHK(ctx, d_vals.upload(std::vector<double>(vals_host, vals_host + n_rows), ctx));
   HIPCHK(ctx, d_out.alloc((size_t)n_rows * 8));
   gat::StatsArgs A;
   A.counts = (const int64_t*)counts_dev; A.row_stride = n_samples; A.n_rows = (int32_t)n_rows; A.S = (int32_t)n_samples;
   A.is_double = d_dbl.p; A.vals = d_vals.p; A.out = d_out.p; A.lo_i = (int32_t)lo_index; A.hi_i = (int32_t)hi_index;
-  A.leaf_off = d_off.p; A.leaf_len = d_len.p; A.n_leaves = rest > 0 ? (int32_t)leaf_off.size() : 0;
-  A.prog = d_prog.p; A.n_prog = rest > 0 ? (int32_t)prog.size() : 0;
-  const size_t lds = (size_t)(n_samples / gat::kNpChunk + 1 + leaf_off.size()) * 8;
-  if ((int64_t)lds > ctx->max_lds - 4096) return set_err(ctx, GAT_ERR_CAPACITY, "gat_null_stats: %lld samples per row", (long long)n_samples);
-  HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_null_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  plan.fill(A);
   for (int64_t r0 = 0; r0 < n_rows; r0 += 1 << 20) {               // (grid x: rows)
     gat::StatsArgs B = A;
     const int64_t nr = std::min<int64_t>(n_rows - r0, 1 << 20);
     B.counts = A.counts + r0 * n_samples; B.is_double = A.is_double + r0; B.vals = A.vals + r0; B.out = A.out + r0 * 8; B.n_rows = (int32_t)nr;
-    hipLaunchKernelGGL(gat::k_null_stats, dim3((unsigned)nr), dim3(gat::kStatsThreads), lds, ctx->stream, B);
+    hipLaunchKernelGGL(gat::k_null_stats, dim3((unsigned)nr), dim3(gat::kStatsThreads), plan.lds, ctx->stream, B);
     HIPCHK(ctx, hipGetLastError());
   }
   HIPCHK(ctx, staged_d2h(ctx, out_host, d_out.p, (size_t)n_rows * 64));
+  return GAT_OK;
+}
+
+// gat-compare's statistics (include/gat_mi355.h): k_compare_rows fills a scratch block with the rows of a batch of pairs,
+// k_null_stats reads it; the rows never leave the device.  The batch is what the call's GAT_COMPARE_SCRATCH_MB holds.
+extern "C" int gat_compare_stats(gat_ctx* ctx, const void* a_dev, int64_t n_rows_a, const void* b_dev, int64_t n_rows_b,
+                                 int64_t n_samples, const int32_t* ia_host, const int32_t* ib_host, int64_t n_pairs,
+                                 const double* obs_a_host, const double* obs_b_host, const double* delta_host,
+                                 double pseudo_count, int64_t lo_index, int64_t hi_index, double* out_host) {
+  if (!ctx || !a_dev || !b_dev || !ia_host || !ib_host || !obs_a_host || !obs_b_host || !delta_host || !out_host)
+    return set_err(ctx, GAT_ERR_ARG, "gat_compare_stats: NULL argument");
+  if (n_pairs <= 0) return GAT_OK;
+  if (n_samples < 1 || n_samples >= ((int64_t)1 << 31) - 1 || lo_index < 0 || hi_index < 0 || lo_index >= n_samples || hi_index >= n_samples)
+    return set_err(ctx, GAT_ERR_ARG, "gat_compare_stats: bad sample count / positions");
+  if (n_rows_a < 1 || n_rows_b < 1 || n_rows_a >= ((int64_t)1 << 31) || n_rows_b >= ((int64_t)1 << 31))
+    return set_err(ctx, GAT_ERR_ARG, "gat_compare_stats: bad row counts");
+  for (int64_t p = 0; p < n_pairs; ++p)
+    if (ia_host[p] < 0 || ia_host[p] >= n_rows_a || ib_host[p] < 0 || ib_host[p] >= n_rows_b)
+      return set_err(ctx, GAT_ERR_ARG, "gat_compare_stats: pair %lld names row (%d, %d) of (%lld, %lld)", (long long)p, ia_host[p],
+                     ib_host[p], (long long)n_rows_a, (long long)n_rows_b);
+  const Knobs kn = read_knobs(ctx);                 // the call's
+  if (!(kn.compare_scratch_mb > 0.0)) return set_err(ctx, GAT_ERR_ARG, "gat_compare_stats: GAT_COMPARE_SCRATCH_MB must be positive");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int64_t stride = (n_samples + 1) & ~(int64_t)1;             // even: every scratch row starts on a 16-byte boundary
+  const double budget_rows = kn.compare_scratch_mb * 1048576.0 / (double)(stride * 8);
+  const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_pairs, 1 << 20), budget_rows >= 1048576.0 ? (1 << 20) : (int64_t)budget_rows));
+  StatsPlan plan;
+  { const int rc = stats_plan(ctx, n_samples, plan, "gat_compare_stats"); if (rc != GAT_OK) return rc; }
+  DevBuf<int32_t> d_ia, d_ib;
+  DevBuf<double> d_oa, d_ob, d_delta, d_rows, d_out;
+  DevBuf<uint8_t> d_dbl;
+  DevBuf<uint32_t> d_bad;
+  HIPCHK(ctx, d_ia.upload(std::vector<int32_t>(ia_host, ia_host + n_pairs), ctx));
+  HIPCHK(ctx, d_ib.upload(std::vector<int32_t>(ib_host, ib_host + n_pairs), ctx));
+  HIPCHK(ctx, d_oa.upload(std::vector<double>(obs_a_host, obs_a_host + n_pairs), ctx));
+  HIPCHK(ctx, d_ob.upload(std::vector<double>(obs_b_host, obs_b_host + n_pairs), ctx));
+  HIPCHK(ctx, d_delta.upload(std::vector<double>(delta_host, delta_host + n_pairs), ctx));
+  HIPCHK(ctx, d_dbl.upload(std::vector<uint8_t>((size_t)batch, (uint8_t)1), ctx));
+  HIPCHK(ctx, d_rows.alloc((size_t)batch * (size_t)stride));
+  HIPCHK(ctx, d_out.alloc((size_t)n_pairs * 8));
+  HIPCHK(ctx, d_bad.alloc((size_t)n_pairs));
+  gat::CompareArgs C;
+  C.a = (const double*)a_dev; C.b = (const double*)b_dev; C.S = (int32_t)n_samples; C.pseudo_count = pseudo_count;
+  C.rows = d_rows.p; C.row_stride = stride;
+  gat::StatsArgs A;
+  A.counts = (const int64_t*)d_rows.p; A.row_stride = stride; A.S = (int32_t)n_samples; A.is_double = d_dbl.p;
+  A.lo_i = (int32_t)lo_index; A.hi_i = (int32_t)hi_index;
+  plan.fill(A);
+  for (int64_t p0 = 0; p0 < n_pairs; p0 += batch) {                 // (one stream: a batch's rows are read before the next one's are written)
+    const int64_t np = std::min<int64_t>(batch, n_pairs - p0);
+    C.n_pairs = (int32_t)np; C.ia = d_ia.p + p0; C.ib = d_ib.p + p0; C.obs_a = d_oa.p + p0; C.obs_b = d_ob.p + p0; C.delta = d_delta.p + p0;
+    C.n_nonfinite = d_bad.p + p0;
+    hipLaunchKernelGGL(gat::k_compare_rows, dim3((unsigned)np), dim3(gat::kCompareThreads), 0, ctx->stream, C);
+    HIPCHK(ctx, hipGetLastError());
+    A.n_rows = (int32_t)np; A.vals = d_delta.p + p0; A.out = d_out.p + p0 * 8;
+    hipLaunchKernelGGL(gat::k_null_stats, dim3((unsigned)np), dim3(gat::kStatsThreads), plan.lds, ctx->stream, A);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  HIPCHK(ctx, staged_d2h(ctx, out_host, d_out.p, (size_t)n_pairs * 64));
+  std::vector<uint32_t> bad((size_t)n_pairs);
+  HIPCHK(ctx, staged_d2h(ctx, bad.data(), d_bad.p, (size_t)n_pairs * 4));
+  for (int64_t p = 0; p < n_pairs; ++p) out_host[p * 8 + 6] = (double)bad[(size_t)p];
   return GAT_OK;
 }

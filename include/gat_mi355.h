@@ -369,6 +369,26 @@ int gat_null_stats(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t
                    const uint8_t* is_double_host, const double* vals_host, int64_t lo_index, int64_t hi_index,
                    double* out_host);
 
+/* ---- gat-compare: the null distribution of a fold-change difference, and its statistics -------
+ * What scripts/gat-compare.py:214-231 of the reference forms for a pair (data1, data2) of result rows read from counts
+ * files, and what AnnotatorResult then takes from it, without the row ever existing on the host.  a_dev / b_dev: DEVICE
+ * matrices [n_rows_a][n_samples] / [n_rows_b][n_samples] of float64 sampled counts (the same matrix when annotations of one
+ * run are compared).  Pair p = rows (ia[p], ib[p]); for every sample i, in this order of IEEE operations,
+ *     fc1 = obs_a[p] / (a[ia[p]][i] + pseudo_count) + 0.0001,  fc2 = obs_b[p] / (b[ib[p]][i] + pseudo_count) + 0.0001,
+ *     row[i] = log(fc1 / fc2) + delta[p]
+ * (the additions and divisions are numpy's bit for bit; the device's log and numpy's each are good to about an ulp and not
+ * the same function).  out_host[8p..8p+8) = what gat_null_stats returns for that row with vals = delta[p] -- { mean, sum of
+ * squared deviations, the values at sorted positions lo_index and hi_index, samples < delta[p], samples == delta[p] } --
+ * then, slot 6, the number of samples of the row that are not finite (a zero denominator: inf, inf / inf: nan, as numpy
+ * gives them; the other slots of such a pair are not to be used -- the host recomputes it), and 0.  Pairs are worked on in
+ * batches whose rows fit GAT_COMPARE_SCRATCH_MB megabytes of device scratch (a context option, default 1024; read once at
+ * the top of the call).  GAT_ERR_ARG: a NULL argument, a row index outside its matrix, bad positions; GAT_ERR_CAPACITY:
+ * more samples per row than k_null_stats takes. */
+int gat_compare_stats(gat_ctx* ctx, const void* a_dev, int64_t n_rows_a, const void* b_dev, int64_t n_rows_b,
+                      int64_t n_samples, const int32_t* ia_host, const int32_t* ib_host, int64_t n_pairs,
+                      const double* obs_a_host, const double* obs_b_host, const double* delta_host,
+                      double pseudo_count, int64_t lo_index, int64_t hi_index, double* out_host);
+
 /* ---- multi-GPU: the one collective of the path ---------------------------------------------
  * Replaces the result collation of the reference's process pool (gat/__init__.py:681-700, :770-774):
  * every rank has computed the columns of its own contiguous sample range (gat_sample_and_count with
