@@ -10,7 +10,7 @@ import numpy as np
 from . import intervals, problem, synthetic            # noqa: F401
 from . import io as IO                                   # noqa: F401
 from . import stats as Stats                             # noqa: F401
-from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation,  # noqa: F401
+from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerBruteForce,  # noqa: F401
                      Counter, computeCountsAll, overlap_sizes, CounterNucleotideOverlap, CounterNucleotideDensity, CounterSegmentOverlap,
                      CounterSegmentMidpointOverlap, CounterAnnotationOverlap, CounterAnnotationMidpointOverlap,
                      UnconditionalWorkspace, ConditionalWorkspaceCooccurance, ConditionalWorkspaceCentered,
@@ -182,6 +182,8 @@ def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, 
     flat["sampler"] = getattr(sampler, "kind", 0)
     if flat["sampler"] == SamplerShift.kind:
         flat["shift_radius"], flat["shift_extension"] = sampler.radius, sampler.extension
+    if flat["sampler"] == SamplerBruteForce.kind:
+        flat["brute_ntries_inner"], flat["brute_ntries_outer"] = sampler.ntries_inner, sampler.ntries_outer
     job.flat = flat
     names = job.names
     if flat["n_contigs"] == 0:
@@ -458,9 +460,10 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
             dist.broadcast_object_list(box, src=0)
             seed = int(box[0])
     conditional = getattr(workspace_generator, "is_conditional", False)
-    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation)):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation and "
-                                  "SamplerLocalPermutation run on the GPU path")
+    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation,
+                                SamplerBruteForce)):
+        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
+                                  "SamplerLocalPermutation and SamplerBruteForce run on the GPU path")
     mt_state = None
     if reference_stream and isinstance(sampler, SamplerShift):
         raise NotImplementedError("reference_stream: SamplerShift runs on the per-unit streams only")
@@ -468,6 +471,8 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
         raise NotImplementedError("reference_stream: SamplerGlobalPermutation runs on the per-unit streams only")
     if reference_stream and isinstance(sampler, SamplerLocalPermutation):
         raise NotImplementedError("reference_stream: SamplerLocalPermutation runs on the per-unit streams only")
+    if reference_stream and isinstance(sampler, SamplerBruteForce):
+        raise NotImplementedError("reference_stream: SamplerBruteForce runs on the per-unit streams only")
     if reference_stream:
         # the reference's own stream: numpy.random.seed(seed) once (scripts/gat-run.py:267-271), every work unit of every
         # segment track drawing from it in order -- an unpatched reference's table, number for number, at one stream's speed
@@ -652,12 +657,16 @@ def fromCounts(filename):
 # asks for it, so the command line takes --sampler=local-permutation.
 SAMPLERS = ("annotator", "segments", "shift", "global-permutation")
 ALL_SAMPLERS = SAMPLERS + ("local-permutation",)
+# ... and CLI_SAMPLERS brute-force, the last sampler the reference's command line can start (its `uniform` cannot: gat-run.py
+# builds SamplerUniform without its increment): what scripts/gat-run.py passes.  A run whose sampling does not converge
+# ends in the reference's ValueError (DESIGN §5 "k_brute_force").
+CLI_SAMPLERS = ALL_SAMPLERS + ("brute-force",)
 
 
 def buildParser(usage=None, samplers=SAMPLERS):
     """gat command line parser: the options of the reference's buildParser (gat/__init__.py:54-429)
     that concern the accelerated path, with the same names, destinations and defaults.  `samplers`: the choices of
-    --sampler (SAMPLERS, or ALL_SAMPLERS as scripts/gat-run.py passes)."""
+    --sampler (SAMPLERS, ALL_SAMPLERS, or CLI_SAMPLERS as scripts/gat-run.py passes)."""
     import optparse
     parser = optparse.OptionParser(version="%prog (gat_amd " + __version__ + ")", usage=usage)
     g = optparse.OptionGroup(parser, "Input options")
@@ -783,6 +792,8 @@ def fromSegments(options, args=None):
         sampler = SamplerGlobalPermutation()             # scripts/gat-run.py:137-138
     elif options.sampler == "local-permutation":
         sampler = SamplerLocalPermutation()              # scripts/gat-run.py:135-136
+    elif options.sampler == "brute-force":
+        sampler = SamplerBruteForce()                    # scripts/gat-run.py:139-140 (no bucket arguments: bucket_size 1)
     else:
         raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
     counters = []

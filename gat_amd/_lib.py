@@ -38,6 +38,7 @@ SYMBOLS = [
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
 # gat_problem_desc::sampler (GAT_SAMPLER_*)
 SAMPLER_ANNOTATOR, SAMPLER_SEGMENTS, SAMPLER_SHIFT, SAMPLER_GLOBAL_PERMUTATION, SAMPLER_LOCAL_PERMUTATION = 0, 1, 2, 3, 4
+SAMPLER_BRUTE_FORCE = 5
 
 
 def mt19937_seed(seed):
@@ -77,6 +78,8 @@ class ProblemDesc(C.Structure):
         ("annotations", C.c_void_p),
         ("shift_radius", C.c_double),
         ("shift_extension", C.c_int32),
+        ("brute_ntries_inner", C.c_int32),
+        ("brute_ntries_outer", C.c_int32),
     ]
 
 
@@ -127,6 +130,8 @@ class Stats(C.Structure):
         ("kernel_times", C.c_int64),
         ("n_queued_units", C.c_int64),
         ("n_empty_windows", C.c_int64),
+        ("n_restarts", C.c_int64),
+        ("n_unconverged", C.c_int64),
     ]
 
     def asdict(self):
@@ -570,6 +575,8 @@ class Problem(object):
         d.sampler = int(flat.get("sampler", 0))
         d.shift_radius = float(flat.get("shift_radius", 2.0))
         d.shift_extension = int(flat.get("shift_extension", 0))
+        d.brute_ntries_inner = int(flat.get("brute_ntries_inner", 0))
+        d.brute_ntries_outer = int(flat.get("brute_ntries_outer", 0))
         assert len(keep["seg_off"]) == d.n_units + 1 and len(keep["ws_off"]) == d.n_units + 1
         assert len(keep["cws_nseg"]) == d.n_contigs
         if annotations is not None:
@@ -612,10 +619,10 @@ class Problem(object):
         """the batch seam, results left on the device ([counter][track][sample] 8-byte slots)."""
         ids = np.array([COUNTER_IDS[c] for c in counters], dtype=np.int32)
         st = Stats()
-        _check(lib().gat_sample_and_count(self.ctx._h, self._h, _p(ids), len(ids), int(seed) & 0xFFFFFFFF,
-                                          int(sample_begin), int(sample_end), C.c_void_p(counts_dev_ptr), C.byref(st)),
-               self.ctx._h)
-        self.last_stats = st.asdict()
+        rc = lib().gat_sample_and_count(self.ctx._h, self._h, _p(ids), len(ids), int(seed) & 0xFFFFFFFF,
+                                        int(sample_begin), int(sample_end), C.c_void_p(counts_dev_ptr), C.byref(st))
+        self.last_stats = st.asdict()           # (of a failed call too: SamplerBruteForce's n_unconverged)
+        _check(rc, self.ctx._h)
         return self.last_stats
 
     def enqueue(self, counters, seed, sample_begin, sample_end, counts_dev_ptr):
@@ -628,8 +635,9 @@ class Problem(object):
     def wait(self):
         """second half (gat_wait): blocks until the call has completed, raises what sample_and_count_device would have"""
         st = Stats()
-        _check(lib().gat_wait(self.ctx._h, self._h, C.byref(st)), self.ctx._h)
+        rc = lib().gat_wait(self.ctx._h, self._h, C.byref(st))
         self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
         return self.last_stats
 
     def sample_and_count(self, counters, seed, sample_begin, sample_end):
@@ -682,7 +690,7 @@ class Problem(object):
             if rc == -3 and off[-1] > cap:
                 cap = int(off[-1])
                 continue
+            self.last_stats = st.asdict()
             _check(rc, self.ctx._h)
             break
-        self.last_stats = st.asdict()
         return out[: off[-1]].copy(), off

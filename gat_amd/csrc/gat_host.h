@@ -367,6 +367,8 @@ struct gat_problem {
   DevBuf<uint32_t> d_lperm_len;
   int32_t lperm_max_n = 0;               // ... the most working segments of one piece, the longest raw list (sum of 2n) of a unit
   int64_t lperm_max_out = 0;
+  // GAT_SAMPLER_BRUTE_FORCE: SamplerBruteForce(ntries_inner, ntries_outer) (the desc's 0 replaced by the reference's 100 / 10)
+  int32_t brute_ntries_inner = 100, brute_ntries_outer = 10;
   gat_annotations* anno = nullptr;       // the annotation tables: its own (made from the lists of its desc) or a shared object
   // per-batch scratch
   int64_t batch = 0;

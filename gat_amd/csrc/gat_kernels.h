@@ -1932,18 +1932,9 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
       full_units = 1;
       const int target = Up->n_target;
       for (int x = 0; x < target; ++x) {
-        uint32_t r = 1;
-        if (hist_total > 1) r = 1u + rng_range(rng, hist_total - 2u, lane);
-        uint32_t len_u = rank_len[r] * bucket;
-        if (bucket > 1) len_u += rng_range(rng, bucket - 1u, lane);
-        const int32_t length = (int32_t)len_u;
-        const uint32_t p = rng_range(rng, ws_total - 1u, lane);
-        const int k = ws_bisect(p);
-        const uint2 chosen = ws[k];
-        int32_t sampling_start = (int32_t)chosen.x - length + 1;
-        if (k > 0) { const int32_t pe = (int32_t)ws[k - 1].y; sampling_start = pe > sampling_start ? pe : sampling_start; }
-        const uint32_t range = chosen.y - 1u - (uint32_t)sampling_start;
-        const int32_t q = sampling_start + (int32_t)rng_range(rng, range, lane);
+        const int32_t length = (int32_t)hist_sample(rng, hist_total, rank_len, bucket, lane);
+        int k;
+        const int32_t q = ws_sample(rng, ws, ws_total, length, ws_bisect, lane, k);
         if (nout >= cap) { status |= kStatusOverflow; break; }
         if (lane == 0) out[nout] = make_uint2((uint32_t)(q > 0 ? q : 0), (uint32_t)(q + length));
         nout++;

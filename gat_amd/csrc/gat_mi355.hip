@@ -31,6 +31,7 @@
 #include "gat_shift.h"
 #include "gat_permute.h"
 #include "gat_local_permute.h"
+#include "gat_brute_force.h"
 #include "gat_stats.h"
 #include "gat_compare.h"
 
@@ -586,6 +587,21 @@ static int enqueue_permute_local(gat_ctx* ctx, gat_problem* P, const BatchPlan& 
                               (size_t)(gat::kMtLdsWords + 2 * gat::kLpBatchDraws + words) * 4);
 }
 
+// SamplerBruteForce: k_brute_force
+static int enqueue_brute_force(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
+  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerBruteForce has no reference-stream mode");
+  gat::BruteForceArgs H;
+  memset(&H, 0, sizeof(H));
+  // (LDS for the first kBruteLdsCap accepted segments -- the kernel is a chain of dependent draws, hidden by the waves a CU
+  //  holds, and LDS is what bounds them; a longer list goes on in the unit's slab region)
+  H.lds_cap = std::max<int32_t>(64, std::min<int32_t>(P->max_unit_cap, gat::kBruteLdsCap));
+  H.ntries_inner = P->brute_ntries_inner; H.ntries_outer = P->brute_ntries_outer;
+  H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.rank_len = P->d_rank_len.p;
+  H.stat = P->d_stat.p;
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p + gat::kBruteFirstWord, 0, 8, ctx->stream));
+  return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_brute_force, H, (size_t)(gat::kMtLdsWords + 2 * (size_t)H.lds_cap) * 4);
+}
+
 // the arguments every kernel of SamplerAnnotator / SamplerSegments starts from
 static int base_sampler_args(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin, gat::SamplerArgs& A) {
   memset(&A, 0, sizeof(A));
@@ -1001,6 +1017,7 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
     if (P->sampler == GAT_SAMPLER_SHIFT) rc = enqueue_shift(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) rc = enqueue_permute(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) rc = enqueue_permute_local(ctx, P, B, seed, begin);
+    else if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) rc = enqueue_brute_force(ctx, P, B, seed, begin);
     else rc = enqueue_placement_sampler(ctx, P, B, seed, begin, A);
     if (rc) return rc;
   }
@@ -1019,6 +1036,8 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
     fprintf(stderr, "round broken by: empty segment %llu, placeholder neighbour %llu, both neighbours and more %llu, two on the right %llu, two logged %llu, logged + neighbour %llu\n", w[10], w[11], w[12], w[13], w[14], w[15]); }
 #endif
   HIPCHK(ctx, hipMemcpyAsync(h_stat, P->d_stat.p, 10 * 8, hipMemcpyDeviceToHost, ctx->stream));   // (word 9: the queue's length)
+  if (P->sampler == GAT_SAMPLER_BRUTE_FORCE)                                                       // (the first unit that did not converge)
+    HIPCHK(ctx, hipMemcpyAsync(h_stat + gat::kBruteFirstWord, P->d_stat.p + gat::kBruteFirstWord, 8, hipMemcpyDeviceToHost, ctx->stream));
   if (o.defer) return GAT_OK;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return finish_sampler_batch(ctx, P, kn, nb, st, timed, h_stat);
@@ -1055,6 +1074,17 @@ static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, i
       if ((rc = upload_layout(ctx, P, kn))) return rc;
       if (st) st->n_retried += nb * (int64_t)P->h_order.size();
       return kRelayout;
+    }
+    if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) {
+      // (behind the overflow check: a batch that is repeated is counted once, as it stands in the end)
+      const int64_t unconv = (int64_t)(stat[6] >> gat::kBruteUnconvShift);
+      if (st) { st->n_restarts += (int64_t)(stat[6] & ((1ull << gat::kBruteUnconvShift) - 1ull)); st->n_unconverged += unconv; }
+      if (unconv) {
+        const unsigned long long first = ~h_stat[gat::kBruteFirstWord];
+        return set_err(ctx, GAT_ERR_VALUE, "SamplerBruteForce: sampling did not converge: sample %lld, unit %d used up its %d passes of %d tries "
+                                           "(%lld work units of the batch; gat/Engine.pyx:868-869)", (long long)(first >> 32), (int)(first & 0xffffffffull),
+                       (int)P->brute_ntries_outer, (int)P->brute_ntries_inner, (long long)unconv);
+      }
     }
     {
       // k_units_overlap: overlaps between the units' lists that were not pairwise, or more candidates than the buffer holds --
@@ -1427,7 +1457,8 @@ static int call_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) {
   CallState& K = P->call;
   if (!K.active) return set_err(ctx, GAT_ERR_ARG, "gat_wait: no call in flight on this problem");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); call_end(ctx, P); return code; };
+  // (a failed call returns no counts; its statistics as far as they go are written: SamplerBruteForce's n_unconverged)
+  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); if (stats) *stats = K.local; call_end(ctx, P); return code; };
   PrepTimer tm;
   int rc;
   if (K.count_pending && (rc = call_enqueue_more(ctx, P, true))) return fail(rc);   // (the tables were still being built)
@@ -1506,6 +1537,8 @@ extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const i
     return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerGlobalPermutation runs on the per-unit streams only");
   if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION)
     return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerLocalPermutation runs on the per-unit streams only");
+  if (P->sampler == GAT_SAMPLER_BRUTE_FORCE)
+    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerBruteForce runs on the per-unit streams only");
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
   const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state);
   return rc ? rc : call_wait(ctx, P, stats);
@@ -1557,7 +1590,7 @@ static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sam
     BatchOpts o;
     o.need_unit_lists = unit_level;
     if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr, o)) == kRelayout) continue;
-    if (rc) return rc;
+    if (rc) { if (stats) *stats = local; return rc; }
     const bool from_contigs = P->merge_contigs && !unit_level;
     const uint2* src = from_contigs ? P->d_cslab.p : P->final_slab();
     const int32_t* nsrc = from_contigs ? P->d_contig_n.p : P->d_unit_n.p;

@@ -1131,8 +1131,16 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   P->n_tracks = d->n_tracks;
   P->merge_contigs = d->merge_contigs ? 1 : 0;
   if (d->sampler != GAT_SAMPLER_ANNOTATOR && d->sampler != GAT_SAMPLER_SEGMENTS && d->sampler != GAT_SAMPLER_SHIFT &&
-      d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION && d->sampler != GAT_SAMPLER_LOCAL_PERMUTATION)
+      d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION && d->sampler != GAT_SAMPLER_LOCAL_PERMUTATION &&
+      d->sampler != GAT_SAMPLER_BRUTE_FORCE)
     return set_err(ctx, GAT_ERR_ARG, "unknown sampler %d", d->sampler);
+  if (d->sampler == GAT_SAMPLER_BRUTE_FORCE) {
+    if (d->brute_ntries_inner < 0 || d->brute_ntries_outer < 0)
+      return set_err(ctx, GAT_ERR_VALUE, "SamplerBruteForce: ntries_inner %d and ntries_outer %d must be >= 0 (0: the reference's 100 / 10)",
+                     (int)d->brute_ntries_inner, (int)d->brute_ntries_outer);
+    if (d->brute_ntries_inner) P->brute_ntries_inner = d->brute_ntries_inner;
+    if (d->brute_ntries_outer) P->brute_ntries_outer = d->brute_ntries_outer;
+  }
   if (d->sampler == GAT_SAMPLER_SHIFT && !(d->shift_radius >= 0.0 && d->shift_radius <= 1e9))
     return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: radius %g must be >= 0", d->shift_radius);
   if (d->sampler == GAT_SAMPLER_SHIFT && d->shift_extension < 0)
@@ -1371,6 +1379,13 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
       }
     }
     U.ltotal = (int32_t)ltotal;
+    if (d->sampler == GAT_SAMPLER_BRUTE_FORCE) {
+      // remaining = segments.sum() (gat/Engine.pyx:830): ALL of the unit's segments, neither filtered nor intersected, the
+      // uint32 sum (gat/SegmentList.pyx:1607) assigned to an int32
+      uint32_t all = 0;
+      for (int64_t i = 0; i < nus; ++i) all += us[i].end - us[i].start;
+      U.ltotal = (int32_t)all;
+    }
     U.n_target = (int32_t)nus;                       // SamplerSegments places len(segments) segments
     if (d->sampler == GAT_SAMPLER_SHIFT) shift_windows(R.shift, us, nus, uw, nuw, R.cdf, d->shift_radius, d->shift_extension);
     if (d->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
@@ -1423,6 +1438,13 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     //  the overflow path takes)
     P->h_base_cap[u] = cap_for(kn, d->sampler == GAT_SAMPLER_SEGMENTS ? std::max<int64_t>(R.nwork, d->seg_off[u + 1] - d->seg_off[u])
                                   : d->sampler == GAT_SAMPLER_SHIFT ? 2 * R.nwork : R.nwork);
+    if (d->sampler == GAT_SAMPLER_BRUTE_FORCE) {
+      // (every accepted segment covers a base of the workspace, so `remaining` bounds the list; expected are about as many
+      //  segments as the unit has -- more where some of them lie outside the workspace, whose bases are sampled too: twice
+      //  the unit's segments to begin with, the overflow path beyond)
+      const int64_t nall = d->seg_off[u + 1] - d->seg_off[u];
+      P->h_base_cap[u] = cap_for(kn, std::min<int64_t>(std::max<int32_t>(U.ltotal, 0), 2 * nall));
+    }
     if (d->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
       // (exact: the lengths and the sorted points at the top of the region when the unit is too long for LDS, the pieces --
       //  at most n + |W| -- below them)
@@ -1532,6 +1554,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     if (P->sampler == GAT_SAMPLER_SHIFT) P->sampler_mode = 0;       // (k_shift: a wave per work unit, its stream in LDS)
     if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) P->sampler_mode = 0;    // (k_permute: the same)
     if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) P->sampler_mode = 0;     // (k_permute_local: the same)
+    if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) P->sampler_mode = 0;           // (k_brute_force: the same)
     auto expect = [](uint64_t range) {
       if (range == 0) return 0.0;
       uint64_t m = range; m |= m >> 1; m |= m >> 2; m |= m >> 4; m |= m >> 8; m |= m >> 16; m |= m >> 32;

@@ -61,6 +61,8 @@ enum : int32_t {
                          // buffer holds): host repeats the batch through k_contig and keeps to it for the problem
   kStatusCoordRange = 32, // k_permute_local: a start or end of the walk beyond 2^31 - 1, where the reference's assignment to its C int
                          // raises OverflowError (gat/Engine.pyx:1208, :1212)
+  // (SamplerBruteForce's "sampling did not converge" is no status bit: it is counted, and the first such work unit named, in
+  //  the batch's statistics words -- gat_brute_force.h)
   kStatusContigLds = 8,  // k_contig: a contig's lists exceed the LDS the launch was given (sized for what is expected,
                          // not for every unit at its capacity): host repeats the batch with the full size
 };

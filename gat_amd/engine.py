@@ -1292,6 +1292,47 @@ class SamplerLocalPermutation(Sampler):
         return r
 
 
+class SamplerBruteForce(Sampler):
+    """gat/Engine.pyx:746: SamplerAnnotator's rejection counterpart.  A length from the working segments' histogram and
+    a position in the workspace give a segment; it is kept only if its overlap with the workspace piece it was drawn
+    in does not exceed the bases still to place (segments.sum() to begin with: ALL segments, whether they reach the
+    workspace or not) and it overlaps no segment kept before.  `ntries_inner` rejections in a row drop the list and
+    start again -- the stream goes on --, `ntries_outer` such passes raise ValueError("sampling did not converge"), as
+    the reference does: convergence needs the overlaps to add up exactly.  The list is sorted, free of overlap by
+    construction and not clipped to the workspace.  0 for either number of tries means the reference's default.  Same
+    per-unit stream convention as SamplerAnnotator.sample."""
+
+    kind = 5
+
+    def __init__(self, bucket_size=1, nbuckets=100000, ntries_inner=100, ntries_outer=10):
+        if int(ntries_inner) < 0 or int(ntries_outer) < 0:
+            raise ValueError("SamplerBruteForce: ntries_inner and ntries_outer must be >= 0")
+        self.bucket_size = bucket_size
+        self.nbuckets = nbuckets
+        self.ntries_inner = int(ntries_inner)
+        self.ntries_outer = int(ntries_outer)
+
+    def sample(self, segments, workspace, seed=None):
+        assert workspace.isNormalized, "workspace is not normalized"
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 32))
+        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
+            return SegmentList()
+        s, w = segments.asArray(), workspace.asArray()
+        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
+                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)],
+                    bucket_size=self.bucket_size, nbuckets=self.nbuckets, sampler=self.kind,
+                    brute_ntries_inner=self.ntries_inner, brute_ntries_outer=self.ntries_outer)
+        P = _lib.Problem(get_context(), flat)
+        try:
+            seg, _ = P.sample(seed, 0, 1)
+        finally:
+            P.close()
+        r = SegmentList(array=seg)
+        r.isNormalized = 1
+        return r
+
+
 class Counter(object):
     name = None
 

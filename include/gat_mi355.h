@@ -62,6 +62,13 @@ typedef struct gat_annotations gat_annotations;
                                   /* is active when some piece has a working segment; free < 0 in a piece or a   */
                                   /* coordinate beyond 2^31 - 1 (where the reference raises): GAT_ERR_ASSERT;    */
                                   /* Python's random; per-unit streams only                                     */
+#define GAT_SAMPLER_BRUTE_FORCE 5  /* SamplerBruteForce(bucket_size, nbuckets, ntries_inner, ntries_outer)          */
+                                  /* (gat/Engine.pyx:746-871): SamplerAnnotator's draws, a segment kept only if   */
+                                  /* it overlaps no earlier one, until the overlaps with the workspace add up to  */
+                                  /* segments.sum() exactly; ntries_inner rejections in a row restart the list    */
+                                  /* (the stream goes on), ntries_outer passes without success fail the call with */
+                                  /* GAT_ERR_VALUE "sampling did not converge", gat_last_error naming the first   */
+                                  /* (sample, unit); numpy's stream; per-unit streams only                        */
 
 /*
  * Flat description of what gat.computeSample (gat/__init__.py:494-591) walks for one segment
@@ -87,7 +94,7 @@ typedef struct {
   const int64_t* cws_nseg;      /* n_contigs: len(contig_workspace[contig]) (Engine.pyx:1437)   */
   uint32_t bucket_size;         /* SamplerAnnotator(bucket_size, nbuckets): gat/Engine.pyx:498  */
   int32_t nbuckets;
-  int32_t sampler;              /* GAT_SAMPLER_ANNOTATOR (gat/Engine.pyx:445), GAT_SAMPLER_SEGMENTS (:653), GAT_SAMPLER_SHIFT (:998), GAT_SAMPLER_GLOBAL_PERMUTATION (:1234) or GAT_SAMPLER_LOCAL_PERMUTATION (:1117) */
+  int32_t sampler;              /* GAT_SAMPLER_ANNOTATOR (gat/Engine.pyx:445), GAT_SAMPLER_SEGMENTS (:653), GAT_SAMPLER_SHIFT (:998), GAT_SAMPLER_GLOBAL_PERMUTATION (:1234), GAT_SAMPLER_LOCAL_PERMUTATION (:1117) or GAT_SAMPLER_BRUTE_FORCE (:746) */
   /* Optional (all 0 / NULL: annos / anno_off are the [track][contig] lists above).  With anno_group set, the caller hands
    * over the annotation lists as it holds them -- one per (track, isochore key), the `annotations` argument of
    * UnconditionalSampler.sample (gat/__init__.py:704) -- and the library forms computeSample's contig_annotations itself
@@ -106,6 +113,10 @@ typedef struct {
    * >= 0 (GAT_ERR_VALUE): the reference's unsigned casts give a negative value no meaning. */
   double shift_radius;
   int32_t shift_extension;
+  /* GAT_SAMPLER_BRUTE_FORCE only (ignored otherwise): SamplerBruteForce(ntries_inner, ntries_outer); 0: the reference's
+   * defaults, 100 and 10; negative: GAT_ERR_VALUE. */
+  int32_t brute_ntries_inner;
+  int32_t brute_ntries_outer;
 } gat_problem_desc;
 
 /* The annotation side of gat_problem_desc by itself: the tracks' lists per contig -- [track][contig] CSR, or with
@@ -186,6 +197,9 @@ typedef struct {
   int64_t n_empty_windows;      /* GAT_SAMPLER_SHIFT: segments whose window held no workspace base -- the reference's         */
                                 /* randint(0, 0) raises inside getRandomPosition, which returns 0; the direction is still     */
                                 /* drawn and the segment contributes nothing (gat/SegmentList.pyx:902-917)                     */
+  int64_t n_restarts;           /* GAT_SAMPLER_BRUTE_FORCE: outer passes beyond a work unit's first, summed over the call      */
+  int64_t n_unconverged;        /* ... and work units that used up ntries_outer passes: the call fails with GAT_ERR_VALUE (its */
+                                /* statistics are still written)                                                               */
 } gat_stats;
 
 #define GAT_COUNT_KERNEL_NONE 0
