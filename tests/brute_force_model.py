@@ -63,30 +63,58 @@ def bisect_position(cdf, p):
     return lo
 
 
-def sls_sample(rng, workspace, cdf, total, length):
-    """SegmentListSampler.sample (gat/Engine.pyx:279-348): (start, end, overlap with the chosen piece)."""
+def sls_sample(rng, workspace, cdf, total, length, notes=None):
+    """SegmentListSampler.sample (gat/Engine.pyx:279-348): (start, end, overlap with the chosen piece).  notes, when a
+    dict, counts the placements with q < 0 (q_negative), with an overlap smaller than their length (partial_overlap) and
+    those of a piece k > 0 whose sampling_start is the previous piece's end (start_at_prev_end)."""
     p = rng.randint(0, total)
     k = bisect_position(cdf, p)
     cs, ce = workspace[k]
     sampling_start = cs - length + 1
     if k > 0:
+        if notes is not None and lmax(workspace[k - 1][1], sampling_start) != sampling_start:
+            notes["start_at_prev_end"] += 1
         sampling_start = lmax(workspace[k - 1][1], sampling_start)
     q = rng.randint(sampling_start, ce)
     start = u32(lmax(0, q))
     end = u32(q + length)
     overlap = lmax(0, lmin(ce, end) - lmax(cs, start))
+    if notes is not None:
+        notes["q_negative"] += q < 0
+        notes["partial_overlap"] += overlap < length
     return start, end, overlap
+
+
+EVENTS = ("q_negative", "partial_overlap", "start_at_prev_end", "rej_remaining_only", "rej_hit", "touching")
+
+
+def new_notes():
+    """what sample() notes per call under stats["notes"] (a list, one dict per call): the EVENTS as counts --
+    rej_remaining_only: rejections by overlap > remaining where no accepted segment is hit; rej_hit: rejections by a hit;
+    touching: accepted segments with an earlier one ending at their start or starting at their end -- and
+    hit_lowest (the lowest index, in the order of acceptance, of a hitting entry, per rejection by a hit), hit_only (the
+    same where that entry is the only one hit), touching_both (accepted segments touched on both sides), passes ((list
+    length when the pass ended, converged) per pass) and words (raw MT19937 outputs consumed)."""
+    d = dict((k, 0) for k in EVENTS)
+    d.update(hit_lowest=[], hit_only=[], touching_both=0, passes=[], words=0)
+    return d
 
 
 def sample(rng, segments, workspace, bucket_size=1, nbuckets=100000, ntries_inner=100, ntries_outer=10, stats=None):
     """SamplerBruteForce(bucket_size, nbuckets, ntries_inner, ntries_outer).sample(segments, workspace) drawing from rng
     (an oracle RandomState).  Raises ValueError("sampling did not converge") as the reference does.  stats gathers
     restarts (outer passes beyond the first), tries (rejected placements), placed (accepted ones, dropped lists included),
-    unconverged and the longest list (list_max)."""
+    unconverged and the longest list (list_max); where it holds a list under "notes", a new_notes() dict of the call's
+    events is appended to it (none of this changes what is drawn or returned)."""
     if stats is None:
         stats = {}
     for key in ("restarts", "tries", "placed", "unconverged", "list_max"):
         stats.setdefault(key, 0)
+    notes = None
+    if isinstance(stats.get("notes"), list):
+        notes = new_notes()
+        stats["notes"].append(notes)
+        words0 = rng.ndraws
     segments = [tuple(x) for x in segments]
     workspace = [tuple(x) for x in workspace]
     working = O.aslist(O.filter(segments, workspace)) if segments and workspace else []
@@ -107,16 +135,32 @@ def sample(rng, segments, workspace, bucket_size=1, nbuckets=100000, ntries_inne
         inner = ntries_inner
         while remaining > 0 and inner > 0:
             length = hs.sample(rng)
-            start, end, overlap = sls_sample(rng, workspace, cdf, total, length)
+            start, end, overlap = sls_sample(rng, workspace, cdf, total, length, notes)
             if overlap > remaining or any(lmin(e, end) - lmax(s, start) > 0 for s, e in out):
                 inner -= 1
                 stats["tries"] += 1
+                if notes is not None:
+                    hits = [i for i, (s, e) in enumerate(out) if lmin(e, end) - lmax(s, start) > 0]
+                    if overlap > remaining:
+                        notes["rej_remaining_only"] += not hits
+                    else:
+                        notes["rej_hit"] += 1
+                        notes["hit_lowest"].append(hits[0])
+                        if len(hits) == 1:
+                            notes["hit_only"].append(hits[0])
                 continue
+            if notes is not None:
+                sides = any(e == start for _, e in out) + any(s == end for s, _ in out)
+                notes["touching"] += sides > 0
+                notes["touching_both"] += sides == 2
             out.append((start, end))
             stats["placed"] += 1
             stats["list_max"] = max(stats["list_max"], len(out))
             inner = ntries_inner
             remaining = i32(remaining - overlap)
+        if notes is not None:
+            notes["passes"].append((len(out), inner > 0))
+            notes["words"] = rng.ndraws - words0
         if inner > 0:
             break
         outer -= 1

@@ -1,7 +1,9 @@
 """one-off sweep of the fuzz generator of tests/test_hip_parity.py over many seeds (GPU vs oracle, bit-exact), or of the
 shift / global permutation edge cases of tests/test_sampler_edges_gpu.py (GPU vs tests/shift_model.py, permutation_model.py),
-or of the local permutation sampler's random units (tests/local_permutation_edges.py, GPU vs local_permutation_model.py);
-usage: tools/fuzz_sweep.py first_seed n_seeds [edge|merged|long|scan|frag|units|shift|perm|local]"""
+or of the local permutation sampler's random units (tests/local_permutation_edges.py, GPU vs local_permutation_model.py),
+or of the brute-force sampler's edge cases (tests/brute_force_edges.py edge_units, GPU vs brute_force_model.py; a seed
+whose model does not converge is counted and left out);
+usage: tools/fuzz_sweep.py first_seed n_seeds [edge|merged|long|scan|frag|units|shift|perm|local|brute]"""
 import importlib.util, os, sys, time
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, root)
@@ -15,6 +17,10 @@ spec.loader.exec_module(se)
 from gat_amd import _lib
 import random
 import local_permutation_edges as LE
+import brute_force_edges as BE
+spec = importlib.util.spec_from_file_location("tbe", os.path.join(root, "tests", "test_sampler_brute_force_edges_gpu.py"))
+be = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(be)
 
 
 class MP(object):                      # minimal monkeypatch stand-in: the knobs go through the context's options
@@ -42,6 +48,8 @@ units = len(sys.argv) > 3 and sys.argv[3] == "units"
 shift = len(sys.argv) > 3 and sys.argv[3] == "shift"
 perm = len(sys.argv) > 3 and sys.argv[3] == "perm"
 local = len(sys.argv) > 3 and sys.argv[3] == "local"
+brute = len(sys.argv) > 3 and sys.argv[3] == "brute"
+unconverged = 0
 uo = [0, 0, 0]
 handed = 0
 bad = 0
@@ -58,6 +66,11 @@ for seed in range(first, first + n):
             se.shift_case(ctx, seed)
         elif perm:
             se.perm_case(ctx, seed)
+        elif brute:                    # the call of test_brute_fuzz[seed], for any seed
+            if BE.model_units(*BE.fuzz_call(seed))[1]["unconverged"]:
+                unconverged += 1
+            else:
+                be.brute_case(ctx, seed)
         elif local:                    # 12 random units (a third fragmented) x 3 samples: lists and words drawn
             flat = LE.units_flat(LE.random_units(random.Random(0x10CA1 + seed), 12))
             got, st = LE.device_units(ctx, flat, seed, 0, 3)
@@ -84,6 +97,6 @@ for seed in range(first, first + n):
     except Exception as e:             # noqa: BLE001
         bad += 1
         print("seed %d: %s: %s" % (seed, type(e).__name__, str(e)[:300]), flush=True)
-    if (seed - first + 1) % (100 if shift or perm or local else 2000) == 0:  # (a sweep cut short by `timeout` still says how far it came)
+    if (seed - first + 1) % (100 if shift or perm or local or brute else 2000) == 0:  # (a sweep cut short by `timeout` still says how far it came)
         print("... %d seeds, %d failures, %.0f s" % (seed - first + 1, bad, time.time() - t0), flush=True)
-print("%d seeds, %d failures, %.1f s %s" % (n, bad, time.time() - t0, outcomes if edge else ("units through k_tail_big: %d" % handed if long_lists else ("units finished by k_tail: %d" % handed if frag else ("candidates %d, overlaps taken off %d, problems repeated through k_contig %d" % tuple(uo) if units else "")))))
+print("%d seeds, %d failures, %.1f s %s" % (n, bad, time.time() - t0, outcomes if edge else ("units through k_tail_big: %d" % handed if long_lists else ("units finished by k_tail: %d" % handed if frag else ("candidates %d, overlaps taken off %d, problems repeated through k_contig %d" % tuple(uo) if units else ("seeds left out (the model does not converge): %d" % unconverged if brute else ""))))))
