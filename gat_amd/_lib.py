@@ -33,6 +33,7 @@ SYMBOLS = [
     "gat_sample_and_count_serial", "gat_mt19937_seed", "gat_sample_and_count_enqueue", "gat_wait",
     "gat_annotations_create", "gat_annotations_destroy", "gat_annotations_wait", "gat_list_sums", "gat_problem_rng_rows",
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
+    "gat_call_lane_for",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -206,6 +207,8 @@ def lib():
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
     L.gat_count_list_ranges.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, vp, i32, vp, i32, vp]
+    L.gat_call_lane_for.restype = C.c_int
+    L.gat_call_lane_for.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.gat_intersection_sizes.restype = C.c_int
     L.gat_intersection_sizes.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
     L.gat_problem_rng_rows.restype = i64
@@ -403,6 +406,13 @@ class Context(object):
                                                _p(anno_off), _p(anno_end), n_tracks, _p(ws_nseg), n_groups, _p(out)), self._h)
         return [out[k].view(np.float64).copy() if c == "nucleotide-density" else out[k].copy()
                 for k, c in enumerate(counters)]
+
+
+def call_lane_for(n_lanes, asynchronous, timed, serial_state, others_in_flight, lane_busy):
+    """The lane (0..n_lanes-1) an enqueued call would take, or -1: the context's stream (gat_call_lane_for: the library's own rule)."""
+    busy = np.ascontiguousarray(list(lane_busy) + [0] * 4, dtype=np.int32)
+    return int(lib().gat_call_lane_for(int(n_lanes), int(bool(asynchronous)), int(bool(timed)), int(bool(serial_state)),
+                                       int(others_in_flight), _p(busy)))
 
 
 def intersection_sizes(a, a_off, b, b_begin, b_end, n_tracks):

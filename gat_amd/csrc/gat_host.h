@@ -38,9 +38,13 @@ struct CallBlock {
   unsigned long long* h_mstat = nullptr;      // pinned, 512 words: k_count_merged's traffic counters of the call
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   hipEvent_t ev_main[kMaxInflight][2] = {};   // around the dominant count kernel of every batch in flight
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // (no timing) a call on a lane: the caller's stream at the enqueue; the lane
+                                              // behind what the enqueue put on it (see call_lane_for)
 };
 struct CallState {
   bool active = false;
+  int lane = -1;                              // the context's lane the call runs on, or -1: the context's stream (call_stream)
+  bool fork_waited = false;                   // ... the lane waits for ev_fork in front of the call's first count kernel
   CallBlock* blk = nullptr;
   int32_t ids[GAT_NUM_COUNTERS] = {0, 0, 0, 0, 0, 0};
   int n_counters = 0;
@@ -63,6 +67,23 @@ struct CallState {
   gat_stats local;
 };
 
+// Call lanes: calls of different problems of a context are independent -- scratch, rows, slabs, records and status slots are the
+// problem's, the annotation tables are only read -- so an asynchronous call enqueued while another problem's call is in flight
+// goes onto a stream of its own and its kernels run beside the other's.  GAT_CALL_LANES (at most kMaxLanes) is the number of
+// such streams; below 2 there is none and every call is on the context's stream.
+constexpr int kMaxLanes = 4;
+// The rules, as a function of what is known at the enqueue.  lane_busy: per lane, whether a call in flight runs on it;
+// others_in_flight: calls of OTHER problems in flight on the context (on its stream or a lane).  -1: the context's stream --
+// with no lanes, for the synchronous entry points, for calls with per-kernel timing (their events exist once per context) or
+// the caller's serial MT19937 state, and when nothing else is in flight (the single call pays nothing).  Else the first idle
+// lane; with every lane busy, the one of lowest index (its calls queue one behind the other)
+inline int call_lane_for(int n_lanes, bool asynchronous, bool timed, bool serial_state, int others_in_flight, const bool* lane_busy) {
+  n_lanes = std::min(n_lanes, kMaxLanes);
+  if (n_lanes < 2 || !asynchronous || timed || serial_state || others_in_flight <= 0) return -1;
+  for (int l = 0; l < n_lanes; ++l) if (!lane_busy[l]) return l;
+  return 0;
+}
+
 struct gat_ctx {
   int refs = 1;                    // the handle + one per live problem: gat_ctx_destroy frees when the last one is gone
   bool closed = false;             // gat_ctx_destroy was called (problems still alive)
@@ -73,6 +94,9 @@ struct gat_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
+  hipStream_t lanes[kMaxLanes] = {};            // made at the first call that takes one (call_lane_for); non-blocking
+  int lane_calls[kMaxLanes] = {};               // calls in flight per lane
+  int calls_in_flight = 0;                      // ... and on the context in all
   size_t stage_used = 0;           // bytes at the start of h_stage that copies in flight read from (stage_push_h2d)
   bool kernel_times = false;       // gat_ctx_set_kernel_times: events behind the sampler's kernels, their times in gat_stats
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -435,6 +459,9 @@ struct gat_problem {
   int swap_capx = 0;                     // > 0: count with k_count_swap, sample lists of up to this many segments in LDS
   bool swap_decided = false;             // (decided at the first call: it takes the size of the annotation tables)
 };
+
+// the stream a problem's kernels, memsets and copies go onto: the lane of its call in flight, else the context's
+inline hipStream_t call_stream(const gat_ctx* ctx, const gat_problem* P) { return P->call.lane >= 0 ? ctx->lanes[P->call.lane] : ctx->stream; }
 
 // gat_prep.hip
 int build_annos(gat_ctx* ctx, const Knobs& kn, AnnoDev& A, const gat_segment* annos, const int64_t* lbeg, const int64_t* lend, int64_t n_lists,

@@ -44,6 +44,7 @@ struct gat_ctx;
   FLAG(count_no_merged, "GAT_COUNT_NO_MERGED")                                                                               \
   /* the call */                                                                                                             \
   REAL(slab_bytes, "GAT_SLAB_BYTES", 72.0 * 1024 * 1024 * 1024)                                                              \
+  INT(call_lanes, "GAT_CALL_LANES", 2)                                                                                       \
   FLAG(kernel_times, "GAT_KERNEL_TIMES")                                                                                     \
   TEXT(diag_out, "GAT_DIAG_OUT")                                                                                             \
   FLAG(test_huge, "GAT_TEST_HUGE")                                                                                           \

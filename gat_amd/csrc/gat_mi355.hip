@@ -93,6 +93,8 @@ static int call_block_get(gat_ctx* ctx, CallBlock** out) {
   HIPCHK(ctx, hipEventCreate(&b->ev_begin));
   HIPCHK(ctx, hipEventCreate(&b->ev_end));
   for (auto& pair : b->ev_main) for (auto& ev : pair) HIPCHK(ctx, hipEventCreate(&ev));
+  HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
+  HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
   *out = b.release();
   return GAT_OK;
 }
@@ -102,6 +104,8 @@ static void call_block_free(CallBlock* b) {
   if (b->ev_begin) (void)hipEventDestroy(b->ev_begin);
   if (b->ev_end) (void)hipEventDestroy(b->ev_end);
   for (auto& pair : b->ev_main) for (auto& ev : pair) if (ev) (void)hipEventDestroy(ev);
+  if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
+  if (b->ev_join) (void)hipEventDestroy(b->ev_join);
   delete b;
 }
 
@@ -116,6 +120,7 @@ void ctx_release(gat_ctx* ctx) {
   if (--ctx->refs > 0) return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  for (auto& lane : ctx->lanes) if (lane) { (void)hipStreamSynchronize(lane); (void)hipStreamDestroy(lane); lane = nullptr; }
   ctx->stage_used = 0;
   for (CallBlock* b : ctx->call_blocks) call_block_free(b);
   ctx->call_blocks.clear();
@@ -137,6 +142,12 @@ extern "C" int gat_ctx_set_kernel_times(gat_ctx* ctx, int on) {
   if (!ctx) return set_err(nullptr, GAT_ERR_ARG, "ctx is NULL");
   ctx->kernel_times = on != 0;
   return GAT_OK;
+}
+
+extern "C" int gat_call_lane_for(int n_lanes, int asynchronous, int timed, int serial_state, int others_in_flight, const int32_t* lane_busy) {
+  bool busy[kMaxLanes] = {};
+  for (int l = 0; l < kMaxLanes && l < n_lanes; ++l) busy[l] = lane_busy != nullptr && lane_busy[l] != 0;
+  return call_lane_for(n_lanes, asynchronous != 0, timed != 0, serial_state != 0, others_in_flight, busy);
 }
 
 extern "C" void* gat_ctx_stream(const gat_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
@@ -206,9 +217,9 @@ static int ensure_scratch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t
   HIPCHK(ctx, P->d_unit_n.alloc((size_t)(b * std::max(1, P->n_units))));
   HIPCHK(ctx, P->d_contig_n.alloc((size_t)(b * std::max(1, P->n_contigs))));
   HIPCHK(ctx, P->d_ws_stat.alloc((size_t)(b * std::max(1, P->n_units)) * 4));
-  HIPCHK(ctx, hipMemsetAsync(P->d_unit_n.p, 0, (size_t)(b * std::max(1, P->n_units)) * 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(P->d_contig_n.p, 0, (size_t)(b * std::max(1, P->n_contigs)) * 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(P->d_ws_stat.p, 0, (size_t)(b * std::max(1, P->n_units)) * 16, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(P->d_unit_n.p, 0, (size_t)(b * std::max(1, P->n_units)) * 4, call_stream(ctx, P)));
+  HIPCHK(ctx, hipMemsetAsync(P->d_contig_n.p, 0, (size_t)(b * std::max(1, P->n_contigs)) * 4, call_stream(ctx, P)));
+  HIPCHK(ctx, hipMemsetAsync(P->d_ws_stat.p, 0, (size_t)(b * std::max(1, P->n_units)) * 16, call_stream(ctx, P)));
   if (P->sampler_mode) {
     const int64_t nsb = (b + 63) / 64;
     P->h_rng_off.assign(P->h_order.size() + 1, 0);
@@ -222,7 +233,7 @@ static int ensure_scratch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t
     HIPCHK(ctx, P->d_st2.alloc(ns));
     if (!P->split_path && P->long_lists) {                                      // k_tail_big's hand-over records
       HIPCHK(ctx, P->d_patch.alloc(ns));
-      HIPCHK(ctx, hipMemsetAsync(P->d_patch.p, 0, ns * sizeof(gat::TailPatch), ctx->stream));
+      HIPCHK(ctx, hipMemsetAsync(P->d_patch.p, 0, ns * sizeof(gat::TailPatch), call_stream(ctx, P)));
       HIPCHK(ctx, P->d_todo.alloc(ns));                                         // ... and the queue of what k_resume_big leaves
     }
     if (P->split_path) {
@@ -271,6 +282,7 @@ static int count_route(const gat_ctx* ctx, const Knobs& kn, bool has_merged, con
 // launch the count kernels over n_lists sample lists
 // ev_main: the pair of events recorded around the dominant kernel; main_recorded / count_kernel: what was launched
 struct CountLaunch {
+  hipStream_t stream = nullptr;  // where the kernels and the events go: the call's (call_stream), the context's (gat_count_lists)
   hipEvent_t* ev_main = nullptr;
   bool main_recorded = false;
   int count_kernel = GAT_COUNT_KERNEL_NONE;
@@ -352,14 +364,14 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
                              : (blk == 8 ? (const void*)gat::k_count_merged<false, 8> : blk == 1 ? (const void*)gat::k_count_merged<false, 1>
                                                                                                   : (const void*)gat::k_count_merged<false, 2>);
       HIPCHK(ctx, hipFuncSetAttribute(km, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_merged));
-      HIPCHK(ctx, hipEventRecord(L.ev_main[0], ctx->stream));
+      HIPCHK(ctx, hipEventRecord(L.ev_main[0], L.stream));
       const dim3 gm((unsigned)nblocks), bm(gat::kMergedThreads);
-      if (patch && blk == 8) hipLaunchKernelGGL((gat::k_count_merged<true, 8>), gm, bm, lds_merged, ctx->stream, A);
-      else if (patch && blk == 1) hipLaunchKernelGGL((gat::k_count_merged<true, 1>), gm, bm, lds_merged, ctx->stream, A);
-      else if (patch) hipLaunchKernelGGL((gat::k_count_merged<true, 2>), gm, bm, lds_merged, ctx->stream, A);
-      else if (blk == 8) hipLaunchKernelGGL((gat::k_count_merged<false, 8>), gm, bm, lds_merged, ctx->stream, A);
-      else if (blk == 1) hipLaunchKernelGGL((gat::k_count_merged<false, 1>), gm, bm, lds_merged, ctx->stream, A);
-      else hipLaunchKernelGGL((gat::k_count_merged<false, 2>), gm, bm, lds_merged, ctx->stream, A);
+      if (patch && blk == 8) hipLaunchKernelGGL((gat::k_count_merged<true, 8>), gm, bm, lds_merged, L.stream, A);
+      else if (patch && blk == 1) hipLaunchKernelGGL((gat::k_count_merged<true, 1>), gm, bm, lds_merged, L.stream, A);
+      else if (patch) hipLaunchKernelGGL((gat::k_count_merged<true, 2>), gm, bm, lds_merged, L.stream, A);
+      else if (blk == 8) hipLaunchKernelGGL((gat::k_count_merged<false, 8>), gm, bm, lds_merged, L.stream, A);
+      else if (blk == 1) hipLaunchKernelGGL((gat::k_count_merged<false, 1>), gm, bm, lds_merged, L.stream, A);
+      else hipLaunchKernelGGL((gat::k_count_merged<false, 2>), gm, bm, lds_merged, L.stream, A);
       HIPCHK(ctx, hipGetLastError());
       if (A.cu_rec != nullptr) {
         // the contig lists were only concatenated (k_contig<., true>): what fromIsochores would have united -- the overlaps
@@ -367,15 +379,15 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
         gat::UnitsOverlapArgs B;
         B.C = A; B.units = L.units; B.ws = L.ws; B.ws_tree = L.ws_tree;
         const int64_t items = (int64_t)A.cand_cap * std::max(1, L.max_units);
-        hipLaunchKernelGGL(gat::k_units_overlap, dim3((unsigned)((items + 255) / 256), gat::kCandSlots), dim3(256), 0, ctx->stream, B,
+        hipLaunchKernelGGL(gat::k_units_overlap, dim3((unsigned)((items + 255) / 256), gat::kCandSlots), dim3(256), 0, L.stream, B,
                            std::max(1, L.max_units));
         HIPCHK(ctx, hipGetLastError());
       }
-      HIPCHK(ctx, hipEventRecord(L.ev_main[1], ctx->stream));
+      HIPCHK(ctx, hipEventRecord(L.ev_main[1], L.stream));
       L.main_recorded = true;
       L.count_kernel = GAT_COUNT_KERNEL_MERGED;
       const int64_t tiles = (int64_t)((A.n_tracks + 15) / 16) * ((A.n_samples + 15) / 16);
-      hipLaunchKernelGGL(gat::k_count_merged_finish, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, A);
+      hipLaunchKernelGGL(gat::k_count_merged_finish, dim3((unsigned)tiles), dim3(256), 0, L.stream, A);
       HIPCHK(ctx, hipGetLastError());
       goto seg_done;
     }
@@ -388,16 +400,16 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
       B.lds_grid = lcells;
       const size_t lds_swap = (size_t)3 * swap_capx * 4 + ((size_t)(1 << lcells) + 1) * 4;
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_count_swap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_swap));
-      HIPCHK(ctx, hipEventRecord(L.ev_main[0], ctx->stream));
-      hipLaunchKernelGGL(gat::k_count_swap, grid_yz((unsigned)A.n_samples, (unsigned)std::max(1, A.n_contigs)), dim3(gat::kSwapThreads), lds_swap, ctx->stream, B);
+      HIPCHK(ctx, hipEventRecord(L.ev_main[0], L.stream));
+      hipLaunchKernelGGL(gat::k_count_swap, grid_yz((unsigned)A.n_samples, (unsigned)std::max(1, A.n_contigs)), dim3(gat::kSwapThreads), lds_swap, L.stream, B);
       HIPCHK(ctx, hipGetLastError());
-      HIPCHK(ctx, hipEventRecord(L.ev_main[1], ctx->stream));
+      HIPCHK(ctx, hipEventRecord(L.ev_main[1], L.stream));
       L.main_recorded = true;
       L.count_kernel = GAT_COUNT_KERNEL_SWAP;
     } else
     if (A.n_contigs > 0) {
     const bool hits = C.slot[GAT_COUNTER_SEGMENT_OVERLAP] >= 0 || C.slot[GAT_COUNTER_SEGMENT_MIDOVERLAP] >= 0;
-    HIPCHK(ctx, hipEventRecord(L.ev_main[0], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(L.ev_main[0], L.stream));
     const int kv = (staged ? 4 : 0) + (hits ? 2 : 0) + (A.seg_merged != nullptr ? 1 : 0);
     typedef void (*count_fn)(gat::CountArgs);
     static const count_fn kCountSegFns[8] = {
@@ -405,15 +417,15 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
         gat::k_count_seg<false, true, true>, gat::k_count_seg<true, false, false>, gat::k_count_seg<true, false, true>,
         gat::k_count_seg<true, true, false>, gat::k_count_seg<true, true, true>};
     if (staged) HIPCHK(ctx, hipFuncSetAttribute((const void*)kCountSegFns[kv], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kCountSegFns[kv], grid, dim3(256), lds, ctx->stream, A);
+    hipLaunchKernelGGL(kCountSegFns[kv], grid, dim3(256), lds, L.stream, A);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(L.ev_main[1], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(L.ev_main[1], L.stream));
     L.main_recorded = true;
     L.count_kernel = GAT_COUNT_KERNEL_SEG;
     }
     {
       const int64_t nfin = (int64_t)A.n_tracks * A.n_samples;
-      hipLaunchKernelGGL(gat::k_count_finish, dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, ctx->stream, A);
+      hipLaunchKernelGGL(gat::k_count_finish, dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, L.stream, A);
       HIPCHK(ctx, hipGetLastError());
     }
   seg_done:;
@@ -432,14 +444,14 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
       if (part.n < need) HIPCHK(ctx, part.alloc(need));
       B.part = part.p;
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_count_anno_idx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
-      hipLaunchKernelGGL(gat::k_count_anno_idx, grid_yz((unsigned)A.n_samples, (unsigned)A.n_contigs), dim3(gat::kAnnoThreads), lds_a, ctx->stream, B);
+      hipLaunchKernelGGL(gat::k_count_anno_idx, grid_yz((unsigned)A.n_samples, (unsigned)A.n_contigs), dim3(gat::kAnnoThreads), lds_a, L.stream, B);
       HIPCHK(ctx, hipGetLastError());
       const int64_t nfin = (int64_t)A.n_tracks * A.n_samples;
-      hipLaunchKernelGGL(gat::k_count_anno_finish, dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, ctx->stream, B);
+      hipLaunchKernelGGL(gat::k_count_anno_finish, dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, L.stream, B);
       HIPCHK(ctx, hipGetLastError());
     } else {
       const int64_t waves = (int64_t)A.n_samples * A.n_tracks;
-      hipLaunchKernelGGL(gat::k_count_anno, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, ctx->stream, A);
+      hipLaunchKernelGGL(gat::k_count_anno, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, L.stream, A);
       HIPCHK(ctx, hipGetLastError());
     }
   }
@@ -534,7 +546,7 @@ static int enqueue_list_sampler(gat_ctx* ctx, gat_problem* P, const BatchPlan& B
   H.slab = P->d_slab.p; H.slab_stride = P->slab_stride;
   H.unit_n = P->d_unit_n.p; H.flags = P->flags_dev(); H.ws_stat = P->d_ws_stat.p;
   HIPCHK(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kernel, grid_yz((unsigned)B.nb, B.n_act), dim3(64), lds, ctx->stream, H);
+  hipLaunchKernelGGL(kernel, grid_yz((unsigned)B.nb, B.n_act), dim3(64), lds, call_stream(ctx, P), H);
   HIPCHK(ctx, hipGetLastError());
   return GAT_OK;
 }
@@ -598,7 +610,7 @@ static int enqueue_brute_force(gat_ctx* ctx, gat_problem* P, const BatchPlan& B,
   H.ntries_inner = P->brute_ntries_inner; H.ntries_outer = P->brute_ntries_outer;
   H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.rank_len = P->d_rank_len.p;
   H.stat = P->d_stat.p;
-  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p + gat::kBruteFirstWord, 0, 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p + gat::kBruteFirstWord, 0, 8, call_stream(ctx, P)));
   return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_brute_force, H, (size_t)(gat::kMtLdsWords + 2 * (size_t)H.lds_cap) * 4);
 }
 
@@ -617,7 +629,7 @@ static int base_sampler_args(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, u
   {
     const size_t nd = (size_t)B.nb * std::max(1, P->n_units) * 8;
     if (P->d_diag.n < nd) HIPCHK(ctx, P->d_diag.alloc(nd));
-    HIPCHK(ctx, hipMemsetAsync(P->d_diag.p, 0, nd * 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(P->d_diag.p, 0, nd * 8, call_stream(ctx, P)));
     A.diag = P->d_diag.p;
   }
 #endif
@@ -625,11 +637,11 @@ static int base_sampler_args(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, u
   {
     const size_t np = std::max<size_t>(1, P->h_order.size()) * 8;
     if (P->d_diag_place.n < np) HIPCHK(ctx, P->d_diag_place.alloc(np));
-    HIPCHK(ctx, hipMemsetAsync(P->d_diag_place.p, 0, np * 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(P->d_diag_place.p, 0, np * 8, call_stream(ctx, P)));
     A.diag_place = P->d_diag_place.p;
     const size_t nt = std::max<size_t>(1, P->h_order.size()) * (size_t)((B.nb + 63) / 64) * 2;
     if (P->d_diag_tiles.n < nt) HIPCHK(ctx, P->d_diag_tiles.alloc(nt));
-    HIPCHK(ctx, hipMemsetAsync(P->d_diag_tiles.p, 0, nt * 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(P->d_diag_tiles.p, 0, nt * 8, call_stream(ctx, P)));
     A.diag_tiles = P->d_diag_tiles.p;
   }
 #endif
@@ -664,15 +676,15 @@ static int launch_place(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B, 
   if (scan) {
     const int64_t n_tiles = (int64_t)nsb * B.n_act;
     const unsigned nblocks = (unsigned)(((n_tiles + 7) / 8) * 8 * 4);
-    hipLaunchKernelGGL(gat::k_place_scan, dim3(nblocks), dim3(gat::kScanWaves * 64), 0, ctx->stream, A, (int)nsb,
+    hipLaunchKernelGGL(gat::k_place_scan, dim3(nblocks), dim3(gat::kScanWaves * 64), 0, call_stream(ctx, P), A, (int)nsb,
                        B.kn.place_scan_seq ? 1 : 0);
   } else if (P->sampler == GAT_SAMPLER_SEGMENTS) {
     if (mode == 3) {
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_wide<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide));
-      hipLaunchKernelGGL((gat::k_place_wide<1>), gw, dim3(gat::kPlaceWide * 64), lds_wide, ctx->stream, A);
-    } else if (mode == 1) hipLaunchKernelGGL((gat::k_place<1, 1>), gp, dim3(64), 0, ctx->stream, A);
-    else if (mode == 0) hipLaunchKernelGGL((gat::k_place<1, 0>), gp, dim3(64), 0, ctx->stream, A);
-    else hipLaunchKernelGGL((gat::k_place<1, 2>), gp, dim3(64), 0, ctx->stream, A);
+      hipLaunchKernelGGL((gat::k_place_wide<1>), gw, dim3(gat::kPlaceWide * 64), lds_wide, call_stream(ctx, P), A);
+    } else if (mode == 1) hipLaunchKernelGGL((gat::k_place<1, 1>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else if (mode == 0) hipLaunchKernelGGL((gat::k_place<1, 0>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else hipLaunchKernelGGL((gat::k_place<1, 2>), gp, dim3(64), 0, call_stream(ctx, P), A);
   } else {
     // (k_place_pipe: the rows of the single-workspace-segment units prefetched by hand, see GAT_PLACE_LOOP_PIPE)
     const bool pipe = P->pipe_pays && !B.kn.place_no_pipe;
@@ -684,19 +696,19 @@ static int launch_place(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B, 
     if (grid_k) {
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_grid));
       hipLaunchKernelGGL(gat::k_place_grid, grid_yz((nsb + gat::kPlaceGridTiles - 1) / gat::kPlaceGridTiles, B.n_act),
-                         dim3(gat::kPlaceGridTiles * 64), lds_grid, ctx->stream, A);
+                         dim3(gat::kPlaceGridTiles * 64), lds_grid, call_stream(ctx, P), A);
     } else if (mode == 3) {
       HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_place_wide<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide));
-      hipLaunchKernelGGL((gat::k_place_wide<0>), gw, dim3(gat::kPlaceWide * 64), lds_wide, ctx->stream, A);
-    } else if (mode == 1 && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 1>), gp, dim3(64), 0, ctx->stream, A);
-    else if (mode == 1) hipLaunchKernelGGL((gat::k_place<0, 1>), gp, dim3(64), 0, ctx->stream, A);
-    else if (mode == 0 && P->small_tables && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0, 1>), gp, dim3(64), 0, ctx->stream, A);
-    else if (mode == 0 && P->small_tables) hipLaunchKernelGGL((gat::k_place<0, 0, 1>), gp, dim3(64), 0, ctx->stream, A);
-    else if (mode == 0 && P->max_nws <= 64 && rank_fits && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0, 2>), gp, dim3(64), 0, ctx->stream, A);
-    else if (mode == 0 && P->max_nws <= 64) hipLaunchKernelGGL((gat::k_place<0, 0, 2>), gp, dim3(64), 0, ctx->stream, A);
-    else if (mode == 0 && rank_fits && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0>), gp, dim3(64), 0, ctx->stream, A);
-    else if (mode == 0) hipLaunchKernelGGL((gat::k_place<0, 0>), gp, dim3(64), 0, ctx->stream, A);
-    else hipLaunchKernelGGL((gat::k_place<0, 2>), gp, dim3(64), 0, ctx->stream, A);
+      hipLaunchKernelGGL((gat::k_place_wide<0>), gw, dim3(gat::kPlaceWide * 64), lds_wide, call_stream(ctx, P), A);
+    } else if (mode == 1 && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 1>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else if (mode == 1) hipLaunchKernelGGL((gat::k_place<0, 1>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else if (mode == 0 && P->small_tables && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0, 1>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else if (mode == 0 && P->small_tables) hipLaunchKernelGGL((gat::k_place<0, 0, 1>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else if (mode == 0 && P->max_nws <= 64 && rank_fits && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0, 2>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else if (mode == 0 && P->max_nws <= 64) hipLaunchKernelGGL((gat::k_place<0, 0, 2>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else if (mode == 0 && rank_fits && pipe) hipLaunchKernelGGL((gat::k_place_pipe<0, 0>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else if (mode == 0) hipLaunchKernelGGL((gat::k_place<0, 0>), gp, dim3(64), 0, call_stream(ctx, P), A);
+    else hipLaunchKernelGGL((gat::k_place<0, 2>), gp, dim3(64), 0, call_stream(ctx, P), A);
   }
   HIPCHK(ctx, hipGetLastError());
   return GAT_OK;
@@ -708,17 +720,17 @@ static int enqueue_front_end(gat_ctx* ctx, const gat_problem* P, const BatchPlan
   const unsigned nsb = (unsigned)((B.nb + 63) / 64);
   // the streams' seeding chains at full occupancy, 16 checkpoints each; k_rng's waves regenerate the rest
   const int64_t n_tiles = (int64_t)nsb * B.n_act, per_block = gat::kSeedThreads / gat::kWave;
-  hipLaunchKernelGGL(gat::k_seed, dim3((unsigned)((n_tiles + per_block - 1) / per_block)), dim3(gat::kSeedThreads), 0, ctx->stream,
+  hipLaunchKernelGGL(gat::k_seed, dim3((unsigned)((n_tiles + per_block - 1) / per_block)), dim3(gat::kSeedThreads), 0, call_stream(ctx, P),
                      A, (int)nsb);
   HIPCHK(ctx, hipGetLastError());
   const size_t lds_rng = (size_t)gat::kMtN * 64 * 4;
   HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_rng, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rng));
-  hipLaunchKernelGGL(gat::k_rng, grid_yz(nsb, B.n_act), dim3(gat::kRngThreads), lds_rng, ctx->stream, A);
+  hipLaunchKernelGGL(gat::k_rng, grid_yz(nsb, B.n_act), dim3(gat::kRngThreads), lds_rng, call_stream(ctx, P), A);
   HIPCHK(ctx, hipGetLastError());
-  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[0], ctx->stream));
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[0], call_stream(ctx, P)));
   const int rc = launch_place(ctx, P, B, A, nsb);
   if (rc) return rc;
-  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[1], ctx->stream));
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[1], call_stream(ctx, P)));
   return GAT_OK;
 }
 
@@ -766,7 +778,7 @@ static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
       lds_k = ((size_t)ccap + (size_t)std::max(ccap, cnbk + gat::kMergeThreads + 1)) * 4;   // (short lists: the 1 024 buckets and their padding need their own words)
     }
     M.a_base = a0; M.a_end = a1; M.lds_cap = ccap; M.big_buckets = cnbk;
-    hipLaunchKernelGGL(fns[form], grid_yz((unsigned)B.nb, (unsigned)(a1 - a0)), dim3(gat::kMergeThreads), lds_k, ctx->stream, M);
+    hipLaunchKernelGGL(fns[form], grid_yz((unsigned)B.nb, (unsigned)(a1 - a0)), dim3(gat::kMergeThreads), lds_k, call_stream(ctx, P), M);
     HIPCHK(ctx, hipGetLastError());
   }
   A.st2 = P->d_st2.p; A.n_long = (int32_t)n_long;       // (k_sampler reads st2 for those units only)
@@ -782,14 +794,14 @@ static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
   TB.no_bridge = 0;
   if (B.kn.tb_no_bridge_set) { const int v = (int)B.kn.tb_no_bridge; TB.no_bridge = (v == 2 || v == 5) ? (v == 2 ? 2 : 1) : 3; }
   TB.no_log_map = B.kn.tb_no_log_map ? 1 : 0;
-  hipLaunchKernelGGL(gat::k_tail_big, grid_yz((unsigned)((B.nb + 63) / 64), n_long), dim3(64), 0, ctx->stream, TB);
+  hipLaunchKernelGGL(gat::k_tail_big, grid_yz((unsigned)((B.nb + 63) / 64), n_long), dim3(64), 0, call_stream(ctx, P), TB);
   HIPCHK(ctx, hipGetLastError());
   if (B.resume_big) {
     // ... and the rest of the unit -- log inserted, trim, final filter -- with the list where it is
     // (a reader that takes the segments one by one in any order -- k_count_merged on the units' lists, no contig lists
     //  in between --: the log stays behind the merged list, the trim works on virtual indices)
     const bool virt = TB.loose_ok && !P->merge_contigs && !B.kn.resume_insert;
-    hipLaunchKernelGGL(virt ? gat::k_resume_big<true> : gat::k_resume_big<false>, grid_yz((unsigned)B.nb, n_long), dim3(64), 0, ctx->stream, TB);
+    hipLaunchKernelGGL(virt ? gat::k_resume_big<true> : gat::k_resume_big<false>, grid_yz((unsigned)B.nb, n_long), dim3(64), 0, call_stream(ctx, P), TB);
     HIPCHK(ctx, hipGetLastError());
   }
   A.tb = reinterpret_cast<const int32_t*>(P->d_patch.p);
@@ -799,7 +811,7 @@ static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
     // lists in LDS -- it took 3.1 ms per 12 500 samples of the config-4 shape to find every unit finished
     TB.todo = P->d_todo.p; TB.todo_count = P->todo_count_dev();
     const int64_t tot = (int64_t)B.nb * B.n_act;
-    hipLaunchKernelGGL(gat::k_queue_rest, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, TB, (int)B.n_act);
+    hipLaunchKernelGGL(gat::k_queue_rest, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, call_stream(ctx, P), TB, (int)B.n_act);
     HIPCHK(ctx, hipGetLastError());
     A.todo = P->d_todo.p; A.todo_count = P->todo_count_dev();
   }
@@ -840,22 +852,22 @@ static int enqueue_split_path(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
     gat::TailArgs C = T;
     C.S.a_base = a0; C.S.a_end = a1; C.S.lds_cap = ccap;
     const size_t lds_c = (size_t)(gat::kSortScratchWords + 2 * (size_t)ccap) * 4;
-    hipLaunchKernelGGL(consolidate, grid_yz((unsigned)nb, (unsigned)(a1 - a0)), dim3(64), lds_c, ctx->stream, C);
+    hipLaunchKernelGGL(consolidate, grid_yz((unsigned)nb, (unsigned)(a1 - a0)), dim3(64), lds_c, call_stream(ctx, P), C);
     HIPCHK(ctx, hipGetLastError());
   }
-  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], ctx->stream));
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], call_stream(ctx, P)));
   const bool long_ws = P->tail_long_ws && P->max_nws > gat::kTailMaxWs;
-  hipLaunchKernelGGL(long_ws ? gat::k_tail<true> : gat::k_tail<false>, grid_yz((unsigned)((nb + 63) / 64), B.n_act), dim3(64), 0, ctx->stream, T);
+  hipLaunchKernelGGL(long_ws ? gat::k_tail<true> : gat::k_tail<false>, grid_yz((unsigned)((nb + 63) / 64), B.n_act), dim3(64), 0, call_stream(ctx, P), T);
   HIPCHK(ctx, hipGetLastError());
-  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_t[0], ctx->stream));
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_t[0], call_stream(ctx, P)));
   // isochore problems: k_contig re-sorts the units of a contig anyway and takes (merged list, k_tail's record) as
   // it is -- no final unit lists unless somebody asked for them (gat_sample_units)
   P->patched_contigs = P->merge_contigs && P->n_contigs > 0 && !B.o.need_unit_lists && !B.kn.contig_final_lists;
   P->units_direct = B.o.units_direct && P->patched_contigs && P->units_direct_ok && B.o.serial_state == nullptr;
   P->patched_counts = !P->merge_contigs && B.o.records_ok && !B.o.need_unit_lists;
-  if (!P->patched_contigs && !P->patched_counts) hipLaunchKernelGGL(gat::k_finalize, grid_yz((unsigned)nb, B.n_act), dim3(64), 0, ctx->stream, T);
+  if (!P->patched_contigs && !P->patched_counts) hipLaunchKernelGGL(gat::k_finalize, grid_yz((unsigned)nb, B.n_act), dim3(64), 0, call_stream(ctx, P), T);
   HIPCHK(ctx, hipGetLastError());
-  if (B.timed) { HIPCHK(ctx, hipEventRecord(ctx->ev_t[1], ctx->stream)); ctx->t_recorded = true; }
+  if (B.timed) { HIPCHK(ctx, hipEventRecord(ctx->ev_t[1], call_stream(ctx, P))); ctx->t_recorded = true; }
   A.st2 = P->d_st2.p; A.n_long = (int32_t)B.n_act;
   A.slab_final = P->d_fslab.p;
   A.skip = &P->d_patch.p->state;
@@ -886,7 +898,7 @@ static int enqueue_sampler(gat_ctx* ctx, const gat_problem* P, const BatchPlan& 
   if (variant == 0 && (int64_t)B.lds * 20 <= ctx->max_lds && !B.kn.no_wpe5) variant = 8;
   HIPCHK(ctx, hipFuncSetAttribute((const void*)kSamplerFns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.lds));
   auto launch_sampler = [&](const dim3& gs, size_t lds_, const gat::SamplerArgs& K) {
-    hipLaunchKernelGGL(kSamplerFns[variant], gs, dim3(64), lds_, ctx->stream, K);
+    hipLaunchKernelGGL(kSamplerFns[variant], gs, dim3(64), lds_, call_stream(ctx, P), K);
   };
   const dim3 off_queue((unsigned)std::min<int64_t>((int64_t)nb * B.n_act, 8192));
   const bool list_in_lds = !B.huge && P->sampler != GAT_SAMPLER_SEGMENTS;
@@ -896,7 +908,7 @@ static int enqueue_sampler(gat_ctx* ctx, const gat_problem* P, const BatchPlan& 
     K.serial_state = B.o.serial_state; K.unit_pos = P->d_unit_pos.p;
     const sampler_fn serial = kSerialFns[variant == 8 ? 0 : variant];
     HIPCHK(ctx, hipFuncSetAttribute((const void*)serial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.lds));
-    hipLaunchKernelGGL(serial, dim3(1), dim3(64), B.lds, ctx->stream, K);
+    hipLaunchKernelGGL(serial, dim3(1), dim3(64), B.lds, call_stream(ctx, P), K);
   } else if (B.split) {
     launch_sampler(off_queue, B.lds, A);
   } else if (list_in_lds && A.big_buckets == 0 && P->h_class_start.size() > 2 &&
@@ -935,10 +947,10 @@ static int enqueue_placement_sampler(gat_ctx* ctx, gat_problem* P, const BatchPl
   if (B.merge_big && (rc = enqueue_long_lists(ctx, P, B, A))) return rc;
   P->split_ran = B.split;
   if (B.split) rc = enqueue_split_path(ctx, P, B, A);
-  else if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], ctx->stream));
+  else if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], call_stream(ctx, P)));
   if (!rc) rc = enqueue_sampler(ctx, P, B, A);
   if (rc) return rc;
-  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[3], ctx->stream));
+  if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[3], call_stream(ctx, P)));
   return GAT_OK;
 }
 
@@ -984,7 +996,7 @@ static int enqueue_contigs(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_
     B.count = one ? P->n_contigs : c1 - c0;
     B.lds_cap = one ? 0 : std::max(64, P->h_contig_need[(size_t)P->h_contig_order[(size_t)c0]]);
     const size_t lds_k = nosort ? 64 : (huge_c ? lds : (size_t)B.lds_cap * 8 + gat::kSortScratchWords * 4);
-    hipLaunchKernelGGL(kc, grid_yz((unsigned)nb, (unsigned)B.count), dim3(64), lds_k, ctx->stream, B);
+    hipLaunchKernelGGL(kc, grid_yz((unsigned)nb, (unsigned)B.count), dim3(64), lds_k, call_stream(ctx, P), B);
     HIPCHK(ctx, hipGetLastError());
   }
   return GAT_OK;
@@ -1002,16 +1014,16 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
   // (unit_n, contig_n and ws_stat are zeroed once when allocated: the kernels rewrite every entry of the active units
   //  in every batch and never touch the others)
 #ifdef GAT_DBG_QUEUE
-  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 16 * 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 16 * 8, call_stream(ctx, P)));
 #else
-  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 10 * 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 10 * 8, call_stream(ctx, P)));
 #endif         // (statistics, status word, k_tail's queue length)
-  if (o.units_direct && P->d_cand_count.n) HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, P->d_cand_count.n * 4, ctx->stream));
-  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+  if (o.units_direct && P->d_cand_count.n) HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, P->d_cand_count.n * 4, call_stream(ctx, P)));
+  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[0], call_stream(ctx, P)));
   gat::SamplerArgs A = {};                 // (SamplerAnnotator / SamplerSegments: what k_sampler saw)
   if (!P->h_order.empty()) {
     // (what a stage records or leaves in place of final lists, it says itself)
-    ctx->k_recorded = ctx->t_recorded = false;
+    if (timed) ctx->k_recorded = ctx->t_recorded = false;     // (the timed call's: another problem's call beside it leaves them)
     P->split_ran = P->patched_contigs = P->patched_counts = false;
     const BatchPlan B = plan_batch(ctx, kn, P, nb, timed, o);
     if (P->sampler == GAT_SAMPLER_SHIFT) rc = enqueue_shift(ctx, P, B, seed, begin);
@@ -1021,25 +1033,25 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
     else rc = enqueue_placement_sampler(ctx, P, B, seed, begin, A);
     if (rc) return rc;
   }
-  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[1], call_stream(ctx, P)));
   if (P->merge_contigs && P->n_contigs > 0 && (rc = enqueue_contigs(ctx, P, kn, nb))) return rc;
-  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[2], call_stream(ctx, P)));
   if (!P->h_order.empty()) {
     // (behind k_contig: on isochore problems it is k_contig that writes the statistics of the units k_tail finished)
     const int32_t* skip_ptr = A.skip != nullptr ? A.skip : A.tb;     // (n_tail_units: finished by k_tail / carried on by k_tail_big)
-    hipLaunchKernelGGL(gat::k_reduce_stats, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)P->d_ws_stat.p,
+    hipLaunchKernelGGL(gat::k_reduce_stats, dim3(256), dim3(256), 0, call_stream(ctx, P), (const uint32_t*)P->d_ws_stat.p,
                        (int64_t)nb, (int64_t)P->n_units, (int64_t)P->batch, P->d_stat.p, skip_ptr, A.skip_stride);
     HIPCHK(ctx, hipGetLastError());
   }
 #ifdef GAT_DBG_QUEUE
-  { unsigned long long w[16]; hipStreamSynchronize(ctx->stream); hipMemcpy(w, P->d_stat.p, 16 * 8, hipMemcpyDeviceToHost);
+  { unsigned long long w[16]; hipStreamSynchronize(call_stream(ctx, P)); hipMemcpy(w, P->d_stat.p, 16 * 8, hipMemcpyDeviceToHost);
     fprintf(stderr, "round broken by: empty segment %llu, placeholder neighbour %llu, both neighbours and more %llu, two on the right %llu, two logged %llu, logged + neighbour %llu\n", w[10], w[11], w[12], w[13], w[14], w[15]); }
 #endif
-  HIPCHK(ctx, hipMemcpyAsync(h_stat, P->d_stat.p, 10 * 8, hipMemcpyDeviceToHost, ctx->stream));   // (word 9: the queue's length)
+  HIPCHK(ctx, hipMemcpyAsync(h_stat, P->d_stat.p, 10 * 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));   // (word 9: the queue's length)
   if (P->sampler == GAT_SAMPLER_BRUTE_FORCE)                                                       // (the first unit that did not converge)
-    HIPCHK(ctx, hipMemcpyAsync(h_stat + gat::kBruteFirstWord, P->d_stat.p + gat::kBruteFirstWord, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h_stat + gat::kBruteFirstWord, P->d_stat.p + gat::kBruteFirstWord, 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));
   if (o.defer) return GAT_OK;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(call_stream(ctx, P)));
   return finish_sampler_batch(ctx, P, kn, nb, st, timed, h_stat);
 }
 
@@ -1241,8 +1253,9 @@ static void fill_count_args(gat_problem* P, gat::CountArgs& A, int64_t nb) {
 }
 
 // ---- the batch seam: enqueue / wait ---------------------------------------------------------------------------
-// A call is cut into batches that fit the scratch budget.  call_begin enqueues them one behind the other on the context's
-// stream -- sampler kernels, count kernels, the copy of the batch's status word and statistics into a pinned slot of its own
+// A call is cut into batches that fit the scratch budget.  call_begin enqueues them one behind the other on the call's
+// stream (call_stream: the context's, or -- with another problem's call in flight -- one of its lanes, call_lane_for:
+// the fork in front of the first count kernel, the join behind the enqueue) -- sampler kernels, count kernels, the copy of the batch's status word and statistics into a pinned slot of its own
 // -- up to kMaxInflight of them, and returns; the host does what else it has to do.  call_wait synchronises once, reads the
 // slots in order, and where a batch has to be repeated (a unit's region overflowed, a contig's lists beyond the launch's
 // LDS) lays the slab out again and enqueues that batch and everything behind it once more: results do not depend on the
@@ -1276,6 +1289,8 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
   // (the events behind every kernel and the serial stream's saved state exist once: such calls keep one batch in flight)
   const int max_flight = (K.timed || serial) ? 1 : kMaxInflight;
   PrepTimer tm;
+  // (a layout made again was uploaded on the context's stream: it has arrived before a lane's kernels read it)
+  if (K.lane >= 0) HIPCHK(ctx, stage_flush(ctx));
   for (;;) {
     if (K.count_pending) {
       // ---- the count kernels of the newest batch
@@ -1286,11 +1301,18 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
       const int64_t nb = K.nb[slot];
       const int swap_capx = call_swap_capx(ctx, P);
       K.mstat_on = P->anno->dev.has_merged;
+      if (K.lane >= 0 && !K.fork_waited) {
+        // the fork: the count kernels are the call's first access to memory of the caller's (the count matrix) -- what the
+        // caller ordered in front of the call on its stream is in front of them.  The sampler kernels before this point
+        // touch the problem's own scratch and the read-only tables alone and started without waiting
+        HIPCHK(ctx, hipStreamWaitEvent(call_stream(ctx, P), K.blk->ev_fork, 0));
+        K.fork_waited = true;
+      }
       if (K.mstat_on && K.enq == nb) {
         // (k_count_merged's own traffic counters: only a problem with a merged index can take that kernel; zeroed in front of
         //  the call's first count kernel)
         if (P->d_mstat.n < 512) HIPCHK(ctx, P->d_mstat.alloc(512));
-        HIPCHK(ctx, hipMemsetAsync(P->d_mstat.p, 0, 512 * 8, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(P->d_mstat.p, 0, 512 * 8, call_stream(ctx, P)));
       }
       gat::CountArgs A;
       memset(&A, 0, sizeof(A));
@@ -1299,25 +1321,26 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
       A.out_stride = K.S;
       A.out_begin = K.enq - nb;
       A.mstat = K.mstat_on ? P->d_mstat.p : nullptr;
-      if (K.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_cnt[0], ctx->stream));
+      if (K.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_cnt[0], call_stream(ctx, P)));
       CountLaunch L;
+      L.stream = call_stream(ctx, P);
       L.ev_main = K.blk->ev_main[slot];
       L.units = P->d_units.p; L.ws = P->d_ws.p; L.ws_tree = P->d_ws_tree.p;
       for (int c = 0; c < P->n_contigs; ++c) L.max_units = std::max(L.max_units, P->h_contig_unit_off[(size_t)c + 1] - P->h_contig_unit_off[(size_t)c]);
       if ((rc = launch_count(ctx, kn, P->anno->dev, C, A, P->d_part, swap_capx,
                              P->merge_contigs ? P->max_contig_cap : P->max_unit_cap, L))) return rc;
       if (A.cu_rec != nullptr)       // k_units_overlap's words (candidates, "not pairwise", overlaps taken off) into the batch's slot
-        HIPCHK(ctx, hipMemcpyAsync(K.blk->h_stat + (size_t)slot * 16 + 10, P->d_cand_count.p + gat::kCandSlots, 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(K.blk->h_stat + (size_t)slot * 16 + 10, P->d_cand_count.p + gat::kCandSlots, 16, hipMemcpyDeviceToHost, call_stream(ctx, P)));
       else { K.blk->h_stat[(size_t)slot * 16 + 10] = 0; K.blk->h_stat[(size_t)slot * 16 + 11] = 0; }
-      if (K.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_cnt[1], ctx->stream));
+      if (K.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_cnt[1], call_stream(ctx, P)));
       K.main_rec[slot] = L.main_recorded;
       K.count_kernel[slot] = L.count_kernel;
       K.count_pending = false;
       if (K.enq == K.S) {
         // (the call's end rides on the last batch's synchronisation -- one round trip to the device less per call; a batch
         //  that has to be repeated enqueues it again)
-        if (K.mstat_on) HIPCHK(ctx, hipMemcpyAsync(K.blk->h_mstat, P->d_mstat.p, 512 * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(K.blk->ev_end, ctx->stream));
+        if (K.mstat_on) HIPCHK(ctx, hipMemcpyAsync(K.blk->h_mstat, P->d_mstat.p, 512 * 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));
+        HIPCHK(ctx, hipEventRecord(K.blk->ev_end, call_stream(ctx, P)));
         K.end_recorded = true;
       }
     }
@@ -1350,7 +1373,7 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
     const int64_t nb = std::min<int64_t>(P->batch, K.S - K.enq);
     const int slot = K.n_flight;
     if (d_state != nullptr)
-      HIPCHK(ctx, hipMemcpyAsync(d_state + GAT_MT_STATE_WORDS, d_state, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      HIPCHK(ctx, hipMemcpyAsync(d_state + GAT_MT_STATE_WORDS, d_state, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, call_stream(ctx, P)));
     // counts alone, all of them k_count_seg's: it reads the units as k_tail left them (no final lists are written)
     const bool records_ok = !C.any_anno && !kn.count_final_lists &&
                             (route == GAT_COUNT_KERNEL_SEG || route == GAT_COUNT_KERNEL_MERGED);
@@ -1368,12 +1391,12 @@ static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
       if (kn.test_small_caps) est = 1.0;        // (tests: regions that overflow, the batch repeated with larger ones)
       const size_t want = (size_t)std::min(est * P->cand_scale, 1024.0 * 1024) * gat::kCandSlots;
       if (P->d_cand.n < want && K.n_flight == 0) {
-        if (P->d_cand.n > 0) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier call's kernels may still read the old buffer)
+        if (P->d_cand.n > 0) HIPCHK(ctx, hipStreamSynchronize(call_stream(ctx, P)));   // (an earlier call's kernels may still read the old buffer)
         HIPCHK(ctx, P->d_cand.alloc(want));
       }
       if (P->d_cand_count.n == 0) {
         HIPCHK(ctx, P->d_cand_count.alloc(gat::kCandSlots + 4));
-        HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, (gat::kCandSlots + 4) * 4, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, (gat::kCandSlots + 4) * 4, call_stream(ctx, P)));
       }
     }
     BatchOpts o;
@@ -1397,12 +1420,17 @@ static void call_end(gat_ctx* ctx, gat_problem* P) {
   CallState& K = P->call;
   if (K.blk) ctx->call_blocks.push_back(K.blk);
   K.blk = nullptr;
+  if (K.active) {
+    ctx->calls_in_flight -= 1;
+    if (K.lane >= 0) ctx->lane_calls[K.lane] -= 1;
+  }
+  K.lane = -1;
   K.active = false;
   if (ctx->timed_owner == (const void*)P) ctx->timed_owner = nullptr;
 }
 
 static int call_begin(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, int n_counters, uint32_t seed,
-                      int64_t sample_begin, int64_t sample_end, void* counts_dev, uint32_t* state_host) {
+                      int64_t sample_begin, int64_t sample_end, void* counts_dev, uint32_t* state_host, bool asynchronous) {
   if (!ctx || !P || !counts_dev || (n_counters > 0 && !counter_ids)) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count: NULL argument");
   if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
   if (n_counters < 0 || n_counters > GAT_NUM_COUNTERS) return set_err(ctx, GAT_ERR_ARG, "%d counters (0..%d)", n_counters, GAT_NUM_COUNTERS);
@@ -1418,6 +1446,9 @@ static int call_begin(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, 
                    "(keys without isochores): the counters assert (gat/SegmentList.pyx:1031)");
   if ((rc = call_block_get(ctx, &K.blk))) return rc;
   K.active = true;
+  K.lane = -1;
+  K.fork_waited = false;
+  ctx->calls_in_flight += 1;                       // (this one included: call_end takes it off)
   K.knobs = read_knobs(ctx);                       // the call's: every batch of it, the ones gat_wait enqueues too
   for (int i = 0; i < n_counters; ++i) K.ids[i] = counter_ids[i];
   K.n_counters = n_counters;
@@ -1435,8 +1466,21 @@ static int call_begin(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, 
   K.mstat_on = false;                              // (set with the first count kernels: it takes the tables)
   K.count_pending = false;
   K.end_recorded = false;
-  auto fail = [&](int code) { call_end(ctx, P); return code; };
-  if (hipEventRecord(K.blk->ev_begin, ctx->stream) != hipSuccess) return fail(set_err(ctx, GAT_ERR_DEVICE, "hipEventRecord failed"));
+  // (a call that failed half enqueued: what it put on a lane has run before the problem's next call, on whatever stream, starts)
+  auto fail = [&](int code) { if (K.lane >= 0) (void)hipStreamSynchronize(call_stream(ctx, P)); call_end(ctx, P); return code; };
+  {
+    bool busy[kMaxLanes];
+    for (int l = 0; l < kMaxLanes; ++l) busy[l] = ctx->lane_calls[l] > 0;
+    const int lane = K.S > 0 ? call_lane_for((int)K.knobs.call_lanes, asynchronous, times_wanted, state_host != nullptr, ctx->calls_in_flight - 1, busy) : -1;
+    if (lane >= 0) {
+      if (ctx->lanes[lane] == nullptr && hipStreamCreateWithFlags(&ctx->lanes[lane], hipStreamNonBlocking) != hipSuccess)
+        return fail(set_err(ctx, GAT_ERR_DEVICE, "hipStreamCreateWithFlags failed (call lane %d)", lane));
+      if (hipEventRecord(K.blk->ev_fork, ctx->stream) != hipSuccess) return fail(set_err(ctx, GAT_ERR_DEVICE, "hipEventRecord failed"));
+      K.lane = lane;
+      ctx->lane_calls[lane] += 1;
+    }
+  }
+  if (hipEventRecord(K.blk->ev_begin, call_stream(ctx, P)) != hipSuccess) return fail(set_err(ctx, GAT_ERR_DEVICE, "hipEventRecord failed"));
   if (state_host != nullptr) {
     // the run's one stream: its state lives on the device over the batches (a copy restores it when a batch is repeated)
     if (P->d_serial.n < 2 * (size_t)GAT_MT_STATE_WORDS && P->d_serial.alloc(2 * (size_t)GAT_MT_STATE_WORDS) != hipSuccess)
@@ -1449,6 +1493,12 @@ static int call_begin(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, 
     return GAT_OK;
   }
   if ((rc = call_enqueue_more(ctx, P, false))) return fail(rc);
+  if (K.lane >= 0) {
+    // the join: what the caller puts on its stream from here on is behind what this enqueue put on the lane (what gat_wait
+    // enqueues later -- count kernels that waited for the tables, batches beyond kMaxInflight, repeats -- it also waits for)
+    if (hipEventRecord(K.blk->ev_join, call_stream(ctx, P)) != hipSuccess || hipStreamWaitEvent(ctx->stream, K.blk->ev_join, 0) != hipSuccess)
+      return fail(set_err(ctx, GAT_ERR_DEVICE, "joining the call's lane failed"));
+  }
   return GAT_OK;
 }
 
@@ -1458,7 +1508,7 @@ static int call_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) {
   if (!K.active) return set_err(ctx, GAT_ERR_ARG, "gat_wait: no call in flight on this problem");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // (a failed call returns no counts; its statistics as far as they go are written: SamplerBruteForce's n_unconverged)
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); if (stats) *stats = K.local; call_end(ctx, P); return code; };
+  auto fail = [&](int code) { (void)hipStreamSynchronize(call_stream(ctx, P)); if (stats) *stats = K.local; call_end(ctx, P); return code; };
   PrepTimer tm;
   int rc;
   if (K.count_pending && (rc = call_enqueue_more(ctx, P, true))) return fail(rc);   // (the tables were still being built)
@@ -1473,7 +1523,7 @@ static int call_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) {
     // (the call's own end where it is on the stream -- its last batch enqueued --, not the stream's: another problem's call
     //  enqueued behind this one -- run() keeps two segment tracks in flight, bench.py two steps -- goes on running while the
     //  host reads this one's status words and enqueues the next)
-    const hipError_t se = K.end_recorded ? hipEventSynchronize(K.blk->ev_end) : hipStreamSynchronize(ctx->stream);
+    const hipError_t se = K.end_recorded ? hipEventSynchronize(K.blk->ev_end) : hipStreamSynchronize(call_stream(ctx, P));
     if (se != hipSuccess) return fail(set_err(ctx, GAT_ERR_DEVICE, "synchronising with the call's batches failed: %s", hipGetErrorString(hipGetLastError())));
     K.end_recorded = false;
     tm.lap("batches synchronised");
@@ -1481,7 +1531,7 @@ static int call_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) {
       rc = finish_sampler_batch(ctx, P, K.knobs, K.nb[slot], &K.local, K.timed, K.blk->h_stat + (size_t)slot * 16);
       if (rc == kRelayout) {
         if (K.state_host != nullptr)        // (the repeated batch draws from where this one began)
-          if (hipMemcpyAsync(P->d_serial.p, P->d_serial.p + GAT_MT_STATE_WORDS, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+          if (hipMemcpyAsync(P->d_serial.p, P->d_serial.p + GAT_MT_STATE_WORDS, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, call_stream(ctx, P)) != hipSuccess)
             return fail(set_err(ctx, GAT_ERR_DEVICE, "restoring the stream's state failed"));
         break;
       }
@@ -1516,7 +1566,7 @@ static int call_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) {
 
 extern "C" int gat_sample_and_count_enqueue(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, int n_counters,
                                             uint32_t seed, int64_t sample_begin, int64_t sample_end, void* counts_dev) {
-  return call_begin(ctx, P, counter_ids, n_counters, seed, sample_begin, sample_end, counts_dev, nullptr);
+  return call_begin(ctx, P, counter_ids, n_counters, seed, sample_begin, sample_end, counts_dev, nullptr, true);
 }
 
 extern "C" int gat_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) { return call_wait(ctx, P, stats); }
@@ -1524,7 +1574,7 @@ extern "C" int gat_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) { return
 extern "C" int gat_sample_and_count(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, int n_counters,
                                     uint32_t seed, int64_t sample_begin, int64_t sample_end, void* counts_dev,
                                     gat_stats* stats) {
-  const int rc = call_begin(ctx, P, counter_ids, n_counters, seed, sample_begin, sample_end, counts_dev, nullptr);
+  const int rc = call_begin(ctx, P, counter_ids, n_counters, seed, sample_begin, sample_end, counts_dev, nullptr, false);
   return rc ? rc : call_wait(ctx, P, stats);
 }
 
@@ -1540,7 +1590,7 @@ extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const i
   if (P->sampler == GAT_SAMPLER_BRUTE_FORCE)
     return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerBruteForce runs on the per-unit streams only");
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
-  const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state);
+  const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state, false);
   return rc ? rc : call_wait(ctx, P, stats);
 }
 
@@ -1723,6 +1773,7 @@ static int count_lists_body(gat_ctx* ctx, const Knobs& kn, const int32_t* counte
     int32_t longest = 0;
     for (int g = 0; g < n_groups; ++g) longest = std::max(longest, h_n[(size_t)(l * n_groups + g)]);
     CountLaunch L;
+    L.stream = ctx->stream;
     L.ev_main = ctx->ev_main;
     if ((rc = launch_count(ctx, kn, A, C, K, d_part, 0, longest, L))) return rc;
   }

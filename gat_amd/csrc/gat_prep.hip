@@ -1732,10 +1732,19 @@ extern "C" void gat_problem_destroy(gat_problem* p) {
   gat_ctx* ctx = p->ctx;
   if (ctx) {
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);         // its blocks go back to the pool: nothing may still be running on them
+    // its blocks go back to the pool: nothing may still be running on them -- the lane of a call in flight first (what gat_wait
+    // would have waited for), then the context's stream
+    if (p->call.active && p->call.lane >= 0) (void)hipStreamSynchronize(call_stream(ctx, p));
+    (void)hipStreamSynchronize(ctx->stream);
     ctx->stage_used = 0;
     if (p->call.blk) ctx->call_blocks.push_back(p->call.blk);     // (destroyed with a call in flight: the call is dropped)
     p->call.blk = nullptr;
+    if (p->call.active) {
+      ctx->calls_in_flight -= 1;
+      if (p->call.lane >= 0) ctx->lane_calls[p->call.lane] -= 1;
+      if (ctx->timed_owner == (const void*)p) ctx->timed_owner = nullptr;
+      p->call.active = false;
+    }
   }
   delete p;                                          // (lets go of its annotation tables)
   if (ctx) ctx_release(ctx);

@@ -230,6 +230,16 @@ const char* gat_ctx_get_option(const gat_ctx* ctx, const char* key);   /* NULL: 
  * runs other work on the device -- a collective over the count matrix, a copy -- orders it against the library's with
  * events on this stream instead of synchronising the device */
 void* gat_ctx_stream(const gat_ctx* ctx);
+/* Call lanes (GAT_CALL_LANES, default 2, at most 4; below 2: none).  A call enqueued with gat_sample_and_count_enqueue while a
+ * call of ANOTHER problem of the context is in flight runs on a stream of the library's own, beside that call.  Towards the
+ * caller's stream it is ordered both ways: its count kernels -- its first access to the caller's count matrix -- wait for what
+ * was on the caller's stream at the enqueue, and the caller's stream waits for the call before it takes up what is put on it
+ * after the enqueue.  Its sampler kernels touch only the problem's own scratch and start at once.
+ * gat_call_lane_for is the rule itself, a pure function (no device): the lane (0 .. n_lanes - 1) a call takes, or -1 for the
+ * context's stream.  lane_busy: n_lanes flags, a call in flight runs on that lane; others_in_flight: calls of other problems
+ * in flight on the context.  Synchronous entry points, calls with per-kernel timing and calls with a serial MT19937 state
+ * stay on the context's stream; so does a call with nothing else in flight. */
+int gat_call_lane_for(int n_lanes, int asynchronous, int timed, int serial_state, int others_in_flight, const int32_t* lane_busy);
 /* per-kernel device times in gat_stats (see there) on / off; off by default.  GAT_KERNEL_TIMES=1 in the environment
  * switches them on for every context. */
 int gat_ctx_set_kernel_times(gat_ctx* ctx, int on);
@@ -282,13 +292,14 @@ int gat_sample_and_count(gat_ctx* ctx, gat_problem* p,
 /* The same call in two halves, for a host that has work of its own to do while the device samples (gat.run computes the
  * observed counts, gat/__init__.py:933-940, and the sizes of its result rows, :1000-1068, around the sampling; the
  * reference's process pool -- map_async, gat/__init__.py:681-700 -- is asynchronous in the same way).
- * gat_sample_and_count_enqueue validates the arguments, enqueues the call's batches on the ctx stream (up to 8 ahead) and
+ * gat_sample_and_count_enqueue validates the arguments, enqueues the call's batches (up to 8 ahead; on the ctx stream or a call lane, below) and
  * returns; counts_dev must stay valid and untouched until gat_wait.  gat_wait(ctx, p, stats) blocks until the batches have
  * completed, checks their status words -- a batch that has to be repeated (a unit's region of the slab overflowed) is
  * repeated in here, with everything that was enqueued behind it -- and reports what gat_sample_and_count would have
  * (GAT_ERR_ASSERT where the reference's sampler asserts, :645).  One call in flight per problem; several problems of one
- * context may each have one (they run one behind the other on the context's stream; gat_wait waits for the end of ITS call
- * -- an event behind its last batch --, not for the stream: what another problem has enqueued behind it keeps running
+ * context may each have one (their kernels run side by side on the context's call lanes, gat_call_lane_for; with
+ * GAT_CALL_LANES=1 one behind the other on the context's stream; gat_wait waits for the end of ITS call
+ * -- an event behind its last batch --, not for a stream: what another problem has enqueued keeps running
  * while the host reads the results and enqueues the next call).  gat_problem_destroy drops a call in flight.  gat_sample_and_count(...) == enqueue + wait. */
 int gat_sample_and_count_enqueue(gat_ctx* ctx, gat_problem* p,
                                  const int32_t* counter_ids, int n_counters,
