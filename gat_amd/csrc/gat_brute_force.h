@@ -44,13 +44,12 @@ struct BruteForceArgs {
   int64_t slab_stride;
   int32_t* unit_n;            // [batch][n_units]
   int32_t* flags;
-  unsigned long long* stat;   // word 6: restarts + (units not converged << kBruteUnconvShift); word 12: ~(the first of them)
+  unsigned long long* stat;   // the batch's status block: kStatRestarts, kStatBruteFirst (gat_types.h)
   uint32_t* ws_stat;
 };
 
 constexpr int kBruteLdsCap = 256;          // accepted segments in LDS: 2 KB beside the generator's 2.5
-constexpr int kBruteUnconvShift = 40;
-constexpr int kBruteFirstWord = 12;        // (words 10 and 11 of a batch's pinned statistics belong to k_units_overlap)
+constexpr int kBruteUnconvShift = 40;     // kStatRestarts: the restarts below this bit, the work units not converged from it up
 
 __global__ __launch_bounds__(64) void k_brute_force(BruteForceArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -143,8 +142,8 @@ __global__ __launch_bounds__(64) void k_brute_force(BruteForceArgs A) {
     *reinterpret_cast<uint4*>(A.ws_stat + ((int64_t)u * A.rec_stride + sidx) * 4) = make_uint4(placed, rng.ndraws, rejected, 1u);
     if (!status) {
       const unsigned long long unconv = converged ? 0ull : 1ull;
-      if (passes > 1 || unconv) atomicAdd(&A.stat[6], (unsigned long long)(passes - 1) + (unconv << kBruteUnconvShift));
-      if (unconv) atomicMax(&A.stat[kBruteFirstWord], ~((sample_id << 32) | (unsigned long long)(uint32_t)u));
+      if (passes > 1 || unconv) atomicAdd(&A.stat[kStatRestarts], (unsigned long long)(passes - 1) + (unconv << kBruteUnconvShift));
+      if (unconv) atomicMax(&A.stat[kStatBruteFirst], ~((sample_id << 32) | (unsigned long long)(uint32_t)u));
     }
   }
 }

@@ -34,8 +34,10 @@ extern thread_local std::string g_last_error;
 // page tables (see staged_h2d), so the blocks belong to the context and are lent to a problem for the length of a call.
 constexpr int kMaxInflight = 8;               // batches of one call enqueued before the first status word is read
 struct CallBlock {
-  unsigned long long* h_stat = nullptr;       // pinned, kMaxInflight x 16 words: per batch the statistics, the status word in word 8
-  unsigned long long* h_mstat = nullptr;      // pinned, 512 words: k_count_merged's traffic counters of the call
+  unsigned long long* h_stat = nullptr;       // pinned, kMaxInflight slots: per batch in flight its status block (gat_types.h: kStat*)
+  unsigned long long* h_mstat = nullptr;      // pinned, 512 words behind them: k_count_merged's traffic counters of the call
+  static constexpr size_t kStatBytes = (size_t)kMaxInflight * gat::kStatSlotWords * sizeof(unsigned long long);
+  unsigned long long* stat_slot(int i) const { return h_stat + (size_t)i * gat::kStatSlotWords; }   // the pinned words of slot i
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   hipEvent_t ev_main[kMaxInflight][2] = {};   // around the dominant count kernel of every batch in flight
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // (no timing) a call on a lane: the caller's stream at the enqueue; the lane
@@ -109,12 +111,12 @@ struct gat_ctx {
   const void* timed_owner = nullptr;            // the problem whose call in flight owns the per-kernel events above (they exist once
                                                 // per context: a second call enqueued meanwhile -- run() keeps two problems' calls
                                                 // in flight -- runs untimed instead of re-recording them under the first: ADVICE r4)
-  // status word and statistics of a sampler batch, copied behind its kernels and read after the batch's ONE synchronisation
   std::vector<std::pair<void*, size_t>> user_allocs;   // gat_dev_alloc'ed blocks and their sizes (back to the pool at gat_dev_free)
   void* h_stage = nullptr;                      // pinned staging buffer of gat_memcpy_d2h (grows; pageable targets are filled from it)
   size_t h_stage_bytes = 0;
   int32_t* h_flags = nullptr;                   // pinned
-  unsigned long long* h_stat = nullptr;         // pinned, 16 words: statistics and status word of a gat_sample batch
+  unsigned long long* h_stat = nullptr;         // pinned, one slot (kStatSlotWords): the status block of a gat_sample batch, copied behind
+                                                // its kernels and read after the batch's ONE synchronisation
   std::string err;
   int max_lds = 65536;
   // gat_ctx_set_option: the context's own values of the tuning / testing knobs (GAT_*), in front of the process's -- the
@@ -398,10 +400,10 @@ struct gat_problem {
   int64_t batch = 0;
   DevBuf<uint2> d_slab, d_cslab;
   DevBuf<int32_t> d_unit_n, d_contig_n;
-  // the status word of a batch lives behind its statistics (word 8 of d_stat): one memset, one read-back for both
-  int32_t* flags_dev() const { return reinterpret_cast<int32_t*>(d_stat.p + 8); }
-  uint32_t* todo_count_dev() const { return reinterpret_cast<uint32_t*>(d_stat.p + 9); }   // (k_tail's queue length: word 9)
-  DevBuf<unsigned long long> d_stat;
+  // the status word of a batch and k_tail's queue length live behind its statistics in d_stat: one memset, one read-back for all
+  int32_t* flags_dev() const { return reinterpret_cast<int32_t*>(d_stat.p + gat::kStatFlags); }
+  uint32_t* todo_count_dev() const { return reinterpret_cast<uint32_t*>(d_stat.p + gat::kStatQueued); }
+  DevBuf<unsigned long long> d_stat;     // the batch's status block, kStatSlotWords words (gat_types.h: kStat*)
   DevBuf<unsigned long long> d_mstat;    // k_count_merged: 256 pairs {index entries read, segments looked up} (CountArgs::mstat)
   // lane-parallel front end (k_rng + k_place)
   std::vector<int32_t> h_rng_rows;       // per active index: raw outputs generated per stream

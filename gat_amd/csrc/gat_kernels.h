@@ -38,7 +38,7 @@ struct SamplerArgs {
   int64_t slab_stride;
   int32_t* unit_n;            // [batch][n_units]
   int32_t* flags;             // OR of kStatus*
-  unsigned long long* stat;   // [0]=placed [1]=draws [2]=unsuccessful rounds [3]=output segments [4]=full-mode units
+  unsigned long long* stat;   // the batch's status block, kStatSlotWords words (gat_types.h: kStat*)
   uint32_t* ws_stat;          // [unit][rec_stride][4]: the same per work unit (summed by k_reduce_stats; one
                               // atomic per work unit on a single line costs more than the sampling itself)
   // lane-parallel front end (k_rng + k_place); all null/0 when the sampler runs stand-alone
@@ -2428,16 +2428,19 @@ __global__ __launch_bounds__(256) void k_reduce_stats(const uint32_t* __restrict
     // work units finished on the split path (k_tail's records are indexed by launch position: n_units rows as well)
     if (skip != nullptr) a3 += skip[r * skip_stride] != 0 ? 1 : 0;
   }
-  __shared__ unsigned long long red[4][6];
+  __shared__ unsigned long long red[4][kStatReduced];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {
     a0 += __shfl_xor(a0, d); a1 += __shfl_xor(a1, d); a2 += __shfl_xor(a2, d); a4 += __shfl_xor(a4, d); a3 += __shfl_xor(a3, d);
     a5 += __shfl_xor(a5, d);
   }
-  if (lane == 0) { red[wave][0] = a0; red[wave][1] = a1; red[wave][2] = a2; red[wave][3] = a3; red[wave][4] = a4; red[wave][5] = a5; }
+  if (lane == 0) {
+    red[wave][kStatPlaced] = a0; red[wave][kStatDraws] = a1; red[wave][kStatUnsuccessful] = a2;
+    red[wave][kStatTailUnits] = a3; red[wave][kStatFullUnits] = a4; red[wave][kStatResumedUnits] = a5;
+  }
   __syncthreads();
-  if (threadIdx.x < 6) {
+  if (threadIdx.x < kStatReduced) {           // (words 0 .. kStatReduced - 1 in the names' order: asserted in gat_types.h)
     const unsigned long long t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
     atomicAdd(&stat[threadIdx.x], t);
   }

@@ -78,8 +78,8 @@ extern "C" int gat_ctx_create(gat_ctx** out, int device_id, void* stream) {
   for (auto& ev : ctx->ev_t) HIPCHK(ctx, hipEventCreate(&ev));
   for (auto& ev : ctx->ev_cnt) HIPCHK(ctx, hipEventCreate(&ev));
   HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_flags, 64, hipHostMallocDefault));
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_stat, 128, hipHostMallocDefault));
-  memset(ctx->h_stat, 0, 128);
+  HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_stat, gat::kStatSlotWords * 8, hipHostMallocDefault));
+  memset(ctx->h_stat, 0, gat::kStatSlotWords * 8);
   *out = ctx;
   return GAT_OK;
 }
@@ -88,8 +88,9 @@ extern "C" int gat_ctx_create(gat_ctx** out, int device_id, void* stream) {
 static int call_block_get(gat_ctx* ctx, CallBlock** out) {
   if (!ctx->call_blocks.empty()) { *out = ctx->call_blocks.back(); ctx->call_blocks.pop_back(); return GAT_OK; }
   std::unique_ptr<CallBlock> b(new CallBlock());
-  HIPCHK(ctx, hipHostMalloc((void**)&b->h_stat, (size_t)kMaxInflight * 16 * 8 + 512 * 8, hipHostMallocDefault));
-  b->h_mstat = b->h_stat + (size_t)kMaxInflight * 16;
+  static_assert(CallBlock::kStatBytes == (size_t)kMaxInflight * gat::kStatSlotWords * 8, "the slots as allocated and as stat_slot() indexes them");
+  HIPCHK(ctx, hipHostMalloc((void**)&b->h_stat, CallBlock::kStatBytes + 512 * 8, hipHostMallocDefault));
+  b->h_mstat = b->stat_slot(kMaxInflight);         // (behind the last slot)
   HIPCHK(ctx, hipEventCreate(&b->ev_begin));
   HIPCHK(ctx, hipEventCreate(&b->ev_end));
   for (auto& pair : b->ev_main) for (auto& ev : pair) HIPCHK(ctx, hipEventCreate(&ev));
@@ -463,7 +464,6 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
 // capacities (scratch released: the batch that fits the budget may now be smaller) and nothing of this batch is valid;
 // the caller sizes the batch again and repeats it (results do not depend on the batching: streams are per unit).
 constexpr int kRelayout = 1;
-static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb, gat_stats* st, bool timed, const unsigned long long* h_stat);
 
 // what a caller of run_sampler_batch asks for beyond the defaults
 struct BatchOpts {
@@ -610,7 +610,7 @@ static int enqueue_brute_force(gat_ctx* ctx, gat_problem* P, const BatchPlan& B,
   H.ntries_inner = P->brute_ntries_inner; H.ntries_outer = P->brute_ntries_outer;
   H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.rank_len = P->d_rank_len.p;
   H.stat = P->d_stat.p;
-  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p + gat::kBruteFirstWord, 0, 8, call_stream(ctx, P)));
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p + gat::kStatBruteFirst, 0, 8, call_stream(ctx, P)));
   return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_brute_force, H, (size_t)(gat::kMtLdsWords + 2 * (size_t)H.lds_cap) * 4);
 }
 
@@ -1002,6 +1002,182 @@ static int enqueue_contigs(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_
   return GAT_OK;
 }
 
+// ---- a sampler batch whose kernels have completed (the stream has been synchronised): its checks, then its statistics ----
+// a batch that did not fit: the slab laid out again (the caller has set what the new layout takes), the batch to be repeated
+static int relayout_and_repeat(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb, gat_stats* st, const char* too_large) {
+  if (layout_slab(P, kn)) return set_err(ctx, GAT_ERR_CAPACITY, "%s", too_large);
+  if (const int rc = upload_layout(ctx, P, kn)) return rc;
+  if (st) st->n_retried += nb * (int64_t)P->h_order.size();
+  return kRelayout;
+}
+
+// The status checks: an error, kRelayout (nothing of the batch is valid: the caller repeats it), or GAT_OK.  The statistics that go
+// with a check -- SamplerBruteForce's, k_units_overlap's -- are added here: a call that fails on them still reports them
+static int check_batch_status(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb, gat_stats* st, const unsigned long long* h_stat) {
+  const int32_t flags = *reinterpret_cast<const int32_t*>(h_stat + gat::kStatFlags);
+  if (flags & gat::kStatusCoordRange)
+    return set_err(ctx, GAT_ERR_ASSERT, "SamplerLocalPermutation: a sampled coordinate exceeds 2^31 - 1 before it wraps (flags=%d): the reference "
+                                        "raises OverflowError (gat/Engine.pyx:1208, :1212)", flags);
+  if (flags & (gat::kStatusAssert | gat::kStatusTrimAssert))
+    return set_err(ctx, GAT_ERR_ASSERT, "sampler assertion failed on device (flags=%d): %s", flags,
+                   (flags & gat::kStatusAssert) ? "sampled list has no overlap with the workspace (gat/Engine.pyx:645)"
+                                                : "trimming more than the total length (gat/SegmentList.pyx:560)");
+  if ((flags & gat::kStatusContigLds) && !(flags & gat::kStatusOverflow)) {
+    // a contig's lists were longer than expected: LDS for every unit at its capacity from now on, batch repeated
+    P->contig_tight = false;
+    return relayout_and_repeat(ctx, P, kn, nb, st, "per-sample slab exceeds 2^31 segments");
+  }
+  if (flags & gat::kStatusOverflow) {
+    // (doubled until the lists fit: a unit whose segments are longer than its whole workspace beside one of a few bases places
+    //  thousands of the small one between the large one's trims -- two of 200 000 edge-case seeds needed more than 64 x 128 slots,
+    //  which the reference's lists simply grow to (round 6); the per-sample slab's 2^31 segments and the device's memory end it)
+    if (P->cap_scale >= (1 << 20)) return set_err(ctx, GAT_ERR_CAPACITY, "sampler slab overflow even at 2^20 x capacity");
+    P->cap_scale *= 2;
+    return relayout_and_repeat(ctx, P, kn, nb, st, "per-sample slab exceeds 2^31 segments after growth");
+  }
+  if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) {
+    // (behind the overflow check: a batch that is repeated is counted once, as it stands in the end)
+    const unsigned long long restarts = h_stat[gat::kStatRestarts];
+    const int64_t unconv = (int64_t)(restarts >> gat::kBruteUnconvShift);
+    if (st) { st->n_restarts += (int64_t)(restarts & ((1ull << gat::kBruteUnconvShift) - 1ull)); st->n_unconverged += unconv; }
+    if (unconv) {
+      const unsigned long long first = ~h_stat[gat::kStatBruteFirst];
+      return set_err(ctx, GAT_ERR_VALUE, "SamplerBruteForce: sampling did not converge: sample %lld, unit %d used up its %d passes of %d tries "
+                                         "(%lld work units of the batch; gat/Engine.pyx:868-869)", (long long)(first >> 32), (int)(first & 0xffffffffull),
+                     (int)P->brute_ntries_outer, (int)P->brute_ntries_inner, (long long)unconv);
+    }
+  }
+  // k_units_overlap: overlaps between the units' lists that were not pairwise, or more candidates than the buffer holds --
+  // the batch is repeated through k_contig, and the problem keeps to that
+  const uint32_t* uw = reinterpret_cast<const uint32_t*>(h_stat + gat::kStatUnitsOverlap);
+  if (P->units_direct && P->units_direct_ok && uw[0] != 0u) {
+    if ((uw[0] & 1u) != 0u || P->cand_scale >= 64) P->units_direct_ok = false;   // not pairwise (or a buffer that will not do)
+    else P->cand_scale *= 4;                                                       // a candidate region was too small
+    if (st) st->n_retried += nb * (int64_t)P->h_order.size();
+    return kRelayout;
+  }
+  if (st && P->units_direct) { st->n_straddle_candidates += (int64_t)uw[2]; st->n_unit_overlaps += (int64_t)uw[1]; }
+  return GAT_OK;
+}
+
+#if defined(GAT_DIAG) || defined(GAT_DIAG_CONS)
+// diagnostic builds: what the kernels noted about the batch, appended to the file GAT_DIAG_OUT names
+static int dump_batch_diag(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb) {
+  if (const char* fn = kn.diag_out.empty() ? nullptr : kn.diag_out.c_str()) {
+    // shares of a k_sampler work unit's life per phase, summed over the batch (tools/diag_sampler.sh)
+    const size_t nd = (size_t)nb * std::max(1, P->n_units) * 8;
+    std::vector<unsigned long long> h(nd);
+    HIPCHK(ctx, staged_d2h(ctx, h.data(), P->d_diag.p, nd * 8));
+    double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t i = 0; i < nd; ++i) sum[i & 7] += (double)h[i];
+    if (FILE* f = fopen(fn, "a")) {
+      fprintf(f, "{\"work_units\": %lld, \"cycles\": {\"prologue\": %.0f, \"sort\": %.0f, \"merge\": %.0f, \"coverage\": %.0f, "
+                 "\"fast_paths\": %.0f, \"trim\": %.0f, \"draws_placement\": %.0f, \"final_filter_write\": %.0f}}\n",
+              (long long)nb * (long long)P->h_order.size(), sum[0], sum[1], sum[2], sum[3], sum[4], sum[5], sum[6], sum[7]);
+      if (P->d_diag_place.n >= P->h_order.size() * 8 && !P->h_order.empty()) {
+        // k_place's loop, per phase: over all tiles, and for the largest unit alone (launch position 0: the tile the kernel ends with)
+        std::vector<unsigned long long> hp(P->h_order.size() * 8);
+        if (staged_d2h(ctx, hp.data(), P->d_diag_place.p, hp.size() * 8) == hipSuccess) {
+          double all[7] = {0, 0, 0, 0, 0, 0, 0};
+          for (size_t i = 0; i < hp.size(); ++i) all[i & 7] += (i & 7) < 7 ? (double)hp[i] : 0.0;
+          fprintf(f, "{\"k_place\": {\"all_tiles\": {\"row_wait\": %.0f, \"lookups\": %.0f, \"steps\": %.0f, \"flush\": %.0f, \"loop_control\": %.0f, "
+                     "\"rows\": %.0f, \"tiles\": %.0f}, \"largest_unit\": {\"row_wait\": %llu, \"lookups\": %llu, \"steps\": %llu, \"flush\": %llu, "
+                     "\"loop_control\": %llu, \"rows\": %llu, \"tiles\": %llu}}}\n",
+                  all[0], all[1], all[2], all[3], all[4], all[5], all[6], hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6]);
+        }
+      }
+      {
+        // k_place's hand-over records by kind: pending length (triggered), -1 run in full, -2 complete, -3 resume
+        const size_t n_act = P->h_order.size();
+        std::vector<int4> hs(n_act * (size_t)P->batch);
+        if (n_act && P->d_st.n >= hs.size() && staged_d2h(ctx, hs.data(), P->d_st.p, hs.size() * sizeof(int4)) == hipSuccess) {
+          long long kinds[5] = {0, 0, 0, 0, 0};
+          int shown = 0;
+          fprintf(f, "{\"k_place_handover_examples\": [");
+          for (size_t a = 0; a < n_act; ++a)
+            for (int64_t i = 0; i < nb; ++i) {
+              const int4 r = hs[a * (size_t)P->batch + (size_t)i];
+              kinds[r.z > 0 ? 0 : (r.z == -1 ? 1 : (r.z == -2 ? 2 : (r.z == -3 ? 3 : 4)))]++;
+              if (r.z <= 0 && shown < 12) fprintf(f, "%s[%zu, %lld, %d, %d, %d, %d, %d]", shown++ ? ", " : "", a, (long long)i, r.x, r.y, r.z, r.w, P->h_rng_rows.empty() ? -1 : P->h_rng_rows[a]);
+            }
+          {
+            long long sx = 0, sy = 0, sz = 0, sw = 0;
+            for (size_t a = 0; a < n_act; ++a) for (int64_t i = 0; i < nb; ++i) { const int4 r = hs[a * (size_t)P->batch + (size_t)i]; sx += r.x; sy += r.y; sz += r.z; sw += r.w; }
+            fprintf(f, "], \"k_place_handover_sums\": [%lld, %lld, %lld, %lld", sx, sy, sz, sw);
+          }
+          fprintf(f, "], \"k_place_handover\": {\"triggered\": %lld, \"in_full\": %lld, \"complete\": %lld, \"resume\": %lld, \"other\": %lld}}\n",
+                  kinds[0], kinds[1], kinds[2], kinds[3], kinds[4]);
+        }
+      }
+      {
+        // k_place's tiles in time: per unit (launch position) the first begin, the median begin, the median and the last end of
+        // its tiles, in microseconds from the kernel's first begin
+        const size_t n_act = P->h_order.size(), ntl = (size_t)((nb + 63) / 64);
+        std::vector<unsigned long long> ht(n_act * ntl * 2);
+        if (n_act && ntl && P->d_diag_tiles.n >= ht.size() && staged_d2h(ctx, ht.data(), P->d_diag_tiles.p, ht.size() * 8) == hipSuccess) {
+          unsigned long long t_min = ~0ull;
+          for (size_t i = 0; i < ht.size(); i += 2) if (ht[i] && ht[i] < t_min) t_min = ht[i];
+          fprintf(f, "{\"k_place_tiles\": [");
+          for (size_t a = 0; a < n_act; ++a) {
+            std::vector<double> b0, e0;
+            for (size_t t = 0; t < ntl; ++t) {
+              const unsigned long long x = ht[(a * ntl + t) * 2], y = ht[(a * ntl + t) * 2 + 1];
+              if (x && y) { b0.push_back((double)(x - t_min) / 100.0); e0.push_back((double)(y - t_min) / 100.0); }
+            }
+            if (b0.empty()) continue;
+            std::sort(b0.begin(), b0.end()); std::sort(e0.begin(), e0.end());
+            fprintf(f, "%s{\"a\": %zu, \"segments\": %u, \"tiles\": %zu, \"begin_first\": %.1f, \"begin_median\": %.1f, \"begin_last\": %.1f, "
+                       "\"end_first\": %.1f, \"end_median\": %.1f, \"end_last\": %.1f}", a ? ", " : "", a,
+                    P->h_units[(size_t)P->h_order[a]].hist_total, b0.size(), b0.front(), b0[b0.size() / 2], b0.back(), e0.front(), e0[e0.size() / 2], e0.back());
+          }
+          fprintf(f, "]}\n");
+        }
+      }
+      fclose(f);
+    }
+  }
+  return GAT_OK;
+}
+#endif
+
+// the batch's statistics words and, in a timed call, its event laps into the caller's gat_stats
+static void add_batch_stats(gat_ctx* ctx, const gat_problem* P, gat_stats* st, bool timed, const unsigned long long* h_stat) {
+  st->n_placed += (int64_t)h_stat[gat::kStatPlaced];
+  st->n_draws += (int64_t)h_stat[gat::kStatDraws];
+  st->n_unsuccessful += (int64_t)h_stat[gat::kStatUnsuccessful];
+  st->n_tail_units += (int64_t)h_stat[gat::kStatTailUnits];
+  if (P->split_ran && (P->patched_contigs || P->patched_counts)) st->lists_from_records += 1;
+  st->n_full_units += (int64_t)h_stat[gat::kStatFullUnits];
+  st->n_resumed_units += (int64_t)h_stat[gat::kStatResumedUnits];
+  st->n_queued_units += (int64_t)(h_stat[gat::kStatQueued] & 0xffffffffull);
+  st->n_empty_windows += (int64_t)h_stat[gat::kStatEmptyWindows];
+  if (timed) {
+    // (a timing query that fails leaves its figure at 0: it must not turn a call that computed its counts into an error)
+    auto lap = [](hipEvent_t a, hipEvent_t b) { float ms = 0; if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); ms = 0; } return ms; };
+    st->ms_sampler += lap(ctx->ev[0], ctx->ev[1]);
+    st->ms_contig += lap(ctx->ev[1], ctx->ev[2]);
+    if (ctx->k_recorded && !P->h_order.empty()) {
+      st->ms_rng += lap(ctx->ev[0], ctx->ev_k[0]);
+      st->ms_place += lap(ctx->ev_k[0], ctx->ev_k[1]);
+      st->ms_merge += lap(ctx->ev_k[1], ctx->ev_k[2]);
+      st->ms_tail += lap(ctx->ev_k[2], ctx->ev_k[3]);
+      if (ctx->t_recorded) {
+        st->ms_ktail += lap(ctx->ev_k[2], ctx->ev_t[0]);
+        st->ms_finalize += lap(ctx->ev_t[0], ctx->ev_t[1]);
+      }
+    }
+  }
+}
+
+static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb, gat_stats* st, bool timed, const unsigned long long* h_stat) {
+  int rc = check_batch_status(ctx, P, kn, nb, st, h_stat);
+#if defined(GAT_DIAG) || defined(GAT_DIAG_CONS)
+  if (!rc) rc = dump_batch_diag(ctx, P, kn, nb);
+#endif
+  if (!rc && st) add_batch_stats(ctx, P, st, timed, h_stat);
+  return rc;
+}
+
 // One batch as the sequence of its stages: scratch and statistics reset, the units' sampler, fromIsochores, the statistics and
 // -- unless deferred -- the synchronisation and the batch's checks.
 static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t begin, int64_t nb,
@@ -1014,10 +1190,10 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
   // (unit_n, contig_n and ws_stat are zeroed once when allocated: the kernels rewrite every entry of the active units
   //  in every batch and never touch the others)
 #ifdef GAT_DBG_QUEUE
-  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 16 * 8, call_stream(ctx, P)));
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, gat::kStatSlotWords * 8, call_stream(ctx, P)));     // (kStatDbgWhy too)
 #else
-  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, 10 * 8, call_stream(ctx, P)));
-#endif         // (statistics, status word, k_tail's queue length)
+  HIPCHK(ctx, hipMemsetAsync(P->d_stat.p, 0, gat::kStatCopied * 8, call_stream(ctx, P)));
+#endif
   if (o.units_direct && P->d_cand_count.n) HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, P->d_cand_count.n * 4, call_stream(ctx, P)));
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[0], call_stream(ctx, P)));
   gat::SamplerArgs A = {};                 // (SamplerAnnotator / SamplerSegments: what k_sampler saw)
@@ -1044,176 +1220,16 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
     HIPCHK(ctx, hipGetLastError());
   }
 #ifdef GAT_DBG_QUEUE
-  { unsigned long long w[16]; hipStreamSynchronize(call_stream(ctx, P)); hipMemcpy(w, P->d_stat.p, 16 * 8, hipMemcpyDeviceToHost);
-    fprintf(stderr, "round broken by: empty segment %llu, placeholder neighbour %llu, both neighbours and more %llu, two on the right %llu, two logged %llu, logged + neighbour %llu\n", w[10], w[11], w[12], w[13], w[14], w[15]); }
+  { unsigned long long w[gat::kStatSlotWords]; hipStreamSynchronize(call_stream(ctx, P)); hipMemcpy(w, P->d_stat.p, sizeof(w), hipMemcpyDeviceToHost);
+    const unsigned long long* why = w + gat::kStatDbgWhy;          // (kStatDbgWhyWords = 6 of them)
+    fprintf(stderr, "round broken by: empty segment %llu, placeholder neighbour %llu, both neighbours and more %llu, two on the right %llu, two logged %llu, logged + neighbour %llu\n", why[0], why[1], why[2], why[3], why[4], why[5]); }
 #endif
-  HIPCHK(ctx, hipMemcpyAsync(h_stat, P->d_stat.p, 10 * 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));   // (word 9: the queue's length)
-  if (P->sampler == GAT_SAMPLER_BRUTE_FORCE)                                                       // (the first unit that did not converge)
-    HIPCHK(ctx, hipMemcpyAsync(h_stat + gat::kBruteFirstWord, P->d_stat.p + gat::kBruteFirstWord, 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));
+  HIPCHK(ctx, hipMemcpyAsync(h_stat, P->d_stat.p, gat::kStatCopied * 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));
+  if (P->sampler == GAT_SAMPLER_BRUTE_FORCE)
+    HIPCHK(ctx, hipMemcpyAsync(h_stat + gat::kStatBruteFirst, P->d_stat.p + gat::kStatBruteFirst, 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));
   if (o.defer) return GAT_OK;
   HIPCHK(ctx, hipStreamSynchronize(call_stream(ctx, P)));
   return finish_sampler_batch(ctx, P, kn, nb, st, timed, h_stat);
-}
-
-// the checks and statistics of a sampler batch whose kernels have completed (the stream has been synchronised)
-static int finish_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, int64_t nb, gat_stats* st, bool timed, const unsigned long long* h_stat) {
-  {
-    int rc;
-    const int32_t flags = *reinterpret_cast<const int32_t*>(h_stat + 8);
-    const unsigned long long* stat = h_stat;
-    if (flags & gat::kStatusCoordRange)
-      return set_err(ctx, GAT_ERR_ASSERT, "SamplerLocalPermutation: a sampled coordinate exceeds 2^31 - 1 before it wraps (flags=%d): the reference "
-                                          "raises OverflowError (gat/Engine.pyx:1208, :1212)", flags);
-    if (flags & (gat::kStatusAssert | gat::kStatusTrimAssert))
-      return set_err(ctx, GAT_ERR_ASSERT, "sampler assertion failed on device (flags=%d): %s", flags,
-                     (flags & gat::kStatusAssert) ? "sampled list has no overlap with the workspace (gat/Engine.pyx:645)"
-                                                  : "trimming more than the total length (gat/SegmentList.pyx:560)");
-    if ((flags & gat::kStatusContigLds) && !(flags & gat::kStatusOverflow)) {
-      // a contig's lists were longer than expected: LDS for every unit at its capacity from now on, batch repeated
-      P->contig_tight = false;
-      if (layout_slab(P, kn)) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments");
-      if ((rc = upload_layout(ctx, P, kn))) return rc;
-      if (st) st->n_retried += nb * (int64_t)P->h_order.size();
-      return kRelayout;
-    }
-    if (flags & gat::kStatusOverflow) {
-      // (doubled until the lists fit: a unit whose segments are longer than its whole workspace beside one of a few bases places
-      //  thousands of the small one between the large one's trims -- two of 200 000 edge-case seeds needed more than 64 x 128 slots,
-      //  which the reference's lists simply grow to (round 6); the per-sample slab's 2^31 segments and the device's memory end it)
-      if (P->cap_scale >= (1 << 20)) return set_err(ctx, GAT_ERR_CAPACITY, "sampler slab overflow even at 2^20 x capacity");
-      P->cap_scale *= 2;
-      if (layout_slab(P, kn)) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments after growth");
-      if ((rc = upload_layout(ctx, P, kn))) return rc;
-      if (st) st->n_retried += nb * (int64_t)P->h_order.size();
-      return kRelayout;
-    }
-    if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) {
-      // (behind the overflow check: a batch that is repeated is counted once, as it stands in the end)
-      const int64_t unconv = (int64_t)(stat[6] >> gat::kBruteUnconvShift);
-      if (st) { st->n_restarts += (int64_t)(stat[6] & ((1ull << gat::kBruteUnconvShift) - 1ull)); st->n_unconverged += unconv; }
-      if (unconv) {
-        const unsigned long long first = ~h_stat[gat::kBruteFirstWord];
-        return set_err(ctx, GAT_ERR_VALUE, "SamplerBruteForce: sampling did not converge: sample %lld, unit %d used up its %d passes of %d tries "
-                                           "(%lld work units of the batch; gat/Engine.pyx:868-869)", (long long)(first >> 32), (int)(first & 0xffffffffull),
-                       (int)P->brute_ntries_outer, (int)P->brute_ntries_inner, (long long)unconv);
-      }
-    }
-    {
-      // k_units_overlap: overlaps between the units' lists that were not pairwise, or more candidates than the buffer holds --
-      // the batch is repeated through k_contig, and the problem keeps to that
-      const uint32_t* uw = reinterpret_cast<const uint32_t*>(h_stat + 10);
-      if (P->units_direct && P->units_direct_ok && uw[0] != 0u) {
-        if ((uw[0] & 1u) != 0u || P->cand_scale >= 64) P->units_direct_ok = false;   // not pairwise (or a buffer that will not do)
-        else P->cand_scale *= 4;                                                       // a candidate region was too small
-        if (st) st->n_retried += nb * (int64_t)P->h_order.size();
-        return kRelayout;
-      }
-      if (st && P->units_direct) { st->n_straddle_candidates += (int64_t)uw[2]; st->n_unit_overlaps += (int64_t)uw[1]; }
-    }
-#if defined(GAT_DIAG) || defined(GAT_DIAG_CONS)
-    if (const char* fn = kn.diag_out.empty() ? nullptr : kn.diag_out.c_str()) {
-      // shares of a k_sampler work unit's life per phase, summed over the batch (tools/diag_sampler.sh)
-      const size_t nd = (size_t)nb * std::max(1, P->n_units) * 8;
-      std::vector<unsigned long long> h(nd);
-      HIPCHK(ctx, staged_d2h(ctx, h.data(), P->d_diag.p, nd * 8));
-      double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (size_t i = 0; i < nd; ++i) sum[i & 7] += (double)h[i];
-      if (FILE* f = fopen(fn, "a")) {
-        fprintf(f, "{\"work_units\": %lld, \"cycles\": {\"prologue\": %.0f, \"sort\": %.0f, \"merge\": %.0f, \"coverage\": %.0f, "
-                   "\"fast_paths\": %.0f, \"trim\": %.0f, \"draws_placement\": %.0f, \"final_filter_write\": %.0f}}\n",
-                (long long)nb * (long long)P->h_order.size(), sum[0], sum[1], sum[2], sum[3], sum[4], sum[5], sum[6], sum[7]);
-        if (P->d_diag_place.n >= P->h_order.size() * 8 && !P->h_order.empty()) {
-          // k_place's loop, per phase: over all tiles, and for the largest unit alone (launch position 0: the tile the kernel ends with)
-          std::vector<unsigned long long> hp(P->h_order.size() * 8);
-          if (staged_d2h(ctx, hp.data(), P->d_diag_place.p, hp.size() * 8) == hipSuccess) {
-            double all[7] = {0, 0, 0, 0, 0, 0, 0};
-            for (size_t i = 0; i < hp.size(); ++i) all[i & 7] += (i & 7) < 7 ? (double)hp[i] : 0.0;
-            fprintf(f, "{\"k_place\": {\"all_tiles\": {\"row_wait\": %.0f, \"lookups\": %.0f, \"steps\": %.0f, \"flush\": %.0f, \"loop_control\": %.0f, "
-                       "\"rows\": %.0f, \"tiles\": %.0f}, \"largest_unit\": {\"row_wait\": %llu, \"lookups\": %llu, \"steps\": %llu, \"flush\": %llu, "
-                       "\"loop_control\": %llu, \"rows\": %llu, \"tiles\": %llu}}}\n",
-                    all[0], all[1], all[2], all[3], all[4], all[5], all[6], hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6]);
-          }
-        }
-        {
-          // k_place's hand-over records by kind: pending length (triggered), -1 run in full, -2 complete, -3 resume
-          const size_t n_act = P->h_order.size();
-          std::vector<int4> hs(n_act * (size_t)P->batch);
-          if (n_act && P->d_st.n >= hs.size() && staged_d2h(ctx, hs.data(), P->d_st.p, hs.size() * sizeof(int4)) == hipSuccess) {
-            long long kinds[5] = {0, 0, 0, 0, 0};
-            int shown = 0;
-            fprintf(f, "{\"k_place_handover_examples\": [");
-            for (size_t a = 0; a < n_act; ++a)
-              for (int64_t i = 0; i < nb; ++i) {
-                const int4 r = hs[a * (size_t)P->batch + (size_t)i];
-                kinds[r.z > 0 ? 0 : (r.z == -1 ? 1 : (r.z == -2 ? 2 : (r.z == -3 ? 3 : 4)))]++;
-                if (r.z <= 0 && shown < 12) fprintf(f, "%s[%zu, %lld, %d, %d, %d, %d, %d]", shown++ ? ", " : "", a, (long long)i, r.x, r.y, r.z, r.w, P->h_rng_rows.empty() ? -1 : P->h_rng_rows[a]);
-              }
-            {
-              long long sx = 0, sy = 0, sz = 0, sw = 0;
-              for (size_t a = 0; a < n_act; ++a) for (int64_t i = 0; i < nb; ++i) { const int4 r = hs[a * (size_t)P->batch + (size_t)i]; sx += r.x; sy += r.y; sz += r.z; sw += r.w; }
-              fprintf(f, "], \"k_place_handover_sums\": [%lld, %lld, %lld, %lld", sx, sy, sz, sw);
-            }
-            fprintf(f, "], \"k_place_handover\": {\"triggered\": %lld, \"in_full\": %lld, \"complete\": %lld, \"resume\": %lld, \"other\": %lld}}\n",
-                    kinds[0], kinds[1], kinds[2], kinds[3], kinds[4]);
-          }
-        }
-        {
-          // k_place's tiles in time: per unit (launch position) the first begin, the median begin, the median and the last end of
-          // its tiles, in microseconds from the kernel's first begin
-          const size_t n_act = P->h_order.size(), ntl = (size_t)((nb + 63) / 64);
-          std::vector<unsigned long long> ht(n_act * ntl * 2);
-          if (n_act && ntl && P->d_diag_tiles.n >= ht.size() && staged_d2h(ctx, ht.data(), P->d_diag_tiles.p, ht.size() * 8) == hipSuccess) {
-            unsigned long long t_min = ~0ull;
-            for (size_t i = 0; i < ht.size(); i += 2) if (ht[i] && ht[i] < t_min) t_min = ht[i];
-            fprintf(f, "{\"k_place_tiles\": [");
-            for (size_t a = 0; a < n_act; ++a) {
-              std::vector<double> b0, e0;
-              for (size_t t = 0; t < ntl; ++t) {
-                const unsigned long long x = ht[(a * ntl + t) * 2], y = ht[(a * ntl + t) * 2 + 1];
-                if (x && y) { b0.push_back((double)(x - t_min) / 100.0); e0.push_back((double)(y - t_min) / 100.0); }
-              }
-              if (b0.empty()) continue;
-              std::sort(b0.begin(), b0.end()); std::sort(e0.begin(), e0.end());
-              fprintf(f, "%s{\"a\": %zu, \"segments\": %u, \"tiles\": %zu, \"begin_first\": %.1f, \"begin_median\": %.1f, \"begin_last\": %.1f, "
-                         "\"end_first\": %.1f, \"end_median\": %.1f, \"end_last\": %.1f}", a ? ", " : "", a,
-                      P->h_units[(size_t)P->h_order[a]].hist_total, b0.size(), b0.front(), b0[b0.size() / 2], b0.back(), e0.front(), e0[e0.size() / 2], e0.back());
-            }
-            fprintf(f, "]}\n");
-          }
-        }
-        fclose(f);
-      }
-    }
-#endif
-    if (st) {
-      st->n_placed += (int64_t)stat[0];
-      st->n_draws += (int64_t)stat[1];
-      st->n_unsuccessful += (int64_t)stat[2];
-      st->n_tail_units += (int64_t)stat[3];
-      if (P->split_ran && (P->patched_contigs || P->patched_counts)) st->lists_from_records += 1;
-      st->n_full_units += (int64_t)stat[4];
-      st->n_resumed_units += (int64_t)stat[5];
-      st->n_queued_units += (int64_t)(stat[9] & 0xffffffffull);
-      st->n_empty_windows += (int64_t)stat[7];
-      if (timed) {
-        // (a timing query that fails leaves its figure at 0: it must not turn a call that computed its counts into an error)
-        auto lap = [](hipEvent_t a, hipEvent_t b) { float ms = 0; if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); ms = 0; } return ms; };
-        st->ms_sampler += lap(ctx->ev[0], ctx->ev[1]);
-        st->ms_contig += lap(ctx->ev[1], ctx->ev[2]);
-        if (ctx->k_recorded && !P->h_order.empty()) {
-          st->ms_rng += lap(ctx->ev[0], ctx->ev_k[0]);
-          st->ms_place += lap(ctx->ev_k[0], ctx->ev_k[1]);
-          st->ms_merge += lap(ctx->ev_k[1], ctx->ev_k[2]);
-          st->ms_tail += lap(ctx->ev_k[2], ctx->ev_k[3]);
-          if (ctx->t_recorded) {
-            st->ms_ktail += lap(ctx->ev_k[2], ctx->ev_t[0]);
-            st->ms_finalize += lap(ctx->ev_t[0], ctx->ev_t[1]);
-          }
-        }
-      }
-    }
-    return GAT_OK;
-  }
 }
 
 static void fill_count_args(gat_problem* P, gat::CountArgs& A, int64_t nb) {
@@ -1235,15 +1251,12 @@ static void fill_count_args(gat_problem* P, gat::CountArgs& A, int64_t nb) {
     A.seg_units_merged = P->d_slab.p;
     A.cand = P->d_cand.p; A.cand_cap = (uint32_t)(P->d_cand.n / gat::kCandSlots);
     A.cand_count = P->d_cand_count.p;
-    A.st2 = P->d_st2.p;
-    A.patch = reinterpret_cast<const int32_t*>(P->d_patch.p);
-    A.patch_stride = (int32_t)(sizeof(gat::TailPatch) / 4);
-    A.n_units = P->n_units;
-    A.rec_stride = (int32_t)P->batch;
   }
   if (P->split_ran && P->patched_counts) {     // no k_finalize ran: k_count_seg<.., PATCH> reads merged lists + records
     A.seg_merged = P->d_slab.p;
     A.unit_pos = P->d_unit_pos.p;
+  }
+  if (P->split_ran && (P->units_direct || P->patched_counts)) {     // (either way: k_merge_big's and k_tail's records)
     A.st2 = P->d_st2.p;
     A.patch = reinterpret_cast<const int32_t*>(P->d_patch.p);
     A.patch_stride = (int32_t)(sizeof(gat::TailPatch) / 4);
@@ -1276,141 +1289,153 @@ static int call_swap_capx(const gat_ctx* ctx, const gat_problem* P) {
   return ((int64_t)3 * capx * 4 + (8192 + 1) * 4 <= (int64_t)ctx->max_lds - 1024) ? capx : 0;
 }
 
+// (the stages call_enqueue_more schedules)  The count kernels of the newest batch (the tables are there, or are waited for), behind them k_units_overlap's words into the
+// batch's slot and -- behind the call's last batch -- the call's end
+static int enqueue_count_stage(gat_ctx* ctx, gat_problem* P, const Counters& C) {
+  CallState& K = P->call;
+  int rc = annotations_wait(ctx, P->anno);
+  if (rc) return rc;
+  decide_swap(P);
+  const int slot = K.n_flight - 1;
+  const int64_t nb = K.nb[slot];
+  const int swap_capx = call_swap_capx(ctx, P);
+  K.mstat_on = P->anno->dev.has_merged;
+  if (K.lane >= 0 && !K.fork_waited) {
+    // the fork: the count kernels are the call's first access to memory of the caller's (the count matrix) -- what the
+    // caller ordered in front of the call on its stream is in front of them.  The sampler kernels before this point
+    // touch the problem's own scratch and the read-only tables alone and started without waiting
+    HIPCHK(ctx, hipStreamWaitEvent(call_stream(ctx, P), K.blk->ev_fork, 0));
+    K.fork_waited = true;
+  }
+  if (K.mstat_on && K.enq == nb) {
+    // (k_count_merged's own traffic counters: only a problem with a merged index can take that kernel; zeroed in front of
+    //  the call's first count kernel)
+    if (P->d_mstat.n < 512) HIPCHK(ctx, P->d_mstat.alloc(512));
+    HIPCHK(ctx, hipMemsetAsync(P->d_mstat.p, 0, 512 * 8, call_stream(ctx, P)));
+  }
+  gat::CountArgs A;
+  memset(&A, 0, sizeof(A));
+  fill_count_args(P, A, nb);
+  A.out = (int64_t*)K.counts_dev; A.out_stride = K.S; A.out_begin = K.enq - nb;
+  A.mstat = K.mstat_on ? P->d_mstat.p : nullptr;
+  if (K.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_cnt[0], call_stream(ctx, P)));
+  CountLaunch L;
+  L.stream = call_stream(ctx, P); L.ev_main = K.blk->ev_main[slot];
+  L.units = P->d_units.p; L.ws = P->d_ws.p; L.ws_tree = P->d_ws_tree.p;
+  for (int c = 0; c < P->n_contigs; ++c) L.max_units = std::max(L.max_units, P->h_contig_unit_off[(size_t)c + 1] - P->h_contig_unit_off[(size_t)c]);
+  if ((rc = launch_count(ctx, K.knobs, P->anno->dev, C, A, P->d_part, swap_capx,
+                         P->merge_contigs ? P->max_contig_cap : P->max_unit_cap, L))) return rc;
+  unsigned long long* uo = K.blk->stat_slot(slot) + gat::kStatUnitsOverlap;
+  if (A.cu_rec != nullptr)       // (k_units_overlap ran)
+    HIPCHK(ctx, hipMemcpyAsync(uo, P->d_cand_count.p + gat::kCandSlots, gat::kStatUnitsOverlapWords * 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));
+  else std::fill(uo, uo + gat::kStatUnitsOverlapWords, 0ull);
+  if (K.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_cnt[1], call_stream(ctx, P)));
+  K.main_rec[slot] = L.main_recorded; K.count_kernel[slot] = L.count_kernel;
+  K.count_pending = false;
+  if (K.enq == K.S) {
+    // (the call's end rides on the last batch's synchronisation -- one round trip to the device less per call; a batch
+    //  that has to be repeated enqueues it again)
+    if (K.mstat_on) HIPCHK(ctx, hipMemcpyAsync(K.blk->h_mstat, P->d_mstat.p, 512 * 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));
+    HIPCHK(ctx, hipEventRecord(K.blk->ev_end, call_stream(ctx, P)));
+    K.end_recorded = true;
+  }
+  return GAT_OK;
+}
+
+// Which count kernel will follow the next batch: it decides the sampler's last steps (final lists or not).  ONE rule, count_route,
+// over what is known of the merged index: from the tables once they are built; while they are being built from what was announced
+// of them -- will_merge alone where that says the merged index (many tracks, nucleotide counters: whatever the swap decision
+// would be), with the announced sizes for the swap decision otherwise -- and with nothing announced the tables are waited for
+static int next_batch_route(gat_ctx* ctx, gat_problem* P, const Counters& C, int* route) {
+  gat_annotations* an = P->anno;
+  const Knobs& kn = P->call.knobs;
+  bool tables = annotations_ready(an);                       // decide from the tables themselves (built, or waited for)
+  if (!tables) {
+    if (count_route(ctx, kn, an->will_merge, C, P->n_contigs, P->n_tracks, 0) == GAT_COUNT_KERNEL_MERGED) { *route = GAT_COUNT_KERNEL_MERGED; return GAT_OK; }
+    tables = !(an->shape_known && an->total_known >= 0);
+  }
+  if (tables) { const int rc = annotations_wait(ctx, an); if (rc) return rc; }
+  decide_swap(P);                                            // (announced: from the sizes known before the build)
+  *route = count_route(ctx, kn, tables ? an->dev.has_merged : an->will_merge, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P),
+                       tables && !an->dev.per_track);
+  return GAT_OK;
+}
+
+// units_direct: the buffer of the candidates k_contig notes for k_units_overlap -- segments with a workspace boundary in their cells,
+// of units that have a segment reaching out of their workspace: a fraction of a per cent of a batch's segments on isochore blocks
+// much longer than the segments --, dealt to kCandSlots regions by (sample, contig).  Sized for THIS batch (a call's first batch is
+// its largest; a later, larger call makes it anew while nothing of the problem is in flight); a region that overflows anyway has
+// the batch repeated with four times the buffer (cand_scale), and beyond 64 times through the sorted contig lists
+static int size_candidate_buffer(gat_ctx* ctx, gat_problem* P, int64_t nb) {
+  double est = 0.006 * (double)nb * (double)std::max<int64_t>(1, P->n_seg_total) / gat::kCandSlots + 512.0;
+  if (P->call.knobs.test_small_caps) est = 1.0;        // (tests: regions that overflow, the batch repeated with larger ones)
+  const size_t want = (size_t)std::min(est * P->cand_scale, 1024.0 * 1024) * gat::kCandSlots;
+  if (P->d_cand.n < want && P->call.n_flight == 0) {
+    if (P->d_cand.n > 0) HIPCHK(ctx, hipStreamSynchronize(call_stream(ctx, P)));   // (an earlier call's kernels may still read the old buffer)
+    HIPCHK(ctx, P->d_cand.alloc(want));
+  }
+  if (P->d_cand_count.n == 0) {
+    HIPCHK(ctx, P->d_cand_count.alloc(gat::kCandSlots + 4));
+    HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, (gat::kCandSlots + 4) * 4, call_stream(ctx, P)));
+  }
+  return GAT_OK;
+}
+
+// The sampler kernels of the next batch, their last steps by the count kernel that will follow (route), into the next free slot
+static int enqueue_sampler_stage(gat_ctx* ctx, gat_problem* P, const Counters& C, int route) {
+  CallState& K = P->call;
+  const Knobs& kn = K.knobs;
+  int rc;
+  // the scratch is sized while nothing of this problem is in flight; batches behind the first fit by construction
+  if (K.n_flight == 0 && (rc = ensure_scratch(ctx, P, kn, K.S - K.enq))) return rc;
+  const int64_t nb = std::min<int64_t>(P->batch, K.S - K.enq);
+  const int slot = K.n_flight;
+  // (the run's one stream: the state at the batch's start is kept, a repeated batch draws from there)
+  uint32_t* d_state = K.state_host != nullptr ? P->d_serial.p : nullptr;
+  if (d_state != nullptr)
+    HIPCHK(ctx, hipMemcpyAsync(d_state + GAT_MT_STATE_WORDS, d_state, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, call_stream(ctx, P)));
+  BatchOpts o;
+  o.defer = true;                      // (enqueued only)
+  // counts alone, all of them k_count_seg's: it reads the units as k_tail left them (no final lists are written)
+  o.records_ok = !C.any_anno && !kn.count_final_lists && (route == GAT_COUNT_KERNEL_SEG || route == GAT_COUNT_KERNEL_MERGED);
+  // (k_count_merged skips empty segments: long lists may keep what a trim emptied, no compaction pass in k_resume_big)
+  o.loose_ok = o.records_ok && route == GAT_COUNT_KERNEL_MERGED;
+  // isochore problems: the merged index takes the units' lists as they are, no k_contig (round 6)
+  o.units_direct = o.loose_ok && P->merge_contigs && P->units_direct_ok && !kn.count_via_contigs;
+  if (o.units_direct && (rc = size_candidate_buffer(ctx, P, nb))) return rc;
+  o.serial_state = d_state;
+  o.h_stat = K.blk->stat_slot(slot);
+  if ((rc = run_sampler_batch(ctx, P, kn, K.seed, K.begin + K.enq, nb, &K.local, K.timed, o))) return rc;
+  K.nb[slot] = nb;
+  K.main_rec[slot] = false; K.count_kernel[slot] = GAT_COUNT_KERNEL_NONE;
+  K.n_flight = slot + 1;
+  K.enq += nb;
+  K.count_pending = true;
+  return GAT_OK;
+}
+
+// The scheduler: count kernels of the newest batch, sampler kernels of the next, until the call is enqueued or its flight is full.
 // block: wait for annotation tables that are still being built (gat_wait); else return with the newest batch's count
 // kernels still to come (gat_sample_and_count_enqueue: the host goes on, the device samples)
 static int call_enqueue_more(gat_ctx* ctx, gat_problem* P, bool block) {
   CallState& K = P->call;
-  const Knobs& kn = K.knobs;
   Counters C;
   int rc = parse_counters(ctx, K.ids, K.n_counters, C);
   if (rc) return rc;
-  const bool serial = K.state_host != nullptr;
-  uint32_t* d_state = serial ? P->d_serial.p : nullptr;
   // (the events behind every kernel and the serial stream's saved state exist once: such calls keep one batch in flight)
-  const int max_flight = (K.timed || serial) ? 1 : kMaxInflight;
+  const int max_flight = (K.timed || K.state_host != nullptr) ? 1 : kMaxInflight;
   PrepTimer tm;
   // (a layout made again was uploaded on the context's stream: it has arrived before a lane's kernels read it)
   if (K.lane >= 0) HIPCHK(ctx, stage_flush(ctx));
   for (;;) {
     if (K.count_pending) {
-      // ---- the count kernels of the newest batch
       if (!annotations_ready(P->anno) && !block) break;
-      if ((rc = annotations_wait(ctx, P->anno))) return rc;
-      decide_swap(P);
-      const int slot = K.n_flight - 1;
-      const int64_t nb = K.nb[slot];
-      const int swap_capx = call_swap_capx(ctx, P);
-      K.mstat_on = P->anno->dev.has_merged;
-      if (K.lane >= 0 && !K.fork_waited) {
-        // the fork: the count kernels are the call's first access to memory of the caller's (the count matrix) -- what the
-        // caller ordered in front of the call on its stream is in front of them.  The sampler kernels before this point
-        // touch the problem's own scratch and the read-only tables alone and started without waiting
-        HIPCHK(ctx, hipStreamWaitEvent(call_stream(ctx, P), K.blk->ev_fork, 0));
-        K.fork_waited = true;
-      }
-      if (K.mstat_on && K.enq == nb) {
-        // (k_count_merged's own traffic counters: only a problem with a merged index can take that kernel; zeroed in front of
-        //  the call's first count kernel)
-        if (P->d_mstat.n < 512) HIPCHK(ctx, P->d_mstat.alloc(512));
-        HIPCHK(ctx, hipMemsetAsync(P->d_mstat.p, 0, 512 * 8, call_stream(ctx, P)));
-      }
-      gat::CountArgs A;
-      memset(&A, 0, sizeof(A));
-      fill_count_args(P, A, nb);
-      A.out = (int64_t*)K.counts_dev;
-      A.out_stride = K.S;
-      A.out_begin = K.enq - nb;
-      A.mstat = K.mstat_on ? P->d_mstat.p : nullptr;
-      if (K.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_cnt[0], call_stream(ctx, P)));
-      CountLaunch L;
-      L.stream = call_stream(ctx, P);
-      L.ev_main = K.blk->ev_main[slot];
-      L.units = P->d_units.p; L.ws = P->d_ws.p; L.ws_tree = P->d_ws_tree.p;
-      for (int c = 0; c < P->n_contigs; ++c) L.max_units = std::max(L.max_units, P->h_contig_unit_off[(size_t)c + 1] - P->h_contig_unit_off[(size_t)c]);
-      if ((rc = launch_count(ctx, kn, P->anno->dev, C, A, P->d_part, swap_capx,
-                             P->merge_contigs ? P->max_contig_cap : P->max_unit_cap, L))) return rc;
-      if (A.cu_rec != nullptr)       // k_units_overlap's words (candidates, "not pairwise", overlaps taken off) into the batch's slot
-        HIPCHK(ctx, hipMemcpyAsync(K.blk->h_stat + (size_t)slot * 16 + 10, P->d_cand_count.p + gat::kCandSlots, 16, hipMemcpyDeviceToHost, call_stream(ctx, P)));
-      else { K.blk->h_stat[(size_t)slot * 16 + 10] = 0; K.blk->h_stat[(size_t)slot * 16 + 11] = 0; }
-      if (K.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_cnt[1], call_stream(ctx, P)));
-      K.main_rec[slot] = L.main_recorded;
-      K.count_kernel[slot] = L.count_kernel;
-      K.count_pending = false;
-      if (K.enq == K.S) {
-        // (the call's end rides on the last batch's synchronisation -- one round trip to the device less per call; a batch
-        //  that has to be repeated enqueues it again)
-        if (K.mstat_on) HIPCHK(ctx, hipMemcpyAsync(K.blk->h_mstat, P->d_mstat.p, 512 * 8, hipMemcpyDeviceToHost, call_stream(ctx, P)));
-        HIPCHK(ctx, hipEventRecord(K.blk->ev_end, call_stream(ctx, P)));
-        K.end_recorded = true;
-      }
+      if ((rc = enqueue_count_stage(ctx, P, C))) return rc;
     }
     if (!(K.enq < K.S && K.n_flight < max_flight)) break;
-    // ---- the sampler kernels of the next batch
-    // which count kernel will follow decides the sampler's last steps (final lists or not); with the tables still being built
-    // it is known only where the shape alone says so -- many tracks, nucleotide counters: the merged index -- else wait
     int route;
-    if (annotations_ready(P->anno)) {
-      if ((rc = annotations_wait(ctx, P->anno))) return rc;
-      decide_swap(P);
-      route = count_route(ctx, kn, P->anno->dev.has_merged, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P), !P->anno->dev.per_track);
-    } else {
-      const bool only_overlap = C.slot[GAT_COUNTER_SEGMENT_OVERLAP] < 0 && C.slot[GAT_COUNTER_SEGMENT_MIDOVERLAP] < 0;
-      const size_t lds_merged = (size_t)P->n_tracks * 4 * (gat::kMergedThreads / gat::kWave);
-      if (C.any_seg && P->n_contigs > 0 && only_overlap && P->anno->will_merge && (int64_t)lds_merged + 1024 <= ctx->max_lds &&
-          !kn.count_no_merged) {
-        route = GAT_COUNT_KERNEL_MERGED;                       // (whatever the swap decision would be)
-      } else if (P->anno->shape_known && P->anno->total_known >= 0) {
-        decide_swap(P);                                        // (from the sizes announced before the build)
-        route = count_route(ctx, kn, P->anno->will_merge, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P));
-      } else {
-        if ((rc = annotations_wait(ctx, P->anno))) return rc;
-        decide_swap(P);
-        route = count_route(ctx, kn, P->anno->dev.has_merged, C, P->n_contigs, P->n_tracks, call_swap_capx(ctx, P), !P->anno->dev.per_track);
-      }
-    }
-    // the scratch is sized while nothing of this problem is in flight; batches behind the first fit by construction
-    if (K.n_flight == 0 && (rc = ensure_scratch(ctx, P, kn, K.S - K.enq))) return rc;
-    const int64_t nb = std::min<int64_t>(P->batch, K.S - K.enq);
-    const int slot = K.n_flight;
-    if (d_state != nullptr)
-      HIPCHK(ctx, hipMemcpyAsync(d_state + GAT_MT_STATE_WORDS, d_state, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, call_stream(ctx, P)));
-    // counts alone, all of them k_count_seg's: it reads the units as k_tail left them (no final lists are written)
-    const bool records_ok = !C.any_anno && !kn.count_final_lists &&
-                            (route == GAT_COUNT_KERNEL_SEG || route == GAT_COUNT_KERNEL_MERGED);
-    // (k_count_merged skips empty segments: long lists may keep what a trim emptied, no compaction pass in k_resume_big)
-    const bool loose_ok = records_ok && route == GAT_COUNT_KERNEL_MERGED;
-    // isochore problems: the merged index takes the units' lists as they are, no k_contig (round 6)
-    const bool units_direct = loose_ok && P->merge_contigs && P->units_direct_ok && !kn.count_via_contigs;
-    if (units_direct) {
-      // candidates: segments with a workspace boundary in their cells, of units that have a segment reaching out of their workspace
-      // -- a fraction of a per cent of a batch's segments on isochore blocks much longer than the segments --, dealt to kCandSlots
-      // regions by (sample, contig).  Sized for THIS batch (a call's first batch is its largest; a later, larger call makes it
-      // anew while nothing of the problem is in flight); a region that overflows anyway has the batch repeated with four
-      // times the buffer (cand_scale), and beyond 64 times through the sorted contig lists
-      double est = 0.006 * (double)nb * (double)std::max<int64_t>(1, P->n_seg_total) / gat::kCandSlots + 512.0;
-      if (kn.test_small_caps) est = 1.0;        // (tests: regions that overflow, the batch repeated with larger ones)
-      const size_t want = (size_t)std::min(est * P->cand_scale, 1024.0 * 1024) * gat::kCandSlots;
-      if (P->d_cand.n < want && K.n_flight == 0) {
-        if (P->d_cand.n > 0) HIPCHK(ctx, hipStreamSynchronize(call_stream(ctx, P)));   // (an earlier call's kernels may still read the old buffer)
-        HIPCHK(ctx, P->d_cand.alloc(want));
-      }
-      if (P->d_cand_count.n == 0) {
-        HIPCHK(ctx, P->d_cand_count.alloc(gat::kCandSlots + 4));
-        HIPCHK(ctx, hipMemsetAsync(P->d_cand_count.p, 0, (gat::kCandSlots + 4) * 4, call_stream(ctx, P)));
-      }
-    }
-    BatchOpts o;
-    o.defer = true;                      // (enqueued only)
-    o.records_ok = records_ok; o.loose_ok = loose_ok; o.units_direct = units_direct;
-    o.serial_state = d_state;
-    o.h_stat = K.blk->h_stat + (size_t)slot * 16;
-    if ((rc = run_sampler_batch(ctx, P, kn, K.seed, K.begin + K.enq, nb, &K.local, K.timed, o))) return rc;
-    K.nb[slot] = nb;
-    K.main_rec[slot] = false;
-    K.count_kernel[slot] = GAT_COUNT_KERNEL_NONE;
-    K.n_flight = slot + 1;
-    K.enq += nb;
-    K.count_pending = true;
+    if ((rc = next_batch_route(ctx, P, C, &route))) return rc;
+    if ((rc = enqueue_sampler_stage(ctx, P, C, route))) return rc;
   }
   tm.lap("batches enqueued");
   return GAT_OK;
@@ -1528,7 +1553,7 @@ static int call_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) {
     K.end_recorded = false;
     tm.lap("batches synchronised");
     for (int slot = 0; slot < K.n_flight; ++slot) {
-      rc = finish_sampler_batch(ctx, P, K.knobs, K.nb[slot], &K.local, K.timed, K.blk->h_stat + (size_t)slot * 16);
+      rc = finish_sampler_batch(ctx, P, K.knobs, K.nb[slot], &K.local, K.timed, K.blk->stat_slot(slot));
       if (rc == kRelayout) {
         if (K.state_host != nullptr)        // (the repeated batch draws from where this one began)
           if (hipMemcpyAsync(P->d_serial.p, P->d_serial.p + GAT_MT_STATE_WORDS, GAT_MT_STATE_WORDS * 4, hipMemcpyDeviceToDevice, call_stream(ctx, P)) != hipSuccess)
@@ -1537,9 +1562,7 @@ static int call_wait(gat_ctx* ctx, gat_problem* P, gat_stats* stats) {
       }
       if (rc) return fail(rc);
       float ms = 0;
-      if (K.timed) {
-        if (hipEventElapsedTime(&ms, ctx->ev_cnt[0], ctx->ev_cnt[1]) == hipSuccess) K.local.ms_count += ms;
-      }
+      if (K.timed && hipEventElapsedTime(&ms, ctx->ev_cnt[0], ctx->ev_cnt[1]) == hipSuccess) K.local.ms_count += ms;
       if (K.main_rec[slot] && hipEventElapsedTime(&ms, K.blk->ev_main[slot][0], K.blk->ev_main[slot][1]) == hipSuccess)
         K.local.ms_count_main += ms;
       K.local.count_kernel = K.count_kernel[slot];
@@ -1581,14 +1604,11 @@ extern "C" int gat_sample_and_count(gat_ctx* ctx, gat_problem* P, const int32_t*
 extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, int n_counters,
                                            uint32_t* mt_state, int64_t n_samples, void* counts_dev, gat_stats* stats) {
   if (!mt_state) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: NULL state");
-  if (P->sampler == GAT_SAMPLER_SHIFT)
-    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerShift runs on the per-unit streams only");
-  if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION)
-    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerGlobalPermutation runs on the per-unit streams only");
-  if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION)
-    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerLocalPermutation runs on the per-unit streams only");
-  if (P->sampler == GAT_SAMPLER_BRUTE_FORCE)
-    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: SamplerBruteForce runs on the per-unit streams only");
+  const char* const per_unit_only = P->sampler == GAT_SAMPLER_SHIFT ? "SamplerShift"      // (the list samplers: no k_serial)
+                                  : P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION ? "SamplerGlobalPermutation"
+                                  : P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION ? "SamplerLocalPermutation"
+                                  : P->sampler == GAT_SAMPLER_BRUTE_FORCE ? "SamplerBruteForce" : nullptr;
+  if (per_unit_only) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: %s runs on the per-unit streams only", per_unit_only);
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
   const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state, false);
   return rc ? rc : call_wait(ctx, P, stats);
@@ -1603,19 +1623,6 @@ extern "C" void gat_mt19937_seed(uint32_t seed, uint32_t* mt_state) {
 
 // gat_sample / gat_sample_units: the lists of every (sample, contig) after fromIsochores, or of every (sample, unit)
 // as the sampler returned them
-static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
-                        gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats, bool unit_level);
-
-extern "C" int gat_sample(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
-                          gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats) {
-  return sample_lists(ctx, P, seed, sample_begin, sample_end, out_host, cap, off_host, stats, false);
-}
-
-extern "C" int gat_sample_units(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
-                                gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats) {
-  return sample_lists(ctx, P, seed, sample_begin, sample_end, out_host, cap, off_host, stats, true);
-}
-
 static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
                         gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats, bool unit_level) {
   if (!ctx || !P || !off_host) return set_err(ctx, GAT_ERR_ARG, "gat_sample: NULL argument");
@@ -1669,34 +1676,23 @@ static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sam
   return GAT_OK;
 }
 
-static int count_lists_on(gat_ctx* ctx, const Knobs& kn, const int32_t* counter_ids, int n_counters,
-                          const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
-                          const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
-                          const int64_t* ws_nseg, int32_t n_groups, void* counts_host);
-
-// Observed counts are independent of whatever samples are in flight on the caller's context: they run on a stream (and
-// through a staging buffer) of their own -- every staged upload waits for its stream, and on the caller's stream that would
-// be the end of the sampling (run() computes them while the device samples, gat/__init__.py:933-940)
-static int count_lists_impl(gat_ctx* ctx, const int32_t* counter_ids, int n_counters,
-                            const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
-                            const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
-                            const int64_t* ws_nseg, int32_t n_groups, void* counts_host) {
-  if (!ctx || !list_off || !anno_begin || !anno_end || !counts_host || (n_groups > 0 && !ws_nseg))
-    return set_err(ctx, GAT_ERR_ARG, "gat_count_lists: NULL argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->aux_ctx == nullptr) {
-    int rc = gat_ctx_create(&ctx->aux_ctx, ctx->device, nullptr);
-    if (rc) return rc;
-  }
-  gat_ctx* x = ctx->aux_ctx;
-  const Knobs kn = read_knobs(ctx);                 // (the caller's: the auxiliary context has no options of its own)
-  const int rc = count_lists_on(x, kn, counter_ids, n_counters, lists, list_off, n_lists, annos, anno_begin, anno_end, n_tracks, ws_nseg,
-                                n_groups, counts_host);
-  x->stage_used = 0;                                // (count_lists_on has drained the stream before its buffers went back to the pool)
-  if (rc) return set_err(ctx, rc, "%s", x->err.c_str());
-  return GAT_OK;
+extern "C" int gat_sample(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                          gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats) {
+  return sample_lists(ctx, P, seed, sample_begin, sample_end, out_host, cap, off_host, stats, false);
+}
+extern "C" int gat_sample_units(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats) {
+  return sample_lists(ctx, P, seed, sample_begin, sample_end, out_host, cap, off_host, stats, true);
 }
 
+// what gat_count_lists / gat_count_list_ranges were given, as it goes down to the launches
+struct CountListsIn {
+  const int32_t* counter_ids; int n_counters;
+  const gat_segment* lists; const int64_t* list_off; int64_t n_lists;
+  const gat_segment* annos; const int64_t *anno_begin, *anno_end; int32_t n_tracks;
+  const int64_t* ws_nseg; int32_t n_groups;
+  void* counts_host;
+};
 // The device buffers of a gat_count_lists call.  They go back to the process-wide pool when they are destroyed, and the pool
 // hands an idle block to any context or stream: on EVERY path out of the call -- an error in the middle of its launches
 // too -- the stream is drained before that (count_lists_on owns them and synchronises behind count_lists_body: ADVICE r4)
@@ -1707,77 +1703,83 @@ struct CountListBufs {
   DevBuf<int64_t> d_nseg, d_out;
   DevBuf<uint32_t> d_part;
 };
-static int count_lists_body(gat_ctx* ctx, const Knobs& kn, const int32_t* counter_ids, int n_counters,
-                            const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
-                            const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
-                            const int64_t* ws_nseg, int32_t n_groups, void* counts_host, CountListBufs& B);
-static int count_lists_on(gat_ctx* ctx, const Knobs& kn, const int32_t* counter_ids, int n_counters,
-                          const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
-                          const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
-                          const int64_t* ws_nseg, int32_t n_groups, void* counts_host) {
-  CountListBufs B;
-  const int rc = count_lists_body(ctx, kn, counter_ids, n_counters, lists, list_off, n_lists, annos, anno_begin, anno_end, n_tracks,
-                                  ws_nseg, n_groups, counts_host, B);
-  (void)hipStreamSynchronize(ctx->stream);
-  return rc;
-}
-static int count_lists_body(gat_ctx* ctx, const Knobs& kn, const int32_t* counter_ids, int n_counters,
-                            const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
-                            const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
-                            const int64_t* ws_nseg, int32_t n_groups, void* counts_host, CountListBufs& B) {
+static int count_lists_body(gat_ctx* ctx, const Knobs& kn, const CountListsIn& in, CountListBufs& B) {
+  const int64_t n_lists = in.n_lists;
+  const int32_t n_groups = in.n_groups, n_tracks = in.n_tracks;
   Counters C;
-  int rc = parse_counters(ctx, counter_ids, n_counters, C);
+  int rc = parse_counters(ctx, in.counter_ids, in.n_counters, C);
   if (rc) return rc;
-  AnnoDev& A = B.A;
   // (the merged index pays when many lists are counted against it; for a handful -- the observed counts of a run's
   //  segment tracks -- building it costs more than the per-track kernel's extra look-ups)
   const bool want_merged = n_lists >= 16 || kn.count_lists_merged;
-  if ((rc = build_annos(ctx, kn, A, annos, anno_begin, anno_end, (int64_t)n_tracks * n_groups, n_groups, want_merged, false))) return rc;
+  if ((rc = build_annos(ctx, kn, B.A, in.annos, in.anno_begin, in.anno_end, (int64_t)n_tracks * n_groups, n_groups, want_merged, false))) return rc;
   for (int64_t l = 0; l < n_lists * n_groups; ++l)
-    if ((rc = check_list(ctx, lists + list_off[l], list_off[l + 1] - list_off[l], "segment", l))) return rc;
-  const int64_t total = list_off[n_lists * n_groups];
+    if ((rc = check_list(ctx, in.lists + in.list_off[l], in.list_off[l + 1] - in.list_off[l], "segment", l))) return rc;
+  const int64_t total = in.list_off[n_lists * n_groups];
   std::vector<uint2> h_seg((size_t)total);
-  for (int64_t i = 0; i < total; ++i) h_seg[(size_t)i] = make_uint2(lists[i].start, lists[i].end);
-  DevBuf<uint2>& d_seg = B.d_seg;
-  DevBuf<int32_t>&d_c_off = B.d_c_off, &d_n = B.d_n, &d_index = B.d_index;
-  DevBuf<int64_t>&d_nseg = B.d_nseg, &d_out = B.d_out;
-  DevBuf<uint32_t>& d_part = B.d_part;
-  HIPCHK(ctx, d_seg.upload(h_seg, ctx));
-  std::vector<int64_t> h_nseg(ws_nseg, ws_nseg + n_groups);
-  HIPCHK(ctx, d_nseg.upload(h_nseg, ctx));
-  const size_t nslots = (size_t)n_counters * n_tracks * n_lists;
-  HIPCHK(ctx, d_out.alloc(nslots));
-  HIPCHK(ctx, hipMemsetAsync(d_out.p, 0, std::max<size_t>(1, nslots) * 8, ctx->stream));
+  for (int64_t i = 0; i < total; ++i) h_seg[(size_t)i] = make_uint2(in.lists[i].start, in.lists[i].end);
+  HIPCHK(ctx, B.d_seg.upload(h_seg, ctx));
+  std::vector<int64_t> h_nseg(in.ws_nseg, in.ws_nseg + n_groups);
+  HIPCHK(ctx, B.d_nseg.upload(h_nseg, ctx));
+  const size_t nslots = (size_t)in.n_counters * n_tracks * n_lists;
+  HIPCHK(ctx, B.d_out.alloc(nslots));
+  HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, std::max<size_t>(1, nslots) * 8, ctx->stream));
   std::vector<int32_t> h_index((size_t)n_groups);
   for (int g = 0; g < n_groups; ++g) h_index[(size_t)g] = g;
-  HIPCHK(ctx, d_index.upload(h_index, ctx));
+  HIPCHK(ctx, B.d_index.upload(h_index, ctx));
   // the group offsets and lengths of every list, uploaded once; one launch per list (they differ from list to list)
   std::vector<int32_t> h_c_off((size_t)std::max<int64_t>(1, n_lists * n_groups)), h_n((size_t)std::max<int64_t>(1, n_lists * n_groups));
   for (int64_t l = 0; l < n_lists; ++l) {
-    const int64_t base = list_off[l * n_groups];
+    const int64_t base = in.list_off[l * n_groups];
     for (int g = 0; g < n_groups; ++g) {
-      h_c_off[(size_t)(l * n_groups + g)] = (int32_t)(list_off[l * n_groups + g] - base);
-      h_n[(size_t)(l * n_groups + g)] = (int32_t)(list_off[l * n_groups + g + 1] - list_off[l * n_groups + g]);
+      h_c_off[(size_t)(l * n_groups + g)] = (int32_t)(in.list_off[l * n_groups + g] - base);
+      h_n[(size_t)(l * n_groups + g)] = (int32_t)(in.list_off[l * n_groups + g + 1] - in.list_off[l * n_groups + g]);
     }
   }
-  HIPCHK(ctx, d_c_off.upload(h_c_off, ctx));
-  HIPCHK(ctx, d_n.upload(h_n, ctx));
+  HIPCHK(ctx, B.d_c_off.upload(h_c_off, ctx));
+  HIPCHK(ctx, B.d_n.upload(h_n, ctx));
   for (int64_t l = 0; l < n_lists; ++l) {
-    const int64_t base = list_off[l * n_groups];
+    const int64_t base = in.list_off[l * n_groups];
     gat::CountArgs K;
     memset(&K, 0, sizeof(K));
-    K.seg = d_seg.p + base; K.seg_stride = 0; K.c_off = d_c_off.p + l * n_groups;
-    K.n_arr = d_n.p + l * n_groups; K.n_stride = 0; K.n_index = d_index.p;
-    K.cws_nseg = d_nseg.p; K.n_contigs = n_groups; K.n_tracks = n_tracks; K.n_samples = 1;
-    K.out = d_out.p; K.out_stride = n_lists; K.out_begin = l;
+    K.seg = B.d_seg.p + base; K.seg_stride = 0; K.c_off = B.d_c_off.p + l * n_groups;
+    K.n_arr = B.d_n.p + l * n_groups; K.n_stride = 0; K.n_index = B.d_index.p;
+    K.cws_nseg = B.d_nseg.p; K.n_contigs = n_groups; K.n_tracks = n_tracks; K.n_samples = 1;
+    K.out = B.d_out.p; K.out_stride = n_lists; K.out_begin = l;
     int32_t longest = 0;
     for (int g = 0; g < n_groups; ++g) longest = std::max(longest, h_n[(size_t)(l * n_groups + g)]);
     CountLaunch L;
     L.stream = ctx->stream;
     L.ev_main = ctx->ev_main;
-    if ((rc = launch_count(ctx, kn, A, C, K, d_part, 0, longest, L))) return rc;
+    if ((rc = launch_count(ctx, kn, B.A, C, K, B.d_part, 0, longest, L))) return rc;
   }
-  HIPCHK(ctx, staged_d2h(ctx, counts_host, d_out.p, nslots * 8));
+  HIPCHK(ctx, staged_d2h(ctx, in.counts_host, B.d_out.p, nslots * 8));
+  return GAT_OK;
+}
+
+static int count_lists_on(gat_ctx* ctx, const Knobs& kn, const CountListsIn& in) {
+  CountListBufs B;
+  const int rc = count_lists_body(ctx, kn, in, B);
+  (void)hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
+// Observed counts are independent of whatever samples are in flight on the caller's context: they run on a stream (and
+// through a staging buffer) of their own -- every staged upload waits for its stream, and on the caller's stream that would
+// be the end of the sampling (run() computes them while the device samples, gat/__init__.py:933-940)
+static int count_lists_impl(gat_ctx* ctx, const CountListsIn& in) {
+  if (!ctx || !in.list_off || !in.anno_begin || !in.anno_end || !in.counts_host || (in.n_groups > 0 && !in.ws_nseg))
+    return set_err(ctx, GAT_ERR_ARG, "gat_count_lists: NULL argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->aux_ctx == nullptr) {
+    int rc = gat_ctx_create(&ctx->aux_ctx, ctx->device, nullptr);
+    if (rc) return rc;
+  }
+  gat_ctx* x = ctx->aux_ctx;
+  const Knobs kn = read_knobs(ctx);                 // (the caller's: the auxiliary context has no options of its own)
+  const int rc = count_lists_on(x, kn, in);
+  x->stage_used = 0;                                // (count_lists_on has drained the stream before its buffers went back to the pool)
+  if (rc) return set_err(ctx, rc, "%s", x->err.c_str());
   return GAT_OK;
 }
 
@@ -1786,16 +1788,14 @@ extern "C" int gat_count_lists(gat_ctx* ctx, const int32_t* counter_ids, int n_c
                                const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks,
                                const int64_t* ws_nseg, int32_t n_groups, void* counts_host) {
   if (!anno_off) return set_err(ctx, GAT_ERR_ARG, "gat_count_lists: NULL argument");
-  return count_lists_impl(ctx, counter_ids, n_counters, lists, list_off, n_lists, annos, anno_off, anno_off + 1, n_tracks, ws_nseg,
-                          n_groups, counts_host);
+  return count_lists_impl(ctx, {counter_ids, n_counters, lists, list_off, n_lists, annos, anno_off, anno_off + 1, n_tracks, ws_nseg, n_groups, counts_host});
 }
 
 extern "C" int gat_count_list_ranges(gat_ctx* ctx, const int32_t* counter_ids, int n_counters,
                                      const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
                                      const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
                                      const int64_t* ws_nseg, int32_t n_groups, void* counts_host) {
-  return count_lists_impl(ctx, counter_ids, n_counters, lists, list_off, n_lists, annos, anno_begin, anno_end, n_tracks, ws_nseg,
-                          n_groups, counts_host);
+  return count_lists_impl(ctx, {counter_ids, n_counters, lists, list_off, n_lists, annos, anno_begin, anno_end, n_tracks, ws_nseg, n_groups, counts_host});
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1720,7 +1720,7 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
     P->anno = A;
   }
   tm.lap("annotation tables (total)");
-  HIPCHK(ctx, P->d_stat.alloc(16));                 // (8 statistics words, the status word in word 8)
+  HIPCHK(ctx, P->d_stat.alloc(gat::kStatSlotWords));
   HIPCHK(ctx, stage_flush(ctx));                    // the small tables' copies (one wait for all of them)
   ctx->refs += 1;                                   // (the context outlives its handle while a problem made on it is alive)
   *out = P.release();

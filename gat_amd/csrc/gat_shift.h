@@ -31,7 +31,7 @@ struct ShiftArgs {
   int64_t slab_stride;
   int32_t* unit_n;            // [batch][n_units]
   int32_t* flags;
-  unsigned long long* stat;   // word 7: segments with an empty window
+  unsigned long long* stat;   // the batch's status block: kStatEmptyWindows (gat_types.h)
   uint32_t* ws_stat;
 };
 
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(64) void k_shift(ShiftArgs A) {
     A.unit_n[(int64_t)sidx * A.n_units + u] = n;
     if (status) atomicOr(A.flags, status);
     *reinterpret_cast<uint4*>(A.ws_stat + ((int64_t)u * A.rec_stride + sidx) * 4) = make_uint4((uint32_t)nwork, rng.ndraws, 0u, 1u);
-    if (empty) atomicAdd(&A.stat[7], (unsigned long long)empty);
+    if (empty) atomicAdd(&A.stat[kStatEmptyWindows], (unsigned long long)empty);
   }
 }
 

@@ -856,7 +856,8 @@ __global__ __launch_bounds__(64) void k_tail_big(TailArgs T) {
     // only the bookkeeping is left): where it stands in the merged list, what it touches there and in the log
     bool applied = false;
 #ifdef GAT_DBG_QUEUE
-    int dbg_why = 10;
+    int dbg_why = kStatDbgWhy;     // (the counters in reading order: empty segment, placeholder neighbour, both neighbours and
+                                   //  more, two on the right, two logged, logged + neighbour)
 #endif
     if (!broken && x.x != x.y) {
       // merged-list elements with start <= x.start
@@ -890,7 +891,7 @@ __global__ __launch_bounds__(64) void k_tail_big(TailArgs T) {
       // (a neighbour that is the placeholder of an earlier bridge says nothing about what stands there: left to the round's end)
       const bool gone = (lo > 0 && pv.x == pv.y) || (lo < nU && nv.x == nv.y);
 #ifdef GAT_DBG_QUEUE
-      dbg_why = gone ? 11 : (tl && tr) ? 12 : tr2 ? 13 : nt >= 2 ? 14 : 15;
+      dbg_why = kStatDbgWhy + (gone ? 1 : (tl && tr) ? 2 : tr2 ? 3 : nt >= 2 ? 4 : 5);
 #endif
       if (!gone && tl && tr && !tr2 && nt == 0 && !(T.no_bridge & 1)) {
         // a bridge (round 6): it touches both neighbours and nothing else -- the three are one segment where the left one stands,

@@ -67,4 +67,42 @@ enum : int32_t {
                          // not for every unit at its capacity): host repeats the batch with the full size
 };
 
+// The status block of a sampler batch: kStatSlotWords 64-bit words on the device (gat_problem::d_stat), mirrored per batch in a
+// pinned slot (gat_ctx::h_stat, CallBlock::stat_slot).  The host zeroes words [0, kStatCopied) in front of a batch's kernels and
+// copies them into the slot behind them; the words beyond have an owner each that zeroes / copies its own.  This is the one place
+// that says what a word means: kernels and host refer to the names.
+enum : int {
+  // k_reduce_stats, summed over the batch's work units (contiguous from 0: it stores them as stat[threadIdx.x])
+  kStatPlaced = 0,         // segments placed
+  kStatDraws = 1,          // draws
+  kStatUnsuccessful = 2,   // unsuccessful rounds
+  kStatTailUnits = 3,      // work units finished by k_tail / carried on by k_tail_big
+  kStatFullUnits = 4,      // work units k_sampler ran in full
+  kStatResumedUnits = 5,   // work units k_sampler resumed with a stream moved up
+  kStatReduced = 6,        // (their number)
+  kStatRestarts = 6,       // k_brute_force: restarts + (work units not converged << kBruteUnconvShift)
+  kStatEmptyWindows = 7,   // k_shift: segments with an empty window
+  kStatFlags = 8,          // int32, OR of kStatus*: every sampler kernel, through gat_problem::flags_dev()
+  kStatQueued = 9,         // uint32, k_tail's queue length: through gat_problem::todo_count_dev()
+  kStatCopied = 10,        // words [0, kStatCopied): zeroed and copied per batch
+  kStatUnitsOverlap = 10,  // PINNED SLOT ONLY, kStatUnitsOverlapWords words: k_units_overlap's four 32-bit words {status (bit 0: not
+                           // pairwise; else a candidate region overflowed), overlaps taken off, candidates, free}, copied from
+                           // d_cand_count + kCandSlots behind the count kernels or zeroed by the host
+  kStatUnitsOverlapWords = 2,
+  kStatBruteFirst = 12,    // k_brute_force: ~((sample << 32) | unit) of the first work unit that did not converge (atomicMax);
+                           // zeroed and copied by the brute-force stage alone
+  kStatDbgWhy = 10,        // DEVICE ONLY, -DGAT_DBG_QUEUE builds only, kStatDbgWhyWords words: k_tail's counters of why a round was
+                           // broken (such a build zeroes and prints the whole slot)
+  kStatDbgWhyWords = 6,
+  kStatSlotWords = 16,
+};
+static_assert(kStatPlaced == 0 && kStatDraws == 1 && kStatUnsuccessful == 2 && kStatTailUnits == 3 && kStatFullUnits == 4 &&
+              kStatResumedUnits == 5 && kStatReduced == 6, "k_reduce_stats stores its six sums as stat[threadIdx.x]");
+static_assert(kStatReduced <= kStatRestarts && kStatRestarts < kStatCopied && kStatEmptyWindows < kStatCopied &&
+              kStatFlags < kStatCopied && kStatQueued < kStatCopied, "the words every batch zeroes and copies");
+static_assert(kStatCopied <= kStatUnitsOverlap, "the batch's copy must not overwrite k_units_overlap's words in the pinned slot");
+static_assert(kStatUnitsOverlap + kStatUnitsOverlapWords <= kStatBruteFirst, "k_units_overlap's words end before k_brute_force's");
+static_assert(kStatBruteFirst < kStatSlotWords && kStatDbgWhy >= kStatCopied && kStatDbgWhy + kStatDbgWhyWords <= kStatSlotWords,
+              "everything fits in the slot");
+
 }  // namespace gat
