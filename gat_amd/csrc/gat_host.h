@@ -131,6 +131,13 @@ struct gat_ctx {
 // (build_annos: lists beyond it get the merged index) -- they had drifted apart by three entries
 inline bool count_lists_staged(const Knobs& kn, int64_t max_m) { return max_m > 0 && max_m + 4 <= kn.count_lds_entries; }
 
+// gat_problem_desc::sampler: the samplers there are; those whose kernel is a wave per work unit with its stream in LDS
+// (k_shift, k_permute, k_permute_local, k_brute_force: no k_rng + k_place in front).  sampler_draws_lengths: gat_prep_units.h
+inline bool sampler_runs_wave_per_unit(int32_t s) {
+  return s == GAT_SAMPLER_SHIFT || s == GAT_SAMPLER_GLOBAL_PERMUTATION || s == GAT_SAMPLER_LOCAL_PERMUTATION || s == GAT_SAMPLER_BRUTE_FORCE;
+}
+inline bool sampler_is_known(int32_t s) { return s == GAT_SAMPLER_ANNOTATOR || s == GAT_SAMPLER_SEGMENTS || sampler_runs_wave_per_unit(s); }
+
 void ctx_release(gat_ctx* ctx);     // gat_mi355.hip: drops one reference, frees the context with the last
 
 inline int set_err(gat_ctx* ctx, int code, const char* fmt, ...) {

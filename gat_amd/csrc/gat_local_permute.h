@@ -5,7 +5,7 @@
 // wave's in-LDS MT19937, as in k_permute.  The reference walks the unit's workspace pieces in order and draws, for every
 // piece with working segments, random.shuffle(lengths), n x randint(0, free) (the points, sorted) and one more (the shift)
 // from that ONE stream: where a piece's draws begin depends on the rejections of the pieces before it, so the pieces are
-// serial within the wave.  Problem creation (gat_prep.hip: local_permute_tables) laid down, per active piece, {first, n,
+// serial within the wave.  Problem creation (gat_prep_units.h: local_permute_tables) laid down, per active piece, {first, n,
 // work_end, free}: the working segments are the run [first, first + n) of the unit's list (getOverlappingSegments' set: the
 // segment in front of the piece is in it whether it reaches the piece or not) and work_start is 0 -- the reference's
 // min() / max() of that set return 0 (their assertions fire where nothing can be raised), so every piece is permuted over

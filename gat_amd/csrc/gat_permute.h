@@ -2,7 +2,7 @@
 //
 // Per work unit the stream is random.seed((seed + sample*n_units + unit) mod 2^32) -- the per-unit family of every sampler
 // here with CPython's seeding (rng_seed_by_array) and _randbelow (py_randbelow*) on the wave's in-LDS MT19937.
-// Problem creation (gat_prep.hip: permute_tables) laid down, per unit, the working segments' lengths in list order and W,
+// Problem creation (gat_prep_units.h: permute_tables) laid down, per unit, the working segments' lengths in list order and W,
 // the workspace extended by them and merge(0)ed, with its cumulated lengths and free = Wsum - sum(lengths).
 //
 // The draws, in the reference's order: random.shuffle(lengths) (j = _randbelow(i + 1) for i = n-1..1, then the swap --

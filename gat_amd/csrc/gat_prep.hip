@@ -13,6 +13,7 @@
 #include <unistd.h>
 
 #include "gat_host.h"
+#include "gat_prep_units.h"
 
 // ------------------------------------------------------------------------------------------
 // the device-memory pool behind DevBuf (gat_host.h)
@@ -752,109 +753,7 @@ static int group_annotations(gat_ctx* ctx, const gat_problem_desc* d, std::vecto
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side hoisted setup of one unit (gat/Engine.pyx:543-565)
-static uint32_t host_overlap(const gat_segment* w, int64_t nw, uint32_t s, uint32_t e) {
-  // bases of [s,e) inside the normalized list w
-  uint32_t ov = 0;
-  const gat_segment* it = std::lower_bound(w, w + nw, s, [](const gat_segment& a, uint32_t v) { return a.end <= v; });
-  for (; it != w + nw && it->start < e; ++it) ov += std::min(e, it->end) - std::max(s, it->start);
-  return ov;
-}
-
-// SamplerShift (gat/Engine.pyx:1063-1084): the window of every working segment -- [max(0, mid - area), max(0, mid + area)]
-// in the reference's int32 lmax, the workspace segments overlapping it, truncated to it and normalized (empties dropped:
-// gat/SegmentList.pyx:1186-1203).  Those are the workspace segments with end > window start and start < window end, a
-// contiguous run [lo, hi]; only the run's first start and last end are clipped.  Two records per working segment.
-static void shift_windows(std::vector<uint4>& out, const gat_segment* us, int64_t nus, const gat_segment* uw, int64_t nuw,
-                          const std::vector<uint32_t>& cdf, double radius, int32_t extension) {
-  const double half_radius = radius / 2;
-  for (int64_t i = 0; i < nus; ++i) {
-    if (host_overlap(uw, nuw, us[i].start, us[i].end) == 0) continue;          // working = segments.filter(workspace)
-    const uint32_t length = us[i].end - us[i].start;
-    const uint32_t mid = us[i].start + length / 2u;
-    const int32_t area = extension ? extension / 2 : (int32_t)(uint32_t)(uint64_t)std::floor((double)length * half_radius);
-    const int32_t ws_start = std::max<int32_t>(0, (int32_t)(mid - (uint32_t)area));
-    const int32_t ws_end = std::max<int32_t>(0, (int32_t)(mid + (uint32_t)area));
-    const uint32_t s0 = (uint32_t)ws_start, e0 = (uint32_t)ws_end;
-    const gat_segment* lo_it = std::upper_bound(uw, uw + nuw, s0, [](uint32_t v, const gat_segment& g) { return v < g.end; });
-    const gat_segment* hi_it = std::lower_bound(uw, uw + nuw, e0, [](const gat_segment& g, uint32_t v) { return g.start < v; });
-    const int64_t lo = lo_it - uw, hi = (hi_it - uw) - 1;                     // pieces lo..hi
-    uint32_t k = 0, fs = 0, le = 0, sum = 0;
-    if (hi >= lo && s0 < e0) {
-      k = (uint32_t)(hi - lo + 1);
-      fs = std::max(uw[lo].start, s0);
-      le = std::min(uw[hi].end, e0);
-      if (k == 1) sum = le - fs;
-      else {
-        sum = (uw[lo].end - fs) + (le - uw[hi].start) + (cdf[(size_t)hi - 1] - cdf[(size_t)lo]);   // (cdf: cumulated lengths - 1)
-      }
-    }
-    out.push_back(make_uint4(length, k ? (uint32_t)lo : 0u, k, sum));
-    out.push_back(make_uint4(fs, le, 0u, 0u));
-  }
-}
-
-// SamplerGlobalPermutation (gat/Engine.pyx:1284-1299): working = segments.filter(workspace) (kept whole), W = the workspace
-// extended by them and merge(0)ed (adjacent pieces united), free = W.sum() - sum(lengths).  Appends W and its cumulated
-// lengths; returns free (negative: the reference's randint(0, free) raises).
-static int64_t permute_tables(std::vector<uint2>& w, std::vector<uint32_t>& cum, const gat_segment* us, int64_t nus,
-                              const gat_segment* uw, int64_t nuw) {
-  std::vector<uint2> all;
-  int64_t total = 0;
-  all.reserve((size_t)(nus + nuw));
-  for (int64_t i = 0; i < nuw; ++i) all.push_back(make_uint2(uw[i].start, uw[i].end));
-  for (int64_t i = 0; i < nus; ++i) {
-    if (host_overlap(uw, nuw, us[i].start, us[i].end) == 0) continue;
-    all.push_back(make_uint2(us[i].start, us[i].end));
-    total += us[i].end - us[i].start;
-  }
-  std::stable_sort(all.begin(), all.end(), [](const uint2& a, const uint2& b) { return a.x < b.x; });
-  for (const uint2& p : all) {
-    if (!w.empty() && p.x <= w.back().y) w.back().y = std::max(w.back().y, p.y);
-    else w.push_back(p);
-  }
-  int64_t sum = 0;
-  for (const uint2& p : w) { sum += p.y - p.x; cum.push_back((uint32_t)sum); }
-  return sum - total;
-}
-
-// SamplerLocalPermutation (gat/Engine.pyx:1174-1188): per workspace piece (ws, we) the working segments are
-// getOverlappingSegments' set (gat/SegmentList.pyx:952-983) -- from the last segment with start <= ws (the first one when
-// there is none) on, every segment with start <= we, whether or not it reaches the piece --, a contiguous run of the
-// unit's list.  work_start / work_end come out as 0 / we: min() and max() of the run's list (built with _add, normalized
-// flag 0) fail their assertion inside a cpdef that cannot raise and return 0.  free = we - sum(lengths).  Appends one
-// record {first, n, we, free} per piece with n > 0; returns the index of the first piece with free < 0 (the reference's
-// randint(0, free) raises), -1 when there is none.  sum_n / max_n: the run lengths' sum and maximum.
-static int64_t local_permute_tables(std::vector<uint4>& pieces, int64_t& sum_n, int64_t& max_n, const gat_segment* us, int64_t nus,
-                                    const gat_segment* uw, int64_t nuw) {
-  std::vector<uint64_t> cum((size_t)nus + 1, 0);
-  for (int64_t i = 0; i < nus; ++i) cum[(size_t)i + 1] = cum[(size_t)i] + (us[i].end - us[i].start);
-  auto starts_le = [&](uint32_t x) {                       // segments with start <= x
-    int64_t lo = 0, hi = nus;
-    while (lo < hi) { const int64_t m = (lo + hi) >> 1; if (us[m].start <= x) lo = m + 1; else hi = m; }
-    return lo;
-  };
-  int64_t bad = -1;
-  sum_n = max_n = 0;
-  for (int64_t k = 0; k < nuw; ++k) {
-    const int64_t first = std::max<int64_t>(0, starts_le(uw[k].start) - 1), n = starts_le(uw[k].end) - first;
-    if (n <= 0) continue;
-    const int64_t free_len = (int64_t)uw[k].end - (int64_t)(cum[(size_t)(first + n)] - cum[(size_t)first]);
-    if (free_len < 0 && bad < 0) bad = k;
-    pieces.push_back(make_uint4((uint32_t)first, (uint32_t)n, uw[k].end, (uint32_t)std::max<int64_t>(free_len, 0)));
-    sum_n += n;
-    max_n = std::max(max_n, n);
-  }
-  return bad;
-}
-
-static int32_t cap_for(const Knobs& kn, int64_t n) {
-  int64_t c = n + n / 4 + 96;
-  if (kn.test_small_caps) c = n / 2 + 8;      // tests: force the overflow / retry path
-  c = (c + 63) / 64 * 64;
-  return (int32_t)c;
-}
-
+// the per-sample slab (a unit by itself: gat_prep_units.h)
 int layout_slab(gat_problem* P, const Knobs& kn) {
   // regions in contig-major order so that a contig's units are adjacent (k_contig output region)
   int64_t off = 0;
@@ -1113,12 +1012,398 @@ extern "C" void gat_annotations_destroy(gat_annotations* a) {
   annotations_release(a);
 }
 
+// ------------------------------------------------------------------------------------------
+// gat_problem_create, stage by stage.  Per unit: gat_prep_units.h.
+
+// The tables the units share.  gather_unit_tables appends every active unit's part in unit order and notes the offsets in
+// the unit's record; the samplers' tables are filled for the problem's sampler alone.
+struct UnitTables {
+  std::vector<uint2> ws;
+  std::vector<uint32_t> ws_cdf, rank_len, ws_tree;
+  std::vector<std::pair<int64_t, int32_t>> work;   // (working segments, unit) of the active units
+  std::vector<double> len_cv2;                     // per unit, squared coefficient of variation of its lengths (size_rng_rows)
+  std::vector<uint4> shift;                        // GAT_SAMPLER_SHIFT: the windows (gat_problem::d_shift)
+  std::vector<int32_t> shift_off;
+  std::vector<uint4> perm_unit;                    // GAT_SAMPLER_GLOBAL_PERMUTATION: gat_problem::d_perm_*
+  std::vector<uint32_t> perm_len, perm_cum;
+  std::vector<uint2> perm_w;
+  std::vector<uint4> lperm_unit, lperm_piece;      // GAT_SAMPLER_LOCAL_PERMUTATION: gat_problem::d_lperm_*
+  std::vector<uint32_t> lperm_len;
+  explicit UnitTables(size_t n)                    // (per-unit arrays: at least one element, for the upload)
+      : len_cv2(n, 0.0), shift_off(n, 0), perm_unit(n, make_uint4(0u, 0u, 0u, 0u)), lperm_unit(n, make_uint4(0u, 0u, 0u, 0u)) {}
+};
+
+static int check_problem_desc(gat_ctx* ctx, const gat_problem_desc* d) {
+  if (d->n_units < 0 || d->n_contigs < 0 || d->n_tracks < 0 || d->nbuckets <= 0)
+    return set_err(ctx, GAT_ERR_ARG, "gat_problem_create: negative size / nbuckets <= 0");
+  if (!sampler_is_known(d->sampler)) return set_err(ctx, GAT_ERR_ARG, "unknown sampler %d", d->sampler);
+  if (d->sampler == GAT_SAMPLER_BRUTE_FORCE && (d->brute_ntries_inner < 0 || d->brute_ntries_outer < 0))
+    return set_err(ctx, GAT_ERR_VALUE, "SamplerBruteForce: ntries_inner %d and ntries_outer %d must be >= 0 (0: the reference's 100 / 10)",
+                   (int)d->brute_ntries_inner, (int)d->brute_ntries_outer);
+  if (d->sampler == GAT_SAMPLER_SHIFT && !(d->shift_radius >= 0.0 && d->shift_radius <= 1e9))
+    return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: radius %g must be >= 0", d->shift_radius);
+  if (d->sampler == GAT_SAMPLER_SHIFT && d->shift_extension < 0)
+    return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: extension %d must be >= 0", (int)d->shift_extension);
+  return GAT_OK;
+}
+
+// the units' records zeroed but for their contig; per contig its non-skipped units, in unit order
+static int assign_units_to_contigs(gat_ctx* ctx, const gat_problem_desc* d, gat_problem* P, std::vector<std::vector<int32_t>>& per_contig) {
+  P->h_units.resize((size_t)d->n_units);
+  P->h_base_cap.assign((size_t)d->n_units, 0);
+  P->h_cws_nseg.assign(d->cws_nseg, d->cws_nseg + d->n_contigs);
+  per_contig.resize((size_t)d->n_contigs);
+  for (int u = 0; u < d->n_units; ++u) {
+    UnitDev& U = P->h_units[u];
+    memset(&U, 0, sizeof(U));
+    const int64_t nus = d->seg_off[u + 1] - d->seg_off[u], nuw = d->ws_off[u + 1] - d->ws_off[u];
+    const int c = d->unit_contig[u];
+    U.contig = c;
+    P->n_seg_total += nus;
+    const bool skipped = (nus == 0 || nuw == 0);     // gat/__init__.py:536-538
+    if (c >= d->n_contigs || (c < 0 && !skipped))
+      return set_err(ctx, GAT_ERR_ARG, "unit %d: contig index %d invalid (skipped units carry -1)", u, c);
+    if (!skipped) per_contig[(size_t)c].push_back(u);
+  }
+  return GAT_OK;
+}
+
+// the tables of the problem's list sampler: unit u's part behind the others', where it begins in the unit's record
+static void append_sampler_tables(gat_problem* P, UnitTables& T, int u, const UnitPrep& R) {
+  if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
+    T.perm_unit[(size_t)u] = make_uint4((uint32_t)T.perm_len.size(), (uint32_t)T.perm_w.size(), (uint32_t)R.perm_w.size(), (uint32_t)R.perm_free);
+    T.perm_len.insert(T.perm_len.end(), R.lens.begin(), R.lens.end());
+    T.perm_w.insert(T.perm_w.end(), R.perm_w.begin(), R.perm_w.end());
+    T.perm_cum.insert(T.perm_cum.end(), R.perm_cum.begin(), R.perm_cum.end());
+  }
+  if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) {
+    T.lperm_unit[(size_t)u] = make_uint4((uint32_t)T.lperm_piece.size(), (uint32_t)R.lperm.size(), (uint32_t)T.lperm_len.size(), (uint32_t)R.lperm_sum_n);
+    T.lperm_piece.insert(T.lperm_piece.end(), R.lperm.begin(), R.lperm.end());
+    T.lperm_len.insert(T.lperm_len.end(), R.lens.begin(), R.lens.end());
+    P->lperm_max_n = std::max<int32_t>(P->lperm_max_n, (int32_t)R.lperm_max_n);
+    P->lperm_max_out = std::max<int64_t>(P->lperm_max_out, 2 * R.lperm_sum_n);
+  }
+  if (P->sampler == GAT_SAMPLER_SHIFT) {
+    T.shift_off[(size_t)u] = (int32_t)(T.shift.size() / 2);
+    T.shift.insert(T.shift.end(), R.shift.begin(), R.shift.end());
+  }
+}
+
+// In unit order: the first unit's error, if any (a list that is not normalized: in the reference's words), else the active
+// units' parts appended to the shared tables, their offsets and capacities noted.
+static int gather_unit_tables(gat_ctx* ctx, const gat_problem_desc* d, const Knobs& kn, gat_problem* P, const std::vector<UnitPrep>& prep,
+                              UnitTables& T) {
+  auto append16 = [&](const std::vector<uint32_t>& v) {          // (16-byte aligned: the images are copied in 16-byte pieces)
+    while (T.ws_tree.size() & 3u) T.ws_tree.push_back(0u);
+    const int32_t off = (int32_t)T.ws_tree.size();
+    T.ws_tree.insert(T.ws_tree.end(), v.begin(), v.end());
+    return off;
+  };
+  for (int u = 0; u < d->n_units; ++u) {
+    const UnitPrep& R = prep[(size_t)u];
+    UnitDev& U = P->h_units[u];
+    const int64_t nus = d->seg_off[u + 1] - d->seg_off[u];
+    if (R.rc == GAT_ERR_ASSERT) {                    // (the first offender in unit order, with the reference's message)
+      int rc;
+      if ((rc = check_list(ctx, d->segs + d->seg_off[u], nus, "segment", u))) return rc;                                   // gat/Engine.pyx:535
+      if ((rc = check_list(ctx, d->ws + d->ws_off[u], d->ws_off[u + 1] - d->ws_off[u], "workspace", u))) return rc;       // gat/Engine.pyx:536
+    }
+    if (R.rc) return set_err(ctx, R.rc, "%s", R.err.c_str());
+    if (!R.active) continue;
+    U.rank_off = (int32_t)T.rank_len.size();
+    T.rank_len.insert(T.rank_len.end(), R.rank.begin(), R.rank.end());
+    U.ws_off = (int32_t)T.ws.size();
+    T.ws.insert(T.ws.end(), R.ws.begin(), R.ws.end());
+    T.ws_cdf.insert(T.ws_cdf.end(), R.cdf.begin(), R.cdf.end());
+    if (!R.tree_start.empty()) {
+      U.tree_start_off = (int32_t)T.ws_tree.size();
+      T.ws_tree.insert(T.ws_tree.end(), R.tree_start.begin(), R.tree_start.end());
+      U.tree_cdf_off = (int32_t)T.ws_tree.size();
+      T.ws_tree.insert(T.ws_tree.end(), R.tree_cdf.begin(), R.tree_cdf.end());
+    }
+    U.pgrid_off = R.pgrid.empty() ? -1 : append16(R.pgrid);
+    U.cgrid_off = R.cgrid.empty() ? -1 : append16(R.cgrid);
+    T.len_cv2[(size_t)u] = R.cv2;
+    const int64_t cap = base_cap_for(P->sampler, kn, U, R, nus);
+    if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION && cap > INT32_MAX / 2)
+      return set_err(ctx, GAT_ERR_CAPACITY, "unit %d: SamplerLocalPermutation: %lld working segments over its pieces", u, (long long)R.lperm_sum_n);
+    P->h_base_cap[u] = (int32_t)cap;
+    append_sampler_tables(P, T, u, R);
+    T.work.push_back(std::make_pair(R.nwork, (int32_t)u));
+  }
+  return GAT_OK;
+}
+
+// contig -> units (reference order)
+static int link_contigs(gat_ctx* ctx, gat_problem* P, const std::vector<std::vector<int32_t>>& per_contig) {
+  P->h_contig_unit_off.assign((size_t)P->n_contigs + 1, 0);
+  for (int c = 0; c < P->n_contigs; ++c) {
+    if (per_contig[(size_t)c].empty())
+      return set_err(ctx, GAT_ERR_ARG, "contig %d has no unit: contigs must be those of the non-skipped units", c);
+    if (!P->merge_contigs && per_contig[(size_t)c].size() != 1)
+      return set_err(ctx, GAT_ERR_ARG, "contig %d has %zu units but keys carry no isochore (merge_contigs=0)", c, per_contig[(size_t)c].size());
+    for (int32_t u : per_contig[(size_t)c]) P->h_contig_units.push_back(u);
+    P->h_contig_unit_off[(size_t)c + 1] = (int32_t)P->h_contig_units.size();
+  }
+  return GAT_OK;
+}
+
+// k_place's cm_ok for a simple unit: the offset draw's mask (of the range workspace length - 2 + length) is the position
+// draw's (of the range workspace length - 1) for every length the unit can draw -- no power of two between them
+// (k_place_scan runs only such units)
+static bool unit_cm_ok(const UnitDev& U, const UnitTables& T) {
+  const uint2 w0 = T.ws[(size_t)U.ws_off];
+  const uint32_t range_p = U.ws_total - 1u, mask_p = 0xffffffffu >> __builtin_clz(range_p);
+  const uint32_t lmax = T.rank_len[(size_t)U.rank_off + U.hist_total - 1u];     // (rank_len[1 + rangeL], rangeL = hist_total - 2)
+  return (uint64_t)(w0.y - w0.x - 2u) + (uint64_t)lmax <= (uint64_t)mask_p;
+}
+
+// k_place_grid (MODE 4): some workspace is beyond k_place's LDS table and every such unit has the grid over its cumulated
+// lengths (UnitDev::cgrid_off); *words: the largest image, which must fit in the LDS the rings leave
+static bool grid_place_possible(const gat_problem* P, const UnitTables& T, int32_t* words) {
+  bool any = false;
+  *words = 0;
+  for (int32_t u : P->h_order) {
+    const UnitDev& U = P->h_units[(size_t)u];
+    if (U.n_ws <= gat::kPlaceWsLds) continue;
+    any = true;
+    if (U.cgrid_off < 0) return false;
+    *words = std::max(*words, (int32_t)T.ws_tree[(size_t)U.cgrid_off + 3]);
+  }
+  return any;
+}
+
+// the split path pays when k_tail can take most units: SamplerAnnotator, lists the wave bucket sorts hold, workspaces
+// of up to kTailMaxWs segments -- or longer ones, P->tail_long_ws
+static bool split_path_pays(const gat_problem* P, const Knobs& kn) {
+  size_t small_ws = 0;
+  for (int32_t u : P->h_order) if (P->h_units[(size_t)u].n_ws <= gat::kTailMaxWs || P->tail_long_ws) ++small_ws;
+  // (long lists: their tail places dozens of segments, not the handful k_tail keeps aside -- 0.2 % finished there on the
+  //  config-4 shape -- so those problems stay with k_merge_big + k_sampler)
+  return P->sampler == GAT_SAMPLER_ANNOTATOR && !P->h_order.empty() && 2 * small_ws >= P->h_order.size() &&
+         P->max_hist + P->max_hist / 8 <= 1024 && !kn.no_split;
+}
+
+// the launch order (the longest draw chain first) and everything that later selects kernels
+static void order_and_classify(gat_problem* P, const Knobs& kn, UnitTables& T) {
+  std::sort(T.work.begin(), T.work.end(), [](const std::pair<int64_t, int32_t>& a, const std::pair<int64_t, int32_t>& b) {
+    return a.first != b.first ? a.first > b.first : a.second < b.second;
+  });
+  for (auto& w : T.work) P->h_order.push_back(w.second);
+  P->all_simple = P->all_one_ws = !P->h_order.empty();
+  P->all_cm_ok = true;
+  uint32_t max_hist = 0;
+  uint64_t work_simple = 0, work_all = 0, work_big_rank = 0;
+  for (int32_t u : P->h_order) {
+    const UnitDev& U = P->h_units[(size_t)u];
+    const bool degenerate = !(U.hist_total > 2 && U.ws_total > 1);          // k_place leaves those to k_sampler
+    const bool simple = U.n_ws == 1 && U.bucket <= 1 && U.hist_total < (uint32_t)gat::kPlaceRankLds && U.ws_total > 1;
+    if (!degenerate && !simple) P->all_simple = false;
+    if (!degenerate && simple && !unit_cm_ok(U, T)) P->all_cm_ok = false;
+    if (!degenerate) { work_all += U.hist_total; if (simple) work_simple += U.hist_total; }
+    if (!degenerate && !(U.n_ws == 1 && U.bucket <= 1)) P->all_one_ws = false;
+    if (!degenerate && U.hist_total >= (uint32_t)gat::kPlaceRankLds) work_big_rank += U.hist_total;
+    P->max_nws = std::max(P->max_nws, U.n_ws);
+    max_hist = std::max(max_hist, U.hist_total);
+  }
+  P->max_hist = max_hist;
+  P->small_tables = !P->h_order.empty() && P->max_nws <= 64 && max_hist < 256;
+  P->grid_place = grid_place_possible(P, T, &P->grid_lds_words) && !kn.place_no_grid;
+  P->pipe_pays = 2 * work_simple >= work_all;
+  P->all_one_ws = P->all_one_ws && !P->all_simple && 2 * work_big_rank >= work_all && max_hist <= (uint32_t)gat::kPlaceWideMaxRank;
+  P->long_lists = max_hist + max_hist / 8 > 1024;
+  // (round 6: k_tail takes the longer workspaces too -- their position draw through the tree over the cumulated lengths, their
+  //  overlaps through the position grid; GAT_TAIL_NO_LONG_WS: as before, such units are k_sampler's)
+  P->tail_long_ws = !kn.tail_no_long_ws;
+  P->split_path = split_path_pays(P, kn);
+}
+
+// expected raw MT19937 outputs of one draw under masked rejection: (mask + 1) / (range + 1)
+static double expected_outputs(uint64_t range) {
+  if (range == 0) return 0.0;
+  uint64_t m = range; m |= m >> 1; m |= m >> 2; m |= m >> 4; m |= m >> 8; m |= m >> 16; m |= m >> 32;
+  return (double)(m + 1) / (double)(range + 1);
+}
+
+// The rows of unit U's streams: expected raw outputs per placement x working segments + slack, in whole k_place chunks (8)
+// and k_rng read groups (16).  Streams that still run out are redone by k_sampler from their seed.
+static int64_t rng_rows_for_unit(const gat_problem* P, const Knobs& kn, const UnitDev& U, const gat_segment* uw, int64_t nuw, double len_cv2) {
+  // offset draw: range = chosen workspace segment + sampled length - 2, weighted by how often a segment
+  // is chosen (its share of the workspace) and taken at the mean working-segment length
+  const double mean_len = U.hist_total ? (double)(uint32_t)U.ltotal / (double)U.hist_total : 1.0;
+  double e = 0.0, v = 0.0;
+  for (int64_t k = 0; k < nuw; ++k) {
+    const double wl = (double)(uw[k].end - uw[k].start);
+    e += wl / (double)U.ws_total * expected_outputs((uint64_t)(wl + mean_len));
+  }
+  auto addvar = [&](double ex) { if (ex > 0) v += (ex - 1.0) * ex; };   // geometric: var = (1-p)/p^2 = ex(ex-1)
+  addvar(e);
+  if (U.hist_total > 2) { const double x = expected_outputs((uint64_t)U.hist_total - 2); e += x; addvar(x); }
+  if (U.bucket > 1) { const double x = expected_outputs((uint64_t)U.bucket - 1); e += x; addvar(x); }
+  if (U.ws_total > 1) { const double x = expected_outputs((uint64_t)U.ws_total - 1); e += x; addvar(x); }
+  // Spread of the raw-output count of a stream: the NUMBER of placements until the unit's bases are reproduced varies
+  // by cv(length) x sqrt(n) (a renewal count) and every placement costs e outputs -- that term dominates (measured on
+  // config 2: 97 / 116 / 58 outputs for units of 778 / 444 / 166 segments = e x cv x sqrt(n)) -- plus the rejection
+  // noise v per placement.  5 to 7.5 sigma and the tail's few dozen outputs: a stream that runs out is redone from its seed
+  // by ONE wave, placement by placement, and such a straggler (0.5 ms) is now longer than the rest of the sampler.
+  const double nplace = P->sampler == GAT_SAMPLER_SEGMENTS ? (double)U.n_target : (double)U.hist_total;
+  const double var_n = P->sampler == GAT_SAMPLER_SEGMENTS ? 0.0 : len_cv2 * e * e;
+  // The multiple follows what running out costs.  A unit of the split path (lists the wave sorts hold) that runs out of
+  // rows is RESUMED by k_sampler where its lane stopped -- behind k_place's last placement, or at the consolidation k_tail
+  // would have continued from -- with the stream moved up to its position by the in-LDS generator (rng_switch: the
+  // seeding chain + a twist per 624 outputs, ~10 us): 3.5 sigma and 32 rows for the tail (one stream in two thousand runs
+  // out; round 3's 5-7.5 sigma + 96, sized for a redo of every placement from the seed at 0.5 ms, generated 1.4x the rows
+  // that were consumed: k_rng 0.48 -> 0.43 ms on config 2, 1.07 -> 0.92 on config 3).  A long list that runs out behind
+  // k_tail_big's in-place unions is still redone from its seed -- milliseconds for thousands of placements: 7.5 sigma + 96.
+  const double s_min = kn.rng_sigma_min, s_max = kn.rng_sigma_max;
+  const bool long_list = U.hist_total + U.hist_total / 8 > 1024 || P->sampler == GAT_SAMPLER_SEGMENTS;
+  // (a resumed unit goes through k_sampler's wave-per-unit consolidation and tail: tens of microseconds for hundreds of
+  //  segments, a few for fifty -- up to five sigma for the larger units of the split path: config 2, k_rng + k_sampler
+  //  0.55 -> 0.51 ms, where 3.5 sigma throughout gave back in k_sampler what it saved in k_rng)
+  const double sigmas = long_list ? s_max : std::min(std::max(s_min, 5.0), std::max(s_min, s_min - 0.5 + nplace / 130.0));
+  const double tail_rows = kn.rng_tail_rows_set ? kn.rng_tail_rows : (long_list ? 96.0 : (nplace < 128 ? 32.0 : 48.0));
+  const double need = e * nplace * kn.rng_slack + sigmas * std::sqrt(nplace * (v + 0.5 + var_n)) + tail_rows;
+  const int64_t rows = ((int64_t)std::ceil(need / 16.0)) * 16;
+  return std::min<int64_t>(rows, (int64_t)gat::kMtN * 2048);
+}
+
+static void size_rng_rows(gat_problem* P, const gat_problem_desc* d, const Knobs& kn, const UnitTables& T) {
+  // (k_shift, k_permute, k_permute_local, k_brute_force: a wave per work unit, its stream in LDS)
+  if (kn.sampler_mode == "wave" || sampler_runs_wave_per_unit(P->sampler)) P->sampler_mode = 0;
+  for (int32_t u : P->h_order) {
+    const int64_t rows = rng_rows_for_unit(P, kn, P->h_units[(size_t)u], d->ws + d->ws_off[u], d->ws_off[u + 1] - d->ws_off[u], T.len_cv2[(size_t)u]);
+    P->h_rng_rows.push_back((int32_t)rows);
+    P->rng_rows_total += rows;
+  }
+}
+
+// the list samplers' tables (a table nothing was put into: one element, so that there is a buffer)
+static int upload_sampler_tables(gat_ctx* ctx, gat_problem* P, UnitTables& T) {
+  if (P->sampler == GAT_SAMPLER_SHIFT) {
+    if (T.shift.empty()) T.shift.push_back(make_uint4(0u, 0u, 0u, 0u));
+    HIPCHK(ctx, P->d_shift.upload(T.shift, ctx));
+    HIPCHK(ctx, P->d_shift_off.upload(T.shift_off, ctx));
+  }
+  if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
+    if (T.perm_len.empty()) T.perm_len.push_back(0u);
+    if (T.perm_w.empty()) { T.perm_w.push_back(make_uint2(0u, 0u)); T.perm_cum.push_back(0u); }
+    HIPCHK(ctx, P->d_perm_unit.upload(T.perm_unit, ctx));
+    HIPCHK(ctx, P->d_perm_len.upload(T.perm_len, ctx));
+    HIPCHK(ctx, P->d_perm_w.upload(T.perm_w, ctx));
+    HIPCHK(ctx, P->d_perm_cum.upload(T.perm_cum, ctx));
+  }
+  if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) {
+    if (T.lperm_piece.empty()) T.lperm_piece.push_back(make_uint4(0u, 0u, 0u, 0u));
+    if (T.lperm_len.empty()) T.lperm_len.push_back(0u);
+    HIPCHK(ctx, P->d_lperm_unit.upload(T.lperm_unit, ctx));
+    HIPCHK(ctx, P->d_lperm_piece.upload(T.lperm_piece, ctx));
+    HIPCHK(ctx, P->d_lperm_len.upload(T.lperm_len, ctx));
+  }
+  return GAT_OK;
+}
+
+static int upload_unit_tables(gat_ctx* ctx, gat_problem* P, UnitTables& T) {
+  HIPCHK(ctx, P->d_order.upload(P->h_order, ctx));
+  P->h_unit_pos.assign((size_t)std::max(1, P->n_units), -1);
+  for (size_t a = 0; a < P->h_order.size(); ++a) P->h_unit_pos[(size_t)P->h_order[a]] = (int32_t)a;
+  HIPCHK(ctx, P->d_unit_pos.upload(P->h_unit_pos, ctx));
+  HIPCHK(ctx, P->d_rng_rows.upload(P->h_rng_rows, ctx));
+  HIPCHK(ctx, P->d_contig_unit_off.upload(P->h_contig_unit_off, ctx));
+  HIPCHK(ctx, P->d_contig_units.upload(P->h_contig_units, ctx));
+  HIPCHK(ctx, P->d_ws.upload(T.ws, ctx));
+  HIPCHK(ctx, P->d_ws_cdf.upload(T.ws_cdf, ctx));
+  int rc = upload_sampler_tables(ctx, P, T);
+  if (rc) return rc;
+  {
+    // what a position draw needs of its workspace segment (gat/Engine.pyx:318-325) as one record
+    std::vector<uint4> rec(std::max<size_t>(1, T.ws.size()));
+    for (int32_t u : P->h_order) {
+      const UnitDev& U = P->h_units[(size_t)u];
+      for (int32_t i = 0; i < U.n_ws; ++i) {
+        const size_t k = (size_t)U.ws_off + (size_t)i;
+        rec[k] = make_uint4(T.ws[k].x, T.ws[k].y, i > 0 ? T.ws[k - 1].y : 0x80000000u, T.ws_cdf[k]);
+      }
+    }
+    HIPCHK(ctx, P->d_ws_rec.upload(rec, ctx));
+  }
+  if (T.ws_tree.empty()) T.ws_tree.assign(16, 0u);
+  HIPCHK(ctx, P->d_ws_tree.upload(T.ws_tree, ctx));
+  HIPCHK(ctx, P->d_rank_len.upload(T.rank_len, ctx));
+  HIPCHK(ctx, P->d_cws_nseg.upload(P->h_cws_nseg, ctx));
+  return GAT_OK;
+}
+
+// of the segments that are placed (0 when there are none)
+static double mean_segment_length(const gat_problem* P) {
+  double bases = 0, segs = 0;
+  for (int32_t u : P->h_order) { bases += (double)(uint32_t)P->h_units[(size_t)u].ltotal; segs += (double)P->h_units[(size_t)u].hist_total; }
+  return segs > 0 ? bases / segs : 0.0;
+}
+
+// Counting an isochore problem from the units' lists: where a segment could reach over the end of its workspace piece.
+// One bit per cell of 2^bshift bases (about two mean segment lengths): a boundary of some unit's workspace piece lies in the
+// cell -- a segment whose cells hold no boundary lies inside one piece (k_count_merged<2, .> tests the bits from its first
+// base's cell to its last's: a 64-bit window of the map)
+static int build_boundary_map(gat_ctx* ctx, gat_problem* P, const Knobs& kn, const std::vector<uint2>& ws) {
+  P->units_direct_ok = false;
+  if (!(P->merge_contigs && P->n_contigs > 0 && P->split_path && !kn.count_via_contigs)) return GAT_OK;
+  const double mean_len = mean_segment_length(P);
+  int bshift = 8;
+  while (bshift < 24 && (double)(1u << bshift) < 2.0 * mean_len) ++bshift;
+  P->bshift = bshift;
+  std::vector<int64_t> boff((size_t)P->n_contigs + 1, 0);
+  std::vector<uint32_t> extent((size_t)P->n_contigs, 0u);
+  for (int32_t u : P->h_order) {
+    const UnitDev& U = P->h_units[(size_t)u];
+    extent[(size_t)U.contig] = std::max(extent[(size_t)U.contig], ws[(size_t)U.ws_off + (size_t)U.n_ws - 1].y);
+  }
+  for (int c = 0; c < P->n_contigs; ++c) boff[(size_t)c + 1] = boff[(size_t)c] + (((int64_t)(extent[(size_t)c] >> bshift) + 2) + 31) / 32 + 2;
+  std::vector<uint32_t> bm((size_t)boff.back() + 2, 0u);
+  for (int32_t u : P->h_order) {
+    const UnitDev& U = P->h_units[(size_t)u];
+    uint32_t* b = bm.data() + boff[(size_t)U.contig];
+    auto mark = [&](uint32_t pos) { const int64_t j = (int64_t)(pos >> bshift); b[j >> 5] |= 1u << (j & 31); };
+    for (int32_t i = 0; i < U.n_ws; ++i) { mark(ws[(size_t)U.ws_off + (size_t)i].x); mark(ws[(size_t)U.ws_off + (size_t)i].y); }
+  }
+  HIPCHK(ctx, P->d_bmap.upload(bm, ctx));
+  HIPCHK(ctx, P->d_bmap_off.upload(boff, ctx));
+  P->units_direct_ok = true;
+  return GAT_OK;
+}
+
+// the annotation tables: the desc's shared object, or one of the problem's own made from the desc's lists
+static int attach_annotations(gat_ctx* ctx, const gat_problem_desc* d, gat_problem* P) {
+  if (d->annotations != nullptr) {
+    // the tables exist: made once for the run's annotations, shared by every segment track with these contigs
+    gat_annotations* A = const_cast<gat_annotations*>(d->annotations);
+    if (A->ctx != ctx) return set_err(ctx, GAT_ERR_ARG, "gat_problem_create: the annotations were made on another context");
+    if (A->n_tracks != d->n_tracks || A->n_groups != d->n_contigs || (A->merge_groups != 0) != (d->merge_contigs != 0))
+      return set_err(ctx, GAT_ERR_ARG, "gat_problem_create: annotations of %d tracks x %d contigs (merge %d) for a problem of %d x %d (merge %d)",
+                     A->n_tracks, A->n_groups, A->merge_groups, d->n_tracks, d->n_contigs, d->merge_contigs);
+    A->refs += 1;
+    P->anno = A;
+    return GAT_OK;
+  }
+  gat_annotations_desc ad;
+  memset(&ad, 0, sizeof(ad));
+  ad.n_tracks = d->n_tracks; ad.n_contigs = d->n_contigs; ad.merge_contigs = d->merge_contigs;
+  ad.annos = d->annos; ad.anno_off = d->anno_off; ad.n_anno_lists = d->n_anno_lists; ad.anno_end = d->anno_end;
+  ad.anno_group = d->anno_group;
+  ad.mean_segment_length = mean_segment_length(P);   // (for the merged index's scan estimate)
+  gat_annotations* A = nullptr;
+  int rc = gat_annotations_create(ctx, &ad, &A);
+  if (rc) return rc;
+  A->closed = true;                                // (no handle of its own: it goes with the problem)
+  P->anno = A;
+  return GAT_OK;
+}
+
 extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_problem** out) {
   if (!ctx || !d || !out) return set_err(ctx, GAT_ERR_ARG, "gat_problem_create: NULL argument");
   *out = nullptr;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (d->n_units < 0 || d->n_contigs < 0 || d->n_tracks < 0 || d->nbuckets <= 0)
-    return set_err(ctx, GAT_ERR_ARG, "gat_problem_create: negative size / nbuckets <= 0");
+  int rc = check_problem_desc(ctx, d);
+  if (rc) return rc;
   PrepTimer tm;
   const Knobs kn = read_knobs(ctx);                   // the knobs of this problem's creation
   std::unique_ptr<gat_problem> P(new gat_problem());
@@ -1130,595 +1415,34 @@ extern "C" int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* d, gat_p
   P->n_contigs = d->n_contigs;
   P->n_tracks = d->n_tracks;
   P->merge_contigs = d->merge_contigs ? 1 : 0;
-  if (d->sampler != GAT_SAMPLER_ANNOTATOR && d->sampler != GAT_SAMPLER_SEGMENTS && d->sampler != GAT_SAMPLER_SHIFT &&
-      d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION && d->sampler != GAT_SAMPLER_LOCAL_PERMUTATION &&
-      d->sampler != GAT_SAMPLER_BRUTE_FORCE)
-    return set_err(ctx, GAT_ERR_ARG, "unknown sampler %d", d->sampler);
-  if (d->sampler == GAT_SAMPLER_BRUTE_FORCE) {
-    if (d->brute_ntries_inner < 0 || d->brute_ntries_outer < 0)
-      return set_err(ctx, GAT_ERR_VALUE, "SamplerBruteForce: ntries_inner %d and ntries_outer %d must be >= 0 (0: the reference's 100 / 10)",
-                     (int)d->brute_ntries_inner, (int)d->brute_ntries_outer);
-    if (d->brute_ntries_inner) P->brute_ntries_inner = d->brute_ntries_inner;
-    if (d->brute_ntries_outer) P->brute_ntries_outer = d->brute_ntries_outer;
-  }
-  if (d->sampler == GAT_SAMPLER_SHIFT && !(d->shift_radius >= 0.0 && d->shift_radius <= 1e9))
-    return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: radius %g must be >= 0", d->shift_radius);
-  if (d->sampler == GAT_SAMPLER_SHIFT && d->shift_extension < 0)
-    return set_err(ctx, GAT_ERR_VALUE, "SamplerShift: extension %d must be >= 0", (int)d->shift_extension);
   P->sampler = d->sampler;
-  P->h_units.resize((size_t)d->n_units);
-  P->h_base_cap.assign((size_t)d->n_units, 0);
-  P->h_cws_nseg.assign(d->cws_nseg, d->cws_nseg + d->n_contigs);
+  if (d->sampler == GAT_SAMPLER_BRUTE_FORCE && d->brute_ntries_inner) P->brute_ntries_inner = d->brute_ntries_inner;
+  if (d->sampler == GAT_SAMPLER_BRUTE_FORCE && d->brute_ntries_outer) P->brute_ntries_outer = d->brute_ntries_outer;
 
-  std::vector<uint2> h_ws;
-  std::vector<uint32_t> h_ws_cdf, h_rank_len, h_ws_tree;
-  std::vector<std::pair<int64_t, int32_t>> work;   // (working segments, unit)
-  std::vector<uint4> h_shift;                      // GAT_SAMPLER_SHIFT: the windows (gat_problem::d_shift)
-  std::vector<int32_t> h_shift_off((size_t)std::max(1, d->n_units), 0);
-  // GAT_SAMPLER_GLOBAL_PERMUTATION: gat_problem::d_perm_*
-  std::vector<uint4> h_perm_unit((size_t)std::max(1, d->n_units), make_uint4(0u, 0u, 0u, 0u));
-  std::vector<uint32_t> h_perm_len, h_perm_cum;
-  std::vector<uint2> h_perm_w;
-  // GAT_SAMPLER_LOCAL_PERMUTATION: gat_problem::d_lperm_*
-  std::vector<uint4> h_lperm_unit((size_t)std::max(1, d->n_units), make_uint4(0u, 0u, 0u, 0u));
-  std::vector<uint4> h_lperm_piece;
-  std::vector<uint32_t> h_lperm_len;
-  std::vector<std::vector<int32_t>> per_contig((size_t)d->n_contigs);
-  std::vector<double> len_cv2((size_t)std::max(1, d->n_units), 0.0);
-
+  std::vector<std::vector<int32_t>> per_contig;
+  if ((rc = assign_units_to_contigs(ctx, d, P.get(), per_contig))) return rc;
   // Per unit, on the host threads (192 isochore units x ~50 segments, or 24 contigs x hundreds: the overlaps with the
   // workspace, the rank table -- a sort of the unit's lengths --, the search trees): everything a unit needs by itself into a
-  // record of its own; the offsets into the shared tables are dealt out in unit order behind it.
-  struct UnitPrep {
-    int rc = 0;
-    std::string err;
-    bool active = false;
-    std::vector<uint32_t> rank;          // rank 0 (never drawn) + the bucket indices in ascending order
-    std::vector<uint2> ws;
-    std::vector<uint32_t> cdf, tree_start, tree_cdf;
-    std::vector<uint32_t> pgrid, cgrid;  // the grids of a fragmented workspace, header included (UnitDev::pgrid_off / cgrid_off)
-    std::vector<uint4> shift;            // GAT_SAMPLER_SHIFT: two records per working segment (gat_problem::d_shift)
-    std::vector<uint32_t> lens;          // GAT_SAMPLER_GLOBAL_PERMUTATION: the working lengths, W, its cumulated lengths, free
-    std::vector<uint2> perm_w;
-    std::vector<uint32_t> perm_cum;
-    int64_t perm_free = 0;
-    std::vector<uint4> lperm;            // GAT_SAMPLER_LOCAL_PERMUTATION: the active pieces, the sum and maximum of their n
-    int64_t lperm_sum_n = 0, lperm_max_n = 0;
-    int64_t nwork = 0;
-    double cv2 = 0.0;
-  };
-  std::vector<UnitPrep> prep((size_t)std::max(0, d->n_units));
-  for (int u = 0; u < d->n_units; ++u) {
-    UnitDev& U = P->h_units[u];
-    memset(&U, 0, sizeof(U));
-    const int64_t nus = d->seg_off[u + 1] - d->seg_off[u], nuw = d->ws_off[u + 1] - d->ws_off[u];
-    const int c = d->unit_contig[u];
-    U.contig = c;
-    P->n_seg_total += nus;
-    const bool skipped = (nus == 0 || nuw == 0);     // gat/__init__.py:536-538
-    if (c >= d->n_contigs || (c < 0 && !skipped))
-      return set_err(ctx, GAT_ERR_ARG, "unit %d: contig index %d invalid (skipped units carry -1)", u, c);
-    if (skipped) continue;
-    per_contig[(size_t)c].push_back(u);
-  }
-  auto fail_unit = [&](UnitPrep& R, int code, const char* fmt, auto... args) {
-    char buf[512];
-    snprintf(buf, sizeof(buf), fmt, args...);
-    R.rc = code; R.err = buf;
-  };
+  // record of its own, eight units to a job; the offsets into the shared tables are dealt out in unit order behind it.
+  std::vector<UnitPrep> prep((size_t)d->n_units);
   parallel_for((d->n_units + 7) / 8, [&](int64_t blk) {
-  for (int u = (int)blk * 8; u < std::min<int>(d->n_units, (int)blk * 8 + 8); ++u) {
-    UnitDev& U = P->h_units[u];
-    UnitPrep& R = prep[(size_t)u];
-    const gat_segment* us = d->segs + d->seg_off[u];
-    const int64_t nus = d->seg_off[u + 1] - d->seg_off[u];
-    const gat_segment* uw = d->ws + d->ws_off[u];
-    const int64_t nuw = d->ws_off[u + 1] - d->ws_off[u];
-    if (nus == 0 || nuw == 0) continue;
-    for (int pass = 0; pass < 2 && R.rc == 0; ++pass) {              // gat/Engine.pyx:535-536: both lists normalized
-      const gat_segment* l = pass ? uw : us;
-      const int64_t nl = pass ? nuw : nus;
-      for (int64_t i = 0; i < nl; ++i)
-        if (l[i].start >= l[i].end || l[i].end >= 0x80000000u || (i > 0 && l[i - 1].end > l[i].start)) { R.rc = GAT_ERR_ASSERT; R.err = pass ? "workspace" : "segment"; break; }
-    }
-    if (R.rc) continue;                                              // (the message comes from check_list below, in unit order)
-    const bool local = d->sampler == GAT_SAMPLER_LOCAL_PERMUTATION;
-    if (local) {
-      // the unit is active when some piece has a working segment (the segment in front of a piece counts): not filter()'s rule
-      const int64_t bad = local_permute_tables(R.lperm, R.lperm_sum_n, R.lperm_max_n, us, nus, uw, nuw);
-      if (bad >= 0) {
-        fail_unit(R, GAT_ERR_ASSERT, "unit %d: SamplerLocalPermutation: the working segments of workspace piece %lld [%u, %u) are longer "
-                  "than [0, %u) (free length < 0): the reference's randint raises ValueError", u, (long long)bad, uw[bad].start, uw[bad].end, uw[bad].end);
-        continue;
-      }
-      if (R.lperm.empty()) continue;     // no piece draws: an empty list, no RNG use
-    }
-    // working = segments.filter(workspace); ltotal = working.intersect(workspace).sum()
-    uint32_t ltotal = 0, maxlen = 0;
-    int64_t nwork = 0;
-    std::vector<uint32_t> lens;
-    lens.reserve((size_t)nus);
-    for (int64_t i = 0; i < nus; ++i) {
-      // (SamplerLocalPermutation: the unit's list as it is, no overlap asked)
-      const uint32_t ov = local ? 0u : host_overlap(uw, nuw, us[i].start, us[i].end);
-      if (ov == 0 && !local) continue;
-      ltotal += ov;
-      const uint32_t l = us[i].end - us[i].start;
-      lens.push_back(l);
-      maxlen = std::max(maxlen, l);
-      nwork++;
-    }
-    if (nwork == 0) continue;          // sample() returns an empty list, no RNG use (gat/Engine.pyx:545-546)
-    // getLengthDistribution (gat/SegmentList.pyx:1148-1184)
-    int64_t bucket = d->bucket_size;
-    if (bucket == 0) bucket = (int64_t)std::ceil((double)(int32_t)maxlen / (double)d->nbuckets);
-    // the histogram over the buckets, cumulated, read as "rank r -> bucket": the bucket indices in ascending order (a sort
-    // of the unit's lengths; a std::map insertion per segment was most of this stage: 0.8 of config 2's 1.2 ms)
-    R.rank.reserve(lens.size() + 1);
-    R.rank.push_back(0u);                           // rank 0 is never drawn (r >= 1, gat/Engine.pyx:419-422)
-    for (uint32_t l : lens) {
-      const int64_t i = ((int64_t)l + bucket - 1) / bucket;
-      if (i >= d->nbuckets && d->sampler != GAT_SAMPLER_SHIFT && d->sampler != GAT_SAMPLER_GLOBAL_PERMUTATION && !local) {   // (no length histogram)
-        fail_unit(R, GAT_ERR_VALUE, "unit %d: segment of length %u too large: increase nbuckets (%d) or bucket_size (%lld)",
-                  u, l, d->nbuckets, (long long)bucket);
-        break;
-      }
-      R.rank.push_back((uint32_t)i);
-    }
-    if (R.rc) continue;
-    std::sort(R.rank.begin() + 1, R.rank.end());                    // ranks (cum-count, cum] of a bucket hold it
-    U.hist_total = (uint32_t)lens.size();
-    U.bucket = (uint32_t)bucket;
-    {
-      double m1 = 0, m2 = 0;                               // squared coefficient of variation of the lengths drawn
-      for (uint32_t l : lens) { m1 += (double)l; m2 += (double)l * (double)l; }
-      m1 /= (double)lens.size(); m2 /= (double)lens.size();
-      R.cv2 = m1 > 0 ? std::max(0.0, m2 / (m1 * m1) - 1.0) : 0.0;
-    }
-    // SegmentListSampler(workspace) (gat/Engine.pyx:261-277)
-    U.n_ws = (int32_t)nuw;
-    uint32_t tot = 0;
-    R.ws.reserve((size_t)nuw); R.cdf.reserve((size_t)nuw);
-    for (int64_t i = 0; i < nuw; ++i) {
-      tot += uw[i].end - uw[i].start;
-      R.ws.push_back(make_uint2(uw[i].start, uw[i].end));
-      R.cdf.push_back(tot - 1u);
-    }
-    U.ws_total = tot;
-    // long workspaces: 16-ary search trees (gat_device.h, WsTree) over the starts and over the cumulated lengths
-    U.tree_start_off = -1;
-    U.tree_cdf_off = -1;
-    if (nuw > ((int64_t)1 << (4 * gat::kWsTreeLevels))) {
-      fail_unit(R, GAT_ERR_CAPACITY, "unit %d: %lld workspace segments (> %lld)", u, (long long)nuw, (long long)((int64_t)1 << (4 * gat::kWsTreeLevels)));
-      continue;
-    }
-    // (k_permute_local reads its own tables: no grids, no trees)
-    if (!local && (nuw > gat::kWsTreeMin || (d->merge_contigs && nuw > 2))) {   // (isochore problems: k_units_overlap asks every candidate's unit)
-      // Round 6, fragmented workspaces (the reference's own test data: 6 600 - 21 000 workspace segments per contig).  A tree
-      // search is four dependent 64-byte node reads; the two questions asked of a workspace have cheaper answers:
-      // (a) "how many bases of [s, e) lie inside?" (SegmentList.intersect(workspace).sum(), gat/Engine.pyx:596-598): a grid over
-      //     the POSITIONS, entry c = the first segment whose end lies beyond c << shift -- the segments that can overlap [s, e)
-      //     are walked from entry s >> shift (one or two for segments shorter than the workspace's pieces).  About two cells
-      //     per segment, at most 2^16.
-      {
-        const uint32_t top = uw[nuw - 1].end;                      // (coordinates are below 2^31)
-        int shift = 0;
-        int64_t want = 2 * nuw;
-        if (want > 65536) want = 65536;
-        while (((int64_t)top >> shift) + 1 > want) ++shift;
-        const int64_t cells = ((int64_t)top >> shift) + 1;
-        R.pgrid.assign((size_t)gat::kGridHeader + (size_t)cells + 1, 0u);
-        R.pgrid[0] = (uint32_t)shift; R.pgrid[1] = (uint32_t)cells;
-        int64_t j = 0;
-        uint32_t span = 0, prev = 0;
-        for (int64_t c = 0; c <= cells; ++c) {
-          const uint64_t x = (uint64_t)c << shift;
-          while (j < nuw && (uint64_t)uw[j].end <= x) ++j;
-          R.pgrid[(size_t)gat::kGridHeader + (size_t)c] = (uint32_t)j;
-          if (c > 0) span = std::max(span, (uint32_t)j - prev);
-          prev = (uint32_t)j;
-        }
-        R.pgrid[(size_t)gat::kGridHeader + (size_t)cells] = (uint32_t)nuw;       // (a position beyond the last cell: nothing to walk)
-        R.pgrid[2] = span;
-      }
-    }
-    if (!local && nuw > gat::kWsTreeMin) {
-      auto build = [&](std::vector<uint32_t>& tree, auto key, uint32_t pad) {
-        std::vector<uint32_t> level((size_t)nuw);
-        for (int64_t i = 0; i < nuw; ++i) level[(size_t)i] = key(i);
-        for (;;) {
-          const size_t n = level.size(), nodes = (n + 15) / 16;
-          tree.insert(tree.end(), level.begin(), level.end());
-          tree.insert(tree.end(), nodes * 16 - n, pad);
-          if (n <= 16) break;
-          std::vector<uint32_t> up(nodes);
-          for (size_t j = 0; j < nodes; ++j) up[j] = level[std::min(16 * j + 15, n - 1)];   // largest key of node j
-          level.swap(up);
-        }
-      };
-      build(R.tree_start, [&](int64_t i) { return uw[i].start; }, 0xffffffffu);
-      build(R.tree_cdf, [&](int64_t i) { return R.cdf[(size_t)i]; }, 0x7fffffffu);
-      // (b) "which segment holds base p of the workspace?" (SegmentListSampler.sample, gat/Engine.pyx:299-305: searchsorted over
-      //     cdf[i] = cumulated length - 1 with cmpPosition): a grid over the CUMULATED lengths, g[c] = #{i : cdf[i] < c << shift},
-      //     and 16-bit keys cdf[i] & mask -- within a cell the high bits agree, so #{cdf < p} = g[c] + #{i in [g[c], g[c + 1]) :
-      //     key[i] < (p & mask)}.  2 bytes per segment + 2 per cell: k_place_grid keeps the image in LDS, where the trees (64 bytes
-      //     per node and level, in global memory) were four dependent L2 round trips for EVERY random number of a chunk.  shift
-      //     <= 16 (the keys), at most 65 535 segments (the entries), the widest cell at most 8 segments where the cells allow it.
-      if (nuw > gat::kPlaceWsLds && nuw <= 65535 && tot > 1u && tot <= 0x80000000u) {
-        const uint32_t topc = tot - 1u;                             // the largest p
-        // (one cell per two segments -- GAT_GRID_CELL_SEGS -- to begin with; refdata, k_place_grid with eight tiles: 2.2 ms at
-        //  two, 2.6 at eight: the halving search over a cell's span is LDS round trips on the lane's chain)
-        const int64_t cell_segs = std::max<int64_t>(1, kn.grid_cell_segs);
-        int shift = 16;
-        while (shift > 0 && ((int64_t)topc >> shift) + 1 < nuw / cell_segs) --shift;
-        for (;;) {
-          const int64_t cells = ((int64_t)topc >> shift) + 1;
-          std::vector<uint32_t> g((size_t)cells + 1);
-          int64_t j = 0;
-          uint32_t span = 0;
-          for (int64_t c = 0; c <= cells; ++c) {
-            const uint64_t x = (uint64_t)c << shift;
-            while (j < nuw && (uint64_t)R.cdf[(size_t)j] < x) ++j;
-            g[(size_t)c] = (uint32_t)j;
-            if (c > 0) span = std::max(span, g[(size_t)c] - g[(size_t)c - 1]);
-          }
-          // finer while some cell holds more than 8 segments and the image stays below 96 KB (24 K words)
-          const int64_t cells_next = shift > 0 ? ((int64_t)topc >> (shift - 1)) + 1 : cells;
-          const int64_t words_next = (cells_next + 2) / 2 + (nuw + 1) / 2;
-          if (span > 8 && shift > 0 && words_next <= 24576) { --shift; continue; }
-          const size_t gw = ((size_t)cells + 2) / 2, kw = ((size_t)nuw + 1) / 2;
-          R.cgrid.assign((size_t)gat::kGridHeader + gw + kw, 0u);
-          R.cgrid[0] = (uint32_t)shift; R.cgrid[1] = (uint32_t)cells; R.cgrid[2] = span; R.cgrid[3] = (uint32_t)(gw + kw);
-          uint16_t* g16 = reinterpret_cast<uint16_t*>(R.cgrid.data() + gat::kGridHeader);
-          for (int64_t c = 0; c <= cells; ++c) g16[c] = (uint16_t)g[(size_t)c];
-          uint16_t* k16 = reinterpret_cast<uint16_t*>(R.cgrid.data() + gat::kGridHeader + gw);
-          const uint32_t mask = shift >= 32 ? 0xffffffffu : ((1u << shift) - 1u);
-          for (int64_t i = 0; i < nuw; ++i) k16[i] = (uint16_t)(R.cdf[(size_t)i] & mask);
-          break;
-        }
-      }
-    }
-    U.ltotal = (int32_t)ltotal;
-    if (d->sampler == GAT_SAMPLER_BRUTE_FORCE) {
-      // remaining = segments.sum() (gat/Engine.pyx:830): ALL of the unit's segments, neither filtered nor intersected, the
-      // uint32 sum (gat/SegmentList.pyx:1607) assigned to an int32
-      uint32_t all = 0;
-      for (int64_t i = 0; i < nus; ++i) all += us[i].end - us[i].start;
-      U.ltotal = (int32_t)all;
-    }
-    U.n_target = (int32_t)nus;                       // SamplerSegments places len(segments) segments
-    if (d->sampler == GAT_SAMPLER_SHIFT) shift_windows(R.shift, us, nus, uw, nuw, R.cdf, d->shift_radius, d->shift_extension);
-    if (d->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
-      R.perm_free = permute_tables(R.perm_w, R.perm_cum, us, nus, uw, nuw);
-      if (R.perm_free < 0) {
-        fail_unit(R, GAT_ERR_VALUE, "unit %d: SamplerGlobalPermutation: the working segments overlap (free length %lld < 0)",
-                  u, (long long)R.perm_free);
-        continue;
-      }
-      R.lens = lens;
-    }
-    R.nwork = local ? R.lperm_sum_n : nwork;       // (the launch order: the longest draw chain first)
-    if (local) R.lens = lens;
-    R.active = true;
-  }
+    for (int u = (int)blk * 8; u < std::min<int>(d->n_units, (int)blk * 8 + 8); ++u) prepare_unit(*d, kn, u, P->h_units[u], prep[(size_t)u]);
   });
-  for (int u = 0; u < d->n_units; ++u) {
-    UnitPrep& R = prep[(size_t)u];
-    UnitDev& U = P->h_units[u];
-    if (R.rc == GAT_ERR_ASSERT) {                    // (the first offender in unit order, with the reference's message)
-      int rc;
-      if ((rc = check_list(ctx, d->segs + d->seg_off[u], d->seg_off[u + 1] - d->seg_off[u], "segment", u))) return rc;     // gat/Engine.pyx:535
-      if ((rc = check_list(ctx, d->ws + d->ws_off[u], d->ws_off[u + 1] - d->ws_off[u], "workspace", u))) return rc;       // gat/Engine.pyx:536
-    }
-    if (R.rc) return set_err(ctx, R.rc, "%s", R.err.c_str());
-    if (!R.active) continue;
-    U.rank_off = (int32_t)h_rank_len.size();
-    h_rank_len.insert(h_rank_len.end(), R.rank.begin(), R.rank.end());
-    U.ws_off = (int32_t)h_ws.size();
-    h_ws.insert(h_ws.end(), R.ws.begin(), R.ws.end());
-    h_ws_cdf.insert(h_ws_cdf.end(), R.cdf.begin(), R.cdf.end());
-    if (!R.tree_start.empty()) {
-      U.tree_start_off = (int32_t)h_ws_tree.size();
-      h_ws_tree.insert(h_ws_tree.end(), R.tree_start.begin(), R.tree_start.end());
-      U.tree_cdf_off = (int32_t)h_ws_tree.size();
-      h_ws_tree.insert(h_ws_tree.end(), R.tree_cdf.begin(), R.tree_cdf.end());
-    }
-    U.pgrid_off = -1;
-    U.cgrid_off = -1;
-    auto append16 = [&](const std::vector<uint32_t>& v) {          // (16-byte aligned: the images are copied in 16-byte pieces)
-      while (h_ws_tree.size() & 3u) h_ws_tree.push_back(0u);
-      const int32_t off = (int32_t)h_ws_tree.size();
-      h_ws_tree.insert(h_ws_tree.end(), v.begin(), v.end());
-      return off;
-    };
-    if (!R.pgrid.empty()) U.pgrid_off = append16(R.pgrid);
-    if (!R.cgrid.empty()) U.cgrid_off = append16(R.cgrid);
-    len_cv2[(size_t)u] = R.cv2;
-    // (SamplerShift: a segment gives one piece, two where it wraps round its window -- more only in fragmented windows, which
-    //  the overflow path takes)
-    P->h_base_cap[u] = cap_for(kn, d->sampler == GAT_SAMPLER_SEGMENTS ? std::max<int64_t>(R.nwork, d->seg_off[u + 1] - d->seg_off[u])
-                                  : d->sampler == GAT_SAMPLER_SHIFT ? 2 * R.nwork : R.nwork);
-    if (d->sampler == GAT_SAMPLER_BRUTE_FORCE) {
-      // (every accepted segment covers a base of the workspace, so `remaining` bounds the list; expected are about as many
-      //  segments as the unit has -- more where some of them lie outside the workspace, whose bases are sampled too: twice
-      //  the unit's segments to begin with, the overflow path beyond)
-      const int64_t nall = d->seg_off[u + 1] - d->seg_off[u];
-      P->h_base_cap[u] = cap_for(kn, std::min<int64_t>(std::max<int32_t>(U.ltotal, 0), 2 * nall));
-    }
-    if (d->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
-      // (exact: the lengths and the sorted points at the top of the region when the unit is too long for LDS, the pieces --
-      //  at most n + |W| -- below them)
-      P->h_base_cap[u] = (int32_t)(2 * R.nwork + (int64_t)R.perm_w.size());
-      h_perm_unit[(size_t)u] = make_uint4((uint32_t)h_perm_len.size(), (uint32_t)h_perm_w.size(), (uint32_t)R.perm_w.size(),
-                                          (uint32_t)R.perm_free);
-      h_perm_len.insert(h_perm_len.end(), R.lens.begin(), R.lens.end());
-      h_perm_w.insert(h_perm_w.end(), R.perm_w.begin(), R.perm_w.end());
-      h_perm_cum.insert(h_perm_cum.end(), R.perm_cum.begin(), R.perm_cum.end());
-    }
-    if (d->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) {
-      // (exact: two slots per working segment of every piece -- a segment gives one piece, two where it wraps; a piece of
-      //  more working segments than LDS holds keeps its lengths and points at the top of the region)
-      const int64_t cap = 2 * R.lperm_sum_n + (R.lperm_max_n > 2048 ? 2 * R.lperm_max_n : 0);
-      if (cap > INT32_MAX / 2) return set_err(ctx, GAT_ERR_CAPACITY, "unit %d: SamplerLocalPermutation: %lld working segments over its pieces", u, (long long)R.lperm_sum_n);
-      P->h_base_cap[u] = (int32_t)cap;
-      h_lperm_unit[(size_t)u] = make_uint4((uint32_t)h_lperm_piece.size(), (uint32_t)R.lperm.size(), (uint32_t)h_lperm_len.size(),
-                                           (uint32_t)R.lperm_sum_n);
-      h_lperm_piece.insert(h_lperm_piece.end(), R.lperm.begin(), R.lperm.end());
-      h_lperm_len.insert(h_lperm_len.end(), R.lens.begin(), R.lens.end());
-      P->lperm_max_n = std::max<int32_t>(P->lperm_max_n, (int32_t)R.lperm_max_n);
-      P->lperm_max_out = std::max<int64_t>(P->lperm_max_out, 2 * R.lperm_sum_n);
-    }
-    if (d->sampler == GAT_SAMPLER_SHIFT) {
-      h_shift_off[(size_t)u] = (int32_t)(h_shift.size() / 2);
-      h_shift.insert(h_shift.end(), R.shift.begin(), R.shift.end());
-    }
-    work.push_back(std::make_pair(R.nwork, (int32_t)u));
-  }
-  // contig -> units (reference order)
-  P->h_contig_unit_off.assign((size_t)d->n_contigs + 1, 0);
-  for (int c = 0; c < d->n_contigs; ++c) {
-    if (per_contig[(size_t)c].empty())
-      return set_err(ctx, GAT_ERR_ARG, "contig %d has no unit: contigs must be those of the non-skipped units", c);
-    if (!P->merge_contigs && per_contig[(size_t)c].size() != 1)
-      return set_err(ctx, GAT_ERR_ARG, "contig %d has %zu units but keys carry no isochore (merge_contigs=0)", c, per_contig[(size_t)c].size());
-    for (int32_t u : per_contig[(size_t)c]) P->h_contig_units.push_back(u);
-    P->h_contig_unit_off[(size_t)c + 1] = (int32_t)P->h_contig_units.size();
-  }
-  std::sort(work.begin(), work.end(), [](const std::pair<int64_t, int32_t>& a, const std::pair<int64_t, int32_t>& b) {
-    return a.first != b.first ? a.first > b.first : a.second < b.second;
-  });
-  for (auto& w : work) P->h_order.push_back(w.second);
-  P->all_simple = !P->h_order.empty();
-  uint32_t max_hist = 0;
-  uint64_t work_simple = 0, work_all = 0, work_big_rank = 0;
-  P->all_one_ws = !P->h_order.empty();
-  P->all_cm_ok = true;
-  for (int32_t u : P->h_order) {
-    const UnitDev& U = P->h_units[(size_t)u];
-    const bool degenerate = !(U.hist_total > 2 && U.ws_total > 1);          // k_place leaves those to k_sampler
-    const bool simple = U.n_ws == 1 && U.bucket <= 1 && U.hist_total < (uint32_t)gat::kPlaceRankLds && U.ws_total > 1;
-    if (!degenerate && !simple) P->all_simple = false;
-    if (!degenerate && simple) {
-      // k_place's cm_ok: the offset draw's mask (of the range workspace length - 2 + length) is the position draw's (of the range
-      // workspace length - 1) for every length the unit can draw -- no power of two between them (k_place_scan runs only such units)
-      const uint2 w0v = h_ws[(size_t)U.ws_off];
-      const gat_segment w0 = {w0v.x, w0v.y};
-      const uint32_t range_p = U.ws_total - 1u, mask_p = 0xffffffffu >> __builtin_clz(range_p);
-      const uint32_t lmax = h_rank_len[(size_t)U.rank_off + U.hist_total - 1u];     // (rank_len[1 + rangeL], rangeL = hist_total - 2)
-      if ((uint64_t)(w0.end - w0.start - 2u) + (uint64_t)lmax > (uint64_t)mask_p) P->all_cm_ok = false;
-    }
-    if (!degenerate) { work_all += U.hist_total; if (simple) work_simple += U.hist_total; }
-    if (!degenerate && !(U.n_ws == 1 && U.bucket <= 1)) P->all_one_ws = false;
-    if (!degenerate && U.hist_total >= (uint32_t)gat::kPlaceRankLds) work_big_rank += U.hist_total;
-    P->max_nws = std::max(P->max_nws, U.n_ws);
-    max_hist = std::max(max_hist, U.hist_total);
-  }
-  P->small_tables = !P->h_order.empty() && P->max_nws <= 64 && max_hist < 256;
-  {
-    // k_place_grid (MODE 4): some workspace is beyond k_place's LDS table and every such unit has the grid over its cumulated
-    // lengths (UnitDev::cgrid_off), the largest image within the LDS the rings leave
-    bool any = false, all = true;
-    int32_t words = 0;
-    for (int32_t u : P->h_order) {
-      const UnitDev& U = P->h_units[(size_t)u];
-      if (U.n_ws <= gat::kPlaceWsLds) continue;
-      any = true;
-      if (U.cgrid_off < 0) { all = false; break; }
-      words = std::max(words, (int32_t)h_ws_tree[(size_t)U.cgrid_off + 3]);
-    }
-    P->grid_place = any && all && !kn.place_no_grid;
-    P->grid_lds_words = words;
-  }
-  P->pipe_pays = 2 * work_simple >= work_all;
-  P->all_one_ws = P->all_one_ws && !P->all_simple && 2 * work_big_rank >= work_all && max_hist <= (uint32_t)gat::kPlaceWideMaxRank;
-  P->long_lists = max_hist + max_hist / 8 > 1024;
-  P->max_hist = max_hist;
-  {
-    // the split path pays when k_tail can take most units: SamplerAnnotator, lists the wave bucket sorts hold, workspaces
-    // of up to kTailMaxWs segments
-    size_t small_ws = 0;
-    // (round 6: k_tail takes the longer workspaces too -- their position draw through the tree over the cumulated lengths, their
-    //  overlaps through the position grid; GAT_TAIL_NO_LONG_WS: as before, such units are k_sampler's)
-    P->tail_long_ws = !kn.tail_no_long_ws;
-    for (int32_t u : P->h_order) if (P->h_units[(size_t)u].n_ws <= gat::kTailMaxWs || P->tail_long_ws) ++small_ws;
-    // (long lists: their tail places dozens of segments, not the handful k_tail keeps aside -- 0.2 % finished there on the
-    //  config-4 shape -- so those problems stay with k_merge_big + k_sampler)
-    P->split_path = P->sampler == GAT_SAMPLER_ANNOTATOR && !P->h_order.empty() && 2 * small_ws >= P->h_order.size() &&
-                    max_hist + max_hist / 8 <= 1024 && !kn.no_split;
-  }
-  // expected raw MT19937 outputs per placement under masked rejection (mask+1)/(range+1) per draw;
-  // rows = that x working segments + slack, in whole 624-word blocks.  Streams that still run out
-  // are redone by k_sampler from their seed.
-  {
-    if (kn.sampler_mode == "wave") P->sampler_mode = 0;
-    if (P->sampler == GAT_SAMPLER_SHIFT) P->sampler_mode = 0;       // (k_shift: a wave per work unit, its stream in LDS)
-    if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) P->sampler_mode = 0;    // (k_permute: the same)
-    if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) P->sampler_mode = 0;     // (k_permute_local: the same)
-    if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) P->sampler_mode = 0;           // (k_brute_force: the same)
-    auto expect = [](uint64_t range) {
-      if (range == 0) return 0.0;
-      uint64_t m = range; m |= m >> 1; m |= m >> 2; m |= m >> 4; m |= m >> 8; m |= m >> 16; m |= m >> 32;
-      return (double)(m + 1) / (double)(range + 1);
-    };
-    for (int32_t u : P->h_order) {
-      const UnitDev& U = P->h_units[u];
-      // offset draw: range = chosen workspace segment + sampled length - 2, weighted by how often a segment
-      // is chosen (its share of the workspace) and taken at the mean working-segment length
-      const gat_segment* uw = d->ws + d->ws_off[u];
-      const int64_t nuw = d->ws_off[u + 1] - d->ws_off[u];
-      const double mean_len = U.hist_total ? (double)(uint32_t)U.ltotal / (double)U.hist_total : 1.0;
-      double e = 0.0, v = 0.0;
-      for (int64_t k = 0; k < nuw; ++k) {
-        const double wl = (double)(uw[k].end - uw[k].start);
-        const double p = expect((uint64_t)(wl + mean_len)) ;
-        e += wl / (double)U.ws_total * p;
-      }
-      auto addvar = [&](double ex) { if (ex > 0) v += (ex - 1.0) * ex; };   // geometric: var = (1-p)/p^2 = ex(ex-1)
-      addvar(e);
-      if (U.hist_total > 2) { const double x = expect((uint64_t)U.hist_total - 2); e += x; addvar(x); }
-      if (U.bucket > 1) { const double x = expect((uint64_t)U.bucket - 1); e += x; addvar(x); }
-      if (U.ws_total > 1) { const double x = expect((uint64_t)U.ws_total - 1); e += x; addvar(x); }
-      const double slack = kn.rng_slack;
-      // Spread of the raw-output count of a stream: the NUMBER of placements until the unit's bases are reproduced varies
-      // by cv(length) x sqrt(n) (a renewal count) and every placement costs e outputs -- that term dominates (measured on
-      // config 2: 97 / 116 / 58 outputs for units of 778 / 444 / 166 segments = e x cv x sqrt(n)) -- plus the rejection
-      // noise v per placement.  5 to 7.5 sigma and the tail's few dozen outputs: a stream that runs out is redone from its seed
-      // by ONE wave, placement by placement, and such a straggler (0.5 ms) is now longer than the rest of the sampler.
-      const double nplace = P->sampler == GAT_SAMPLER_SEGMENTS ? (double)U.n_target : (double)U.hist_total;
-      const double var_n = P->sampler == GAT_SAMPLER_SEGMENTS ? 0.0 : len_cv2[(size_t)u] * e * e;
-      // The multiple follows what running out costs.  A unit of the split path (lists the wave sorts hold) that runs out of
-      // rows is RESUMED by k_sampler where its lane stopped -- behind k_place's last placement, or at the consolidation k_tail
-      // would have continued from -- with the stream moved up to its position by the in-LDS generator (rng_switch: the
-      // seeding chain + a twist per 624 outputs, ~10 us): 3.5 sigma and 32 rows for the tail (one stream in two thousand runs
-      // out; round 3's 5-7.5 sigma + 96, sized for a redo of every placement from the seed at 0.5 ms, generated 1.4x the rows
-      // that were consumed: k_rng 0.48 -> 0.43 ms on config 2, 1.07 -> 0.92 on config 3).  A long list that runs out behind
-      // k_tail_big's in-place unions is still redone from its seed -- milliseconds for thousands of placements: 7.5 sigma + 96.
-      const double s_min = kn.rng_sigma_min, s_max = kn.rng_sigma_max;
-      const bool long_list = U.hist_total + U.hist_total / 8 > 1024 || P->sampler == GAT_SAMPLER_SEGMENTS;
-      // (a resumed unit goes through k_sampler's wave-per-unit consolidation and tail: tens of microseconds for hundreds of
-      //  segments, a few for fifty -- up to five sigma for the larger units of the split path: config 2, k_rng + k_sampler
-      //  0.55 -> 0.51 ms, where 3.5 sigma throughout gave back in k_sampler what it saved in k_rng)
-      const double sigmas = long_list ? s_max : std::min(std::max(s_min, 5.0), std::max(s_min, s_min - 0.5 + nplace / 130.0));
-      const double tail_rows = kn.rng_tail_rows_set ? kn.rng_tail_rows : (long_list ? 96.0 : (nplace < 128 ? 32.0 : 48.0));
-      const double need = e * nplace * slack + sigmas * std::sqrt(nplace * (v + 0.5 + var_n)) + tail_rows;
-      int64_t rows = ((int64_t)std::ceil(need / 16.0)) * 16;        // whole k_place chunks (8) and k_rng read groups (16)
-      rows = std::min<int64_t>(rows, (int64_t)gat::kMtN * 2048);
-      P->h_rng_rows.push_back((int32_t)rows);
-      P->rng_rows_total += rows;
-    }
-  }
+  UnitTables T((size_t)std::max(1, d->n_units));
+  if ((rc = gather_unit_tables(ctx, d, kn, P.get(), prep, T))) return rc;
+  if ((rc = link_contigs(ctx, P.get(), per_contig))) return rc;
+  order_and_classify(P.get(), kn, T);
+  size_rng_rows(P.get(), d, kn, T);
   P->h_contig_slab_off.assign((size_t)d->n_contigs, 0);
   P->h_count_c_off.assign((size_t)d->n_contigs, 0);
   P->h_count_n_index.assign((size_t)d->n_contigs, 0);
   if (layout_slab(P.get(), kn)) return set_err(ctx, GAT_ERR_CAPACITY, "per-sample slab exceeds 2^31 segments");
 
-  HIPCHK(ctx, P->d_order.upload(P->h_order, ctx));
-  {
-    std::vector<int32_t> pos((size_t)std::max(1, d->n_units), -1);
-    for (size_t a = 0; a < P->h_order.size(); ++a) pos[(size_t)P->h_order[a]] = (int32_t)a;
-    HIPCHK(ctx, P->d_unit_pos.upload(pos, ctx));
-    P->h_unit_pos = pos;
-  }
-  HIPCHK(ctx, P->d_rng_rows.upload(P->h_rng_rows, ctx));
-  HIPCHK(ctx, P->d_contig_unit_off.upload(P->h_contig_unit_off, ctx));
-  HIPCHK(ctx, P->d_contig_units.upload(P->h_contig_units, ctx));
-  HIPCHK(ctx, P->d_ws.upload(h_ws, ctx));
-  HIPCHK(ctx, P->d_ws_cdf.upload(h_ws_cdf, ctx));
-  if (P->sampler == GAT_SAMPLER_SHIFT) {
-    if (h_shift.empty()) h_shift.push_back(make_uint4(0u, 0u, 0u, 0u));
-    HIPCHK(ctx, P->d_shift.upload(h_shift, ctx));
-    HIPCHK(ctx, P->d_shift_off.upload(h_shift_off, ctx));
-  }
-  if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) {
-    if (h_perm_len.empty()) h_perm_len.push_back(0u);
-    if (h_perm_w.empty()) { h_perm_w.push_back(make_uint2(0u, 0u)); h_perm_cum.push_back(0u); }
-    HIPCHK(ctx, P->d_perm_unit.upload(h_perm_unit, ctx));
-    HIPCHK(ctx, P->d_perm_len.upload(h_perm_len, ctx));
-    HIPCHK(ctx, P->d_perm_w.upload(h_perm_w, ctx));
-    HIPCHK(ctx, P->d_perm_cum.upload(h_perm_cum, ctx));
-  }
-  if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) {
-    if (h_lperm_piece.empty()) h_lperm_piece.push_back(make_uint4(0u, 0u, 0u, 0u));
-    if (h_lperm_len.empty()) h_lperm_len.push_back(0u);
-    HIPCHK(ctx, P->d_lperm_unit.upload(h_lperm_unit, ctx));
-    HIPCHK(ctx, P->d_lperm_piece.upload(h_lperm_piece, ctx));
-    HIPCHK(ctx, P->d_lperm_len.upload(h_lperm_len, ctx));
-  }
-  {
-    // what a position draw needs of its workspace segment (gat/Engine.pyx:318-325) as one record
-    std::vector<uint4> rec(std::max<size_t>(1, h_ws.size()));
-    for (int32_t u : P->h_order) {
-      const UnitDev& U = P->h_units[(size_t)u];
-      for (int32_t i = 0; i < U.n_ws; ++i) {
-        const size_t k = (size_t)U.ws_off + (size_t)i;
-        rec[k] = make_uint4(h_ws[k].x, h_ws[k].y, i > 0 ? h_ws[k - 1].y : 0x80000000u, h_ws_cdf[k]);
-      }
-    }
-    HIPCHK(ctx, P->d_ws_rec.upload(rec, ctx));
-  }
-  P->units_direct_ok = false;
-  if (P->merge_contigs && P->n_contigs > 0 && P->split_path && !kn.count_via_contigs) {
-    // counting an isochore problem from the units' lists: where a segment could reach over the end of its workspace piece.
-    // One bit per cell of 2^bshift bases (about two mean segment lengths): a boundary of some unit's workspace piece lies in the
-    // cell -- a segment whose cells hold no boundary lies inside one piece (k_count_merged<2, .> tests the bits from its first
-    // base's cell to its last's: a 64-bit window of the map)
-    double bases = 0, segs = 0;
-    for (int32_t u : P->h_order) { bases += (double)(uint32_t)P->h_units[(size_t)u].ltotal; segs += (double)P->h_units[(size_t)u].hist_total; }
-    const double mean_len = segs > 0 ? bases / segs : 1.0;
-    int bshift = 8;
-    while (bshift < 24 && (double)(1u << bshift) < 2.0 * mean_len) ++bshift;
-    P->bshift = bshift;
-    std::vector<int64_t> boff((size_t)P->n_contigs + 1, 0);
-    std::vector<uint32_t> extent((size_t)P->n_contigs, 0u);
-    for (int32_t u : P->h_order) {
-      const UnitDev& U = P->h_units[(size_t)u];
-      extent[(size_t)U.contig] = std::max(extent[(size_t)U.contig], h_ws[(size_t)U.ws_off + (size_t)U.n_ws - 1].y);
-    }
-    for (int c = 0; c < P->n_contigs; ++c) boff[(size_t)c + 1] = boff[(size_t)c] + (((int64_t)(extent[(size_t)c] >> bshift) + 2) + 31) / 32 + 2;
-    std::vector<uint32_t> bm((size_t)boff.back() + 2, 0u);
-    for (int32_t u : P->h_order) {
-      const UnitDev& U = P->h_units[(size_t)u];
-      uint32_t* b = bm.data() + boff[(size_t)U.contig];
-      auto mark = [&](uint32_t pos) { const int64_t j = (int64_t)(pos >> bshift); b[j >> 5] |= 1u << (j & 31); };
-      for (int32_t i = 0; i < U.n_ws; ++i) { mark(h_ws[(size_t)U.ws_off + (size_t)i].x); mark(h_ws[(size_t)U.ws_off + (size_t)i].y); }
-    }
-    HIPCHK(ctx, P->d_bmap.upload(bm, ctx));
-    HIPCHK(ctx, P->d_bmap_off.upload(boff, ctx));
-    P->units_direct_ok = true;
-  }
-  if (h_ws_tree.empty()) h_ws_tree.assign(16, 0u);
-  HIPCHK(ctx, P->d_ws_tree.upload(h_ws_tree, ctx));
-  HIPCHK(ctx, P->d_rank_len.upload(h_rank_len, ctx));
-  HIPCHK(ctx, P->d_cws_nseg.upload(P->h_cws_nseg, ctx));
-  int rc = upload_layout(ctx, P.get(), kn);
-  if (rc) return rc;
+  if ((rc = upload_unit_tables(ctx, P.get(), T))) return rc;
+  if ((rc = build_boundary_map(ctx, P.get(), kn, T.ws))) return rc;
+  if ((rc = upload_layout(ctx, P.get(), kn))) return rc;
   tm.lap("units, layout, their uploads");
-  double mean_seg_len = 0.0;                         // of the segments that are placed (for the merged index's scan estimate)
-  {
-    double bases = 0, segs = 0;
-    for (int32_t u : P->h_order) { bases += (double)(uint32_t)P->h_units[(size_t)u].ltotal; segs += (double)P->h_units[(size_t)u].hist_total; }
-    mean_seg_len = segs > 0 ? bases / segs : 0.0;
-  }
-  if (d->annotations != nullptr) {
-    // the tables exist: made once for the run's annotations, shared by every segment track with these contigs
-    gat_annotations* A = const_cast<gat_annotations*>(d->annotations);
-    if (A->ctx != ctx) return set_err(ctx, GAT_ERR_ARG, "gat_problem_create: the annotations were made on another context");
-    if (A->n_tracks != d->n_tracks || A->n_groups != d->n_contigs || (A->merge_groups != 0) != (d->merge_contigs != 0))
-      return set_err(ctx, GAT_ERR_ARG, "gat_problem_create: annotations of %d tracks x %d contigs (merge %d) for a problem of %d x %d (merge %d)",
-                     A->n_tracks, A->n_groups, A->merge_groups, d->n_tracks, d->n_contigs, d->merge_contigs);
-    A->refs += 1;
-    P->anno = A;
-  } else {
-    gat_annotations_desc ad;
-    memset(&ad, 0, sizeof(ad));
-    ad.n_tracks = d->n_tracks; ad.n_contigs = d->n_contigs; ad.merge_contigs = d->merge_contigs;
-    ad.annos = d->annos; ad.anno_off = d->anno_off; ad.n_anno_lists = d->n_anno_lists; ad.anno_end = d->anno_end;
-    ad.anno_group = d->anno_group; ad.mean_segment_length = mean_seg_len;
-    gat_annotations* A = nullptr;
-    if ((rc = gat_annotations_create(ctx, &ad, &A))) return rc;
-    A->closed = true;                                // (no handle of its own: it goes with the problem)
-    P->anno = A;
-  }
+  if ((rc = attach_annotations(ctx, d, P.get()))) return rc;
   tm.lap("annotation tables (total)");
   HIPCHK(ctx, P->d_stat.alloc(gat::kStatSlotWords));
   HIPCHK(ctx, stage_flush(ctx));                    // the small tables' copies (one wait for all of them)

@@ -3,7 +3,7 @@
 // Per work unit the stream is the per-unit one of every sampler here (numpy.random.seed((seed + sample*n_units + unit)
 // mod 2^32)), run by the wave's in-LDS MT19937 (WaveRng).  The unit's working segments are walked in order;
 // each one's window -- the workspace pieces within `area` of its midpoint, truncated -- was laid down at problem creation
-// (gat_prep.hip: shift_windows) as a run [lo, lo + k) of the unit's workspace with its first start and last end clipped,
+// (gat_prep_units.h: shift_windows) as a run [lo, lo + k) of the unit's workspace with its first start and last end clipped,
 // so the position draw is a search of the workspace cdf restricted to the run and the fills walk the run.  The pieces go
 // to the unit's slab region as they come; the list is then sorted and merged with SegmentList.normalize's rule (overlaps
 // united, adjacent pieces kept apart: gat/SegmentList.pyx:697-750) -- in LDS when it fits, in the slab otherwise.

@@ -6,7 +6,7 @@ The model is tests/brute_force_model.py, pinned to the reference by its known an
 branches a (sample, unit) took.  tests/test_brute_force_edges.py checks on the model that the generators reach what they
 claim and that everything converges; tests/test_sampler_brute_force_edges_gpu.py runs the same cases on the device.
 
-What the launch allows (gat_prep.hip: cap_for, layout_slab; gat_mi355.hip: enqueue_brute_force): a unit's slab region
+What the launch allows (gat_prep_units.h: cap_for, base_cap_for; gat_prep.hip: layout_slab; gat_mi355.hip: enqueue_brute_force): a unit's slab region
 holds cap = cap_for(min(segments.sum(), 2 * len(segments))) entries, doubled by every overflow retry, and the LDS list
 lds_cap = max(64, min(largest cap, 256)).  So lds_cap < 256 means that NO unit's region is larger than lds_cap: a list
 can reach lds_cap exactly (n == cap) there, and the acceptance behind it is an overflow, repeated with doubled regions
