@@ -33,7 +33,7 @@ SYMBOLS = [
     "gat_sample_and_count_serial", "gat_mt19937_seed", "gat_sample_and_count_enqueue", "gat_wait",
     "gat_annotations_create", "gat_annotations_destroy", "gat_annotations_wait", "gat_list_sums", "gat_problem_rng_rows",
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
-    "gat_call_lane_for",
+    "gat_call_lane_for", "gat_sample_coverage",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -203,6 +203,8 @@ def lib():
     L.gat_sample.argtypes = [vp, vp, u32, i64, i64, vp, i64, vp, C.POINTER(Stats)]
     L.gat_sample_units.restype = C.c_int
     L.gat_sample_units.argtypes = [vp, vp, u32, i64, i64, vp, i64, vp, C.POINTER(Stats)]
+    L.gat_sample_coverage.restype = C.c_int
+    L.gat_sample_coverage.argtypes = [vp, vp, u32, i64, i64, i64, vp, vp, vp, vp, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -704,3 +706,23 @@ class Problem(object):
             _check(rc, self.ctx._h)
             break
         return out[: off[-1]].copy(), off
+
+    def sample_coverage(self, seed, sample_begin, sample_end, bin_size, n_bins, want_starts_ends=True):
+        """per-bin coverage of the sampled contig-level lists, summed over the samples (gat_sample_coverage): n_bins[c] bins
+        of bin_size bases for contig c.  Returns (bases, starts, ends, outside, bin_off): int64 arrays, contig c's bins at
+        [bin_off[c], bin_off[c + 1]); starts and ends are None unless wanted; outside[c]: sampled bases beyond the last bin."""
+        n_bins = np.ascontiguousarray(n_bins, dtype=np.int64)
+        assert n_bins.shape == (self.n_contigs,)
+        bin_off = np.zeros(self.n_contigs + 1, dtype=np.int64)
+        np.cumsum(n_bins, out=bin_off[1:])
+        total = max(0, int(bin_off[-1]))
+        bases = np.zeros(total, dtype=np.int64)
+        starts = np.zeros(total, dtype=np.int64) if want_starts_ends else None
+        ends = np.zeros(total, dtype=np.int64) if want_starts_ends else None
+        outside = np.zeros(self.n_contigs, dtype=np.int64)
+        st = Stats()
+        rc = lib().gat_sample_coverage(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
+                                       int(bin_size), _p(bin_off), _p(bases), _p(starts), _p(ends), _p(outside), C.byref(st))
+        self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
+        return bases, starts, ends, outside, bin_off

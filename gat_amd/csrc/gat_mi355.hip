@@ -34,6 +34,7 @@
 #include "gat_brute_force.h"
 #include "gat_stats.h"
 #include "gat_compare.h"
+#include "gat_coverage.h"
 
 
 #include "gat_host.h"
@@ -1683,6 +1684,118 @@ extern "C" int gat_sample(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t s
 extern "C" int gat_sample_units(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
                                 gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats) {
   return sample_lists(ctx, P, seed, sample_begin, sample_end, out_host, cap, off_host, stats, true);
+}
+
+// gat_sample_coverage: sample_lists' batch loop with k_coverage (gat_coverage.h) behind every batch that passed its checks,
+// where sample_lists copies the lists out.  The device result lives for the call (it goes back to the process-wide pool when
+// it is destroyed: sample_coverage drains the stream before that, on every path out).
+struct CoverageBufs {
+  DevBuf<gat::CoverageWindow> d_win;
+  DevBuf<unsigned long long> d_bases, d_starts, d_ends, d_outside;
+};
+static int sample_coverage_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                                int64_t bin_size, const int64_t* bin_off, int64_t* bases_host, int64_t* starts_host,
+                                int64_t* ends_host, int64_t* outside_host, gat_stats& local, CoverageBufs& B) {
+  const int C = P->n_contigs;
+  const int64_t total = bin_off[C];
+  const bool want_se = starts_host != nullptr || ends_host != nullptr;
+  // the windows: W bins each, then the contig's tail.  Coordinates are below 2^32: bins beyond that stay 0 and get no window
+  const int64_t W = std::max<int64_t>(1, std::min<int64_t>(kn.coverage_window_bins, ((int64_t)ctx->max_lds - 1024) / gat::kCoverageBinBytes));
+  const int64_t reach = (((int64_t)1 << 32) + bin_size - 1) / bin_size;
+  std::vector<gat::CoverageWindow> win;
+  for (int c = 0; c < C; ++c) {
+    const int64_t n_bins = bin_off[c + 1] - bin_off[c], eff = std::min(n_bins, reach);
+    for (int64_t b = 0; b < eff; b += W) win.push_back({b * bin_size, bin_off[c] + b, c, (int32_t)std::min(W, eff - b)});
+    win.push_back({n_bins < reach ? n_bins * bin_size : (int64_t)1 << 32, 0, c, 0});
+    if (win.size() >= (size_t)INT32_MAX) return set_err(ctx, GAT_ERR_CAPACITY, "gat_sample_coverage: more than 2^31 windows of %lld bins", (long long)W);
+  }
+  HIPCHK(ctx, B.d_win.upload(win, ctx));
+  HIPCHK(ctx, B.d_bases.alloc((size_t)total));
+  HIPCHK(ctx, B.d_outside.alloc((size_t)C));
+  HIPCHK(ctx, hipMemsetAsync(B.d_bases.p, 0, B.d_bases.bytes, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(B.d_outside.p, 0, B.d_outside.bytes, ctx->stream));
+  if (want_se) {
+    HIPCHK(ctx, B.d_starts.alloc((size_t)total));
+    HIPCHK(ctx, B.d_ends.alloc((size_t)total));
+    HIPCHK(ctx, hipMemsetAsync(B.d_starts.p, 0, B.d_starts.bytes, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(B.d_ends.p, 0, B.d_ends.bytes, ctx->stream));
+  }
+  const size_t lds = gat::coverage_lds_bytes(W);
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_coverage, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc;
+  int64_t done = 0;
+  while (done < S) {
+    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
+    const int64_t nb = std::min<int64_t>(P->batch, S - done);
+    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr)) == kRelayout) continue;
+    if (rc) return rc;
+    // (the batch passed its checks: a batch that is laid out again never got here)
+    if (!win.empty()) {
+      gat::CoverageArgs A;
+      A.seg = P->merge_contigs ? P->d_cslab.p : P->final_slab();
+      A.seg_stride = P->slab_stride;
+      A.c_off = P->d_count_c_off.p;
+      A.n_arr = P->merge_contigs ? P->d_contig_n.p : P->d_unit_n.p;
+      A.n_stride = P->merge_contigs ? P->n_contigs : P->n_units;
+      A.n_index = P->d_count_n_index.p;
+      A.n_samples = (int32_t)nb;
+      A.window_bins = (int32_t)W;
+      A.sorted = (P->sampler == GAT_SAMPLER_SEGMENTS && !P->merge_contigs) ? 0 : 1;
+      A.bin_size = bin_size;
+      A.win = B.d_win.p;
+      A.bases = B.d_bases.p; A.starts = want_se ? B.d_starts.p : nullptr; A.ends = want_se ? B.d_ends.p : nullptr; A.outside = B.d_outside.p;
+      // the chunk: the knob's, else the whole batch halved until the launch has four workgroups for each of 256 compute units;
+      // never so long that a 32-bit word of the window could overflow (a sample holds at most slab_stride segments), and
+      // within the grid's y
+      int64_t spb = kn.coverage_samples_per_block > 0 ? kn.coverage_samples_per_block : nb;
+      if (kn.coverage_samples_per_block <= 0)
+        while (spb > 16 && (int64_t)win.size() * ((nb + spb - 1) / spb) < 1024) spb = (spb + 1) / 2;
+      spb = std::max<int64_t>(1, std::min<int64_t>(std::min(spb, nb), (int64_t)INT32_MAX / std::max<int64_t>(1, P->slab_stride)));
+      spb = std::max(spb, (nb + 65534) / 65535);
+      A.samples_per_block = (int32_t)spb;
+      hipLaunchKernelGGL(gat::k_coverage, dim3((unsigned)win.size(), (unsigned)((nb + spb - 1) / spb)), dim3(gat::kCoverageThreads), lds, ctx->stream, A);
+      HIPCHK(ctx, hipGetLastError());
+    }
+    local.n_batches += 1;
+    done += nb;
+  }
+  if (total > 0) HIPCHK(ctx, staged_d2h(ctx, bases_host, B.d_bases.p, (size_t)total * 8));
+  if (total > 0 && starts_host) HIPCHK(ctx, staged_d2h(ctx, starts_host, B.d_starts.p, (size_t)total * 8));
+  if (total > 0 && ends_host) HIPCHK(ctx, staged_d2h(ctx, ends_host, B.d_ends.p, (size_t)total * 8));
+  if (C > 0) HIPCHK(ctx, staged_d2h(ctx, outside_host, B.d_outside.p, (size_t)C * 8));
+  return GAT_OK;
+}
+
+extern "C" int gat_sample_coverage(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                   int64_t bin_size, const int64_t* bin_off, int64_t* bases_host, int64_t* starts_host,
+                                   int64_t* ends_host, int64_t* outside_host, gat_stats* stats) {
+  if (!ctx || !P || !bin_off || !bases_host || !outside_host) return set_err(ctx, GAT_ERR_ARG, "gat_sample_coverage: NULL argument");
+  if (bin_size < 1 || bin_size > (int64_t)1 << 31) return set_err(ctx, GAT_ERR_ARG, "gat_sample_coverage: bin_size %lld outside [1, 2^31]", (long long)bin_size);
+  if (bin_off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "gat_sample_coverage: bin_off[0] < 0");
+  for (int c = 0; c < P->n_contigs; ++c)
+    if (bin_off[c + 1] < bin_off[c]) return set_err(ctx, GAT_ERR_ARG, "gat_sample_coverage: bin_off decreases at contig %d", c);
+  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
+  if (P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const Knobs kn = read_knobs(ctx);
+  gat_stats local;
+  memset(&local, 0, sizeof(local));
+  const int64_t total = bin_off[P->n_contigs], S = sample_end - sample_begin;
+  if (S == 0) {                                                    // (no batch runs: the sums are empty)
+    memset(bases_host, 0, (size_t)total * 8);
+    if (starts_host) memset(starts_host, 0, (size_t)total * 8);
+    if (ends_host) memset(ends_host, 0, (size_t)total * 8);
+    memset(outside_host, 0, (size_t)P->n_contigs * 8);
+    if (stats) *stats = local;
+    return GAT_OK;
+  }
+  CoverageBufs B;
+  const int rc = sample_coverage_body(ctx, P, kn, seed, sample_begin, S, bin_size, bin_off, bases_host, starts_host, ends_host,
+                                      outside_host, local, B);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->stage_used = 0;
+  if (stats) *stats = local;
+  return rc;
 }
 
 // what gat_count_lists / gat_count_list_ranges were given, as it goes down to the launches

@@ -322,6 +322,33 @@ int gat_sample_units(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                      int64_t sample_begin, int64_t sample_end,
                      gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats);
 
+/* Where a null model puts its segments: per-bin coverage of the sampled lists, summed over the samples
+ * [sample_begin, sample_end), formed on the device where the sampler leaves the lists.  Stands in for
+ * computeSegmentDensityProfile (test/validate_randomization.py:212-247: per-position counts of the samples and histograms
+ * of the segments' starts and ends, by per-base loops on the host).  Bin b of contig c is [b * bin_size, (b + 1) * bin_size),
+ * contig c has n_bins[c] = bin_off[c + 1] - bin_off[c] of them.  Every segment [s, e), e > s, of every contig-level list
+ * (sample i, contig c) -- exactly the lists gat_sample returns, drawn from the same per-unit streams -- adds
+ *     bases[bin_off[c] + b] += |[s, e) n bin b|                    for b < n_bins[c]
+ *     outside[c]            += |[s, e) n [n_bins[c] * bin_size, inf)|
+ *     starts[bin_off[c] + b] += 1 where s lies in bin b,  ends[bin_off[c] + b] += 1 where e - 1 does
+ * (starts and ends beyond the last bin are dropped).  Lists need be neither sorted nor disjoint (SamplerSegments without
+ * isochore keys returns neither): overlapping segments count with their multiplicity, and for every contig
+ * sum(bases) + outside == the summed lengths of its lists.  All sums are exact 64-bit integers and do not depend on how the
+ * sample range is cut into batches or calls.  Where the clipping differs from the reference: that clamps every segment to
+ * [0, workspace.max()); here the caller's n_bins is the extent and `outside` reports what lies beyond it.
+ * bin_off: n_contigs + 1 entries (HOST), bin_off[0] >= 0, not decreasing; bases_host / starts_host / ends_host:
+ * bin_off[n_contigs] entries each (HOST; starts_host / ends_host may be NULL: not wanted); outside_host: n_contigs.
+ * Synchronous, like gat_sample.  GAT_ERR_ARG: a NULL ctx / p / bin_off / bases_host / outside_host, bin_size outside
+ * [1, 2^31], a decreasing bin_off, sample_end < sample_begin, a call in flight on the problem.  An empty sample range gives
+ * zeros.  The sampler's errors pass through (GAT_ERR_ASSERT; SamplerBruteForce's GAT_ERR_VALUE "sampling did not
+ * converge").  Per-unit streams only.  GAT_COVERAGE_WINDOW_BINS / GAT_COVERAGE_SAMPLES_PER_BLOCK (context options): the
+ * bins and samples a workgroup of k_coverage takes; neither changes a result. */
+int gat_sample_coverage(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                        int64_t sample_begin, int64_t sample_end,
+                        int64_t bin_size, const int64_t* bin_off,
+                        int64_t* bases_host, int64_t* starts_host, int64_t* ends_host,
+                        int64_t* outside_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
