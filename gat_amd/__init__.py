@@ -123,10 +123,10 @@ class _TrackJob(object):
     """the sampling of one segment track between its two halves (_sample_start / _sample_finish): the problem on the device,
     the count matrix there, and -- when the call could be enqueued -- the call in flight"""
     __slots__ = ("ctx", "P", "flat", "names", "tracks", "num_samples", "seed", "dev", "enqueued", "samples_outfile", "mt_state",
-                 "result")
+                 "result", "metrics")
 
     def __init__(self, **kw):
-        self.dev, self.enqueued, self.result, self.P = None, False, None, None
+        self.dev, self.enqueued, self.result, self.P, self.metrics = None, False, None, None, None
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -144,7 +144,7 @@ class _TrackJob(object):
 
 
 def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, seed, ctx=None, samples_outfile=None,
-                  workspace_generator=None, only_tracks=None, mt_state=None, _aflat=None, _shared=None):
+                  workspace_generator=None, only_tracks=None, mt_state=None, _aflat=None, _shared=None, _metrics=None):
     """First half of the batch seam (UnconditionalSampler.sample, gat/__init__.py:704-778): the inputs go to the device --
     the annotation tables only if no earlier track of this run() left them there (_shared) -- and, on the plain
     single-process path, the samples are ENQUEUED (gat_sample_and_count_enqueue): the caller computes observed counts and
@@ -153,6 +153,10 @@ def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, 
     from . import _lib
     job = _TrackJob(ctx=None, flat=None, names=[c.name for c in counters], tracks=None, num_samples=num_samples, seed=seed,
                     samples_outfile=samples_outfile, mt_state=mt_state)
+    if _metrics is not None:
+        # (outfile, track): _sample_finish writes the track's sample_metrics rows from the same seed and unit streams, measured
+        # against the workspace as it is here -- only the unconditional generator gets this far, and it changes nothing
+        job.metrics = tuple(_metrics) + (workspace,)
     if workspace.sum() == 0:
         job.result = (None, 0)
         return job
@@ -191,6 +195,9 @@ def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, 
         # (gat/__init__.py:536-538) and each counter sums over no contigs
         zero = [np.zeros(num_samples, dtype=np.float64 if n == "nucleotide-density" else np.int64) for n in names]
         job.result = ([collections.OrderedDict((t, zero[k].copy()) for t in tracks) for k in range(len(names))], flat["n_units"])
+        if job.metrics is not None:
+            from . import metrics
+            metrics.write_empty_sample_metrics(job.metrics[0], job.metrics[1], num_samples)
         return job
     # the annotation tables: one device object per (contigs in order, merge) of this run(), shared by its segment tracks
     shared_annos = None
@@ -281,6 +288,11 @@ def _sample_finish(job, stat_vals=None):
                         continue
                     for s, e in seg[off[i * U + u]:off[i * U + u + 1]].tolist():
                         samples_outfile.write("%s\t%i\t%i\n" % (flat["unit_names"][u], s, e))
+        if job.metrics is not None:
+            # --output-stats=sample_metrics (gat/__init__.py:565-576): every sample's lists measured on the device, drawn again
+            # from the streams the counts came from (one writer, all samples, no sharding)
+            from . import metrics
+            metrics.write_sample_metrics(job.metrics[0], job.metrics[1], P, flat, job.metrics[2], seed, num_samples)
     finally:
         job.abandon()
     out = _CountsPerTrack()
@@ -419,8 +431,9 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
     """run an enrichment analysis: same signature and result type as the reference's gat.run
     (gat/__init__.py:855-1088).
 
-    kwargs: num_samples, pseudo_count, reference, output_counts_pattern, output_samples_pattern
-    (as in the reference) and random_seed (base of the per-unit streams; default: drawn from numpy's
+    kwargs: num_samples, pseudo_count, reference, output_counts_pattern, output_samples_pattern, outfiles
+    (as in the reference; of outfiles the keys "segment_metrics" and "sample_metrics" are used: open files that receive the
+    rows of gat_amd/metrics.py -- run() writes the header of the first, the caller that of the second, as there) and random_seed (base of the per-unit streams; default: drawn from numpy's
     global RandomState, so numpy.random.seed() makes a run reproducible).  reference_stream=True: random_seed seeds ONE
     stream for the whole run, as the reference's gat-run.py --random-seed does (same numbers as an unpatched reference;
     one wave's speed).  num_threads is accepted
@@ -433,6 +446,14 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
     seed = kwargs.get("random_seed", None)
     reference_stream = bool(kwargs.get("reference_stream", False))
     sample_files = kwargs.get("sample_files", None) or []
+    outfiles = kwargs.get("outfiles", None) or {}
+    if "sample_metrics" in outfiles:
+        # (before anything is read or sampled)
+        if type(workspace_generator) is not UnconditionalWorkspace:
+            raise NotImplementedError("--output-stats=sample_metrics: only --conditional=unconditional (the samples of a "
+                                      "generated workspace are not measured)")
+        if reference_stream:
+            raise NotImplementedError("--output-stats=sample_metrics: per-unit streams only, not --reference-stream")
     if sample_files:
         # gat/__init__.py:952-961 + Engine.pyx:3215-3233 (SamplesFile): the files are read (every parse error of the bed
         # reader surfaces), each one's track name is what the samples pattern's "%s" matches in its file name, a run that
@@ -464,6 +485,11 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
                                 SamplerBruteForce)):
         raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
                                   "SamplerLocalPermutation and SamplerBruteForce run on the GPU path")
+    if _dist_state()[0] != 0:
+        outfiles = {}                # (one writer: rank 0 computes and writes the metrics, all samples, no sharding)
+    if "segment_metrics" in outfiles:
+        from . import metrics
+        metrics.write_segment_metrics(outfiles["segment_metrics"], segments, workspace)     # gat/__init__.py:913-925
     mt_state = None
     if reference_stream and isinstance(sampler, SamplerShift):
         raise NotImplementedError("reference_stream: SamplerShift runs on the per-unit streams only")
@@ -594,7 +620,8 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
             try:
                 job = _sample_start(segments[track], annotations, workspace, sampler, counters, num_samples, seed,
                                     samples_outfile=outf, workspace_generator=workspace_generator, mt_state=mt_state,
-                                    _aflat=aflat, _shared=shared)
+                                    _aflat=aflat, _shared=shared,
+                                    _metrics=(outfiles["sample_metrics"], track) if "sample_metrics" in outfiles else None)
             except Exception:
                 observed()           # (the reference has counted before it samples: an error there comes first)
                 raise
@@ -702,8 +729,10 @@ def buildParser(usage=None, samplers=SAMPLERS):
     g.add_option("--output-counts-pattern", dest="output_counts_pattern", type="string")
     g.add_option("--output-samples-pattern", dest="output_samples_pattern", type="string")
     g.add_option("--output-stats", dest="output_stats", type="choice", action="append",
-                 choices=("all", "annotations", "segments", "workspaces", "isochores", "overlap"),
-                 help="write summary statistics of the collections at the stages of the input pipeline")
+                 choices=("all", "annotations", "segments", "workspaces", "isochores", "overlap", "segment_metrics", "sample_metrics"),
+                 help="write summary statistics of the collections at the stages of the input pipeline; segment_metrics / "
+                      "sample_metrics: how the input segments / every sample sit in the workspace (gat_amd/metrics.py; not "
+                      "part of 'all')")
     g.add_option("--output-bed", dest="output_bed", type="choice", action="append",
                  choices=("all", "annotations", "segments", "workspaces", "isochores"),
                  help="write the collections after the isochores were applied as bed files")
@@ -775,48 +804,68 @@ def buildParser(usage=None, samplers=SAMPLERS):
     return parser
 
 
+def _open_metrics_files(options):
+    """the metrics side files (scripts/gat-run.py:91-105): opened only when named -- "all" keeps meaning the collection
+    summaries -- and by one writer; the header of sample_metrics is written here, that of segment_metrics by run()"""
+    from . import metrics
+    outfiles = {}
+    if _dist_state()[0] == 0:
+        for section in metrics.SECTIONS:
+            if section in (getattr(options, "output_stats", None) or []):
+                outfiles[section] = IO.openOutputFile(section, options)
+    if "sample_metrics" in outfiles:
+        outfiles["sample_metrics"].write(metrics.HEADER)
+    return outfiles
+
+
 def fromSegments(options, args=None):
     """run an analysis from BED files: scripts/gat-run.py:77-220 of the reference."""
     segments, annotations, workspaces, isochores = IO.buildSegments(options)
-    workspace = IO.applyIsochores(segments, annotations, workspaces, options, isochores,
-                                  truncate_segments_to_workspace=options.truncate_segments_to_workspace,
-                                  truncate_workspace_to_annotations=options.truncate_workspace_to_annotations,
-                                  restrict_workspace=options.restrict_workspace)
-    if options.sampler == "annotator":
-        sampler = SamplerAnnotator(bucket_size=options.bucket_size, nbuckets=options.nbuckets)
-    elif options.sampler == "segments":
-        sampler = SamplerSegments()                      # scripts/gat-run.py:133 passes no bucket arguments
-    elif options.sampler == "shift":
-        sampler = SamplerShift(radius=options.shift_expansion, extension=options.shift_extension)   # scripts/gat-run.py:129-132
-    elif options.sampler == "global-permutation":
-        sampler = SamplerGlobalPermutation()             # scripts/gat-run.py:137-138
-    elif options.sampler == "local-permutation":
-        sampler = SamplerLocalPermutation()              # scripts/gat-run.py:135-136
-    elif options.sampler == "brute-force":
-        sampler = SamplerBruteForce()                    # scripts/gat-run.py:139-140 (no bucket arguments: bucket_size 1)
-    else:
-        raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
-    counters = []
-    for counter in options.counters:
-        if counter not in COUNTERS:
-            raise ValueError("unknown counter '%s'" % counter)
-        counters.append(COUNTERS[counter]())
-    # scripts/gat-run.py:162-186 (both centered modes insist on --conditional-expansion, as the reference does)
-    if options.conditional == "unconditional":
-        workspace_generator = UnconditionalWorkspace()
-    elif options.conditional == "cooccurance":
-        workspace_generator = ConditionalWorkspaceCooccurance()
-    elif options.conditional in ("annotation-centered", "segment-centered"):
-        if options.conditional_expansion is None:
-            raise ValueError("please specify either --conditional-expansion or --conditional-extension")
-        cls = (ConditionalWorkspaceAnnotationCentered if options.conditional == "annotation-centered"
-               else ConditionalWorkspaceSegmentCentered)
-        workspace_generator = cls(options.conditional_extension, options.conditional_expansion)
-    else:
-        raise ValueError("unknown conditional workspace '%s'" % options.conditional)
-    return run(segments, annotations, workspace, sampler, counters, workspace_generator=workspace_generator,
-               num_samples=options.num_samples, output_counts_pattern=options.output_counts_pattern,
-               output_samples_pattern=options.output_samples_pattern, pseudo_count=options.pseudo_count,
-               num_threads=options.num_threads, random_seed=options.random_seed,
-               reference_stream=getattr(options, "reference_stream", False),
-               sample_files=getattr(options, "sample_files", []))
+    outfiles = _open_metrics_files(options)
+    try:
+        workspace = IO.applyIsochores(segments, annotations, workspaces, options, isochores,
+                                      truncate_segments_to_workspace=options.truncate_segments_to_workspace,
+                                      truncate_workspace_to_annotations=options.truncate_workspace_to_annotations,
+                                      restrict_workspace=options.restrict_workspace)
+        if options.sampler == "annotator":
+            sampler = SamplerAnnotator(bucket_size=options.bucket_size, nbuckets=options.nbuckets)
+        elif options.sampler == "segments":
+            sampler = SamplerSegments()                      # scripts/gat-run.py:133 passes no bucket arguments
+        elif options.sampler == "shift":
+            sampler = SamplerShift(radius=options.shift_expansion, extension=options.shift_extension)   # scripts/gat-run.py:129-132
+        elif options.sampler == "global-permutation":
+            sampler = SamplerGlobalPermutation()             # scripts/gat-run.py:137-138
+        elif options.sampler == "local-permutation":
+            sampler = SamplerLocalPermutation()              # scripts/gat-run.py:135-136
+        elif options.sampler == "brute-force":
+            sampler = SamplerBruteForce()                    # scripts/gat-run.py:139-140 (no bucket arguments: bucket_size 1)
+        else:
+            raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
+        counters = []
+        for counter in options.counters:
+            if counter not in COUNTERS:
+                raise ValueError("unknown counter '%s'" % counter)
+            counters.append(COUNTERS[counter]())
+        # scripts/gat-run.py:162-186 (both centered modes insist on --conditional-expansion, as the reference does)
+        if options.conditional == "unconditional":
+            workspace_generator = UnconditionalWorkspace()
+        elif options.conditional == "cooccurance":
+            workspace_generator = ConditionalWorkspaceCooccurance()
+        elif options.conditional in ("annotation-centered", "segment-centered"):
+            if options.conditional_expansion is None:
+                raise ValueError("please specify either --conditional-expansion or --conditional-extension")
+            cls = (ConditionalWorkspaceAnnotationCentered if options.conditional == "annotation-centered"
+                   else ConditionalWorkspaceSegmentCentered)
+            workspace_generator = cls(options.conditional_extension, options.conditional_expansion)
+        else:
+            raise ValueError("unknown conditional workspace '%s'" % options.conditional)
+        return run(segments, annotations, workspace, sampler, counters, workspace_generator=workspace_generator,
+                   num_samples=options.num_samples, output_counts_pattern=options.output_counts_pattern,
+                   output_samples_pattern=options.output_samples_pattern, pseudo_count=options.pseudo_count,
+                   num_threads=options.num_threads, random_seed=options.random_seed,
+                   reference_stream=getattr(options, "reference_stream", False),
+                   sample_files=getattr(options, "sample_files", []), outfiles=outfiles)
+    finally:
+        for f in outfiles.values():
+            if f is not getattr(options, "stdout", None):
+                f.close()

@@ -33,7 +33,7 @@ SYMBOLS = [
     "gat_sample_and_count_serial", "gat_mt19937_seed", "gat_sample_and_count_enqueue", "gat_wait",
     "gat_annotations_create", "gat_annotations_destroy", "gat_annotations_wait", "gat_list_sums", "gat_problem_rng_rows",
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
-    "gat_call_lane_for", "gat_sample_coverage",
+    "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -205,6 +205,10 @@ def lib():
     L.gat_sample_units.argtypes = [vp, vp, u32, i64, i64, vp, i64, vp, C.POINTER(Stats)]
     L.gat_sample_coverage.restype = C.c_int
     L.gat_sample_coverage.argtypes = [vp, vp, u32, i64, i64, i64, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.gat_list_metrics.restype = C.c_int
+    L.gat_list_metrics.argtypes = [vp, vp, vp, i64, vp, vp, i32, vp]
+    L.gat_sample_metrics.restype = C.c_int
+    L.gat_sample_metrics.argtypes = [vp, vp, u32, i64, i64, vp, vp, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -408,6 +412,24 @@ class Context(object):
                                                _p(anno_off), _p(anno_end), n_tracks, _p(ws_nseg), n_groups, _p(out)), self._h)
         return [out[k].view(np.float64).copy() if c == "nucleotide-density" else out[k].copy()
                 for k, c in enumerate(counters)]
+
+
+METRICS_WORDS = ("n", "bases", "pairs", "inter", "touched", "outside_pieces", "tail_n", "tail_bases")
+
+
+def list_metrics(ctx, lists, list_off, n_lists, ws, ws_off, n_groups):
+    """the eight sums (METRICS_WORDS; gat_list_metrics) of n_lists x n_groups caller-provided lists -- list l of group g is
+    lists[list_off[l * n_groups + g]:list_off[l * n_groups + g + 1]] -- against the n_groups normalized piece lists
+    ws[ws_off[g]:ws_off[g + 1]].  Returns int64 [n_lists, n_groups, 8]."""
+    lists = np.ascontiguousarray(lists, dtype=SEG)
+    ws = np.ascontiguousarray(ws, dtype=SEG)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    ws_off = np.ascontiguousarray(ws_off, dtype=np.int64)
+    n_lists, n_groups = int(n_lists), int(n_groups)
+    assert len(list_off) == n_lists * n_groups + 1 and len(ws_off) == n_groups + 1
+    out = np.zeros((n_lists, n_groups, len(METRICS_WORDS)), dtype=np.int64)
+    _check(lib().gat_list_metrics(ctx._h, _p(lists), _p(list_off), n_lists, _p(ws), _p(ws_off), n_groups, _p(out)), ctx._h)
+    return out
 
 
 def call_lane_for(n_lanes, asynchronous, timed, serial_state, others_in_flight, lane_busy):
@@ -726,3 +748,18 @@ class Problem(object):
         self.last_stats = st.asdict()
         _check(rc, self.ctx._h)
         return bases, starts, ends, outside, bin_off
+
+    def sample_metrics(self, seed, sample_begin, sample_end, ws, ws_off):
+        """the eight sums (METRICS_WORDS; gat_sample_metrics) of every sampled contig-level list of [sample_begin, sample_end)
+        against the pieces ws[ws_off[c]:ws_off[c + 1]] of contig c, in the problem's contig order.  Returns int64
+        [samples, n_contigs, 8]."""
+        ws = np.ascontiguousarray(ws, dtype=SEG)
+        ws_off = np.ascontiguousarray(ws_off, dtype=np.int64)
+        assert ws_off.shape == (self.n_contigs + 1,)
+        out = np.zeros((max(0, int(sample_end) - int(sample_begin)), self.n_contigs, len(METRICS_WORDS)), dtype=np.int64)
+        st = Stats()
+        rc = lib().gat_sample_metrics(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
+                                      _p(ws), _p(ws_off), _p(out), C.byref(st))
+        self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
+        return out

@@ -35,9 +35,11 @@
 #include "gat_stats.h"
 #include "gat_compare.h"
 #include "gat_coverage.h"
+#include "gat_metrics.h"
 
 
 #include "gat_host.h"
+#include "gat_metrics_tables.h"
 
 thread_local std::string g_last_error;
 
@@ -1792,6 +1794,149 @@ extern "C" int gat_sample_coverage(gat_ctx* ctx, gat_problem* P, uint32_t seed, 
   CoverageBufs B;
   const int rc = sample_coverage_body(ctx, P, kn, seed, sample_begin, S, bin_size, bin_off, bases_host, starts_host, ends_host,
                                       outside_host, local, B);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->stage_used = 0;
+  if (stats) *stats = local;
+  return rc;
+}
+
+// gat_list_metrics / gat_sample_metrics: k_metrics (gat_metrics.h) over caller-provided lists, or behind every batch of
+// sample_lists' loop that passed its checks.  The groups' pieces and their prefix tables (gat_metrics_tables.h) are made on
+// the host per call.  The device buffers live for the call: both entry points drain the stream before they go back to the pool.
+struct MetricsBufs {
+  DevBuf<uint32_t> d_start, d_end, d_gaps;
+  DevBuf<unsigned long long> d_cum;
+  DevBuf<int32_t> d_off;
+  DevBuf<uint2> d_seg;
+  DevBuf<int64_t> d_csr;
+  DevBuf<long long> d_out;
+};
+static int metrics_upload_groups(gat_ctx* ctx, const gat_segment* ws, const int64_t* ws_off, int64_t n_groups, MetricsBufs& B, const char* who) {
+  MetricsTables T;
+  std::string err;
+  const int rc = metrics_build_tables(ws, ws_off, n_groups, T, err);
+  if (rc) return set_err(ctx, rc, "%s: %s", who, err.c_str());
+  HIPCHK(ctx, B.d_start.upload(T.start, ctx));
+  HIPCHK(ctx, B.d_end.upload(T.end, ctx));
+  HIPCHK(ctx, B.d_gaps.upload(T.gaps, ctx));
+  HIPCHK(ctx, B.d_cum.upload(T.cum, ctx));
+  HIPCHK(ctx, B.d_off.upload(T.off, ctx));
+  HIPCHK(ctx, stage_flush(ctx));                    // (T goes away with this frame: the pushed copies have read it, but be plain about it)
+  return GAT_OK;
+}
+// the launch over n_lists x A.n_groups lists: a wave per list, a workgroup per group and run of lists -- the run as long as
+// leaves 2 048 workgroups (eight for each of 256 compute units) but at least 16 lists, so that staging a group's pieces is
+// shared by many lists; within the grid's y
+static int launch_metrics(gat_ctx* ctx, const Knobs& kn, gat::MetricsArgs A, int64_t n_lists, const MetricsBufs& B) {
+  if (n_lists == 0 || A.n_groups == 0) return GAT_OK;
+  const int64_t L = std::max<int64_t>(1, std::min<int64_t>(kn.metrics_lds_pieces, ((int64_t)ctx->max_lds - 1024) / 8));
+  int64_t lpb = n_lists;
+  while (lpb > 16 && (int64_t)A.n_groups * ((n_lists + lpb - 1) / lpb) < 2048) lpb = (lpb + 1) / 2;
+  lpb = std::max<int64_t>(std::max<int64_t>(1, std::min(lpb, n_lists)), (n_lists + 65534) / 65535);
+  A.n_lists = (int32_t)n_lists;
+  A.lists_per_block = (int32_t)lpb;
+  A.lds_pieces = (int32_t)L;
+  A.ws_start = B.d_start.p; A.ws_end = B.d_end.p; A.ws_cum = B.d_cum.p; A.ws_gaps = B.d_gaps.p; A.ws_off = B.d_off.p;
+  A.out = B.d_out.p;
+  const size_t lds = gat::metrics_lds_bytes(L);
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_metrics, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(gat::k_metrics, dim3((unsigned)A.n_groups, (unsigned)((n_lists + lpb - 1) / lpb)), dim3(gat::kMetricsThreads), lds, ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  return GAT_OK;
+}
+
+static int list_metrics_body(gat_ctx* ctx, const Knobs& kn, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                             const gat_segment* ws, const int64_t* ws_off, int32_t n_groups, int64_t* out_host, MetricsBufs& B) {
+  const int64_t n = n_lists * n_groups, base = list_off[0], total = list_off[n] - base;
+  int rc;
+  if ((rc = metrics_upload_groups(ctx, ws, ws_off, n_groups, B, "gat_list_metrics"))) return rc;
+  std::vector<uint2> h_seg((size_t)total);
+  for (int64_t i = 0; i < total; ++i) h_seg[(size_t)i] = make_uint2(lists[base + i].start, lists[base + i].end);
+  std::vector<int64_t> h_csr((size_t)n + 1);
+  for (int64_t l = 0; l <= n; ++l) h_csr[(size_t)l] = list_off[l] - base;
+  HIPCHK(ctx, B.d_seg.upload(h_seg, ctx));
+  HIPCHK(ctx, B.d_csr.upload(h_csr, ctx));
+  HIPCHK(ctx, B.d_out.alloc((size_t)n * gat::kMetricsWords));
+  gat::MetricsArgs A;
+  memset(&A, 0, sizeof(A));
+  A.seg = B.d_seg.p;
+  A.csr = B.d_csr.p;
+  A.n_groups = n_groups;
+  if ((rc = launch_metrics(ctx, kn, A, n_lists, B))) return rc;
+  HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, (size_t)n * gat::kMetricsWords * 8));
+  return GAT_OK;
+}
+
+extern "C" int gat_list_metrics(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                                const gat_segment* ws, const int64_t* ws_off, int32_t n_groups, int64_t* out_host) {
+  if (!ctx || !list_off || !ws_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: NULL argument");
+  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: n_lists %lld, n_groups %d", (long long)n_lists, n_groups);
+  const int64_t n = n_lists * n_groups;
+  if (list_off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: list_off[0] < 0");
+  for (int64_t l = 0; l < n; ++l)
+    if (list_off[l + 1] < list_off[l] || list_off[l + 1] - list_off[l] > (int64_t)INT32_MAX)
+      return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: list_off decreases, or a list of more than 2^31 - 1 segments, at list %lld", (long long)l);
+  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: NULL argument");
+  for (int64_t i = list_off[0]; i < list_off[n]; ++i)
+    if (lists[i].end < lists[i].start) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: segment %lld ends before it starts", (long long)i);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (n == 0) {                                     // (no list: only the groups are looked at)
+    MetricsTables T;
+    std::string err;
+    const int rc = metrics_build_tables(ws, ws_off, n_groups, T, err);
+    return rc ? set_err(ctx, rc, "gat_list_metrics: %s", err.c_str()) : GAT_OK;
+  }
+  const Knobs kn = read_knobs(ctx);
+  MetricsBufs B;
+  const int rc = list_metrics_body(ctx, kn, lists, list_off, n_lists, ws, ws_off, n_groups, out_host, B);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->stage_used = 0;
+  return rc;
+}
+
+static int sample_metrics_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                               const gat_segment* ws, const int64_t* ws_off, int64_t* out_host, gat_stats& local, MetricsBufs& B) {
+  const int C = P->n_contigs;
+  int rc;
+  if ((rc = metrics_upload_groups(ctx, ws, ws_off, C, B, "gat_sample_metrics"))) return rc;
+  int64_t done = 0;
+  while (done < S) {
+    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
+    const int64_t nb = std::min<int64_t>(P->batch, S - done);
+    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr)) == kRelayout) continue;
+    if (rc) return rc;
+    // (the batch passed its checks: a batch that is laid out again never got here)
+    if (C > 0) {
+      if (B.d_out.n < (size_t)(nb * C * gat::kMetricsWords)) HIPCHK(ctx, B.d_out.alloc((size_t)(nb * C * gat::kMetricsWords)));
+      gat::MetricsArgs A;
+      memset(&A, 0, sizeof(A));
+      A.seg = P->merge_contigs ? P->d_cslab.p : P->final_slab();
+      A.seg_stride = P->slab_stride;
+      A.c_off = P->d_count_c_off.p;
+      A.n_arr = P->merge_contigs ? P->d_contig_n.p : P->d_unit_n.p;
+      A.n_stride = P->merge_contigs ? P->n_contigs : P->n_units;
+      A.n_index = P->d_count_n_index.p;
+      A.n_groups = C;
+      if ((rc = launch_metrics(ctx, kn, A, nb, B))) return rc;
+      HIPCHK(ctx, staged_d2h(ctx, out_host + done * C * gat::kMetricsWords, B.d_out.p, (size_t)(nb * C * gat::kMetricsWords) * 8));
+    }
+    local.n_batches += 1;
+    done += nb;
+  }
+  return GAT_OK;
+}
+
+extern "C" int gat_sample_metrics(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                  const gat_segment* ws, const int64_t* ws_off, int64_t* out_host, gat_stats* stats) {
+  if (!ctx || !P || !ws_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "gat_sample_metrics: NULL argument");
+  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
+  if (P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const Knobs kn = read_knobs(ctx);
+  gat_stats local;
+  memset(&local, 0, sizeof(local));
+  MetricsBufs B;
+  const int rc = sample_metrics_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, ws, ws_off, out_host, local, B);
   (void)hipStreamSynchronize(ctx->stream);
   ctx->stage_used = 0;
   if (stats) *stats = local;

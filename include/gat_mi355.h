@@ -349,6 +349,52 @@ int gat_sample_coverage(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                         int64_t* bases_host, int64_t* starts_host, int64_t* ends_host,
                         int64_t* outside_host, gat_stats* stats /* nullable */);
 
+/* How lists of segments sit in a workspace: the sums behind SegmentsSummary.update / IO.outputMetrics (gat/IO.py:331-454;
+ * the reference's --output-stats=segment_metrics / sample_metrics), formed on the device by k_metrics.  For a list L and
+ * the normalized pieces W of its group -- sorted, disjoint; adjacent pieces stay two pieces, as normalize leaves them --
+ * every segment [s, e) of L has  lo = the first piece with end > s,  hi = the last piece with start < e,
+ * k = max(0, hi - lo + 1), and adds to eight int64 words (GAT_METRICS_WORDS), in this order:
+ *     n               1
+ *     bases           e - s
+ *     pairs           k
+ *     inter           |[s, e) n W|
+ *     touched         e - s where k > 0
+ *     outside_pieces  1 where k == 0, else [s < W[lo].start] + [e > W[hi].end] + the number of j in lo+1..hi with
+ *                     W[j].start > W[j-1].end
+ *     tail_n          1 where s > M, M = the largest start of a segment of L with k > 0 (-1: none has)
+ *     tail_bases      e - s where s > M
+ * The first six are what L and W say; the last two are what the reference's subtract never reaches: its merge-join ends with
+ * the last piece of the intersection, so the segments behind the last one that touches W (all of them with k == 0; every
+ * segment where none touches W) are missing from its result.  For a sorted, disjoint L: n = len(L), bases = L.sum(),
+ * pairs = len(L.filter(W).intersect(W)), inter = its sum(), touched = L.filter(W).sum(), and L.subtract(that intersection)
+ * has outside_pieces - tail_n segments of bases - inter - tail_bases bases (gat/SegmentList.pyx:1204-1285, :1401-1549).  Lists need be neither sorted nor disjoint (SamplerSegments without
+ * isochore keys returns neither): the per-segment form is then the definition, overlapping segments count with their
+ * multiplicity.  All sums are exact 64-bit integers (the reference's Position accumulator wraps at 2^32).  A word has one
+ * owner on the device and is written once: results are reproducible.  GAT_METRICS_LDS_PIECES (context option): how many
+ * pieces of a group the kernel's searches find in LDS before they go to global memory; it changes no result.
+ *
+ * gat_list_metrics: caller-provided lists.  lists: n_lists * n_groups segment lists (HOST, CSR via list_off, n_lists *
+ * n_groups + 1 entries), list l of group g at index l * n_groups + g; ws / ws_off: the n_groups piece lists (HOST, CSR,
+ * n_groups + 1 entries); out_host: [n_lists][n_groups][8].  Synchronous.  GAT_ERR_ARG: a NULL ctx / list_off / ws_off /
+ * out_host (lists / ws may be NULL where they hold nothing), negative counts, a decreasing offset, a segment that ends
+ * before it starts, a piece list that is not normalized (gat_last_error names the group). */
+#define GAT_METRICS_WORDS 8
+int gat_list_metrics(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                     const gat_segment* ws, const int64_t* ws_off, int32_t n_groups, int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop of gat_sample with k_metrics behind every batch that passed its checks, reading
+ * the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed and
+ * range (per-unit streams only).  ws / ws_off: the pieces each contig's samples are measured against (HOST, CSR,
+ * n_contigs + 1 entries, in the problem's contig order); out_host: [sample][contig][8], sample_end - sample_begin samples.
+ * Synchronous, like gat_sample.  Results do not depend on how the range is cut into batches or calls.  GAT_ERR_ARG: a NULL
+ * ctx / p / ws_off / out_host, sample_end < sample_begin, a decreasing ws_off, a piece list that is not normalized, a call
+ * in flight on the problem.  An empty sample range writes nothing.  The sampler's errors pass through (GAT_ERR_ASSERT;
+ * SamplerBruteForce's GAT_ERR_VALUE "sampling did not converge"). */
+int gat_sample_metrics(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                       int64_t sample_begin, int64_t sample_end,
+                       const gat_segment* ws, const int64_t* ws_off,
+                       int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
