@@ -33,7 +33,8 @@ SYMBOLS = [
     "gat_sample_and_count_serial", "gat_mt19937_seed", "gat_sample_and_count_enqueue", "gat_wait",
     "gat_annotations_create", "gat_annotations_destroy", "gat_annotations_wait", "gat_list_sums", "gat_problem_rng_rows",
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
-    "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics",
+    "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics", "gat_list_distances",
+    "gat_sample_distances",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -209,6 +210,10 @@ def lib():
     L.gat_list_metrics.argtypes = [vp, vp, vp, i64, vp, vp, i32, vp]
     L.gat_sample_metrics.restype = C.c_int
     L.gat_sample_metrics.argtypes = [vp, vp, u32, i64, i64, vp, vp, vp, C.POINTER(Stats)]
+    L.gat_list_distances.restype = C.c_int
+    L.gat_list_distances.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, C.c_int, i64, vp]
+    L.gat_sample_distances.restype = C.c_int
+    L.gat_sample_distances.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, C.c_int, i64, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -429,6 +434,28 @@ def list_metrics(ctx, lists, list_off, n_lists, ws, ws_off, n_groups):
     assert len(list_off) == n_lists * n_groups + 1 and len(ws_off) == n_groups + 1
     out = np.zeros((n_lists, n_groups, len(METRICS_WORDS)), dtype=np.int64)
     _check(lib().gat_list_metrics(ctx._h, _p(lists), _p(list_off), n_lists, _p(ws), _p(ws_off), n_groups, _p(out)), ctx._h)
+    return out
+
+
+DISTANCE_WORDS = ("n", "sum", "near", "none")
+DISTANCE_SEGMENT_TO_ANNOTATION, DISTANCE_ANNOTATION_TO_SEGMENT = 0, 1
+
+
+def list_distances(ctx, lists, list_off, n_lists, annos, anno_off, n_tracks, n_groups, direction, max_distance):
+    """the four sums (DISTANCE_WORDS; gat_list_distances) of the nearest-interval distances between n_lists x n_groups
+    caller-provided lists -- list l of group g is lists[list_off[l * n_groups + g]:list_off[l * n_groups + g + 1]] -- and
+    n_tracks x n_groups annotation lists, track t of group g at index t * n_groups + g, summed over the groups.  direction 0:
+    from every segment to the track; 1: from every interval of the track to the segment list.  Returns int64
+    [n_lists, n_tracks, 4]."""
+    lists = np.ascontiguousarray(lists, dtype=SEG)
+    annos = np.ascontiguousarray(annos, dtype=SEG)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    anno_off = np.ascontiguousarray(anno_off, dtype=np.int64)
+    n_lists, n_tracks, n_groups = int(n_lists), int(n_tracks), int(n_groups)
+    assert len(list_off) == n_lists * n_groups + 1 and len(anno_off) == n_tracks * n_groups + 1
+    out = np.zeros((n_lists, n_tracks, len(DISTANCE_WORDS)), dtype=np.int64)
+    _check(lib().gat_list_distances(ctx._h, _p(lists), _p(list_off), n_lists, _p(annos), _p(anno_off), n_tracks, n_groups,
+                                    int(direction), int(max_distance), _p(out)), ctx._h)
     return out
 
 
@@ -760,6 +787,23 @@ class Problem(object):
         st = Stats()
         rc = lib().gat_sample_metrics(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
                                       _p(ws), _p(ws_off), _p(out), C.byref(st))
+        self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
+        return out
+
+    def sample_distances(self, seed, sample_begin, sample_end, annos, anno_off, n_tracks, direction, max_distance):
+        """the four sums (DISTANCE_WORDS; gat_sample_distances) of the nearest-interval distances between every sampled
+        contig-level list of [sample_begin, sample_end) and n_tracks annotation tracks -- track t of contig c is
+        annos[anno_off[t * n_contigs + c]:anno_off[t * n_contigs + c + 1]], contigs in the problem's order -- summed over the
+        contigs.  Returns int64 [samples, n_tracks, 4]."""
+        annos = np.ascontiguousarray(annos, dtype=SEG)
+        anno_off = np.ascontiguousarray(anno_off, dtype=np.int64)
+        n_tracks = int(n_tracks)
+        assert anno_off.shape == (n_tracks * self.n_contigs + 1,)
+        out = np.zeros((max(0, int(sample_end) - int(sample_begin)), n_tracks, len(DISTANCE_WORDS)), dtype=np.int64)
+        st = Stats()
+        rc = lib().gat_sample_distances(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
+                                        _p(annos), _p(anno_off), n_tracks, int(direction), int(max_distance), _p(out), C.byref(st))
         self.last_stats = st.asdict()
         _check(rc, self.ctx._h)
         return out

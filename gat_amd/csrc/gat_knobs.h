@@ -79,7 +79,8 @@ struct gat_ctx;
   REAL(compare_scratch_mb, "GAT_COMPARE_SCRATCH_MB", 1024.0) /* gat_compare_stats: megabytes of transformed rows per batch */ \
   INT(coverage_window_bins, "GAT_COVERAGE_WINDOW_BINS", 1920) /* gat_sample_coverage: bins of a workgroup's LDS window */      \
   INT(coverage_samples_per_block, "GAT_COVERAGE_SAMPLES_PER_BLOCK", 0) /* ... its chunk of samples; default: by the launch */ \
-  INT(metrics_lds_pieces, "GAT_METRICS_LDS_PIECES", 2048) /* gat_*_metrics: pieces of a group k_metrics' searches find in LDS */
+  INT(metrics_lds_pieces, "GAT_METRICS_LDS_PIECES", 2048) /* gat_*_metrics: pieces of a group k_metrics' searches find in LDS */ \
+  INT(distance_lds_pieces, "GAT_DISTANCE_LDS_PIECES", 2048) /* gat_*_distances: intervals of a list k_distance's search finds in LDS */
 
 struct Knobs {
 #define GAT_KNOB_FLAG(field, name) bool field = false;

@@ -36,6 +36,7 @@
 #include "gat_compare.h"
 #include "gat_coverage.h"
 #include "gat_metrics.h"
+#include "gat_distance.h"
 
 
 #include "gat_host.h"
@@ -1937,6 +1938,204 @@ extern "C" int gat_sample_metrics(gat_ctx* ctx, gat_problem* P, uint32_t seed, i
   memset(&local, 0, sizeof(local));
   MetricsBufs B;
   const int rc = sample_metrics_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, ws, ws_off, out_host, local, B);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->stage_used = 0;
+  if (stats) *stats = local;
+  return rc;
+}
+
+// gat_list_distances / gat_sample_distances: k_distance (gat_distance.h) over caller-provided lists, or behind every batch of
+// sample_lists' loop that passed its checks.  The annotation tracks go up once per call as they are given (CSR, uint2); the
+// device buffers live for the call: both entry points drain the stream before they go back to the pool.
+struct DistanceBufs {
+  DevBuf<uint2> d_anno, d_seg;
+  DevBuf<int64_t> d_anno_csr, d_csr;
+  DevBuf<unsigned long long> d_out;
+};
+// offsets of n lists: GAT_ERR_ARG where they start below 0, decrease, or a list is longer than 2^31 - 1
+static int distance_check_offsets(gat_ctx* ctx, const char* who, const char* what, const int64_t* off, int64_t n) {
+  if (off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: %s[0] < 0", who, what);
+  for (int64_t l = 0; l < n; ++l)
+    if (off[l + 1] < off[l] || off[l + 1] - off[l] > (int64_t)INT32_MAX)
+      return set_err(ctx, GAT_ERR_ARG, "%s: %s decreases, or a list of more than 2^31 - 1 intervals, at list %lld", who, what, (long long)l);
+  return GAT_OK;
+}
+// the searched side: every one of n_entities x n_groups lists sorted, disjoint, without an empty interval
+static int distance_check_normalized(gat_ctx* ctx, const char* who, const char* what, const gat_segment* a, const int64_t* off,
+                                     int64_t n_entities, int32_t n_groups) {
+  for (int64_t i = 0; i < n_entities; ++i)
+    for (int32_t g = 0; g < n_groups; ++g) {
+      const int64_t b = off[i * n_groups + g], e = off[i * n_groups + g + 1];
+      for (int64_t j = b; j < e; ++j)
+        if (a[j].end <= a[j].start || (j > b && a[j].start < a[j - 1].end))
+          return set_err(ctx, GAT_ERR_ARG, "%s: %s %lld, group %d is not normalized at interval %lld (sorted, disjoint, none empty: "
+                         "the nearest interval is searched for in it)", who, what, (long long)i, g, (long long)(j - b));
+    }
+  return GAT_OK;
+}
+static int distance_upload(gat_ctx* ctx, const gat_segment* a, const int64_t* off, int64_t n, DevBuf<uint2>& d_seg, DevBuf<int64_t>& d_csr) {
+  const int64_t base = off[0], total = off[n] - base;
+  HIPCHK(ctx, d_seg.upload_built((size_t)total, ctx, [&](uint2* h) {
+    for (int64_t i = 0; i < total; ++i) h[i] = make_uint2(a[base + i].start, a[base + i].end);
+  }));
+  std::vector<int64_t> h_csr((size_t)n + 1);
+  for (int64_t l = 0; l <= n; ++l) h_csr[(size_t)l] = off[l] - base;
+  HIPCHK(ctx, d_csr.upload(h_csr, ctx));
+  HIPCHK(ctx, stage_flush(ctx));                    // (h_csr goes away with this frame)
+  return GAT_OK;
+}
+static gat::DistanceLists distance_csr(const DistanceBufs& B, bool annos) {
+  gat::DistanceLists S;
+  memset(&S, 0, sizeof(S));
+  S.seg = annos ? B.d_anno.p : B.d_seg.p;
+  S.csr = annos ? B.d_anno_csr.p : B.d_csr.p;
+  return S;
+}
+// the launch over n_lists x n_tracks x n_groups pairs of lists, `lists` in either layout.  A workgroup stages one list of the
+// searched side -- the tracks' in direction 0, the segment lists' in direction 1 -- and takes a run of the other side's: the
+// run as long as leaves 2 048 workgroups (eight for each of 256 compute units) but at least 16 lists, within the grid's y.
+// B.d_out holds n_lists * n_tracks * 4 words, zeroed here.
+static int launch_distance(gat_ctx* ctx, const Knobs& kn, const gat::DistanceLists& lists, int64_t n_lists, int32_t n_tracks,
+                           int32_t n_groups, int direction, int64_t max_distance, const DistanceBufs& B) {
+  const int64_t words = n_lists * n_tracks * gat::kDistanceWords;
+  if (words == 0) return GAT_OK;
+  HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, (size_t)words * 8, ctx->stream));
+  if (n_groups == 0) return GAT_OK;
+  gat::DistanceArgs A;
+  memset(&A, 0, sizeof(A));
+  const bool seg_to_anno = direction == GAT_DISTANCE_SEGMENT_TO_ANNOTATION;
+  A.t = seg_to_anno ? distance_csr(B, true) : lists;
+  A.q = seg_to_anno ? lists : distance_csr(B, true);
+  const int64_t n_t = seg_to_anno ? n_tracks : n_lists, n_q = seg_to_anno ? n_lists : n_tracks;
+  if (n_t * n_groups > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_CAPACITY, "gat distances: %lld x %d searched lists in one launch", (long long)n_t, n_groups);
+  A.n_t = (int32_t)n_t;
+  A.n_q = (int32_t)n_q;
+  A.n_groups = n_groups;
+  A.out_stride_t = seg_to_anno ? 1 : n_tracks;
+  A.out_stride_q = seg_to_anno ? n_tracks : 1;
+  A.max_distance = (unsigned long long)max_distance;
+  A.out = B.d_out.p;
+  const int64_t L = std::max<int64_t>(1, std::min<int64_t>(kn.distance_lds_pieces, ((int64_t)ctx->max_lds - 1024) / 8));
+  A.lds_pieces = (int32_t)L;
+  int64_t qpb = n_q;
+  while (qpb > 16 && n_t * n_groups * ((n_q + qpb - 1) / qpb) < 2048) qpb = (qpb + 1) / 2;
+  qpb = std::max<int64_t>(std::max<int64_t>(1, std::min(qpb, n_q)), (n_q + 65534) / 65535);
+  A.q_per_block = (int32_t)qpb;
+  const size_t lds = gat::distance_lds_bytes(L);
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_distance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(gat::k_distance, dim3((unsigned)(n_t * n_groups), (unsigned)((n_q + qpb - 1) / qpb)), dim3(gat::kDistanceThreads), lds, ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  return GAT_OK;
+}
+// what both entry points ask of the tracks, the direction and the bound
+static int distance_check_common(gat_ctx* ctx, const char* who, const gat_segment* annos, const int64_t* anno_off, int64_t n_tracks,
+                                 int64_t n_groups, int direction, int64_t max_distance) {
+  if (direction != GAT_DISTANCE_SEGMENT_TO_ANNOTATION && direction != GAT_DISTANCE_ANNOTATION_TO_SEGMENT)
+    return set_err(ctx, GAT_ERR_ARG, "%s: direction %d is neither GAT_DISTANCE_SEGMENT_TO_ANNOTATION nor GAT_DISTANCE_ANNOTATION_TO_SEGMENT", who, direction);
+  if (max_distance < 0 || max_distance > (int64_t)1 << 32) return set_err(ctx, GAT_ERR_ARG, "%s: max_distance %lld outside [0, 2^32]", who, (long long)max_distance);
+  if (n_tracks < 0 || n_tracks > (int64_t)INT32_MAX || n_tracks * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_tracks %lld", who, (long long)n_tracks);
+  const int64_t n = n_tracks * n_groups;
+  int rc;
+  if ((rc = distance_check_offsets(ctx, who, "anno_off", anno_off, n))) return rc;
+  if (anno_off[n] > anno_off[0] && !annos) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (direction == GAT_DISTANCE_SEGMENT_TO_ANNOTATION && (rc = distance_check_normalized(ctx, who, "annotation track", annos, anno_off, n_tracks, (int32_t)n_groups))) return rc;
+  return GAT_OK;
+}
+
+static int list_distances_body(gat_ctx* ctx, const Knobs& kn, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                               const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups, int direction,
+                               int64_t max_distance, int64_t* out_host, DistanceBufs& B) {
+  int rc;
+  if ((rc = distance_upload(ctx, annos, anno_off, (int64_t)n_tracks * n_groups, B.d_anno, B.d_anno_csr))) return rc;
+  if ((rc = distance_upload(ctx, lists, list_off, n_lists * n_groups, B.d_seg, B.d_csr))) return rc;
+  const size_t words = (size_t)(n_lists * n_tracks * gat::kDistanceWords);
+  HIPCHK(ctx, B.d_out.alloc(words));
+  if ((rc = launch_distance(ctx, kn, distance_csr(B, false), n_lists, n_tracks, n_groups, direction, max_distance, B))) return rc;
+  HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, words * 8));
+  return GAT_OK;
+}
+
+extern "C" int gat_list_distances(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                                  const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups,
+                                  int direction, int64_t max_distance, int64_t* out_host) {
+  const char* who = "gat_list_distances";
+  if (!ctx || !list_off || !anno_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
+  int rc;
+  if ((rc = distance_check_common(ctx, who, annos, anno_off, n_tracks, n_groups, direction, max_distance))) return rc;
+  const int64_t n = n_lists * n_groups;
+  if ((rc = distance_check_offsets(ctx, who, "list_off", list_off, n))) return rc;
+  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (direction == GAT_DISTANCE_ANNOTATION_TO_SEGMENT && (rc = distance_check_normalized(ctx, who, "segment list", lists, list_off, n_lists, n_groups))) return rc;
+  if (n_lists == 0 || n_tracks == 0) return GAT_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const Knobs kn = read_knobs(ctx);
+  DistanceBufs B;
+  rc = list_distances_body(ctx, kn, lists, list_off, n_lists, annos, anno_off, n_tracks, n_groups, direction, max_distance, out_host, B);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->stage_used = 0;
+  return rc;
+}
+
+static int sample_distances_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                                 const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int direction, int64_t max_distance,
+                                 int64_t* out_host, gat_stats& local, DistanceBufs& B) {
+  const int C = P->n_contigs;
+  int rc;
+  if ((rc = distance_upload(ctx, annos, anno_off, (int64_t)n_tracks * C, B.d_anno, B.d_anno_csr))) return rc;
+  int64_t done = 0;
+  while (done < S) {
+    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
+    const int64_t nb = std::min<int64_t>(P->batch, S - done);
+    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr)) == kRelayout) continue;
+    if (rc) return rc;
+    // (the batch passed its checks: a batch that is laid out again never got here)
+    const size_t words = (size_t)(nb * n_tracks * gat::kDistanceWords);
+    if (words > 0) {
+      if (B.d_out.n < words) HIPCHK(ctx, B.d_out.alloc(words));
+      gat::DistanceLists Sl;
+      memset(&Sl, 0, sizeof(Sl));
+      Sl.seg = P->merge_contigs ? P->d_cslab.p : P->final_slab();
+      Sl.seg_stride = P->slab_stride;
+      Sl.c_off = P->d_count_c_off.p;
+      Sl.n_arr = P->merge_contigs ? P->d_contig_n.p : P->d_unit_n.p;
+      Sl.n_stride = P->merge_contigs ? P->n_contigs : P->n_units;
+      Sl.n_index = P->d_count_n_index.p;
+      if ((rc = launch_distance(ctx, kn, Sl, nb, n_tracks, C, direction, max_distance, B))) return rc;
+      HIPCHK(ctx, staged_d2h(ctx, out_host + done * n_tracks * gat::kDistanceWords, B.d_out.p, words * 8));
+    }
+    local.n_batches += 1;
+    done += nb;
+  }
+  return GAT_OK;
+}
+
+extern "C" int gat_sample_distances(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                    const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int direction,
+                                    int64_t max_distance, int64_t* out_host, gat_stats* stats) {
+  const char* who = "gat_sample_distances";
+  if (!ctx || !P || !anno_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
+  int rc;
+  if ((rc = distance_check_common(ctx, who, annos, anno_off, n_tracks, P->n_contigs, direction, max_distance))) return rc;
+  // the searched side of direction 1 is the sampler's: the flag k_coverage gets
+  if (direction == GAT_DISTANCE_ANNOTATION_TO_SEGMENT && P->sampler == GAT_SAMPLER_SEGMENTS && !P->merge_contigs)
+    return set_err(ctx, GAT_ERR_ARG, "%s: the sampled segment lists are not normalized (SamplerSegments without isochore keys leaves them "
+                   "neither sorted nor disjoint): GAT_DISTANCE_ANNOTATION_TO_SEGMENT searches them and needs normalized lists", who);
+  if (P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
+  gat_stats local;
+  memset(&local, 0, sizeof(local));
+  if (sample_end == sample_begin) {                 // (no batch runs: nothing is written)
+    if (stats) *stats = local;
+    return GAT_OK;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const Knobs kn = read_knobs(ctx);
+  DistanceBufs B;
+  rc = sample_distances_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, annos, anno_off, n_tracks, direction,
+                             max_distance, out_host, local, B);
   (void)hipStreamSynchronize(ctx->stream);
   ctx->stage_used = 0;
   if (stats) *stats = local;

@@ -395,6 +395,57 @@ int gat_sample_metrics(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                        const gat_segment* ws, const int64_t* ws_off,
                        int64_t* out_host, gat_stats* stats /* nullable */);
 
+/* How far the intervals of one list lie from the nearest interval of another: the two counters the reference's to-do list
+ * names and never built (doc/contents.rst:78-81, "Closest distance of segment to annotation" / "Closest distance of annotation
+ * to segment"), formed on the device by k_distance.  T is a normalized list of K >= 1 intervals -- sorted by start, pairwise
+ * disjoint, every interval with end > start; adjacent intervals allowed -- and Q = [s, e) a query with e > s.  With
+ * j = the first index with T[j].end > s (K: none):  T[j].start < e: the two share a base, d = 0;  else d = the smaller of
+ * T[j].start - e + 1 (where j < K) and s - T[j - 1].end + 1 (where j > 0).  This is the convention of `bedtools closest -d`:
+ * bookended intervals are at distance 1, a one-base overlap at 0.  A list of queries is compared with a list T group by
+ * group (contig by contig) and adds to four int64 words (GAT_DISTANCE_WORDS), summed over the groups, in this order:
+ *     n      queries with e > s on groups where T is not empty
+ *     sum    d, over those queries
+ *     near   how many of them have d <= max_distance
+ *     none   queries with e > s on groups where T is empty: they have no neighbour and add nothing else
+ * Queries with e <= s are skipped everywhere.  The queries need be neither sorted nor disjoint (SamplerSegments without
+ * isochore keys returns neither): every query counts on its own.  direction: GAT_DISTANCE_SEGMENT_TO_ANNOTATION -- the queries
+ * are a segment list, T an annotation track; GAT_DISTANCE_ANNOTATION_TO_SEGMENT -- the queries are the track's intervals and T
+ * the segment list, which must then be normalized (GAT_ERR_ARG where it is not, never a wrong number).  All arithmetic is
+ * 64-bit and exact; a partial sum of one group has one owner on the device and is added once with a 64-bit integer add, so
+ * results are reproducible.  GAT_DISTANCE_LDS_PIECES (context option): how many intervals of a searched list the kernel's
+ * search finds in LDS before it goes to global memory; it changes no result.
+ *
+ * gat_list_distances: caller-provided lists.  lists: n_lists * n_groups segment lists (HOST, CSR via list_off, n_lists *
+ * n_groups + 1 entries), list l of group g at index l * n_groups + g; annos / anno_off: n_tracks * n_groups annotation lists
+ * (HOST, CSR, n_tracks * n_groups + 1 entries), track t of group g at index t * n_groups + g -- the layout of gat_list_metrics
+ * and gat_count_lists; max_distance in [0, 2^32]; out_host: [n_lists][n_tracks][4].  Synchronous.  GAT_ERR_ARG: a NULL ctx /
+ * list_off / anno_off / out_host (lists / annos may be NULL where they hold nothing), negative counts, a decreasing offset, a
+ * direction other than the two, max_distance outside its range, a searched list (the tracks' in direction 0, the segment
+ * lists' in direction 1) that is not normalized or holds an empty interval: gat_last_error names the track (or list) and the
+ * group. */
+#define GAT_DISTANCE_WORDS 4
+#define GAT_DISTANCE_SEGMENT_TO_ANNOTATION 0
+#define GAT_DISTANCE_ANNOTATION_TO_SEGMENT 1
+int gat_list_distances(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                       const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups,
+                       int direction, int64_t max_distance, int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop of gat_sample with k_distance behind every batch that passed its checks, reading
+ * the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed and
+ * range (per-unit streams only).  The groups are the problem's contigs in the problem's order: anno_off has n_tracks *
+ * n_contigs + 1 entries; out_host: [sample][track][4], sample_end - sample_begin samples.  Synchronous, like gat_sample.
+ * Results do not depend on how the range is cut into batches or calls.  GAT_ERR_ARG: a NULL ctx / p / anno_off / out_host,
+ * sample_end < sample_begin, a negative n_tracks, a decreasing anno_off, a direction other than the two, max_distance outside
+ * [0, 2^32], in direction 0 a track that is not normalized (gat_last_error names the track and the contig), in direction 1 a
+ * sampler whose lists are not normalized (SamplerSegments on a problem without isochore keys; the message says so), a call
+ * in flight on the problem.  An empty sample range writes nothing.  The sampler's errors pass through (GAT_ERR_ASSERT;
+ * SamplerBruteForce's GAT_ERR_VALUE "sampling did not converge"). */
+int gat_sample_distances(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                         int64_t sample_begin, int64_t sample_end,
+                         const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks,
+                         int direction, int64_t max_distance,
+                         int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
