@@ -756,7 +756,10 @@ def buildParser(usage=None, samplers=SAMPLERS):
     g = optparse.OptionGroup(parser, "Statistics options")
     g.add_option("-p", "--pvalue-method", dest="pvalue_method", type="choice", choices=("empirical", "norm"))
     g.add_option("-q", "--qvalue-method", dest="qvalue_method", type="choice",
-                 choices=("storey", "BH", "bonferroni", "holm", "hommel", "hochberg", "BY", "none"))
+                 choices=("storey", "BH", "bonferroni", "holm", "hommel", "hochberg", "BY", "none", "minp"),
+                 help="multiple-testing correction of the table's p-values; minp (not in the reference): step-down minP "
+                      "family-wise adjusted p-values from the joint null distribution the samples are, on the GPU "
+                      "(needs --pvalue-method=empirical) [default=%default]")
     g.add_option("--qvalue-lambda", dest="qvalue_lambda", type="float", help="fdr computation: lambda")
     g.add_option("--qvalue-pi0-method", dest="qvalue_pi0_method", type="choice", choices=("smoother", "bootstrap"),
                  help="fdr computation: method for estimating pi0")

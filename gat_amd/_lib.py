@@ -34,7 +34,7 @@ SYMBOLS = [
     "gat_annotations_create", "gat_annotations_destroy", "gat_annotations_wait", "gat_list_sums", "gat_problem_rng_rows",
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
     "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics", "gat_list_distances",
-    "gat_sample_distances",
+    "gat_sample_distances", "gat_minp_counts", "gat_minp_times",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -234,6 +234,10 @@ def lib():
     L.gat_null_stats.argtypes = [vp, vp, i64, i64, vp, vp, i64, i64, vp]
     L.gat_compare_stats.restype = C.c_int
     L.gat_compare_stats.argtypes = COMPARE_STATS_ARGTYPES
+    L.gat_minp_counts.restype = C.c_int
+    L.gat_minp_counts.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp]
+    L.gat_minp_times.restype = C.c_int
+    L.gat_minp_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.gat_comm_unique_id.restype = C.c_int
     L.gat_comm_unique_id.argtypes = [vp]
     L.gat_comm_library_preloaded.restype = C.c_int
@@ -396,6 +400,26 @@ class Context(object):
         with np.errstate(invalid="ignore"):
             out[:, 1] = np.sqrt(out[:, 1] / l)                # numpy.std's last two steps
         return out
+
+    def minp_counts(self, counts_dev_ptr, n_rows, n_samples, is_double, means, k_obs):
+        """step-down minP on a device count matrix (gat_minp_counts): per row, in the order of the rows, the number of samples
+        whose running minimum over the rows at and behind it in (k_obs, index) order is at most the row's k_obs -- int64,
+        before the running maximum.  means: each row's `expected`; k_obs: its p-value times n_samples."""
+        n = int(n_rows)
+        is_double = np.ascontiguousarray(is_double, dtype=np.uint8)
+        means = np.ascontiguousarray(means, dtype=np.float64)
+        k_obs = np.ascontiguousarray(k_obs, dtype=np.int32)
+        assert len(is_double) == len(means) == len(k_obs) == max(n, 0)
+        out = np.zeros(max(n, 0), dtype=np.int64)
+        _check(lib().gat_minp_counts(self._h, C.c_void_p(counts_dev_ptr), n, int(n_samples), _p(is_double), _p(means), _p(k_obs),
+                                     _p(out)), self._h)
+        return out
+
+    def minp_times(self):
+        """(ms in k_minp_rank, ms in k_minp_step) of the last minp_counts; zeros unless set_kernel_times(True)"""
+        a, b = C.c_float(), C.c_float()
+        _check(lib().gat_minp_times(self._h, C.byref(a), C.byref(b)), self._h)
+        return a.value, b.value
 
     def count_lists(self, counters, lists, list_off, n_lists, annos, anno_off, n_tracks, ws_nseg, n_groups, anno_end=None):
         """Counter*(list, annotation, workspace) for n_lists x n_groups lists (observed counts).  anno_end given: the

@@ -34,6 +34,7 @@
 #include "gat_brute_force.h"
 #include "gat_stats.h"
 #include "gat_compare.h"
+#include "gat_minp.h"
 #include "gat_coverage.h"
 #include "gat_metrics.h"
 #include "gat_distance.h"
@@ -2503,5 +2504,101 @@ extern "C" int gat_compare_stats(gat_ctx* ctx, const void* a_dev, int64_t n_rows
   std::vector<uint32_t> bad((size_t)n_pairs);
   HIPCHK(ctx, staged_d2h(ctx, bad.data(), d_bad.p, (size_t)n_pairs * 4));
   for (int64_t p = 0; p < n_pairs; ++p) out_host[p * 8 + 6] = (double)bad[(size_t)p];
+  return GAT_OK;
+}
+
+// Step-down minP (include/gat_mi355.h, gat_minp.h): the rows are ordered on the host by (k_obs, row index) and worked on from
+// the last of that order to the first, in batches of as many rows of K as the call's GAT_MINP_SCRATCH_MB holds; k_minp_rank
+// fills the batch's rows of K, k_minp_step takes the running minimum q through them and counts.  q stays on the device from
+// batch to batch; what comes back is one integer per row.
+struct MinpTimer {                                  // device times of the two kernels, only for a call that asks (kernel times)
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  ~MinpTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+extern "C" int gat_minp_counts(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t n_samples,
+                               const uint8_t* is_double_host, const double* means_host, const int32_t* kobs_host,
+                               int64_t* c_out_host) {
+  if (!ctx || !counts_dev || !is_double_host || !means_host || !kobs_host || !c_out_host)
+    return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: NULL argument");
+  if (n_rows <= 0) return GAT_OK;
+  if (n_samples < 1 || n_samples >= ((int64_t)1 << 31) || n_rows >= ((int64_t)1 << 31))
+    return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: bad sample / row count");
+  for (int64_t r = 0; r < n_rows; ++r)
+    if (kobs_host[r] < 1 || (int64_t)kobs_host[r] > n_samples)
+      return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: row %lld has k_obs %d of %lld samples", (long long)r, kobs_host[r], (long long)n_samples);
+  const Knobs kn = read_knobs(ctx);                 // the call's
+  if (!(kn.minp_scratch_mb > 0.0)) return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: GAT_MINP_SCRATCH_MB must be positive");
+  const int64_t lds_max = ((int64_t)ctx->max_lds - gat::kMinpLdsFixed) / gat::kMinpKeyBytes;
+  if (kn.minp_lds_samples < 0 || kn.minp_lds_samples > lds_max)
+    return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: GAT_MINP_LDS_SAMPLES must be in [0, %lld]", (long long)lds_max);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int64_t S = n_samples;
+  // o_1 .. o_R: by (k_obs, row index); proc = that order from its end
+  std::vector<int32_t> proc((size_t)n_rows);
+  for (int64_t r = 0; r < n_rows; ++r) proc[(size_t)r] = (int32_t)r;
+  std::sort(proc.begin(), proc.end(), [&](int32_t a, int32_t b) { return kobs_host[a] != kobs_host[b] ? kobs_host[a] > kobs_host[b] : a > b; });
+  std::vector<int32_t> kobs_proc((size_t)n_rows);
+  for (int64_t p = 0; p < n_rows; ++p) kobs_proc[(size_t)p] = kobs_host[proc[(size_t)p]];
+  const double budget_rows = kn.minp_scratch_mb * 1048576.0 / (double)(S * 4);
+  const int64_t batch = std::max<int64_t>(1, budget_rows >= (double)n_rows ? n_rows : (int64_t)budget_rows);
+  const bool in_lds = S <= kn.minp_lds_samples;
+  const int64_t grid_rank = std::min<int64_t>(batch, gat::kMinpRankGrid);
+  const size_t lds = (size_t)gat::kMinpLdsFixed + (in_lds ? (size_t)S * gat::kMinpKeyBytes : 0);
+  DevBuf<int32_t> d_rows, d_kobs, d_q, d_K;
+  DevBuf<uint8_t> d_dbl;
+  DevBuf<double> d_means;
+  DevBuf<uint32_t> d_c;
+  DevBuf<unsigned long long> d_sort;
+  HIPCHK(ctx, d_rows.upload(proc, ctx));
+  HIPCHK(ctx, d_kobs.upload(kobs_proc, ctx));
+  HIPCHK(ctx, d_dbl.upload(std::vector<uint8_t>(is_double_host, is_double_host + n_rows), ctx));
+  HIPCHK(ctx, d_means.upload(std::vector<double>(means_host, means_host + n_rows), ctx));
+  HIPCHK(ctx, d_c.alloc((size_t)n_rows));
+  HIPCHK(ctx, d_q.alloc((size_t)S));
+  HIPCHK(ctx, d_K.alloc((size_t)batch * (size_t)S));
+  if (!in_lds) HIPCHK(ctx, d_sort.alloc((size_t)grid_rank * 2 * (size_t)S));
+  HIPCHK(ctx, hipMemsetAsync(d_c.p, 0, (size_t)n_rows * 4, ctx->stream));
+  if (in_lds) HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_minp_rank<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const bool timed = ctx->kernel_times || kn.kernel_times;
+  MinpTimer T;
+  ctx->minp_ms[0] = ctx->minp_ms[1] = 0.f;
+  if (timed) for (hipEvent_t& e : T.ev) HIPCHK(ctx, hipEventCreate(&e));
+  gat::MinpRankArgs R;
+  R.counts = (const int64_t*)counts_dev; R.row_stride = S; R.S = (int32_t)S; R.is_double = d_dbl.p; R.means = d_means.p;
+  R.K = d_K.p; R.sort_scratch = d_sort.p; R.skip_passes = kn.minp_all_passes ? 0 : 1;
+  gat::MinpStepArgs Q;
+  Q.K = d_K.p; Q.S = (int32_t)S; Q.q = d_q.p;
+  const unsigned step_grid = (unsigned)((S + gat::kMinpThreads - 1) / gat::kMinpThreads);
+  for (int64_t p0 = 0; p0 < n_rows; p0 += batch) {                   // (one stream: a batch's K is read before the next one's is written)
+    const int64_t nb = std::min<int64_t>(batch, n_rows - p0);
+    R.n_rows = (int32_t)nb; R.rows = d_rows.p + p0;
+    if (timed) HIPCHK(ctx, hipEventRecord(T.ev[0], ctx->stream));
+    if (in_lds) hipLaunchKernelGGL(gat::k_minp_rank<true>, dim3((unsigned)std::min<int64_t>(nb, grid_rank)), dim3(gat::kMinpThreads), lds, ctx->stream, R);
+    else hipLaunchKernelGGL(gat::k_minp_rank<false>, dim3((unsigned)std::min<int64_t>(nb, grid_rank)), dim3(gat::kMinpThreads), lds, ctx->stream, R);
+    HIPCHK(ctx, hipGetLastError());
+    if (timed) HIPCHK(ctx, hipEventRecord(T.ev[1], ctx->stream));
+    Q.n_rows = (int32_t)nb; Q.kobs = d_kobs.p + p0; Q.c = d_c.p + p0; Q.first = p0 == 0 ? 1 : 0;
+    hipLaunchKernelGGL(gat::k_minp_step, dim3(step_grid), dim3(gat::kMinpThreads), 0, ctx->stream, Q);
+    HIPCHK(ctx, hipGetLastError());
+    if (timed) {
+      HIPCHK(ctx, hipEventRecord(T.ev[2], ctx->stream));
+      HIPCHK(ctx, hipEventSynchronize(T.ev[2]));
+      float a = 0.f, b = 0.f;
+      HIPCHK(ctx, hipEventElapsedTime(&a, T.ev[0], T.ev[1]));
+      HIPCHK(ctx, hipEventElapsedTime(&b, T.ev[1], T.ev[2]));
+      ctx->minp_ms[0] += a; ctx->minp_ms[1] += b;
+    }
+  }
+  std::vector<uint32_t> c((size_t)n_rows);
+  HIPCHK(ctx, staged_d2h(ctx, c.data(), d_c.p, (size_t)n_rows * 4));
+  for (int64_t p = 0; p < n_rows; ++p) c_out_host[proc[(size_t)p]] = (int64_t)c[(size_t)p];
+  return GAT_OK;
+}
+
+extern "C" int gat_minp_times(const gat_ctx* ctx, float* ms_rank, float* ms_step) {
+  if (!ctx || !ms_rank || !ms_step) return set_err(nullptr, GAT_ERR_ARG, "gat_minp_times: NULL argument");
+  *ms_rank = ctx->minp_ms[0];
+  *ms_step = ctx->minp_ms[1];
   return GAT_OK;
 }

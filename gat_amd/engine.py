@@ -1559,6 +1559,7 @@ class AnnotatorResult(object):
         self.nsamples = l
         self._sorted_cache = None
         self._val_counts = None
+        self._has_reference = reference is not None        # (expected is then no longer the mean of the samples: minp.adjust)
         self.expected = float(_stats[0]) if _stats is not None else float(np.mean(self._samples))
         if reference is not None:
             self.expected *= reference.fold
@@ -1732,7 +1733,12 @@ def getQValues(pvalues, method="storey", **kwargs):
 
 
 def updateQValues(annotator_results, method="storey", **kwargs):
-    """gat/Engine.pyx:2044-2054."""
-    pvalues = [r.pvalue for r in annotator_results]
-    for r, qvalue in zip(annotator_results, getQValues(pvalues, method, **kwargs)):
+    """gat/Engine.pyx:2044-2054.  method "minp" (not in the reference): step-down minP from the rows' own samples, on the
+    device (gat_amd/minp.py); getQValues, a function of p-values alone, does not know it."""
+    if method == "minp":
+        from . import minp
+        qvalues = minp.adjust(annotator_results)
+    else:
+        qvalues = getQValues([r.pvalue for r in annotator_results], method, **kwargs)
+    for r, qvalue in zip(annotator_results, qvalues):
         r.qvalue = qvalue

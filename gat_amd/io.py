@@ -407,10 +407,18 @@ def readDescriptions(options):
 def outputResults(results, options, header, description_header=(), description_width=0, descriptions=None,
                   format_observed="%i"):
     """gat/IO.py:457-539: q-values, one table per counter, rows ordered by --order."""
-    pvalues = [x.pvalue for x in results]
-    qvalues = stats.getQValues(pvalues, method=options.qvalue_method,
-                               vlambda=getattr(options, "qvalue_lambda", None),
-                               pi0_method=getattr(options, "qvalue_pi0_method", "smoother"))
+    if options.qvalue_method == "minp":
+        # step-down minP (gat_amd/minp.py): from the rows' samples, not from their p-values -- and those samples are scored
+        # with the empirical p-value, so the rows' own p-values have to be empirical too
+        if getattr(options, "pvalue_method", "empirical") != "empirical":
+            raise ValueError("--qvalue-method=minp needs --pvalue-method=empirical (got %s)" % options.pvalue_method)
+        from . import minp
+        qvalues = minp.adjust(results)
+    else:
+        pvalues = [x.pvalue for x in results]
+        qvalues = stats.getQValues(pvalues, method=options.qvalue_method,
+                                   vlambda=getattr(options, "qvalue_lambda", None),
+                                   pi0_method=getattr(options, "qvalue_pi0_method", "smoother"))
     for x, qvalue in zip(results, qvalues):
         x.qvalue = qvalue
         x.format_observed = format_observed

@@ -538,6 +538,30 @@ int gat_compare_stats(gat_ctx* ctx, const void* a_dev, int64_t n_rows_a, const v
                       const double* obs_a_host, const double* obs_b_host, const double* delta_host,
                       double pseudo_count, int64_t lo_index, int64_t hi_index, double* out_host);
 
+/* ---- step-down minP: family-wise adjusted p-values from the joint null distribution --------
+ * Westfall and Young's step-down minP procedure (as formulated by Ge, Dudoit and Speed 2003) on a count matrix: column i is
+ * what every row of the family scored on the same sample.  counts_dev = n_rows rows of n_samples 8-byte slots, the layout
+ * gat_null_stats reads (int64, or IEEE double for rows with is_double != 0; compared as doubles).  With
+ *     n_less = #{i : row_r[i] < x},  n_eq = #{i : row_r[i] == x}
+ *     T(r, x) = max(1, idx),  idx = 1 if n_less == S,  S - (n_less - [n_eq > 0 and n_less > 0] + 1) if x > means[r],
+ *                                   n_less + n_eq otherwise
+ * (S = n_samples; T / S is getTwoSidedPValue, gat/Engine.pyx:1543-1576, with expected = means[r]) and kobs[r] = T(r, the
+ * row's observed value), formed by the caller:  K[r][i] = T(r, row_r[i]);  the rows ordered by (kobs, r) ascending are
+ * o_1 .. o_R;  q_{R+1}[i] = +inf, q_j[i] = min(q_{j+1}[i], K[o_j][i]);  c_out[o_j] = #{i : q_j[i] <= kobs[o_j]}.
+ * c_out is in the order of the input rows and BEFORE the running maximum: the adjusted p-value of o_j is the largest of
+ * max(1, c_out[o_j']) / S over j' <= j, which the caller forms.  All of it is integer arithmetic.
+ * k_minp_rank sorts every row (in LDS up to GAT_MINP_LDS_SAMPLES samples, default 4096, at most what a workgroup's LDS
+ * holds; beyond in device scratch) and ranks its samples in it; k_minp_step takes the running minimum through the rows,
+ * which are worked on in batches of as many rows of K (4 bytes a sample) as fit GAT_MINP_SCRATCH_MB megabytes (default
+ * 1024).  Both are context options read once at the top of the call; neither changes a result.  n_rows <= 0: GAT_OK, nothing
+ * written.  GAT_ERR_ARG: a NULL argument, n_samples < 1 or >= 2^31, a kobs outside [1, n_samples], an option out of range. */
+int gat_minp_counts(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t n_samples,
+                    const uint8_t* is_double_host, const double* means_host, const int32_t* kobs_host,
+                    int64_t* c_out_host /* n_rows, input row order, before the running maximum */);
+/* device time in milliseconds the context's last gat_minp_counts spent in k_minp_rank and in k_minp_step, summed over its
+ * batches; measured only after gat_ctx_set_kernel_times(ctx, 1) (or GAT_KERNEL_TIMES), else 0 */
+int gat_minp_times(const gat_ctx* ctx, float* ms_rank, float* ms_step);
+
 /* ---- multi-GPU: the one collective of the path ---------------------------------------------
  * Replaces the result collation of the reference's process pool (gat/__init__.py:681-700, :770-774):
  * every rank has computed the columns of its own contiguous sample range (gat_sample_and_count with
