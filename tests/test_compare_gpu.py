@@ -102,6 +102,28 @@ def test_compare_stats_equal_the_model(ctx, S, n_pairs, monkeypatch):
         ctx.free(pb)
 
 
+def _large_case(S):
+    """the matrices, results and three pairs of test_compare_stats_at_large_sample_counts (seed 1000 * S + 3: no sample of the
+    three pairs has a fold ratio within 1e-9 of 1 without being 1, which _check asserts on the host for each pair)"""
+    rs = np.random.RandomState(1000 * S + 3)
+    ma, mb = _matrix(rs, 9, S), _matrix(rs, 7, S)
+    A, B = _results(ma, rs.randint(100, 5000, 9), "a"), _results(mb, rs.randint(100, 5000, 7), "b")
+    return ma, mb, A, B, [0, 1, 8], [1, 1, 6]      # ties against constant, constant against constant, the last rows of both
+
+
+@pytest.mark.parametrize("S", [24577, 40961])
+def test_compare_stats_at_large_sample_counts(ctx, S):
+    """k_compare_rows feeding k_null_stats where np_sum has the partial chunk on wave 3 (three full chunks of 8 192 and one
+    element) and where its waves take a second full chunk (five and one element); the bounds are _check's, unchanged"""
+    ma, mb, A, B, ia, ib = _large_case(S)
+    pa, pb = _upload(ctx, ma), _upload(ctx, mb)
+    try:
+        _check(ctx, A, B, pa, pb, ia, ib, 1.0)
+    finally:
+        ctx.free(pa)
+        ctx.free(pb)
+
+
 def test_bad_arguments(ctx):
     m = np.ones((3, 8))
     p = _upload(ctx, m)
