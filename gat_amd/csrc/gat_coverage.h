@@ -21,6 +21,7 @@
 // The 32-bit words cannot overflow: the launch keeps (samples of a chunk) x (slots of a sample's slab) below 2^31.
 #pragma once
 #include "gat_device.h"
+#include "gat_lists.h"
 
 namespace gat {
 
@@ -36,12 +37,7 @@ struct CoverageWindow {
 };
 
 struct CoverageArgs {
-  const uint2* seg;           // the batch's lists: sample i, contig c at seg + i * seg_stride + c_off[c], n_arr[i * n_stride + n_index[c]] long
-  int64_t seg_stride;
-  const int32_t* c_off;
-  const int32_t* n_arr;
-  int32_t n_stride;
-  const int32_t* n_index;
+  ListSet lists;              // the batch's: n_samples x contigs of them
   int32_t n_samples;
   int32_t samples_per_block;
   int32_t window_bins;        // W: the LDS image is sized for it
@@ -98,14 +94,14 @@ __global__ __launch_bounds__(kCoverageThreads) void k_coverage(CoverageArgs A) {
   if (tid == 0) s_outside = 0ull;
   __syncthreads();
 
-  const int64_t coff = A.c_off[win.contig];
-  const int nidx = A.n_index[win.contig];
   const int i0 = (int)blockIdx.y * A.samples_per_block;
   const int i1 = min(i0 + A.samples_per_block, A.n_samples);
   unsigned long long beyond = 0ull;
+  // (always a sampler batch, so no group count; said aloud, the contig's offset and index are read once, not per sample)
+  __builtin_assume(A.lists.csr == nullptr);
   for (int i = i0 + wave; i < i1; i += kCoverageWaves) {
-    const int n = A.n_arr[(int64_t)i * A.n_stride + nidx];
-    const uint2* __restrict__ seg = A.seg + (int64_t)i * A.seg_stride + coff;
+    int n;
+    const uint2* __restrict__ seg = list_at(A.lists, i, win.contig, 0, n);
     const int j0 = A.sorted ? coverage_first_reaching(seg, n, lo, lane) : 0;
     for (int j = j0 + lane; j < n; j += kWave) {
       const uint2 sg = seg[j];

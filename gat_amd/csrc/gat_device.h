@@ -370,6 +370,16 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
   for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
   return v;
 }
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+__device__ __forceinline__ long long wave_max_i64(long long v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) { const long long o = __shfl_xor(v, d); v = o > v ? o : v; }
+  return v;
+}
 // all-lanes reduction on the DPP path (result broadcast from lane 63); id = identity of op
 template <typename Op>
 __device__ __forceinline__ int wave_reduce_dpp(int v, int id, Op op) {

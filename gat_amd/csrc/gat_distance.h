@@ -16,13 +16,13 @@
 // order in which the groups' partial sums arrive cannot change a bit.  (The caller zeroes the output.)
 // Which side is staged is the direction, and nothing else differs: segment-to-annotation stages the track's contig, shared by
 // every list the workgroup takes; annotation-to-segment stages the sample's list and streams the tracks -- the arrangement of
-// k_count_swap.  Both sides come in either layout (DistanceLists): a sampler batch, or a caller's CSR.
+// k_count_swap.  Both sides come in either layout (ListSet, gat_lists.h): a sampler batch, or a caller's CSR.
 // LDS holds what the search starts in: all K of the staged list when K <= lds_pieces (the search then never leaves the chip),
 // else the last end of each of ceil(K / stride) blocks of `stride` consecutive intervals -- the search finds the block in LDS
-// and ends in global memory, log2(stride) probes (metrics_search's scheme, over uint2 intervals).
+// and ends in global memory, log2(stride) probes (block_search, gat_lists.h).
 #pragma once
 #include "gat_device.h"
-#include "gat_metrics.h"      // wave_sum_i64
+#include "gat_lists.h"
 
 namespace gat {
 
@@ -30,20 +30,8 @@ constexpr int kDistanceThreads = 256;
 constexpr int kDistanceWaves = kDistanceThreads / kWave;
 constexpr int kDistanceWords = 4;
 
-// n_entities x n_groups lists.  csr == nullptr: a sampler batch -- list (i, g) at seg + i * seg_stride + c_off[g],
-// n_arr[i * n_stride + n_index[g]] long (CoverageArgs' / MetricsArgs' layout); else seg[csr[i * n_groups + g] .. csr[i * n_groups + g + 1])
-struct DistanceLists {
-  const uint2* seg;
-  int64_t seg_stride;
-  const int32_t* c_off;
-  const int32_t* n_arr;
-  int32_t n_stride;
-  const int32_t* n_index;
-  const int64_t* csr;
-};
-
 struct DistanceArgs {
-  DistanceLists t, q;                     // the staged side (normalized lists) and the streamed side (queries)
+  ListSet t, q;                           // the staged side (normalized lists) and the streamed side (queries)
   int32_t n_t, n_q;                       // entities on either side
   int32_t n_groups;
   int32_t q_per_block;
@@ -55,37 +43,11 @@ struct DistanceArgs {
 
 __host__ __device__ inline size_t distance_lds_bytes(int64_t L) { return (size_t)L * 8; }
 
-__device__ __forceinline__ const uint2* distance_list(const DistanceLists& S, int64_t i, int g, int G, int& n) {
-  if (S.csr != nullptr) {
-    const int64_t b = S.csr[i * G + g];
-    n = (int)(S.csr[i * G + g + 1] - b);
-    return S.seg + b;
-  }
-  n = S.n_arr[i * S.n_stride + S.n_index[g]];
-  return S.seg + i * S.seg_stride + S.c_off[g];
-}
-
 // d of the query [s, e), e > s, against the K >= 1 intervals T.  l_e[t], t < nl: the end of the last interval of block t
 // (blocks of `stride` intervals; stride 1: the intervals themselves, their starts in l_s)
 __device__ __forceinline__ long long distance_of(const uint32_t* l_s, const uint32_t* l_e, int nl, const uint2* __restrict__ T, int K,
                                                  int stride, uint32_t s, uint32_t e) {
-  int a = 0, b = nl;
-  while (a < b) {
-    const int m = (a + b) >> 1;
-    if (l_e[m] > s) b = m; else a = m + 1;
-  }
-  int j = K;
-  if (a < nl) {
-    j = a;
-    if (stride > 1) {
-      int lo = a * stride, hi = min(K, lo + stride) - 1;      // (T[hi].end is l_e[a]: it qualifies)
-      while (lo < hi) {
-        const int m = (lo + hi) >> 1;
-        if (T[m].y > s) hi = m; else lo = m + 1;
-      }
-      j = lo;
-    }
-  }
+  const int j = block_search<true>(l_e, nl, K, stride, s, [&](int m) { return T[m].y; });      // the first end beyond s
   long long d = LLONG_MAX;
   if (j < K) {
     const long long ts = (long long)(stride == 1 ? l_s[j] : T[j].x);
@@ -107,10 +69,10 @@ __global__ __launch_bounds__(kDistanceThreads) void k_distance(DistanceArgs A) {
   const int64_t ti = (int64_t)(blockIdx.x / (unsigned)G);
   const int g = (int)(blockIdx.x % (unsigned)G);
   int K;
-  const uint2* __restrict__ T = distance_list(A.t, ti, g, G, K);
+  const uint2* __restrict__ T = list_at(A.t, ti, g, G, K);
   const int L = A.lds_pieces;
-  const int stride = K <= L ? 1 : (K + L - 1) / L;
-  const int nl = K == 0 ? 0 : (K + stride - 1) / stride;  // <= L
+  const BlockTable bt = block_table(K, L);
+  const int stride = bt.stride, nl = bt.nl;
   uint32_t* l_s = dist_lds;
   uint32_t* l_e = dist_lds + L;
   for (int t = tid; t < nl; t += kDistanceThreads) {
@@ -124,7 +86,7 @@ __global__ __launch_bounds__(kDistanceThreads) void k_distance(DistanceArgs A) {
   const int q1 = min(q0 + A.q_per_block, A.n_q);
   for (int qi = q0 + wave; qi < q1; qi += kDistanceWaves) {
     int n;
-    const uint2* __restrict__ Q = distance_list(A.q, qi, g, G, n);
+    const uint2* __restrict__ Q = list_at(A.q, qi, g, G, n);
     long long cnt = 0, sum = 0, near = 0;
     for (int j = lane; j < n; j += kWave) {
       const uint2 sg = Q[j];

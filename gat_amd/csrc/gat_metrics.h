@@ -24,6 +24,7 @@
 // in LDS and ends in global memory, log2(stride) probes.  Lists are taken in any order: there is no sorted / unsorted route.
 #pragma once
 #include "gat_device.h"
+#include "gat_lists.h"
 
 namespace gat {
 
@@ -32,15 +33,7 @@ constexpr int kMetricsWaves = kMetricsThreads / kWave;
 constexpr int kMetricsWords = 8;
 
 struct MetricsArgs {
-  // the lists.  csr == nullptr: a sampler batch -- list (i, g) at seg + i * seg_stride + c_off[g], n_arr[i * n_stride +
-  // n_index[g]] long (CoverageArgs' layout); else the caller's: seg[csr[i * n_groups + g] .. csr[i * n_groups + g + 1])
-  const uint2* seg;
-  int64_t seg_stride;
-  const int32_t* c_off;
-  const int32_t* n_arr;
-  int32_t n_stride;
-  const int32_t* n_index;
-  const int64_t* csr;
+  ListSet lists;                          // n_lists x n_groups of them, a sampler batch or the caller's
   int32_t n_lists;
   int32_t n_groups;
   int32_t lists_per_block;
@@ -56,38 +49,6 @@ struct MetricsArgs {
 
 __host__ __device__ inline size_t metrics_lds_bytes(int64_t L) { return (size_t)L * 8; }
 
-// first j in [0, K) whose value is > x (UPPER) / >= x (else), K: none.  lds[t], t < nl: the value of the last piece of block t
-// (blocks of `stride` pieces; stride 1: the pieces themselves); glob: all K values, ascending
-template <bool UPPER>
-__device__ __forceinline__ int metrics_search(const uint32_t* lds, int nl, const uint32_t* __restrict__ glob, int K, int stride, uint32_t x) {
-  int a = 0, b = nl;
-  while (a < b) {
-    const int m = (a + b) >> 1;
-    const uint32_t v = lds[m];
-    if (UPPER ? v > x : v >= x) b = m; else a = m + 1;
-  }
-  if (a == nl) return K;
-  if (stride == 1) return a;
-  int lo = a * stride, hi = min(K, lo + stride) - 1;       // (glob[hi] is lds[a]: it qualifies)
-  while (lo < hi) {
-    const int m = (lo + hi) >> 1;
-    const uint32_t v = glob[m];
-    if (UPPER ? v > x : v >= x) hi = m; else lo = m + 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ long long wave_max_i64(long long v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) { const long long o = __shfl_xor(v, d); v = o > v ? o : v; }
-  return v;
-}
-
 __global__ __launch_bounds__(kMetricsThreads) void k_metrics(MetricsArgs A) {
   extern __shared__ uint32_t met_lds[];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
@@ -98,8 +59,8 @@ __global__ __launch_bounds__(kMetricsThreads) void k_metrics(MetricsArgs A) {
   const unsigned long long* __restrict__ cum = A.ws_cum + wb + g;
   const uint32_t* __restrict__ gaps = A.ws_gaps + wb + g;
   const int L = A.lds_pieces;
-  const int stride = K <= L ? 1 : (K + L - 1) / L;
-  const int nl = K == 0 ? 0 : (K + stride - 1) / stride;  // <= L
+  const BlockTable bt = block_table(K, L);
+  const int stride = bt.stride, nl = bt.nl;
   uint32_t* l_s = met_lds;
   uint32_t* l_e = met_lds + L;
   for (int t = tid; t < nl; t += kMetricsThreads) {
@@ -112,16 +73,8 @@ __global__ __launch_bounds__(kMetricsThreads) void k_metrics(MetricsArgs A) {
   const int i0 = (int)blockIdx.y * A.lists_per_block;
   const int i1 = min(i0 + A.lists_per_block, A.n_lists);
   for (int i = i0 + wave; i < i1; i += kMetricsWaves) {
-    const uint2* __restrict__ seg;
     int n;
-    if (A.csr != nullptr) {
-      const int64_t b = A.csr[(int64_t)i * G + g];
-      seg = A.seg + b;
-      n = (int)(A.csr[(int64_t)i * G + g + 1] - b);
-    } else {
-      seg = A.seg + (int64_t)i * A.seg_stride + A.c_off[g];
-      n = A.n_arr[(int64_t)i * A.n_stride + A.n_index[g]];
-    }
+    const uint2* __restrict__ seg = list_at(A.lists, i, g, G, n);
     long long bases = 0, pairs = 0, inter = 0, touched = 0, pieces = 0, last = -1, tail_n = 0, tail_bases = 0;
     for (int j = lane; j < n; j += kWave) {
       const uint2 sg = seg[j];
@@ -129,8 +82,8 @@ __global__ __launch_bounds__(kMetricsThreads) void k_metrics(MetricsArgs A) {
       bases += e - s;
       int lo = 0, hi = -1;
       if (K > 0) {
-        lo = metrics_search<true>(l_e, nl, ge, K, stride, sg.x);
-        hi = metrics_search<false>(l_s, nl, gs, K, stride, sg.y) - 1;
+        lo = block_search<true>(l_e, nl, K, stride, sg.x, [&](int m) { return ge[m]; });
+        hi = block_search<false>(l_s, nl, K, stride, sg.y, [&](int m) { return gs[m]; }) - 1;
       }
       if (hi < lo) { pieces += 1; continue; }
       const long long w_lo = (long long)(stride == 1 ? l_s[lo] : gs[lo]), w_hi = (long long)(stride == 1 ? l_e[hi] : ge[hi]);

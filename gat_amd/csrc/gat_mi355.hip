@@ -1626,33 +1626,102 @@ extern "C" void gat_mt19937_seed(uint32_t seed, uint32_t* mt_state) {
   mt_state[624] = 624u;
 }
 
-// gat_sample / gat_sample_units: the lists of every (sample, contig) after fromIsochores, or of every (sample, unit)
-// as the sampler returned them
-static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
-                        gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats, bool unit_level) {
-  if (!ctx || !P || !off_host) return set_err(ctx, GAT_ERR_ARG, "gat_sample: NULL argument");
-  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
-  if (P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
+// ---- the entry points that read the sampled lists where they are: gat_sample / gat_sample_units copy them out, and
+// gat_sample_coverage, gat_sample_metrics and gat_sample_distances put a kernel (gat_coverage.h, gat_metrics.h,
+// gat_distance.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
+
+// A synchronous call's frame: refused while a call is in flight on the problem (P == nullptr: a call over the caller's own
+// lists); the knobs are read once; body(kn, local) does the work.  Whatever the body returns, the stream is drained behind it:
+// the device buffers of the call -- declared by the entry point BEFORE the frame, so destroyed after it -- go back to the
+// process-wide pool, which hands an idle block to any context or stream, only when no kernel reads them any more.
+template <class Body>
+static int call_frame(gat_ctx* ctx, gat_problem* P, gat_stats* stats, Body body) {
+  if (P && P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const Knobs kn = read_knobs(ctx);
   gat_stats local;
   memset(&local, 0, sizeof(local));
-  const int64_t S = sample_end - sample_begin;
-  const int C = unit_level ? P->n_units : P->n_contigs;
+  const int rc = body(kn, local);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->stage_used = 0;
+  if (stats) *stats = local;
+  return rc;
+}
+
+// S samples in batches as the scratch takes them: after_batch(done, nb) behind every batch that passed its checks -- a batch
+// that is laid out again (kRelayout) or failed never gets there, so nothing of it is seen twice -- and the batch is counted.
+// (timed unless another problem's call in flight owns the context's per-kernel events)
+template <class After>
+static int for_each_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                                  gat_stats& local, const BatchOpts& opts, After after_batch) {
   int rc;
-  int64_t done = 0, total = 0;
+  int64_t done = 0;
+  while (done < S) {
+    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
+    const int64_t nb = std::min<int64_t>(P->batch, S - done);
+    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr, opts)) == kRelayout) continue;
+    if (rc) return rc;
+    if ((rc = after_batch(done, nb))) return rc;
+    local.n_batches += 1;
+    done += nb;
+  }
+  return GAT_OK;
+}
+
+// the contig-level lists of a finished batch, as the kernels reach them (list_at)
+static gat::ListSet sampled_lists(const gat_problem* P) {
+  gat::ListSet S = {};
+  S.seg = P->merge_contigs ? P->d_cslab.p : P->final_slab();
+  S.seg_stride = P->slab_stride;
+  S.c_off = P->d_count_c_off.p;
+  S.n_arr = P->merge_contigs ? P->d_contig_n.p : P->d_unit_n.p;
+  S.n_stride = P->merge_contigs ? P->n_contigs : P->n_units;
+  S.n_index = P->d_count_n_index.p;
+  return S;
+}
+// ... and whether they are normalized: SamplerSegments without isochore keys leaves them neither sorted nor disjoint
+static bool sampled_lists_normalized(const gat_problem* P) { return !(P->sampler == GAT_SAMPLER_SEGMENTS && !P->merge_contigs); }
+
+// offsets of n caller-provided lists of `noun`: GAT_ERR_ARG where they start below 0, decrease, or a list is longer than 2^31 - 1
+static int check_list_offsets(gat_ctx* ctx, const char* who, const char* what, const char* noun, const int64_t* off, int64_t n) {
+  if (off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: %s[0] < 0", who, what);
+  for (int64_t l = 0; l < n; ++l)
+    if (off[l + 1] < off[l] || off[l + 1] - off[l] > (int64_t)INT32_MAX)
+      return set_err(ctx, GAT_ERR_ARG, "%s: %s decreases, or a list of more than 2^31 - 1 %s, at list %lld", who, what, noun, (long long)l);
+  return GAT_OK;
+}
+// n caller-provided lists a[off[0] .. off[n]) on the device: the intervals built in the pinned staging buffer, the offsets from 0
+static int upload_csr_lists(gat_ctx* ctx, const gat_segment* a, const int64_t* off, int64_t n, DevBuf<uint2>& d_seg, DevBuf<int64_t>& d_csr) {
+  const int64_t base = off[0], total = off[n] - base;
+  HIPCHK(ctx, d_seg.upload_built((size_t)total, ctx, [&](uint2* h) {
+    for (int64_t i = 0; i < total; ++i) h[i] = make_uint2(a[base + i].start, a[base + i].end);
+  }));
+  std::vector<int64_t> h_csr((size_t)n + 1);
+  for (int64_t l = 0; l <= n; ++l) h_csr[(size_t)l] = off[l] - base;
+  HIPCHK(ctx, d_csr.upload(h_csr, ctx));
+  HIPCHK(ctx, stage_flush(ctx));                    // (h_csr goes away with this frame)
+  return GAT_OK;
+}
+static gat::ListSet csr_lists(const DevBuf<uint2>& d_seg, const DevBuf<int64_t>& d_csr) {
+  gat::ListSet S = {};
+  S.seg = d_seg.p;
+  S.csr = d_csr.p;
+  return S;
+}
+
+// gat_sample / gat_sample_units: the lists of every (sample, contig) after fromIsochores, or of every (sample, unit)
+// as the sampler returned them
+static int sample_lists_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                             gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats& local, bool unit_level) {
+  const int C = unit_level ? P->n_units : P->n_contigs;
+  int64_t total = 0;
   bool overflow = false;
   off_host[0] = 0;
   std::vector<uint2> h_slab;
   std::vector<int32_t> h_n;
-  while (done < S) {
-    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
-    const int64_t nb = std::min<int64_t>(P->batch, S - done);
-    // (timed unless another problem's call in flight owns the context's per-kernel events)
-    BatchOpts o;
-    o.need_unit_lists = unit_level;
-    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr, o)) == kRelayout) continue;
-    if (rc) { if (stats) *stats = local; return rc; }
+  BatchOpts o;
+  o.need_unit_lists = unit_level;
+  const int rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, o, [&](int64_t done, int64_t nb) {
     const bool from_contigs = P->merge_contigs && !unit_level;
     const uint2* src = from_contigs ? P->d_cslab.p : P->final_slab();
     const int32_t* nsrc = from_contigs ? P->d_contig_n.p : P->d_unit_n.p;
@@ -1673,12 +1742,20 @@ static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sam
         off_host[(done + i) * C + c + 1] = total;
       }
     }
-    done += nb;
-  }
+    return GAT_OK;
+  });
+  if (rc) return rc;
   local.n_sampled_segments = total;
-  if (stats) *stats = local;
   if (overflow) return set_err(ctx, GAT_ERR_CAPACITY, "gat_sample: output needs %lld segments, cap is %lld", (long long)total, (long long)cap);
   return GAT_OK;
+}
+static int sample_lists(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                        gat_segment* out_host, int64_t cap, int64_t* off_host, gat_stats* stats, bool unit_level) {
+  if (!ctx || !P || !off_host) return set_err(ctx, GAT_ERR_ARG, "gat_sample: NULL argument");
+  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    return sample_lists_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, out_host, cap, off_host, local, unit_level);
+  });
 }
 
 extern "C" int gat_sample(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
@@ -1690,9 +1767,8 @@ extern "C" int gat_sample_units(gat_ctx* ctx, gat_problem* P, uint32_t seed, int
   return sample_lists(ctx, P, seed, sample_begin, sample_end, out_host, cap, off_host, stats, true);
 }
 
-// gat_sample_coverage: sample_lists' batch loop with k_coverage (gat_coverage.h) behind every batch that passed its checks,
-// where sample_lists copies the lists out.  The device result lives for the call (it goes back to the process-wide pool when
-// it is destroyed: sample_coverage drains the stream before that, on every path out).
+// gat_sample_coverage: k_coverage (gat_coverage.h) behind every batch, where sample_lists copies the lists out.  The device
+// result lives for the call.
 struct CoverageBufs {
   DevBuf<gat::CoverageWindow> d_win;
   DevBuf<unsigned long long> d_bases, d_starts, d_ends, d_outside;
@@ -1726,43 +1802,23 @@ static int sample_coverage_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, u
   }
   const size_t lds = gat::coverage_lds_bytes(W);
   HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_coverage, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int rc;
-  int64_t done = 0;
-  while (done < S) {
-    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
-    const int64_t nb = std::min<int64_t>(P->batch, S - done);
-    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr)) == kRelayout) continue;
-    if (rc) return rc;
-    // (the batch passed its checks: a batch that is laid out again never got here)
-    if (!win.empty()) {
-      gat::CoverageArgs A;
-      A.seg = P->merge_contigs ? P->d_cslab.p : P->final_slab();
-      A.seg_stride = P->slab_stride;
-      A.c_off = P->d_count_c_off.p;
-      A.n_arr = P->merge_contigs ? P->d_contig_n.p : P->d_unit_n.p;
-      A.n_stride = P->merge_contigs ? P->n_contigs : P->n_units;
-      A.n_index = P->d_count_n_index.p;
-      A.n_samples = (int32_t)nb;
-      A.window_bins = (int32_t)W;
-      A.sorted = (P->sampler == GAT_SAMPLER_SEGMENTS && !P->merge_contigs) ? 0 : 1;
-      A.bin_size = bin_size;
-      A.win = B.d_win.p;
-      A.bases = B.d_bases.p; A.starts = want_se ? B.d_starts.p : nullptr; A.ends = want_se ? B.d_ends.p : nullptr; A.outside = B.d_outside.p;
-      // the chunk: the knob's, else the whole batch halved until the launch has four workgroups for each of 256 compute units;
-      // never so long that a 32-bit word of the window could overflow (a sample holds at most slab_stride segments), and
-      // within the grid's y
-      int64_t spb = kn.coverage_samples_per_block > 0 ? kn.coverage_samples_per_block : nb;
-      if (kn.coverage_samples_per_block <= 0)
-        while (spb > 16 && (int64_t)win.size() * ((nb + spb - 1) / spb) < 1024) spb = (spb + 1) / 2;
-      spb = std::max<int64_t>(1, std::min<int64_t>(std::min(spb, nb), (int64_t)INT32_MAX / std::max<int64_t>(1, P->slab_stride)));
-      spb = std::max(spb, (nb + 65534) / 65535);
-      A.samples_per_block = (int32_t)spb;
-      hipLaunchKernelGGL(gat::k_coverage, dim3((unsigned)win.size(), (unsigned)((nb + spb - 1) / spb)), dim3(gat::kCoverageThreads), lds, ctx->stream, A);
-      HIPCHK(ctx, hipGetLastError());
-    }
-    local.n_batches += 1;
-    done += nb;
-  }
+  const int rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t, int64_t nb) {
+    if (win.empty()) return GAT_OK;
+    gat::CoverageArgs A;
+    A.lists = sampled_lists(P);
+    A.n_samples = (int32_t)nb;
+    A.window_bins = (int32_t)W;
+    A.sorted = sampled_lists_normalized(P) ? 1 : 0;
+    A.bin_size = bin_size;
+    A.win = B.d_win.p;
+    A.bases = B.d_bases.p; A.starts = want_se ? B.d_starts.p : nullptr; A.ends = want_se ? B.d_ends.p : nullptr; A.outside = B.d_outside.p;
+    const int64_t spb = gat::coverage_run_per_block(nb, (int64_t)win.size(), kn.coverage_samples_per_block, P->slab_stride);
+    A.samples_per_block = (int32_t)spb;
+    hipLaunchKernelGGL(gat::k_coverage, dim3((unsigned)win.size(), (unsigned)((nb + spb - 1) / spb)), dim3(gat::kCoverageThreads), lds, ctx->stream, A);
+    HIPCHK(ctx, hipGetLastError());
+    return GAT_OK;
+  });
+  if (rc) return rc;
   if (total > 0) HIPCHK(ctx, staged_d2h(ctx, bases_host, B.d_bases.p, (size_t)total * 8));
   if (total > 0 && starts_host) HIPCHK(ctx, staged_d2h(ctx, starts_host, B.d_starts.p, (size_t)total * 8));
   if (total > 0 && ends_host) HIPCHK(ctx, staged_d2h(ctx, ends_host, B.d_ends.p, (size_t)total * 8));
@@ -1779,32 +1835,24 @@ extern "C" int gat_sample_coverage(gat_ctx* ctx, gat_problem* P, uint32_t seed, 
   for (int c = 0; c < P->n_contigs; ++c)
     if (bin_off[c + 1] < bin_off[c]) return set_err(ctx, GAT_ERR_ARG, "gat_sample_coverage: bin_off decreases at contig %d", c);
   if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
-  if (P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const Knobs kn = read_knobs(ctx);
-  gat_stats local;
-  memset(&local, 0, sizeof(local));
-  const int64_t total = bin_off[P->n_contigs], S = sample_end - sample_begin;
-  if (S == 0) {                                                    // (no batch runs: the sums are empty)
-    memset(bases_host, 0, (size_t)total * 8);
-    if (starts_host) memset(starts_host, 0, (size_t)total * 8);
-    if (ends_host) memset(ends_host, 0, (size_t)total * 8);
-    memset(outside_host, 0, (size_t)P->n_contigs * 8);
-    if (stats) *stats = local;
-    return GAT_OK;
-  }
   CoverageBufs B;
-  const int rc = sample_coverage_body(ctx, P, kn, seed, sample_begin, S, bin_size, bin_off, bases_host, starts_host, ends_host,
-                                      outside_host, local, B);
-  (void)hipStreamSynchronize(ctx->stream);
-  ctx->stage_used = 0;
-  if (stats) *stats = local;
-  return rc;
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    const int64_t total = bin_off[P->n_contigs], S = sample_end - sample_begin;
+    if (S == 0) {                                                  // (no batch runs: the sums are empty)
+      memset(bases_host, 0, (size_t)total * 8);
+      if (starts_host) memset(starts_host, 0, (size_t)total * 8);
+      if (ends_host) memset(ends_host, 0, (size_t)total * 8);
+      memset(outside_host, 0, (size_t)P->n_contigs * 8);
+      return GAT_OK;
+    }
+    return sample_coverage_body(ctx, P, kn, seed, sample_begin, S, bin_size, bin_off, bases_host, starts_host, ends_host,
+                                outside_host, local, B);
+  });
 }
 
-// gat_list_metrics / gat_sample_metrics: k_metrics (gat_metrics.h) over caller-provided lists, or behind every batch of
-// sample_lists' loop that passed its checks.  The groups' pieces and their prefix tables (gat_metrics_tables.h) are made on
-// the host per call.  The device buffers live for the call: both entry points drain the stream before they go back to the pool.
+// gat_list_metrics / gat_sample_metrics: k_metrics (gat_metrics.h) over caller-provided lists, or behind every batch.  The
+// groups' pieces and their prefix tables (gat_metrics_tables.h) are made on the host per call.  The device buffers live for
+// the call.
 struct MetricsBufs {
   DevBuf<uint32_t> d_start, d_end, d_gaps;
   DevBuf<unsigned long long> d_cum;
@@ -1832,9 +1880,7 @@ static int metrics_upload_groups(gat_ctx* ctx, const gat_segment* ws, const int6
 static int launch_metrics(gat_ctx* ctx, const Knobs& kn, gat::MetricsArgs A, int64_t n_lists, const MetricsBufs& B) {
   if (n_lists == 0 || A.n_groups == 0) return GAT_OK;
   const int64_t L = std::max<int64_t>(1, std::min<int64_t>(kn.metrics_lds_pieces, ((int64_t)ctx->max_lds - 1024) / 8));
-  int64_t lpb = n_lists;
-  while (lpb > 16 && (int64_t)A.n_groups * ((n_lists + lpb - 1) / lpb) < 2048) lpb = (lpb + 1) / 2;
-  lpb = std::max<int64_t>(std::max<int64_t>(1, std::min(lpb, n_lists)), (n_lists + 65534) / 65535);
+  const int64_t lpb = gat::run_per_block(n_lists, A.n_groups, 2048, gat::kNoRunCap);
   A.n_lists = (int32_t)n_lists;
   A.lists_per_block = (int32_t)lpb;
   A.lds_pieces = (int32_t)L;
@@ -1849,20 +1895,20 @@ static int launch_metrics(gat_ctx* ctx, const Knobs& kn, gat::MetricsArgs A, int
 
 static int list_metrics_body(gat_ctx* ctx, const Knobs& kn, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
                              const gat_segment* ws, const int64_t* ws_off, int32_t n_groups, int64_t* out_host, MetricsBufs& B) {
-  const int64_t n = n_lists * n_groups, base = list_off[0], total = list_off[n] - base;
+  const int64_t n = n_lists * n_groups;
   int rc;
+  if (n == 0) {                                     // (no list: only the groups are looked at)
+    MetricsTables T;
+    std::string err;
+    rc = metrics_build_tables(ws, ws_off, n_groups, T, err);
+    return rc ? set_err(ctx, rc, "gat_list_metrics: %s", err.c_str()) : GAT_OK;
+  }
   if ((rc = metrics_upload_groups(ctx, ws, ws_off, n_groups, B, "gat_list_metrics"))) return rc;
-  std::vector<uint2> h_seg((size_t)total);
-  for (int64_t i = 0; i < total; ++i) h_seg[(size_t)i] = make_uint2(lists[base + i].start, lists[base + i].end);
-  std::vector<int64_t> h_csr((size_t)n + 1);
-  for (int64_t l = 0; l <= n; ++l) h_csr[(size_t)l] = list_off[l] - base;
-  HIPCHK(ctx, B.d_seg.upload(h_seg, ctx));
-  HIPCHK(ctx, B.d_csr.upload(h_csr, ctx));
+  if ((rc = upload_csr_lists(ctx, lists, list_off, n, B.d_seg, B.d_csr))) return rc;
   HIPCHK(ctx, B.d_out.alloc((size_t)n * gat::kMetricsWords));
   gat::MetricsArgs A;
   memset(&A, 0, sizeof(A));
-  A.seg = B.d_seg.p;
-  A.csr = B.d_csr.p;
+  A.lists = csr_lists(B.d_seg, B.d_csr);
   A.n_groups = n_groups;
   if ((rc = launch_metrics(ctx, kn, A, n_lists, B))) return rc;
   HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, (size_t)n * gat::kMetricsWords * 8));
@@ -1874,26 +1920,15 @@ extern "C" int gat_list_metrics(gat_ctx* ctx, const gat_segment* lists, const in
   if (!ctx || !list_off || !ws_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: NULL argument");
   if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: n_lists %lld, n_groups %d", (long long)n_lists, n_groups);
   const int64_t n = n_lists * n_groups;
-  if (list_off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: list_off[0] < 0");
-  for (int64_t l = 0; l < n; ++l)
-    if (list_off[l + 1] < list_off[l] || list_off[l + 1] - list_off[l] > (int64_t)INT32_MAX)
-      return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: list_off decreases, or a list of more than 2^31 - 1 segments, at list %lld", (long long)l);
+  int rc;
+  if ((rc = check_list_offsets(ctx, "gat_list_metrics", "list_off", "segments", list_off, n))) return rc;
   if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: NULL argument");
   for (int64_t i = list_off[0]; i < list_off[n]; ++i)
     if (lists[i].end < lists[i].start) return set_err(ctx, GAT_ERR_ARG, "gat_list_metrics: segment %lld ends before it starts", (long long)i);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (n == 0) {                                     // (no list: only the groups are looked at)
-    MetricsTables T;
-    std::string err;
-    const int rc = metrics_build_tables(ws, ws_off, n_groups, T, err);
-    return rc ? set_err(ctx, rc, "gat_list_metrics: %s", err.c_str()) : GAT_OK;
-  }
-  const Knobs kn = read_knobs(ctx);
   MetricsBufs B;
-  const int rc = list_metrics_body(ctx, kn, lists, list_off, n_lists, ws, ws_off, n_groups, out_host, B);
-  (void)hipStreamSynchronize(ctx->stream);
-  ctx->stage_used = 0;
-  return rc;
+  return call_frame(ctx, nullptr, nullptr, [&](const Knobs& kn, gat_stats&) {
+    return list_metrics_body(ctx, kn, lists, list_off, n_lists, ws, ws_off, n_groups, out_host, B);
+  });
 }
 
 static int sample_metrics_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
@@ -1901,66 +1936,37 @@ static int sample_metrics_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, ui
   const int C = P->n_contigs;
   int rc;
   if ((rc = metrics_upload_groups(ctx, ws, ws_off, C, B, "gat_sample_metrics"))) return rc;
-  int64_t done = 0;
-  while (done < S) {
-    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
-    const int64_t nb = std::min<int64_t>(P->batch, S - done);
-    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr)) == kRelayout) continue;
-    if (rc) return rc;
-    // (the batch passed its checks: a batch that is laid out again never got here)
-    if (C > 0) {
-      if (B.d_out.n < (size_t)(nb * C * gat::kMetricsWords)) HIPCHK(ctx, B.d_out.alloc((size_t)(nb * C * gat::kMetricsWords)));
-      gat::MetricsArgs A;
-      memset(&A, 0, sizeof(A));
-      A.seg = P->merge_contigs ? P->d_cslab.p : P->final_slab();
-      A.seg_stride = P->slab_stride;
-      A.c_off = P->d_count_c_off.p;
-      A.n_arr = P->merge_contigs ? P->d_contig_n.p : P->d_unit_n.p;
-      A.n_stride = P->merge_contigs ? P->n_contigs : P->n_units;
-      A.n_index = P->d_count_n_index.p;
-      A.n_groups = C;
-      if ((rc = launch_metrics(ctx, kn, A, nb, B))) return rc;
-      HIPCHK(ctx, staged_d2h(ctx, out_host + done * C * gat::kMetricsWords, B.d_out.p, (size_t)(nb * C * gat::kMetricsWords) * 8));
-    }
-    local.n_batches += 1;
-    done += nb;
-  }
-  return GAT_OK;
+  return for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t done, int64_t nb) {
+    if (C == 0) return GAT_OK;
+    if (B.d_out.n < (size_t)(nb * C * gat::kMetricsWords)) HIPCHK(ctx, B.d_out.alloc((size_t)(nb * C * gat::kMetricsWords)));
+    gat::MetricsArgs A;
+    memset(&A, 0, sizeof(A));
+    A.lists = sampled_lists(P);
+    A.n_groups = C;
+    const int lrc = launch_metrics(ctx, kn, A, nb, B);
+    if (lrc) return lrc;
+    HIPCHK(ctx, staged_d2h(ctx, out_host + done * C * gat::kMetricsWords, B.d_out.p, (size_t)(nb * C * gat::kMetricsWords) * 8));
+    return GAT_OK;
+  });
 }
 
 extern "C" int gat_sample_metrics(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
                                   const gat_segment* ws, const int64_t* ws_off, int64_t* out_host, gat_stats* stats) {
   if (!ctx || !P || !ws_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "gat_sample_metrics: NULL argument");
   if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
-  if (P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const Knobs kn = read_knobs(ctx);
-  gat_stats local;
-  memset(&local, 0, sizeof(local));
   MetricsBufs B;
-  const int rc = sample_metrics_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, ws, ws_off, out_host, local, B);
-  (void)hipStreamSynchronize(ctx->stream);
-  ctx->stage_used = 0;
-  if (stats) *stats = local;
-  return rc;
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    return sample_metrics_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, ws, ws_off, out_host, local, B);
+  });
 }
 
-// gat_list_distances / gat_sample_distances: k_distance (gat_distance.h) over caller-provided lists, or behind every batch of
-// sample_lists' loop that passed its checks.  The annotation tracks go up once per call as they are given (CSR, uint2); the
-// device buffers live for the call: both entry points drain the stream before they go back to the pool.
+// gat_list_distances / gat_sample_distances: k_distance (gat_distance.h) over caller-provided lists, or behind every batch.
+// The annotation tracks go up once per call as they are given (CSR, uint2); the device buffers live for the call.
 struct DistanceBufs {
   DevBuf<uint2> d_anno, d_seg;
   DevBuf<int64_t> d_anno_csr, d_csr;
   DevBuf<unsigned long long> d_out;
 };
-// offsets of n lists: GAT_ERR_ARG where they start below 0, decrease, or a list is longer than 2^31 - 1
-static int distance_check_offsets(gat_ctx* ctx, const char* who, const char* what, const int64_t* off, int64_t n) {
-  if (off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: %s[0] < 0", who, what);
-  for (int64_t l = 0; l < n; ++l)
-    if (off[l + 1] < off[l] || off[l + 1] - off[l] > (int64_t)INT32_MAX)
-      return set_err(ctx, GAT_ERR_ARG, "%s: %s decreases, or a list of more than 2^31 - 1 intervals, at list %lld", who, what, (long long)l);
-  return GAT_OK;
-}
 // the searched side: every one of n_entities x n_groups lists sorted, disjoint, without an empty interval
 static int distance_check_normalized(gat_ctx* ctx, const char* who, const char* what, const gat_segment* a, const int64_t* off,
                                      int64_t n_entities, int32_t n_groups) {
@@ -1974,29 +1980,11 @@ static int distance_check_normalized(gat_ctx* ctx, const char* who, const char* 
     }
   return GAT_OK;
 }
-static int distance_upload(gat_ctx* ctx, const gat_segment* a, const int64_t* off, int64_t n, DevBuf<uint2>& d_seg, DevBuf<int64_t>& d_csr) {
-  const int64_t base = off[0], total = off[n] - base;
-  HIPCHK(ctx, d_seg.upload_built((size_t)total, ctx, [&](uint2* h) {
-    for (int64_t i = 0; i < total; ++i) h[i] = make_uint2(a[base + i].start, a[base + i].end);
-  }));
-  std::vector<int64_t> h_csr((size_t)n + 1);
-  for (int64_t l = 0; l <= n; ++l) h_csr[(size_t)l] = off[l] - base;
-  HIPCHK(ctx, d_csr.upload(h_csr, ctx));
-  HIPCHK(ctx, stage_flush(ctx));                    // (h_csr goes away with this frame)
-  return GAT_OK;
-}
-static gat::DistanceLists distance_csr(const DistanceBufs& B, bool annos) {
-  gat::DistanceLists S;
-  memset(&S, 0, sizeof(S));
-  S.seg = annos ? B.d_anno.p : B.d_seg.p;
-  S.csr = annos ? B.d_anno_csr.p : B.d_csr.p;
-  return S;
-}
 // the launch over n_lists x n_tracks x n_groups pairs of lists, `lists` in either layout.  A workgroup stages one list of the
 // searched side -- the tracks' in direction 0, the segment lists' in direction 1 -- and takes a run of the other side's: the
 // run as long as leaves 2 048 workgroups (eight for each of 256 compute units) but at least 16 lists, within the grid's y.
 // B.d_out holds n_lists * n_tracks * 4 words, zeroed here.
-static int launch_distance(gat_ctx* ctx, const Knobs& kn, const gat::DistanceLists& lists, int64_t n_lists, int32_t n_tracks,
+static int launch_distance(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists, int64_t n_lists, int32_t n_tracks,
                            int32_t n_groups, int direction, int64_t max_distance, const DistanceBufs& B) {
   const int64_t words = n_lists * n_tracks * gat::kDistanceWords;
   if (words == 0) return GAT_OK;
@@ -2005,8 +1993,9 @@ static int launch_distance(gat_ctx* ctx, const Knobs& kn, const gat::DistanceLis
   gat::DistanceArgs A;
   memset(&A, 0, sizeof(A));
   const bool seg_to_anno = direction == GAT_DISTANCE_SEGMENT_TO_ANNOTATION;
-  A.t = seg_to_anno ? distance_csr(B, true) : lists;
-  A.q = seg_to_anno ? lists : distance_csr(B, true);
+  const gat::ListSet tracks = csr_lists(B.d_anno, B.d_anno_csr);
+  A.t = seg_to_anno ? tracks : lists;
+  A.q = seg_to_anno ? lists : tracks;
   const int64_t n_t = seg_to_anno ? n_tracks : n_lists, n_q = seg_to_anno ? n_lists : n_tracks;
   if (n_t * n_groups > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_CAPACITY, "gat distances: %lld x %d searched lists in one launch", (long long)n_t, n_groups);
   A.n_t = (int32_t)n_t;
@@ -2018,9 +2007,7 @@ static int launch_distance(gat_ctx* ctx, const Knobs& kn, const gat::DistanceLis
   A.out = B.d_out.p;
   const int64_t L = std::max<int64_t>(1, std::min<int64_t>(kn.distance_lds_pieces, ((int64_t)ctx->max_lds - 1024) / 8));
   A.lds_pieces = (int32_t)L;
-  int64_t qpb = n_q;
-  while (qpb > 16 && n_t * n_groups * ((n_q + qpb - 1) / qpb) < 2048) qpb = (qpb + 1) / 2;
-  qpb = std::max<int64_t>(std::max<int64_t>(1, std::min(qpb, n_q)), (n_q + 65534) / 65535);
+  const int64_t qpb = gat::run_per_block(n_q, n_t * n_groups, 2048, gat::kNoRunCap);
   A.q_per_block = (int32_t)qpb;
   const size_t lds = gat::distance_lds_bytes(L);
   HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_distance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2038,7 +2025,7 @@ static int distance_check_common(gat_ctx* ctx, const char* who, const gat_segmen
     return set_err(ctx, GAT_ERR_ARG, "%s: n_tracks %lld", who, (long long)n_tracks);
   const int64_t n = n_tracks * n_groups;
   int rc;
-  if ((rc = distance_check_offsets(ctx, who, "anno_off", anno_off, n))) return rc;
+  if ((rc = check_list_offsets(ctx, who, "anno_off", "intervals", anno_off, n))) return rc;
   if (anno_off[n] > anno_off[0] && !annos) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
   if (direction == GAT_DISTANCE_SEGMENT_TO_ANNOTATION && (rc = distance_check_normalized(ctx, who, "annotation track", annos, anno_off, n_tracks, (int32_t)n_groups))) return rc;
   return GAT_OK;
@@ -2048,11 +2035,11 @@ static int list_distances_body(gat_ctx* ctx, const Knobs& kn, const gat_segment*
                                const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups, int direction,
                                int64_t max_distance, int64_t* out_host, DistanceBufs& B) {
   int rc;
-  if ((rc = distance_upload(ctx, annos, anno_off, (int64_t)n_tracks * n_groups, B.d_anno, B.d_anno_csr))) return rc;
-  if ((rc = distance_upload(ctx, lists, list_off, n_lists * n_groups, B.d_seg, B.d_csr))) return rc;
+  if ((rc = upload_csr_lists(ctx, annos, anno_off, (int64_t)n_tracks * n_groups, B.d_anno, B.d_anno_csr))) return rc;
+  if ((rc = upload_csr_lists(ctx, lists, list_off, n_lists * n_groups, B.d_seg, B.d_csr))) return rc;
   const size_t words = (size_t)(n_lists * n_tracks * gat::kDistanceWords);
   HIPCHK(ctx, B.d_out.alloc(words));
-  if ((rc = launch_distance(ctx, kn, distance_csr(B, false), n_lists, n_tracks, n_groups, direction, max_distance, B))) return rc;
+  if ((rc = launch_distance(ctx, kn, csr_lists(B.d_seg, B.d_csr), n_lists, n_tracks, n_groups, direction, max_distance, B))) return rc;
   HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, words * 8));
   return GAT_OK;
 }
@@ -2067,17 +2054,14 @@ extern "C" int gat_list_distances(gat_ctx* ctx, const gat_segment* lists, const 
   int rc;
   if ((rc = distance_check_common(ctx, who, annos, anno_off, n_tracks, n_groups, direction, max_distance))) return rc;
   const int64_t n = n_lists * n_groups;
-  if ((rc = distance_check_offsets(ctx, who, "list_off", list_off, n))) return rc;
+  if ((rc = check_list_offsets(ctx, who, "list_off", "intervals", list_off, n))) return rc;
   if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
   if (direction == GAT_DISTANCE_ANNOTATION_TO_SEGMENT && (rc = distance_check_normalized(ctx, who, "segment list", lists, list_off, n_lists, n_groups))) return rc;
   if (n_lists == 0 || n_tracks == 0) return GAT_OK;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const Knobs kn = read_knobs(ctx);
   DistanceBufs B;
-  rc = list_distances_body(ctx, kn, lists, list_off, n_lists, annos, anno_off, n_tracks, n_groups, direction, max_distance, out_host, B);
-  (void)hipStreamSynchronize(ctx->stream);
-  ctx->stage_used = 0;
-  return rc;
+  return call_frame(ctx, nullptr, nullptr, [&](const Knobs& kn, gat_stats&) {
+    return list_distances_body(ctx, kn, lists, list_off, n_lists, annos, anno_off, n_tracks, n_groups, direction, max_distance, out_host, B);
+  });
 }
 
 static int sample_distances_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
@@ -2085,32 +2069,16 @@ static int sample_distances_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, 
                                  int64_t* out_host, gat_stats& local, DistanceBufs& B) {
   const int C = P->n_contigs;
   int rc;
-  if ((rc = distance_upload(ctx, annos, anno_off, (int64_t)n_tracks * C, B.d_anno, B.d_anno_csr))) return rc;
-  int64_t done = 0;
-  while (done < S) {
-    if ((rc = ensure_scratch(ctx, P, kn, S - done))) return rc;
-    const int64_t nb = std::min<int64_t>(P->batch, S - done);
-    if ((rc = run_sampler_batch(ctx, P, kn, seed, sample_begin + done, nb, &local, ctx->timed_owner == nullptr)) == kRelayout) continue;
-    if (rc) return rc;
-    // (the batch passed its checks: a batch that is laid out again never got here)
+  if ((rc = upload_csr_lists(ctx, annos, anno_off, (int64_t)n_tracks * C, B.d_anno, B.d_anno_csr))) return rc;
+  return for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t done, int64_t nb) {
     const size_t words = (size_t)(nb * n_tracks * gat::kDistanceWords);
-    if (words > 0) {
-      if (B.d_out.n < words) HIPCHK(ctx, B.d_out.alloc(words));
-      gat::DistanceLists Sl;
-      memset(&Sl, 0, sizeof(Sl));
-      Sl.seg = P->merge_contigs ? P->d_cslab.p : P->final_slab();
-      Sl.seg_stride = P->slab_stride;
-      Sl.c_off = P->d_count_c_off.p;
-      Sl.n_arr = P->merge_contigs ? P->d_contig_n.p : P->d_unit_n.p;
-      Sl.n_stride = P->merge_contigs ? P->n_contigs : P->n_units;
-      Sl.n_index = P->d_count_n_index.p;
-      if ((rc = launch_distance(ctx, kn, Sl, nb, n_tracks, C, direction, max_distance, B))) return rc;
-      HIPCHK(ctx, staged_d2h(ctx, out_host + done * n_tracks * gat::kDistanceWords, B.d_out.p, words * 8));
-    }
-    local.n_batches += 1;
-    done += nb;
-  }
-  return GAT_OK;
+    if (words == 0) return GAT_OK;
+    if (B.d_out.n < words) HIPCHK(ctx, B.d_out.alloc(words));
+    const int lrc = launch_distance(ctx, kn, sampled_lists(P), nb, n_tracks, C, direction, max_distance, B);
+    if (lrc) return lrc;
+    HIPCHK(ctx, staged_d2h(ctx, out_host + done * n_tracks * gat::kDistanceWords, B.d_out.p, words * 8));
+    return GAT_OK;
+  });
 }
 
 extern "C" int gat_sample_distances(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
@@ -2122,25 +2090,15 @@ extern "C" int gat_sample_distances(gat_ctx* ctx, gat_problem* P, uint32_t seed,
   int rc;
   if ((rc = distance_check_common(ctx, who, annos, anno_off, n_tracks, P->n_contigs, direction, max_distance))) return rc;
   // the searched side of direction 1 is the sampler's: the flag k_coverage gets
-  if (direction == GAT_DISTANCE_ANNOTATION_TO_SEGMENT && P->sampler == GAT_SAMPLER_SEGMENTS && !P->merge_contigs)
+  if (direction == GAT_DISTANCE_ANNOTATION_TO_SEGMENT && !sampled_lists_normalized(P))
     return set_err(ctx, GAT_ERR_ARG, "%s: the sampled segment lists are not normalized (SamplerSegments without isochore keys leaves them "
                    "neither sorted nor disjoint): GAT_DISTANCE_ANNOTATION_TO_SEGMENT searches them and needs normalized lists", who);
-  if (P->call.active) return set_err(ctx, GAT_ERR_ARG, "a call is in flight on this problem (its scratch is in use): gat_wait first");
-  gat_stats local;
-  memset(&local, 0, sizeof(local));
-  if (sample_end == sample_begin) {                 // (no batch runs: nothing is written)
-    if (stats) *stats = local;
-    return GAT_OK;
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const Knobs kn = read_knobs(ctx);
   DistanceBufs B;
-  rc = sample_distances_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, annos, anno_off, n_tracks, direction,
-                             max_distance, out_host, local, B);
-  (void)hipStreamSynchronize(ctx->stream);
-  ctx->stage_used = 0;
-  if (stats) *stats = local;
-  return rc;
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    if (sample_end == sample_begin) return GAT_OK;  // (no batch runs: nothing is written)
+    return sample_distances_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, annos, anno_off, n_tracks, direction,
+                                 max_distance, out_host, local, B);
+  });
 }
 
 // what gat_count_lists / gat_count_list_ranges were given, as it goes down to the launches

@@ -382,7 +382,7 @@ int gat_sample_coverage(gat_ctx* ctx, gat_problem* p, uint32_t seed,
 int gat_list_metrics(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
                      const gat_segment* ws, const int64_t* ws_off, int32_t n_groups, int64_t* out_host);
 
-/* ... of the sampled lists: the batch loop of gat_sample with k_metrics behind every batch that passed its checks, reading
+/* ... of the sampled lists: the batch loop shared with gat_sample, k_metrics behind every batch that passed its checks, reading
  * the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed and
  * range (per-unit streams only).  ws / ws_off: the pieces each contig's samples are measured against (HOST, CSR,
  * n_contigs + 1 entries, in the problem's contig order); out_host: [sample][contig][8], sample_end - sample_begin samples.
@@ -430,7 +430,7 @@ int gat_list_distances(gat_ctx* ctx, const gat_segment* lists, const int64_t* li
                        const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups,
                        int direction, int64_t max_distance, int64_t* out_host);
 
-/* ... of the sampled lists: the batch loop of gat_sample with k_distance behind every batch that passed its checks, reading
+/* ... of the sampled lists: the batch loop shared with gat_sample, k_distance behind every batch that passed its checks, reading
  * the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed and
  * range (per-unit streams only).  The groups are the problem's contigs in the problem's order: anno_off has n_tracks *
  * n_contigs + 1 entries; out_host: [sample][track][4], sample_end - sample_begin samples.  Synchronous, like gat_sample.

@@ -121,6 +121,7 @@ def test_many_batches_and_the_seam(ctx, monkeypatch, kind):
         assert P.last_stats["n_batches"] > 8
         seg, off = P.sample(8, 3, 3 + S, unit_level=True)
         ust = P.last_stats
+        assert ust["n_batches"] > 8, ust
     finally:
         P.close()
     for k, c in enumerate(E.ALL_COUNTERS):
