@@ -67,12 +67,12 @@ __global__ __launch_bounds__(64) void k_brute_force(BruteForceArgs A) {
   const int cap = U.slab_cap;
   const int lcap = A.lds_cap;
   const uint64_t sample_id = (uint64_t)(A.sample_begin + sidx);
-  const uint32_t seed = (uint32_t)((uint64_t)A.seed + sample_id * (uint64_t)A.n_units + (uint64_t)u);
+  const uint32_t seed = unit_stream_seed(A.seed, A.sample_begin, sidx, A.n_units, u);
 
   WaveRng rng;
   rng.mt = lds;
   rng_seed(rng, seed, lane);
-  rng.pre = nullptr; rng.pre_j = 0; rng.pre_rows = 0; rng.pre_base = 0; rng.seed = seed;
+  rng_no_rows(rng); rng.seed = seed;
   uint2* list = reinterpret_cast<uint2*>(lds + kMtLdsWords);
   auto ws_bisect = [&](uint32_t p) -> int { return bisect_u32(cdf, nws, p); };
 

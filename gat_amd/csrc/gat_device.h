@@ -336,32 +336,7 @@ __device__ __forceinline__ int bisect_u32(const uint32_t* __restrict__ a, int n,
   return lo;
 }
 
-// HistogramSampler.sample (gat/Engine.pyx:413-435) on the unit's compressed cdf: rank_len[r] is the bucket searchsorted(cdf, r)
-// returns (tabulated per rank at problem creation); one draw, a second one inside the bucket when bucket > 1.
-__device__ __forceinline__ uint32_t hist_sample(WaveRng& rng, uint32_t hist_total, const uint32_t* __restrict__ rank_len,
-                                                uint32_t bucket, int lane) {
-  uint32_t r = 1;
-  if (hist_total > 1) r = 1u + rng_range(rng, hist_total - 2u, lane);
-  uint32_t len_u = rank_len[r] * bucket;
-  if (bucket > 1) len_u += rng_range(rng, bucket - 1u, lane);
-  return len_u;
-}
-
-// SegmentListSampler.sample (gat/Engine.pyx:299-328): a base of the workspace, the piece k that holds it (bisect: the
-// searchsorted over the cumulated lengths), then the position inside [piece start - length + 1, piece end), its lower end
-// clamped to the piece in front (the reference's int32 lmax).  Returns random_pos_in_segment; the segment is
-// [max(0, q), q + length).
-template <typename Bisect>
-__device__ __forceinline__ int32_t ws_sample(WaveRng& rng, const uint2* __restrict__ ws, uint32_t ws_total, int32_t length,
-                                             Bisect bisect, int lane, int& k) {
-  const uint32_t p = rng_range(rng, ws_total - 1u, lane);
-  k = bisect(p);
-  const uint2 chosen = ws[k];
-  int32_t sampling_start = (int32_t)chosen.x - length + 1;
-  if (k > 0) { const int32_t pe = (int32_t)ws[k - 1].y; sampling_start = pe > sampling_start ? pe : sampling_start; }
-  const uint32_t range = chosen.y - 1u - (uint32_t)sampling_start;
-  return sampling_start + (int32_t)rng_range(rng, range, lane);
-}
+// (hist_sample, ws_sample: gat_annotator_steps.h)
 
 // ------------------------------------------------------------------------------------------
 // wave reductions / scans

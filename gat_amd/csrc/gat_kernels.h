@@ -11,6 +11,7 @@
 //               contigs as gat/__init__.py:578-587 does.
 #pragma once
 #include "gat_device.h"
+#include "gat_annotator_steps.h"
 
 namespace gat {
 
@@ -143,8 +144,7 @@ __global__ __launch_bounds__(kSeedThreads) void k_seed(SamplerArgs A, int n_bloc
   if (tile >= (int64_t)A.n_active * n_blocks) return;
   const int a = (int)(tile / n_blocks), sb = (int)(tile - (int64_t)a * n_blocks);
   const int u = A.units_o[a].pad;
-  const uint64_t sample_id = (uint64_t)(A.sample_begin + (int64_t)sb * kWave + lane);
-  uint32_t x = (uint32_t)((uint64_t)A.seed + sample_id * (uint64_t)A.n_units + (uint64_t)u);
+  uint32_t x = unit_stream_seed(A.seed, A.sample_begin, (int64_t)sb * kWave + lane, A.n_units, u);
   uint32_t* __restrict__ dst = A.rng_ckpt + tile * (kRngWaves * kWave) + lane;
   for (int w = 0; w < kRngWaves; ++w) {
     dst[w * kWave] = x;                                             // word 39 w
@@ -1853,6 +1853,54 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_big(SamplerArgs A) {
 // memory, the sort is the in-place network) but without a size limit.
 // WPE: waves per SIMD the register budget is set for: 4 (LDS allows no more for lists of hundreds of segments), or 5 for
 // problems whose lists are so short that registers, not LDS, decide how many waves a CU holds.
+// sampler_unit's state, grouped for its stages (named scalars only: they stay in registers)
+struct UnitList {
+  int nU, nS;                       // seg[0..nU): unintersected (merged, sorted); seg[nU..nU+nS): sampled since
+  bool dirty;                       // unintersected holds trim placeholders not yet merged away
+  bool cov_valid;                   // cov_known = workspace coverage of unintersected as it stands
+  uint32_t cov_known, total_known;
+};
+struct UnitLoop { int32_t remaining, true_remaining, pending; int nuns; uint32_t placed; int status; };
+
+// stage: a unit of SamplerSegments.sample (gat/Engine.pyx:695-737): len(segments) placements, no consolidation.  Normally
+// k_place has done all of it (st_length == -2); otherwise the unit is run here from its seed.
+template <class Bisect>
+__device__ __forceinline__ void stage_segments_unit(const SamplerArgs& A, int target, int cap, uint32_t hist_total, uint32_t bucket,
+                                                    uint32_t ws_total, const int4& pre, uint32_t seed, uint32_t* mt, uint2* out,
+                                                    const uint2* __restrict__ ws, const uint32_t* __restrict__ rank_len, int64_t so,
+                                                    int64_t sw, int lane, WaveRng* serial, Bisect ws_bisect) {
+  int nout = 0, status = 0;
+  uint32_t placed = 0, ndraws = 0, full_units = 0;
+  if (pre.z == -2) {
+    nout = pre.x;
+    placed = (uint32_t)nout;
+    ndraws = (uint32_t)pre.w;
+  } else {
+    WaveRng rng;
+    rng.mt = mt;
+    if (serial != nullptr) { rng = *serial; rng.ndraws = 0; }     // (k_serial: the run's one stream goes on)
+    else rng_seed(rng, seed, lane);
+    rng_no_rows(rng);
+    full_units = 1;
+    for (int x = 0; x < target; ++x) {
+      const int32_t length = (int32_t)hist_sample(rng, hist_total, rank_len, bucket, lane);
+      int k;
+      const int32_t q = ws_sample(rng, ws, ws_total, length, ws_bisect, lane, k);
+      if (nout >= cap) { status |= kStatusOverflow; break; }
+      if (lane == 0) out[nout] = make_uint2((uint32_t)(q > 0 ? q : 0), (uint32_t)(q + length));
+      nout++;
+    }
+    placed = (uint32_t)nout;
+    ndraws = rng.ndraws;
+    if (serial != nullptr) *serial = rng;
+  }
+  if (lane == 0) {
+    A.unit_n[so] = status ? 0 : nout;
+    if (status) atomicOr(A.flags, status);
+    *reinterpret_cast<uint4*>(A.ws_stat + sw * 4) = make_uint4(placed, ndraws, 0u, full_units);
+  }
+}
+
 template <int KIND, bool BIG, bool TREE, bool HUGE>
 __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sidx, const int a, uint32_t* lds, const int lane,
                                              WaveRng* serial = nullptr) {
@@ -1895,59 +1943,29 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
     else return 0u;                                              // (no such unit in this instantiation)
   };
   const WsRegs W = ws_load(ws, ws_cdf, nws < kWsRegMax ? nws : kWsRegMax, lane);
+  auto ws_overlap_r = [&](uint32_t s, uint32_t e) -> uint32_t { return ws_overlap_regs(W, s, e); };   // ... one within it
   uint2* out = A.slab + (int64_t)sidx * A.slab_stride + Up->slab_off;
   uint2* fin = (!HUGE && A.slab_final != nullptr) ? A.slab_final + (int64_t)sidx * A.slab_stride + Up->slab_off : out;
   uint2* seg = HUGE ? out : reinterpret_cast<uint2*>(lds + kMtLdsWords);
   const int64_t so = (int64_t)sidx * A.n_units + u;     // unit_n: [sample][unit]
   const int64_t sw = GAT_REC(A, sidx, u);                // ws_stat: [unit][sample]
 
-  // per-unit stream: numpy.random.seed((seed + sample*n_units + unit) mod 2^32)
-  const uint64_t sample_id = (uint64_t)(A.sample_begin + sidx);
-  const uint32_t seed = (uint32_t)((uint64_t)A.seed + sample_id * (uint64_t)A.n_units + (uint64_t)u);
+  const uint32_t seed = unit_stream_seed(A.seed, A.sample_begin, sidx, A.n_units, u);
   if (A.skip != nullptr && A.skip[GAT_REC(A, sidx, a) * A.skip_stride] != 0) return;
   const bool have_pre = A.st != nullptr;
   const int4 pre = have_pre ? A.st[GAT_REC(A, sidx, a)] : make_int4(0, 0, -1, 0);
   const int32_t pre_len = pre.z;
 
-  int nout = 0, status = 0, nuns = 0;
-  uint32_t placed = 0, ndraws = 0, full_units = 0;
+  int nout = 0;
+  uint32_t ndraws = 0, full_units = 0;
+  UnitLoop S = {0, 0, -1, 0, 0u, 0};
   bool switched = false;       // the unit was resumed and its rows ran out: the stream went on from the in-LDS generator
 #ifdef GAT_DIAG
   unsigned long long dg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dg_t;
   GAT_STAMP(dg_t);
 #endif
   if constexpr (KIND == 1) {
-    // SamplerSegments.sample (gat/Engine.pyx:695-737): len(segments) placements, no consolidation.  Normally
-    // k_place has done all of it (st_length == -2); otherwise the unit is run here from its seed.
-    if (pre_len == -2) {
-      nout = pre.x;
-      placed = (uint32_t)nout;
-      ndraws = (uint32_t)pre.w;
-    } else {
-      WaveRng rng;
-      rng.mt = mt;
-      if (serial != nullptr) { rng = *serial; rng.ndraws = 0; }     // (k_serial: the run's one stream goes on)
-      else rng_seed(rng, seed, lane);
-      rng.pre = nullptr; rng.pre_j = 0; rng.pre_rows = 0; rng.pre_base = 0;
-      full_units = 1;
-      const int target = Up->n_target;
-      for (int x = 0; x < target; ++x) {
-        const int32_t length = (int32_t)hist_sample(rng, hist_total, rank_len, bucket, lane);
-        int k;
-        const int32_t q = ws_sample(rng, ws, ws_total, length, ws_bisect, lane, k);
-        if (nout >= cap) { status |= kStatusOverflow; break; }
-        if (lane == 0) out[nout] = make_uint2((uint32_t)(q > 0 ? q : 0), (uint32_t)(q + length));
-        nout++;
-      }
-      placed = (uint32_t)nout;
-      ndraws = rng.ndraws;
-      if (serial != nullptr) *serial = rng;
-    }
-    if (lane == 0) {
-      A.unit_n[so] = status ? 0 : nout;
-      if (status) atomicOr(A.flags, status);
-      *reinterpret_cast<uint4*>(A.ws_stat + sw * 4) = make_uint4(placed, ndraws, 0u, full_units);
-    }
+    stage_segments_unit(A, Up->n_target, cap, hist_total, bucket, ws_total, pre, seed, mt, out, ws, rank_len, so, sw, lane, serial, ws_bisect);
     return;
   }
   // (pre_len: > 0 the pending length at the first consolidation; -3: k_place ran out of rows while placing -- the loop goes
@@ -1956,15 +1974,10 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
     const bool resume = attempt == 0;
     WaveRng rng;
     rng.mt = mt;
-    int nU = 0, nS = 0;   // seg[0..nU): unintersected (merged, sorted); seg[nU..nU+nS): sampled since
-    int32_t remaining = ltotal, true_remaining = ltotal;
-    int32_t pending = -1;
-    bool dirty = false;          // unintersected holds trim placeholders not yet merged away
-    bool cov_valid = false;      // cov_known = workspace coverage of unintersected as it stands
-    uint32_t cov_known = 0, total_known = 0;
-    nuns = 0; status = 0; placed = 0;
+    UnitList L = {0, 0, false, false, 0u, 0u};
+    S = {ltotal, ltotal, -1, 0, 0u, 0};
     if (resume) {
-      nS = pre.x;
+      L.nS = pre.x;
       int4 pre2 = make_int4(0, 0, 0, 0);
       if (!HUGE && A.st2 != nullptr && a < A.n_long) pre2 = A.st2[GAT_REC(A, sidx, a)];
       const int32_t* __restrict__ R = nullptr;
@@ -1978,133 +1991,121 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
       if (pre2.w == 1) {
         // k_merge_big has done the first consolidation: the slab holds the merged list; its coverage and total
         // length come with it, and the pending length below makes the loop take them up at once
-        nU = pre2.x;
-        nS = 0;
-        cov_known = (uint32_t)pre2.y;
-        total_known = (uint32_t)pre2.z;
-        cov_valid = true;
-        if (HUGE) { for (int i = lane; i < nU; i += kWave) seg[i] = out[i]; }
+        L.nU = pre2.x;
+        L.nS = 0;
+        L.cov_known = (uint32_t)pre2.y;
+        L.total_known = (uint32_t)pre2.z;
+        L.cov_valid = true;
+        if (HUGE) { for (int i = lane; i < L.nU; i += kWave) seg[i] = out[i]; }
         else {
           // (eight rounds of loads in flight: a list of thousands, one wave, nothing else hides the latency)
-          for (int base = 0; base < nU; base += 8 * kWave) {
+          for (int base = 0; base < L.nU; base += 8 * kWave) {
             uint2 v[8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) { const int i = base + r * kWave + lane; v[r] = i < nU ? out[i] : make_uint2(0u, 0u); }
+            for (int r = 0; r < 8; ++r) { const int i = base + r * kWave + lane; v[r] = i < L.nU ? out[i] : make_uint2(0u, 0u); }
 #pragma unroll
-            for (int r = 0; r < 8; ++r) { const int i = base + r * kWave + lane; if (i < nU) seg[i] = v[r]; }
+            for (int r = 0; r < 8; ++r) { const int i = base + r * kWave + lane; if (i < L.nU) seg[i] = v[r]; }
           }
         }
         if (R != nullptr) {
           // k_tail_big has run the placement rounds behind it: the merged list (unions applied in place), nE new segments
           // that touch nothing (logged from the region's end backwards), and nS it placed but did not consolidate
           const int nE = R[kPatchNExtra], nSp = R[kTbNSampled], at = R[kTbSampledAt];
-          for (int i = lane; i < nE; i += kWave) seg[nU + i] = out[cap - 1 - i];
-          for (int i = lane; i < nSp; i += kWave) seg[nU + nE + i] = out[at + i];
+          for (int i = lane; i < nE; i += kWave) seg[L.nU + i] = out[cap - 1 - i];
+          for (int i = lane; i < nSp; i += kWave) seg[L.nU + nE + i] = out[at + i];
           wave_sync<HUGE>();
           for (int done = 0; done < nE; done += kWave) {
             const int chunk = nE - done < kWave ? nE - done : kWave;
-            wave_insert_sorted<HUGE>(seg, nU + done, chunk, lane);         // (the next chunk stands right behind the grown list)
+            wave_insert_sorted<HUGE>(seg, L.nU + done, chunk, lane);         // (the next chunk stands right behind the grown list)
           }
-          nU += nE;
-          nS = nSp;
+          L.nU += nE;
+          L.nS = nSp;
         }
       } else
       // (a list the counting sort will take straight from the slab need not be copied first -- unless the unit goes on PLACING,
       //  pre_len -3: what it places joins the list in LDS)
-      if (!HUGE && (pre_len == -3 || (!(BIG && nS > 1024 && A.big_buckets > 0) && !(nS > 512 && nS <= 1024))))
-        for (int i = lane; i < nS; i += kWave) seg[i] = out[i];
-      remaining = pre.y;
-      pending = pre_len >= 0 ? pre_len : -1;
-      rng.use_pre = true; rng.exhausted = false; rng.ndraws = (uint32_t)pre.w; rng.pos = 0; rng.rbuf = 0;
+      if (!HUGE && (pre_len == -3 || (!(BIG && L.nS > 1024 && A.big_buckets > 0) && !(L.nS > 512 && L.nS <= 1024))))
+        for (int i = lane; i < L.nS; i += kWave) seg[i] = out[i];
+      S.remaining = pre.y;
+      S.pending = pre_len >= 0 ? pre_len : -1;
       rng.seed = seed; rng.can_switch = true;        // (where the rows run out the stream goes on from the in-LDS generator)
-      rng.pre_rows = (uint32_t)A.rng_rows[a];
-      rng.pre_j = rng.ndraws;
-      rng.pre_base = rng.pre_j - (uint32_t)kWave;     // forces the first prefetch
-      rng.pre = A.rng_out + A.rng_off[a] + (int64_t)(sidx >> 6) * rng.pre_rows * kWave + (sidx & 63);
-      placed = (uint32_t)pre.x;
+      rng_open_rows(rng, A.rng_out, A.rng_off[a], (uint32_t)A.rng_rows[a], sidx, (uint32_t)pre.w);
+      S.placed = (uint32_t)pre.x;
       if (R != nullptr) {
         // ... and the loop goes on where k_tail_big left it: at a consolidation whose bookkeeping (:601-605) is still to do
-        remaining = R[kTbRemaining];
-        pending = R[kTbPending];
-        true_remaining = R[kTbTrueRemaining];
-        nuns = R[kPatchNuns];
-        placed = (uint32_t)R[kPatchPlaced];
-        rng.ndraws = (uint32_t)R[kPatchNdraws];
-        rng.pre_j = rng.ndraws;
-        rng.pre_base = rng.pre_j - (uint32_t)kWave;
+        S.remaining = R[kTbRemaining];
+        S.pending = R[kTbPending];
+        S.true_remaining = R[kTbTrueRemaining];
+        S.nuns = R[kPatchNuns];
+        S.placed = (uint32_t)R[kPatchPlaced];
+        rng_rows_at(rng, (uint32_t)R[kPatchNdraws]);
       }
       wave_sync<HUGE>();
       GAT_PHASE(0)                                   // prologue: unit record, workspace, hand-off record, list into LDS
     } else {
       if (serial != nullptr) { rng = *serial; rng.mt = mt; rng.ndraws = 0; }      // (k_serial: the run's one stream goes on)
       else rng_seed(rng, seed, lane);
-      rng.pre = nullptr; rng.pre_j = 0; rng.pre_rows = 0; rng.pre_base = 0;
+      rng_no_rows(rng);
       full_units = 1;
     }
 
-    while (true_remaining > 0 && nuns < 20) {                       // gat/Engine.pyx:572
+    while (S.true_remaining > 0 && S.nuns < kMaxUnsuccessful) {                       // gat/Engine.pyx:572
       // ---- hs.sample() (:413-435)
       int32_t length;
-      if (pending >= 0) { length = pending; pending = -1; }
-      else {
-        uint32_t r = 1;
-        if (hist_total > 1) r = 1u + rng_range(rng, hist_total - 2u, lane);
-        uint32_t len_u = rank_len[r] * bucket;     // == cdf bisect (utils/gat_utils.c:36), tabulated per rank
-        if (bucket > 1) len_u += rng_range(rng, bucket - 1u, lane);
-        length = (int32_t)len_u;
-      }
+      if (S.pending >= 0) { length = S.pending; S.pending = -1; }
+      else length = (int32_t)hist_sample(rng, hist_total, rank_len, bucket, lane);
       GAT_PHASE(6)                                   // draws + placement arithmetic
 
       // ---- consolidate (:582-606)
-      if (remaining <= length) {
+      if (S.remaining <= length) {
         uint32_t cov;
         bool handled = false;
-        if (nS == 0 && cov_valid) {
+        if (L.nS == 0 && L.cov_valid) {
           // nothing was placed since the last consolidation, only trimmed: merge(0) would just drop the
           // placeholders (left for the final pass) and the coverage is the old one minus what the trim removed
-          cov = cov_known;
+          cov = L.cov_known;
           handled = true;
-        } else if (nS == 1 && cov_valid && !dirty && nU > 0) {
+        } else if (L.nS == 1 && L.cov_valid && !L.dirty && L.nU > 0) {
           // one new segment and a clean merged list: if it neither overlaps nor touches its neighbours
           // (merge(0) joins at start <= previous max end) the merged list is the old one plus this segment
-          const uint2 xv = seg[nU];
+          const uint2 xv = seg[L.nU];
           const uint32_t xs = rfl(xv.x), xe = rfl(xv.y);
           int pcount = 0;                                   // #U with start <= xs
-          for (int base = 0; base < nU; base += kWave) {
+          for (int base = 0; base < L.nU; base += kWave) {
             const int i = base + lane;
-            pcount += __popcll(__ballot(i < nU && seg[i].x <= xs));
+            pcount += __popcll(__ballot(i < L.nU && seg[i].x <= xs));
           }
-          const uint2 pv = seg[pcount > 0 ? pcount - 1 : 0], nv = seg[pcount < nU ? pcount : nU - 1];
+          const uint2 pv = seg[pcount > 0 ? pcount - 1 : 0], nv = seg[pcount < L.nU ? pcount : L.nU - 1];
           const bool touch_prev = pcount > 0 && (int32_t)xs <= (int32_t)rfl(pv.y);
-          const bool touch_next = pcount < nU && (int32_t)rfl(nv.x) <= (int32_t)xe;
+          const bool touch_next = pcount < L.nU && (int32_t)rfl(nv.x) <= (int32_t)xe;
           // (an EMPTY neighbour -- what a trim emptied, or the placeholder one of k_tail_big's bridges left at its start -- says
           //  nothing about what stands there: the full merge below)
-          const bool hole = (pcount > 0 && rfl(pv.x) == rfl(pv.y)) || (pcount < nU && rfl(nv.x) == rfl(nv.y));
+          const bool hole = (pcount > 0 && rfl(pv.x) == rfl(pv.y)) || (pcount < L.nU && rfl(nv.x) == rfl(nv.y));
           if (xs != xe && !touch_prev && !touch_next && !hole) {
-            wave_insert_sorted<HUGE>(seg, nU, 1, lane);
-            nU += 1;
-            nS = 0;
-            cov = cov_known + (nws <= kWsLoopMax ? ws_overlap_regs(W, xs, xe) : ws_overlap1(xs, xe));
-            total_known += xe - xs;
+            wave_insert_sorted<HUGE>(seg, L.nU, 1, lane);
+            L.nU += 1;
+            L.nS = 0;
+            cov = L.cov_known + (nws <= kWsLoopMax ? ws_overlap_regs(W, xs, xe) : ws_overlap1(xs, xe));
+            L.total_known += xe - xs;
             handled = true;
           }
         }
         GAT_PHASE(4)                                 // consolidation fast paths (nothing new / one new segment)
         if (!handled) {
-          if (BIG && dirty && nU > 0 && nS <= kWave && nU + nS > 1024) {      // (up to 1024 the bucket sort is cheaper)
+          if (BIG && L.dirty && L.nU > 0 && L.nS <= kWave && L.nU + L.nS > 1024) {      // (up to 1024 the bucket sort is cheaper)
             // the trim left the merged list sorted but for its placeholders, which merge(0) skips wherever they
             // are: one compaction pass (instead of sorting a long list again with the network) and it is clean and sorted,
             // ready for the few new segments to be inserted
             uint2 moved = make_uint2(0u, 0u);
-            if (lane < nS) moved = seg[nU + lane];
-            const int kept = wave_merge0<HUGE>(seg, nU, lane);
-            if (lane < nS) seg[kept + lane] = moved;
+            if (lane < L.nS) moved = seg[L.nU + lane];
+            const int kept = wave_merge0<HUGE>(seg, L.nU, lane);
+            if (lane < L.nS) seg[kept + lane] = moved;
             wave_sync<HUGE>();
-            nU = kept;
-            dirty = false;
+            L.nU = kept;
+            L.dirty = false;
           }
-          const int n = nU + nS;
-          if (BIG && !HUGE && resume && pre_len >= 0 && nU == 0 && !dirty && n > 1024 && A.big_buckets > 0) {
+          const int n = L.nU + L.nS;
+          if (BIG && !HUGE && resume && pre_len >= 0 && L.nU == 0 && !L.dirty && n > 1024 && A.big_buckets > 0) {
             // long list straight from the slab k_place wrote: counting sort into LDS (it was not copied at resume)
             int nb = 1024;
             while (nb < n && nb < A.big_buckets) nb <<= 1;
@@ -2113,7 +2114,7 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
               for (int i = lane; i < n; i += kWave) seg[i] = out[i];
               wave_sort_by_start<HUGE>(seg, n, lane);
             }
-          } else if (!HUGE && resume && pre_len >= 0 && rng.use_pre && nU == 0 && !dirty && n > 512 && n <= 1024 && n == pre.x) {
+          } else if (!HUGE && resume && pre_len >= 0 && rng.use_pre && L.nU == 0 && !L.dirty && n > 512 && n <= 1024 && n == pre.x) {
             // 513..1024 segments, still where k_place wrote them: the same counting sort with 512 buckets (the bucket sort
             // that holds the whole list in registers needs 16 elements per lane here -- over a hundred registers, which cost
             // every wave of the kernel spills: 128 VGPRs + 76 bytes of scratch against 106 without)
@@ -2121,93 +2122,59 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
               for (int i = lane; i < n; i += kWave) seg[i] = out[i];
               wave_sort_auto<HUGE>(seg, n, lane);
             }
-          } else if (BIG && nU > 0 && !dirty && n > 1024 && nS <= 1024) {
+          } else if (BIG && L.nU > 0 && !L.dirty && n > 1024 && L.nS <= 1024) {
             // a long clean list and some new segments: insert them 64 at a time (a pass over the list each) rather than
             // sort everything with the network (thousands of passes)
-            for (int done = 0; done < nS; done += kWave)
-              wave_insert_sorted<HUGE>(seg, nU + done, nS - done < kWave ? nS - done : kWave, lane);
+            for (int done = 0; done < L.nS; done += kWave)
+              wave_insert_sorted<HUGE>(seg, L.nU + done, L.nS - done < kWave ? L.nS - done : kWave, lane);
           } else
-          if (nU == 0 || nS > kWave || dirty) wave_sort_fast<8, HUGE>(seg, n, (resume && rng.use_pre) ? mt : nullptr, lane);   // SegmentList.sort of everything
+          if (L.nU == 0 || L.nS > kWave || L.dirty) wave_sort_fast<8, HUGE>(seg, n, (resume && rng.use_pre) ? mt : nullptr, lane);   // SegmentList.sort of everything
                                         // (the MT19937 words are idle scratch while the stream comes from k_rng)
-          else if (nS > 0) wave_insert_sorted<HUGE>(seg, nU, nS, lane);         // same order, few new segments
+          else if (L.nS > 0) wave_insert_sorted<HUGE>(seg, L.nU, L.nS, lane);         // same order, few new segments
           GAT_PHASE(1)                               // sort / insert
-          nU = wave_merge0<HUGE>(seg, n, lane);
+          L.nU = wave_merge0<HUGE>(seg, n, lane);
           GAT_PHASE(2)                               // merge(0)
-          nS = 0;
-          dirty = false;
+          L.nS = 0;
+          L.dirty = false;
           cov = 0;
           uint32_t tot = 0;
-          if (nws <= kWsLoopMax) {
-            for (int i = lane; i < nU; i += kWave) { const uint2 v = seg[i]; cov += ws_overlap_regs(W, v.x, v.y); tot += v.y - v.x; }
-          } else if constexpr (TREE) {
-            constexpr int R = 2;                              // segments per lane whose workspace searches run interleaved
-            for (int base = 0; base < nU; base += R * kWave) {
-              uint2 v[R];
-              uint32_t ov[R];
-#pragma unroll
-              for (int r = 0; r < R; ++r) {
-                const int i = base + r * kWave + lane;
-                v[r] = i < nU ? seg[i] : make_uint2(0u, 0u);
-                tot += v[r].y - v[r].x;
-              }
-#pragma unroll
-              for (int r = 0; r < R; ++r) ov[r] = ws_overlap_pgrid(ws, nws, pgrid + kGridHeader, pshift, pcells, v[r].x, v[r].y);
-#pragma unroll
-              for (int r = 0; r < R; ++r) cov += ov[r];
-            }
-          }
+          if (nws <= kWsLoopMax) list_coverage<1>(seg, L.nU, lane, ws_overlap_r, cov, tot);
+          else if constexpr (TREE) list_coverage<2>(seg, L.nU, lane, ws_overlap1, cov, tot);
           cov = wave_total_u32(cov);
-          total_known = wave_total_u32(tot);             // sum() of the merged list, for the trim's position draw
+          L.total_known = wave_total_u32(tot);             // sum() of the merged list, for the trim's position draw
           GAT_PHASE(3)                               // workspace coverage of the merged list
         }
-        cov_known = cov;
-        cov_valid = true;
-        remaining = ltotal - (int32_t)cov;
-        if (true_remaining == remaining) nuns++; else true_remaining = remaining;
+        L.cov_known = cov;
+        L.cov_valid = true;
+        S.remaining = ltotal - (int32_t)cov;
         // the reference still draws a position here (:628) before its loop test fails; the draws and
         // the segment are discarded and the unit's stream ends, so nothing observable depends on them
-        if (!(true_remaining != 0 && nuns < 20)) {
+        if (!consolidate_progress(S.remaining, S.true_remaining, S.nuns)) {
           if (serial != nullptr) {
             // (the run's one stream goes on behind this unit: the draws of that discarded position are consumed -- on both
             //  ways out, nothing left to place or twenty rounds without progress; a negative true_remaining cannot stand
             //  here: it only equals `remaining` right behind a trim, which sets it to 1)
-            const uint32_t p_ = rng_range(rng, ws_total - 1u, lane);
-            int k_;
-            uint2 ch_;
-            int32_t pe_ = 0;
-            if (ws_in_regs) {
-              const uint64_t b_ = __ballot(lane < nws && (int32_t)(W.cdf - p_) >= 0);
-              k_ = (int)__builtin_ctzll(b_);
-              ch_.x = (uint32_t)__builtin_amdgcn_readlane((int)W.start, k_);
-              ch_.y = (uint32_t)__builtin_amdgcn_readlane((int)W.end, k_);
-              if (k_ > 0) pe_ = __builtin_amdgcn_readlane((int)W.end, k_ - 1);
-            } else {
-              k_ = ws_bisect(p_);
-              ch_ = ws[k_];
-              if (k_ > 0) pe_ = (int32_t)ws[k_ - 1].y;
-            }
-            int32_t ss_ = (int32_t)ch_.x - length + 1;
-            if (k_ > 0) ss_ = pe_ > ss_ ? pe_ : ss_;
-            (void)rng_range(rng, ch_.y - 1u - (uint32_t)ss_, lane);
+            const WsPiece c_ = ws_pick(W, nws, ws_in_regs, ws, rng_range(rng, ws_total - 1u, lane), lane, ws_bisect);
+            (void)rng_range(rng, place_range(c_.piece.x, c_.piece.y, c_.prev_end, length).range, lane);
           }
           break;
         }
       }
 
       // ---- overshoot: trim (:608-626)
-      if (true_remaining < 0) {
+      if (S.true_remaining < 0) {
         // SegmentListSampler(unintersected).sample(1): position draw over the cumulated lengths
-        const uint32_t total = total_known;           // kept by the consolidation / earlier trims
+        const uint32_t total = L.total_known;           // kept by the consolidation / earlier trims
         const uint32_t p = rng_range(rng, total - 1u, lane);
         int k = 0;
         uint32_t run = 0;
-        for (int base = 0; base < nU; base += kWave) {
+        for (int base = 0; base < L.nU; base += kWave) {
           const int i = base + lane;
           uint32_t len = 0;
-          if (i < nU) { const uint2 v = seg[i]; len = v.y - v.x; }
+          if (i < L.nU) { const uint2 v = seg[i]; len = v.y - v.x; }
           const uint32_t incl = run + wave_incl_sum_u32(len, lane);
           // cdf[i] = incl-1; leftmost i with (int)(cdf[i]-p) >= 0
-          const bool ge = (i < nU) && ((int32_t)(incl - 1u - p) >= 0);
+          const bool ge = (i < L.nU) && ((int32_t)(incl - 1u - p) >= 0);
           const uint64_t b = __ballot(ge);
           if (b != 0) { k = base + (int)__builtin_ctzll(b); break; }
           run = (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1);
@@ -2217,71 +2184,37 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
         const uint32_t cs = rfl(chosen.x), ce = rfl(chosen.y);
         (void)rng_range(rng, ce - 1u - cs, lane);                       // position inside the segment: only its index k matters
         const uint32_t forward = rng_range(rng, 1u, lane);            // numpy.random.randint(0, 2)
-        int32_t s = -true_remaining;
+        int32_t s = -S.true_remaining;
         if (rng.exhausted) break;
-        if (!((uint64_t)total > (uint64_t)(uint32_t)s)) { status |= kStatusTrimAssert; break; }
+        if (!((uint64_t)total > (uint64_t)(uint32_t)s)) { S.status |= kStatusTrimAssert; break; }
         // trim_ends(pos, s, forward) (gat/SegmentList.pyx:545-597); _getInsertionPoint(pos,pos+1) == k
         wave_sync<HUGE>();
         uint32_t removed = 0;                      // workspace bases taken away by the trim (lane 0)
-        if (lane == 0) {
-          int idx = k;
-          while (s > 0) {
-            const uint2 v = seg[idx];
-            const int32_t l = (int32_t)v.y - (int32_t)v.x;
-            uint32_t ra, rb;                       // removed range
-            if (l < s) { seg[idx] = make_uint2(0u, 0u); s -= l; ra = v.x; rb = v.y; }
-            else {
-              if (forward) { seg[idx] = make_uint2(v.x + (uint32_t)s, v.y); ra = v.x; rb = v.x + (uint32_t)s; }
-              else { seg[idx] = make_uint2(v.x, (uint32_t)((int32_t)v.y - s)); ra = (uint32_t)((int32_t)v.y - s); rb = v.y; }
-              s = 0;
-            }
-            if (rb > ra) removed += nws <= kWsLoopMax ? ws_overlap_regs(W, ra, rb) : ws_overlap1(ra, rb);
-            if (forward) { idx++; if (idx == nU) idx = 0; }
-            else { idx--; if (idx < 0) idx = nU - 1; }
-          }
-        }
-        cov_known -= rfl(removed);
-        total_known -= (uint32_t)(-true_remaining);      // trim_ends removes exactly that many bases
+        if (lane == 0)
+          removed = trim_ends_walk(L.nU, k, s, forward != 0, [&](int i) -> uint2& { return seg[i]; }, [&](uint32_t ra, uint32_t rb) -> uint32_t {
+            return nws <= kWsLoopMax ? ws_overlap_regs(W, ra, rb) : ws_overlap1(ra, rb);
+          }).removed;
+        L.cov_known -= rfl(removed);
+        L.total_known -= (uint32_t)(-S.true_remaining);      // trim_ends removes exactly that many bases
         wave_sync<HUGE>();
-        dirty = true;
-        true_remaining = 1;
+        L.dirty = true;
+        S.true_remaining = 1;
         GAT_PHASE(5)                                 // overshoot trim
         continue;
       }
 
       // ---- sls.sample(length) (:279-343)
-      const uint32_t p = rng_range(rng, ws_total - 1u, lane);
-      int k;
-      uint2 chosen;
-      int32_t prev_end = 0;
-      if (ws_in_regs) {
-        // leftmost i with (int)(cdf[i]-p) >= 0 (utils/gat_utils.c:36 + cmpPosition), one compare per lane
-        const uint64_t b = __ballot(lane < nws && (int32_t)(W.cdf - p) >= 0);
-        k = (int)__builtin_ctzll(b);
-        chosen.x = (uint32_t)__builtin_amdgcn_readlane((int)W.start, k);
-        chosen.y = (uint32_t)__builtin_amdgcn_readlane((int)W.end, k);
-        if (k > 0) prev_end = __builtin_amdgcn_readlane((int)W.end, k - 1);
-      } else {
-        k = ws_bisect(p);
-        chosen = ws[k];
-        if (k > 0) prev_end = (int32_t)ws[k - 1].y;
-      }
-      int32_t sampling_start = (int32_t)chosen.x - length + 1;
-      if (k > 0) sampling_start = prev_end > sampling_start ? prev_end : sampling_start;
-      const uint32_t range = chosen.y - 1u - (uint32_t)sampling_start;
-      const int32_t q = sampling_start + (int32_t)rng_range(rng, range, lane);
+      const WsPiece c = ws_pick(W, nws, ws_in_regs, ws, rng_range(rng, ws_total - 1u, lane), lane, ws_bisect);
+      const PlaceRange pr = place_range(c.piece.x, c.piece.y, c.prev_end, length);
+      const int32_t q = pr.sampling_start + (int32_t)rng_range(rng, pr.range, lane);
       if (rng.exhausted) break;
-      const uint32_t start = (uint32_t)(q > 0 ? q : 0);
-      const uint32_t end = (uint32_t)(q + length);
-      const int32_t omin = (int32_t)chosen.y < (int32_t)end ? (int32_t)chosen.y : (int32_t)end;
-      const int32_t omax = (int32_t)chosen.x > (int32_t)start ? (int32_t)chosen.x : (int32_t)start;
-      const int32_t overlap = omin - omax > 0 ? omin - omax : 0;
-      if (true_remaining > 0) {
-        if (nU + nS >= cap) { status |= kStatusOverflow; break; }
-        if (lane == 0) seg[nU + nS] = make_uint2(start, end);
-        nS++;
-        placed++;
-        remaining -= overlap;
+      const Placed x = place_at(c.piece.x, c.piece.y, q, length);
+      if (S.true_remaining > 0) {
+        if (L.nU + L.nS >= cap) { S.status |= kStatusOverflow; break; }
+        if (lane == 0) seg[L.nU + L.nS] = make_uint2(x.start, x.end);
+        L.nS++;
+        S.placed++;
+        S.remaining -= x.overlap;
       }
       GAT_PHASE(6)
     }
@@ -2293,23 +2226,23 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
 
     // ---- result = unintersected.merge(0).filter(workspace) (:639-646); pending sampled are dropped
     nout = 0;
-    if (status == 0) {
+    if (S.status == 0) {
       // (after a trim the list holds [0, 0) placeholders; nothing touches that did not before -- a trim only shortens --
       //  and the filter below drops what overlaps nothing, placeholders included: no merge(0) pass of its own)
       uint32_t total = 0;
       if (nws <= kWsLoopMax) {
         // (four rounds at a time: their LDS reads and workspace tests do not depend on one another, only the output
         //  positions do -- a long list is worked on by one wave with little else on its SIMD to hide a round's latency)
-        for (int base = 0; base < nU; base += 4 * kWave) {
+        for (int base = 0; base < L.nU; base += 4 * kWave) {
           uint2 v[4];
           bool keep[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int i = base + q * kWave + lane;
-            v[q] = i < nU ? seg[i] : make_uint2(0u, 0u);
+            v[q] = i < L.nU ? seg[i] : make_uint2(0u, 0u);
           }
 #pragma unroll
-          for (int q = 0; q < 4; ++q) keep[q] = base + q * kWave + lane < nU && ws_overlap_regs(W, v[q].x, v[q].y) > 0;
+          for (int q = 0; q < 4; ++q) keep[q] = base + q * kWave + lane < L.nU && ws_overlap_regs(W, v[q].x, v[q].y) > 0;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const uint64_t b = __ballot(keep[q]);
@@ -2319,13 +2252,13 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
         }
       } else if constexpr (TREE) {
         constexpr int R = 2;
-        for (int base = 0; base < nU; base += R * kWave) {
+        for (int base = 0; base < L.nU; base += R * kWave) {
           uint2 v[R];
           uint32_t ov[R];
 #pragma unroll
           for (int r = 0; r < R; ++r) {
             const int i = base + r * kWave + lane;
-            v[r] = i < nU ? seg[i] : make_uint2(0u, 0u);
+            v[r] = i < L.nU ? seg[i] : make_uint2(0u, 0u);
           }
 #pragma unroll
           for (int r = 0; r < R; ++r) ov[r] = ws_overlap_pgrid(ws, nws, pgrid + kGridHeader, pshift, pcells, v[r].x, v[r].y);
@@ -2339,7 +2272,7 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
         }
       }
       total = wave_total_u32(total);
-      if (!(total > 0)) status |= kStatusAssert;
+      if (!(total > 0)) S.status |= kStatusAssert;
     }
     GAT_PHASE(7)                                     // final merge (after a trim), workspace filter, list to the slab
     break;
@@ -2350,8 +2283,8 @@ __device__ __forceinline__ void sampler_unit(const SamplerArgs& A, const int sid
 #endif
   if (lane == 0) {
     A.unit_n[so] = nout;
-    if (status) atomicOr(A.flags, status);
-    *reinterpret_cast<uint4*>(A.ws_stat + sw * 4) = make_uint4(placed, ndraws, (uint32_t)nuns, full_units | (switched ? 0x10000u : 0u));
+    if (S.status) atomicOr(A.flags, S.status);
+    *reinterpret_cast<uint4*>(A.ws_stat + sw * 4) = make_uint4(S.placed, ndraws, (uint32_t)S.nuns, full_units | (switched ? 0x10000u : 0u));
   }
 }
 
@@ -2395,7 +2328,7 @@ __global__ __launch_bounds__(64) void k_serial(SamplerArgs A) {
   rng.pos = (int)A.serial_state[kMtN];
   rng.ndraws = 0;
   rng.use_pre = false; rng.exhausted = false;
-  rng.pre = nullptr; rng.pre_j = 0; rng.pre_rows = 0; rng.pre_base = 0;
+  rng_no_rows(rng);
   wave_sync();
   rng.rbuf = 0;
   if (rng.pos < kMtN && (rng.pos & (kWave - 1)) != 0) {           // inside a block of 64 outputs: its tempered words

@@ -210,12 +210,11 @@ __global__ __launch_bounds__(64) void k_permute_local(LocalPermuteArgs A) {
   const int n_pieces = (int)T.y;
   uint2* out = A.slab + (int64_t)sidx * A.slab_stride + U.slab_off;
   const int cap = U.slab_cap;
-  const uint64_t sample_id = (uint64_t)(A.sample_begin + sidx);
-  const uint32_t seed = (uint32_t)((uint64_t)A.seed + sample_id * (uint64_t)A.n_units + (uint64_t)u);
+  const uint32_t seed = unit_stream_seed(A.seed, A.sample_begin, sidx, A.n_units, u);
 
   WaveRng rng;
   rng.mt = lds;
-  rng.pre = nullptr; rng.pre_j = 0; rng.pre_rows = 0; rng.pre_base = 0; rng.seed = seed;
+  rng_no_rows(rng); rng.seed = seed;
   rng_seed_by_array(rng, seed, lane);
 
   const int cap_even = (A.lds_cap + 1) & ~1;
