@@ -729,10 +729,15 @@ def buildParser(usage=None, samplers=SAMPLERS):
     g.add_option("--output-counts-pattern", dest="output_counts_pattern", type="string")
     g.add_option("--output-samples-pattern", dest="output_samples_pattern", type="string")
     g.add_option("--output-stats", dest="output_stats", type="choice", action="append",
-                 choices=("all", "annotations", "segments", "workspaces", "isochores", "overlap", "segment_metrics", "sample_metrics"),
+                 choices=("all", "annotations", "segments", "workspaces", "isochores", "overlap", "segment_metrics", "sample_metrics",
+                          "fdr_summary"),
                  help="write summary statistics of the collections at the stages of the input pipeline; segment_metrics / "
                       "sample_metrics: how the input segments / every sample sit in the workspace (gat_amd/metrics.py; not "
-                      "part of 'all')")
+                      "part of 'all'); fdr_summary: per --fdr-summary-pvalue the number of significant rows, over- and "
+                      "under-represented, beside its average, median and 95 % limit over the samples (the Annotator's false "
+                      "discovery summary, gat_amd/efdr.py; needs --pvalue-method=empirical; not part of 'all')")
+    g.add_option("--fdr-summary-pvalue", dest="fdr_summary_pvalues", type="float", action="append",
+                 help="a p-value cutoff of --output-stats=fdr_summary; repeatable [default=0.05]")
     g.add_option("--output-bed", dest="output_bed", type="choice", action="append",
                  choices=("all", "annotations", "segments", "workspaces", "isochores"),
                  help="write the collections after the isochores were applied as bed files")
@@ -756,10 +761,12 @@ def buildParser(usage=None, samplers=SAMPLERS):
     g = optparse.OptionGroup(parser, "Statistics options")
     g.add_option("-p", "--pvalue-method", dest="pvalue_method", type="choice", choices=("empirical", "norm"))
     g.add_option("-q", "--qvalue-method", dest="qvalue_method", type="choice",
-                 choices=("storey", "BH", "bonferroni", "holm", "hommel", "hochberg", "BY", "none", "minp"),
+                 choices=("storey", "BH", "bonferroni", "holm", "hommel", "hochberg", "BY", "none", "minp", "efdr"),
                  help="multiple-testing correction of the table's p-values; minp (not in the reference): step-down minP "
-                      "family-wise adjusted p-values from the joint null distribution the samples are, on the GPU "
-                      "(needs --pvalue-method=empirical) [default=%default]")
+                      "family-wise adjusted p-values from the joint null distribution the samples are, on the GPU; efdr (not "
+                      "in the reference): the false discovery rate from the same joint null distribution -- the samples' "
+                      "expected number of false calls over the observed number of calls -- on the GPU "
+                      "(both need --pvalue-method=empirical) [default=%default]")
     g.add_option("--qvalue-lambda", dest="qvalue_lambda", type="float", help="fdr computation: lambda")
     g.add_option("--qvalue-pi0-method", dest="qvalue_pi0_method", type="choice", choices=("smoother", "bootstrap"),
                  help="fdr computation: method for estimating pi0")

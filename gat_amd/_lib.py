@@ -34,7 +34,7 @@ SYMBOLS = [
     "gat_annotations_create", "gat_annotations_destroy", "gat_annotations_wait", "gat_list_sums", "gat_problem_rng_rows",
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
     "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics", "gat_list_distances",
-    "gat_sample_distances", "gat_minp_counts", "gat_minp_times",
+    "gat_sample_distances", "gat_minp_counts", "gat_minp_times", "gat_efdr_counts", "gat_efdr_times",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -238,6 +238,10 @@ def lib():
     L.gat_minp_counts.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp]
     L.gat_minp_times.restype = C.c_int
     L.gat_minp_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.gat_efdr_counts.restype = C.c_int
+    L.gat_efdr_counts.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, C.c_int32, vp, vp]
+    L.gat_efdr_times.restype = C.c_int
+    L.gat_efdr_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.gat_comm_unique_id.restype = C.c_int
     L.gat_comm_unique_id.argtypes = [vp]
     L.gat_comm_library_preloaded.restype = C.c_int
@@ -419,6 +423,30 @@ class Context(object):
         """(ms in k_minp_rank, ms in k_minp_step) of the last minp_counts; zeros unless set_kernel_times(True)"""
         a, b = C.c_float(), C.c_float()
         _check(lib().gat_minp_times(self._h, C.byref(a), C.byref(b)), self._h)
+        return a.value, b.value
+
+    def efdr_counts(self, counts_dev_ptr, n_rows, n_samples, is_double, means, k_obs, levels=()):
+        """the resampling-based FDR's counts on a device count matrix (gat_efdr_counts): (v, per_sample) -- v[r] = (V_1, V_0) at
+        the row's k_obs, int64, in the order of the rows: the samples of ALL rows scoring at or below it, by the tail they lie
+        in (1: above their row's mean); per_sample[l] = (N_1, N_0), int32 [2][n_samples]: per sample the rows scoring at or
+        below levels[l] (at most 8 levels).  means, k_obs: as for minp_counts."""
+        n = int(n_rows)
+        is_double = np.ascontiguousarray(is_double, dtype=np.uint8)
+        means = np.ascontiguousarray(means, dtype=np.float64)
+        k_obs = np.ascontiguousarray(k_obs, dtype=np.int32)
+        levels = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+        assert len(is_double) == len(means) == len(k_obs) == max(n, 0)
+        v = np.zeros((max(n, 0), 2), dtype=np.int64)
+        per_sample = np.zeros((len(levels), 2, max(int(n_samples), 0)), dtype=np.int32)
+        _check(lib().gat_efdr_counts(self._h, C.c_void_p(counts_dev_ptr), n, int(n_samples), _p(is_double), _p(means), _p(k_obs),
+                                     _p(levels) if len(levels) else None, len(levels), _p(v),
+                                     _p(per_sample) if len(levels) else None), self._h)
+        return v, per_sample
+
+    def efdr_times(self):
+        """(ms in k_minp_rank, ms in k_efdr) of the last efdr_counts; zeros unless set_kernel_times(True)"""
+        a, b = C.c_float(), C.c_float()
+        _check(lib().gat_efdr_times(self._h, C.byref(a), C.byref(b)), self._h)
         return a.value, b.value
 
     def count_lists(self, counters, lists, list_off, n_lists, annos, anno_off, n_tracks, ws_nseg, n_groups, anno_end=None):

@@ -108,6 +108,7 @@ struct gat_ctx {
   hipEvent_t ev_t[2] = {nullptr, nullptr};      // split path: behind k_tail, k_finalize
   bool t_recorded = false;
   float minp_ms[2] = {0.f, 0.f};                // the last gat_minp_counts: device time of k_minp_rank / k_minp_step (timed calls; else 0)
+  float efdr_ms[2] = {0.f, 0.f};                // the last gat_efdr_counts: device time of k_minp_rank / k_efdr (timed calls; else 0)
   hipEvent_t ev_cnt[2] = {nullptr, nullptr};    // around the count phase
   const void* timed_owner = nullptr;            // the problem whose call in flight owns the per-kernel events above (they exist once
                                                 // per context: a second call enqueued meanwhile -- run() keeps two problems' calls

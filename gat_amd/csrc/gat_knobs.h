@@ -83,7 +83,8 @@ struct gat_ctx;
   INT(distance_lds_pieces, "GAT_DISTANCE_LDS_PIECES", 2048) /* gat_*_distances: intervals of a list k_distance's search finds in LDS */ \
   INT(minp_lds_samples, "GAT_MINP_LDS_SAMPLES", 4096) /* gat_minp_counts: samples per row up to which k_minp_rank sorts in LDS */   \
   REAL(minp_scratch_mb, "GAT_MINP_SCRATCH_MB", 1024.0) /* ... megabytes of K (4 bytes a sample) per batch of rows */                \
-  FLAG(minp_all_passes, "GAT_MINP_ALL_PASSES") /* ... the sort runs all 16 digit passes (measuring what the skip is worth) */
+  FLAG(minp_all_passes, "GAT_MINP_ALL_PASSES") /* ... the sort runs all 16 digit passes (measuring what the skip is worth) */      \
+  INT(efdr_lds_thresholds, "GAT_EFDR_LDS_THRESHOLDS", 0) /* gat_efdr_counts: thresholds per pass of k_efdr; default: what a workgroup's LDS holds */
 
 struct Knobs {
 #define GAT_KNOB_FLAG(field, name) bool field = false;

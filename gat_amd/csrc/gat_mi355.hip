@@ -35,6 +35,7 @@
 #include "gat_stats.h"
 #include "gat_compare.h"
 #include "gat_minp.h"
+#include "gat_efdr.h"
 #include "gat_coverage.h"
 #include "gat_metrics.h"
 #include "gat_distance.h"
@@ -2472,6 +2473,68 @@ extern "C" int gat_compare_stats(gat_ctx* ctx, const void* a_dev, int64_t n_rows
 struct MinpTimer {                                  // device times of the two kernels, only for a call that asks (kernel times)
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   ~MinpTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  // ev[0] .. ev[1] around the first kernel, ev[1] .. ev[2] around the second: waits for the batch and adds to ms[0], ms[1]
+  int add(gat_ctx* ctx, float* ms) {
+    HIPCHK(ctx, hipEventRecord(ev[2], ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ev[2]));
+    float a = 0.f, b = 0.f;
+    HIPCHK(ctx, hipEventElapsedTime(&a, ev[0], ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&b, ev[1], ev[2]));
+    ms[0] += a; ms[1] += b;
+    return GAT_OK;
+  }
+};
+
+// "rank one batch of rows into K", the step gat_minp_counts and gat_efdr_counts share: the checks of the arguments and of the
+// options both have (`who` names the entry in the error texts), the batch size, K and the sort scratch, and the launch of
+// k_minp_rank for the batch rows a device array names.
+struct MinpRanker {
+  int64_t S = 0, batch = 0, grid_rank = 0;
+  bool in_lds = false;
+  size_t lds = 0;
+  DevBuf<int32_t> d_K;
+  DevBuf<uint8_t> d_dbl;
+  DevBuf<double> d_means;
+  DevBuf<unsigned long long> d_sort;
+  gat::MinpRankArgs R;
+
+  static int check(gat_ctx* ctx, const Knobs& kn, const char* who, int64_t n_rows, int64_t n_samples, const int32_t* kobs_host) {
+    if (n_samples < 1 || n_samples >= ((int64_t)1 << 31) || n_rows >= ((int64_t)1 << 31))
+      return set_err(ctx, GAT_ERR_ARG, "%s: bad sample / row count", who);
+    for (int64_t r = 0; r < n_rows; ++r)
+      if (kobs_host[r] < 1 || (int64_t)kobs_host[r] > n_samples)
+        return set_err(ctx, GAT_ERR_ARG, "%s: row %lld has k_obs %d of %lld samples", who, (long long)r, kobs_host[r], (long long)n_samples);
+    if (!(kn.minp_scratch_mb > 0.0)) return set_err(ctx, GAT_ERR_ARG, "%s: GAT_MINP_SCRATCH_MB must be positive", who);
+    const int64_t lds_max = ((int64_t)ctx->max_lds - gat::kMinpLdsFixed) / gat::kMinpKeyBytes;
+    if (kn.minp_lds_samples < 0 || kn.minp_lds_samples > lds_max)
+      return set_err(ctx, GAT_ERR_ARG, "%s: GAT_MINP_LDS_SAMPLES must be in [0, %lld]", who, (long long)lds_max);
+    return GAT_OK;
+  }
+  int init(gat_ctx* ctx, const Knobs& kn, const void* counts_dev, int64_t n_rows, int64_t n_samples,
+           const uint8_t* is_double_host, const double* means_host) {
+    S = n_samples;
+    const double budget_rows = kn.minp_scratch_mb * 1048576.0 / (double)(S * 4);
+    batch = std::max<int64_t>(1, budget_rows >= (double)n_rows ? n_rows : (int64_t)budget_rows);
+    in_lds = S <= kn.minp_lds_samples;
+    grid_rank = std::min<int64_t>(batch, gat::kMinpRankGrid);
+    lds = (size_t)gat::kMinpLdsFixed + (in_lds ? (size_t)S * gat::kMinpKeyBytes : 0);
+    HIPCHK(ctx, d_dbl.upload(std::vector<uint8_t>(is_double_host, is_double_host + n_rows), ctx));
+    HIPCHK(ctx, d_means.upload(std::vector<double>(means_host, means_host + n_rows), ctx));
+    HIPCHK(ctx, d_K.alloc((size_t)batch * (size_t)S));
+    if (!in_lds) HIPCHK(ctx, d_sort.alloc((size_t)grid_rank * 2 * (size_t)S));
+    if (in_lds) HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_minp_rank<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    R.counts = (const int64_t*)counts_dev; R.row_stride = S; R.S = (int32_t)S; R.is_double = d_dbl.p; R.means = d_means.p;
+    R.K = d_K.p; R.sort_scratch = d_sort.p; R.skip_passes = kn.minp_all_passes ? 0 : 1;
+    return GAT_OK;
+  }
+  // K[b] = the ranks of matrix row rows_dev[b], b < nb <= batch
+  int launch(gat_ctx* ctx, const int32_t* rows_dev, int64_t nb) {
+    R.n_rows = (int32_t)nb; R.rows = rows_dev;
+    if (in_lds) hipLaunchKernelGGL(gat::k_minp_rank<true>, dim3((unsigned)std::min<int64_t>(nb, grid_rank)), dim3(gat::kMinpThreads), lds, ctx->stream, R);
+    else hipLaunchKernelGGL(gat::k_minp_rank<false>, dim3((unsigned)std::min<int64_t>(nb, grid_rank)), dim3(gat::kMinpThreads), lds, ctx->stream, R);
+    HIPCHK(ctx, hipGetLastError());
+    return GAT_OK;
+  }
 };
 
 extern "C" int gat_minp_counts(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t n_samples,
@@ -2480,16 +2543,8 @@ extern "C" int gat_minp_counts(gat_ctx* ctx, const void* counts_dev, int64_t n_r
   if (!ctx || !counts_dev || !is_double_host || !means_host || !kobs_host || !c_out_host)
     return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: NULL argument");
   if (n_rows <= 0) return GAT_OK;
-  if (n_samples < 1 || n_samples >= ((int64_t)1 << 31) || n_rows >= ((int64_t)1 << 31))
-    return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: bad sample / row count");
-  for (int64_t r = 0; r < n_rows; ++r)
-    if (kobs_host[r] < 1 || (int64_t)kobs_host[r] > n_samples)
-      return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: row %lld has k_obs %d of %lld samples", (long long)r, kobs_host[r], (long long)n_samples);
   const Knobs kn = read_knobs(ctx);                 // the call's
-  if (!(kn.minp_scratch_mb > 0.0)) return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: GAT_MINP_SCRATCH_MB must be positive");
-  const int64_t lds_max = ((int64_t)ctx->max_lds - gat::kMinpLdsFixed) / gat::kMinpKeyBytes;
-  if (kn.minp_lds_samples < 0 || kn.minp_lds_samples > lds_max)
-    return set_err(ctx, GAT_ERR_ARG, "gat_minp_counts: GAT_MINP_LDS_SAMPLES must be in [0, %lld]", (long long)lds_max);
+  { const int rc = MinpRanker::check(ctx, kn, "gat_minp_counts", n_rows, n_samples, kobs_host); if (rc != GAT_OK) return rc; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int64_t S = n_samples;
   // o_1 .. o_R: by (k_obs, row index); proc = that order from its end
@@ -2498,55 +2553,31 @@ extern "C" int gat_minp_counts(gat_ctx* ctx, const void* counts_dev, int64_t n_r
   std::sort(proc.begin(), proc.end(), [&](int32_t a, int32_t b) { return kobs_host[a] != kobs_host[b] ? kobs_host[a] > kobs_host[b] : a > b; });
   std::vector<int32_t> kobs_proc((size_t)n_rows);
   for (int64_t p = 0; p < n_rows; ++p) kobs_proc[(size_t)p] = kobs_host[proc[(size_t)p]];
-  const double budget_rows = kn.minp_scratch_mb * 1048576.0 / (double)(S * 4);
-  const int64_t batch = std::max<int64_t>(1, budget_rows >= (double)n_rows ? n_rows : (int64_t)budget_rows);
-  const bool in_lds = S <= kn.minp_lds_samples;
-  const int64_t grid_rank = std::min<int64_t>(batch, gat::kMinpRankGrid);
-  const size_t lds = (size_t)gat::kMinpLdsFixed + (in_lds ? (size_t)S * gat::kMinpKeyBytes : 0);
-  DevBuf<int32_t> d_rows, d_kobs, d_q, d_K;
-  DevBuf<uint8_t> d_dbl;
-  DevBuf<double> d_means;
+  DevBuf<int32_t> d_rows, d_kobs, d_q;
   DevBuf<uint32_t> d_c;
-  DevBuf<unsigned long long> d_sort;
+  MinpRanker rank;
   HIPCHK(ctx, d_rows.upload(proc, ctx));
   HIPCHK(ctx, d_kobs.upload(kobs_proc, ctx));
-  HIPCHK(ctx, d_dbl.upload(std::vector<uint8_t>(is_double_host, is_double_host + n_rows), ctx));
-  HIPCHK(ctx, d_means.upload(std::vector<double>(means_host, means_host + n_rows), ctx));
+  { const int rc = rank.init(ctx, kn, counts_dev, n_rows, n_samples, is_double_host, means_host); if (rc != GAT_OK) return rc; }
   HIPCHK(ctx, d_c.alloc((size_t)n_rows));
   HIPCHK(ctx, d_q.alloc((size_t)S));
-  HIPCHK(ctx, d_K.alloc((size_t)batch * (size_t)S));
-  if (!in_lds) HIPCHK(ctx, d_sort.alloc((size_t)grid_rank * 2 * (size_t)S));
   HIPCHK(ctx, hipMemsetAsync(d_c.p, 0, (size_t)n_rows * 4, ctx->stream));
-  if (in_lds) HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_minp_rank<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const bool timed = ctx->kernel_times || kn.kernel_times;
   MinpTimer T;
   ctx->minp_ms[0] = ctx->minp_ms[1] = 0.f;
   if (timed) for (hipEvent_t& e : T.ev) HIPCHK(ctx, hipEventCreate(&e));
-  gat::MinpRankArgs R;
-  R.counts = (const int64_t*)counts_dev; R.row_stride = S; R.S = (int32_t)S; R.is_double = d_dbl.p; R.means = d_means.p;
-  R.K = d_K.p; R.sort_scratch = d_sort.p; R.skip_passes = kn.minp_all_passes ? 0 : 1;
   gat::MinpStepArgs Q;
-  Q.K = d_K.p; Q.S = (int32_t)S; Q.q = d_q.p;
+  Q.K = rank.d_K.p; Q.S = (int32_t)S; Q.q = d_q.p;
   const unsigned step_grid = (unsigned)((S + gat::kMinpThreads - 1) / gat::kMinpThreads);
-  for (int64_t p0 = 0; p0 < n_rows; p0 += batch) {                   // (one stream: a batch's K is read before the next one's is written)
-    const int64_t nb = std::min<int64_t>(batch, n_rows - p0);
-    R.n_rows = (int32_t)nb; R.rows = d_rows.p + p0;
+  for (int64_t p0 = 0; p0 < n_rows; p0 += rank.batch) {              // (one stream: a batch's K is read before the next one's is written)
+    const int64_t nb = std::min<int64_t>(rank.batch, n_rows - p0);
     if (timed) HIPCHK(ctx, hipEventRecord(T.ev[0], ctx->stream));
-    if (in_lds) hipLaunchKernelGGL(gat::k_minp_rank<true>, dim3((unsigned)std::min<int64_t>(nb, grid_rank)), dim3(gat::kMinpThreads), lds, ctx->stream, R);
-    else hipLaunchKernelGGL(gat::k_minp_rank<false>, dim3((unsigned)std::min<int64_t>(nb, grid_rank)), dim3(gat::kMinpThreads), lds, ctx->stream, R);
-    HIPCHK(ctx, hipGetLastError());
+    { const int rc = rank.launch(ctx, d_rows.p + p0, nb); if (rc != GAT_OK) return rc; }
     if (timed) HIPCHK(ctx, hipEventRecord(T.ev[1], ctx->stream));
     Q.n_rows = (int32_t)nb; Q.kobs = d_kobs.p + p0; Q.c = d_c.p + p0; Q.first = p0 == 0 ? 1 : 0;
     hipLaunchKernelGGL(gat::k_minp_step, dim3(step_grid), dim3(gat::kMinpThreads), 0, ctx->stream, Q);
     HIPCHK(ctx, hipGetLastError());
-    if (timed) {
-      HIPCHK(ctx, hipEventRecord(T.ev[2], ctx->stream));
-      HIPCHK(ctx, hipEventSynchronize(T.ev[2]));
-      float a = 0.f, b = 0.f;
-      HIPCHK(ctx, hipEventElapsedTime(&a, T.ev[0], T.ev[1]));
-      HIPCHK(ctx, hipEventElapsedTime(&b, T.ev[1], T.ev[2]));
-      ctx->minp_ms[0] += a; ctx->minp_ms[1] += b;
-    }
+    if (timed) { const int rc = T.add(ctx, ctx->minp_ms); if (rc != GAT_OK) return rc; }
   }
   std::vector<uint32_t> c((size_t)n_rows);
   HIPCHK(ctx, staged_d2h(ctx, c.data(), d_c.p, (size_t)n_rows * 4));
@@ -2558,5 +2589,98 @@ extern "C" int gat_minp_times(const gat_ctx* ctx, float* ms_rank, float* ms_step
   if (!ctx || !ms_rank || !ms_step) return set_err(nullptr, GAT_ERR_ARG, "gat_minp_times: NULL argument");
   *ms_rank = ctx->minp_ms[0];
   *ms_step = ctx->minp_ms[1];
+  return GAT_OK;
+}
+
+// The resampling-based FDR's counts (include/gat_mi355.h, gat_efdr.h): the rows are ranked into K in batches as for minP, in
+// their own order (V and N are sums over all rows); behind k_minp_rank, k_efdr runs once per chunk of at most
+// GAT_EFDR_LDS_THRESHOLDS thresholds over the batch's K.  The 64-bit bins and the per-sample level counts stay on the device
+// from batch to batch; the prefix sums over the thresholds are the host's.
+extern "C" int gat_efdr_counts(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t n_samples,
+                               const uint8_t* is_double_host, const double* means_host, const int32_t* kobs_host,
+                               const int32_t* levels_host, int32_t n_levels, int64_t* v_out_host, int32_t* per_sample_out_host) {
+  if (!ctx || !counts_dev || !is_double_host || !means_host || !kobs_host || !v_out_host || (n_levels > 0 && (!levels_host || !per_sample_out_host)))
+    return set_err(ctx, GAT_ERR_ARG, "gat_efdr_counts: NULL argument");
+  if (n_rows <= 0) return GAT_OK;
+  const Knobs kn = read_knobs(ctx);                 // the call's
+  { const int rc = MinpRanker::check(ctx, kn, "gat_efdr_counts", n_rows, n_samples, kobs_host); if (rc != GAT_OK) return rc; }
+  if (n_levels < 0 || n_levels > gat::kEfdrLevels) return set_err(ctx, GAT_ERR_ARG, "gat_efdr_counts: %d levels (at most %d)", n_levels, gat::kEfdrLevels);
+  for (int l = 0; l < n_levels; ++l)
+    if (levels_host[l] < 0 || (int64_t)levels_host[l] > n_samples)
+      return set_err(ctx, GAT_ERR_ARG, "gat_efdr_counts: level %d is %d of %lld samples", l, levels_host[l], (long long)n_samples);
+  const int64_t thr_max = (int64_t)ctx->max_lds / gat::kEfdrThresholdBytes;
+  if (kn.efdr_lds_thresholds_set && (kn.efdr_lds_thresholds < 1 || kn.efdr_lds_thresholds > thr_max))
+    return set_err(ctx, GAT_ERR_ARG, "gat_efdr_counts: GAT_EFDR_LDS_THRESHOLDS must be in [1, %lld]", (long long)thr_max);
+  const int64_t chunk = kn.efdr_lds_thresholds_set ? kn.efdr_lds_thresholds : thr_max;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int64_t S = n_samples;
+  std::vector<int32_t> thr(kobs_host, kobs_host + n_rows);          // the sorted distinct k_obs
+  std::sort(thr.begin(), thr.end());
+  thr.erase(std::unique(thr.begin(), thr.end()), thr.end());
+  const int64_t n_thr = (int64_t)thr.size();
+  std::vector<int32_t> ident((size_t)n_rows);
+  for (int64_t r = 0; r < n_rows; ++r) ident[(size_t)r] = (int32_t)r;
+  DevBuf<int32_t> d_rows, d_thr, d_ps;
+  DevBuf<unsigned long long> d_bins;
+  MinpRanker rank;
+  HIPCHK(ctx, d_rows.upload(ident, ctx));
+  HIPCHK(ctx, d_thr.upload(thr, ctx));
+  { const int rc = rank.init(ctx, kn, counts_dev, n_rows, n_samples, is_double_host, means_host); if (rc != GAT_OK) return rc; }
+  HIPCHK(ctx, d_bins.alloc((size_t)(2 * n_thr)));
+  HIPCHK(ctx, hipMemsetAsync(d_bins.p, 0, (size_t)(2 * n_thr) * 8, ctx->stream));
+  const size_t ps_words = (size_t)n_levels * 2 * (size_t)S;
+  HIPCHK(ctx, d_ps.alloc(ps_words));
+  if (ps_words) HIPCHK(ctx, hipMemsetAsync(d_ps.p, 0, ps_words * 4, ctx->stream));
+  // (the largest chunk's, whatever this call's is: the attribute is the kernel's, and another context's call may be in flight)
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_efdr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(thr_max * gat::kEfdrThresholdBytes)));
+  const bool timed = ctx->kernel_times || kn.kernel_times;
+  MinpTimer T;
+  ctx->efdr_ms[0] = ctx->efdr_ms[1] = 0.f;
+  if (timed) for (hipEvent_t& e : T.ev) HIPCHK(ctx, hipEventCreate(&e));
+  gat::EfdrArgs A;
+  A.K = rank.d_K.p; A.counts = (const int64_t*)counts_dev; A.row_stride = S; A.S = (int32_t)S;
+  A.is_double = rank.d_dbl.p; A.means = rank.d_means.p; A.bins_stride = n_thr; A.per_sample = d_ps.p;
+  const int64_t grid_x = (S + gat::kEfdrThreads - 1) / gat::kEfdrThreads;
+  for (int64_t p0 = 0; p0 < n_rows; p0 += rank.batch) {              // (one stream: a batch's K is read before the next one's is written)
+    const int64_t nb = std::min<int64_t>(rank.batch, n_rows - p0);
+    if (timed) HIPCHK(ctx, hipEventRecord(T.ev[0], ctx->stream));
+    { const int rc = rank.launch(ctx, d_rows.p + p0, nb); if (rc != GAT_OK) return rc; }
+    if (timed) HIPCHK(ctx, hipEventRecord(T.ev[1], ctx->stream));
+    A.n_rows = (int32_t)nb; A.rows = d_rows.p + p0;
+    for (int64_t c0 = 0; c0 < n_thr; c0 += chunk) {
+      const int64_t nc = std::min<int64_t>(chunk, n_thr - c0);
+      // slabs of rows: about eight workgroups per compute unit in all, a slab long enough to pay for a workgroup's pass over
+      // its bins (three LDS words and up to two global adds per threshold) and short enough for its 32-bit LDS bins
+      // (256 x rows < 2^32), at most 65535 of them (grid y)
+      const int64_t slabs_wanted = std::max<int64_t>(1, (2048 + grid_x - 1) / grid_x);
+      int64_t rps = std::max<int64_t>((nb + slabs_wanted - 1) / slabs_wanted, (nc + 31) / 32);
+      rps = std::min<int64_t>(rps, ((int64_t)1 << 24) - 1);
+      rps = std::min<int64_t>(std::max<int64_t>(rps, (nb + 65534) / 65535), nb);
+      A.rows_per_slab = (int32_t)rps;
+      A.thr = d_thr.p + c0; A.n_thr = (int32_t)nc; A.below = c0 > 0 ? thr[(size_t)c0 - 1] : 0; A.bins = d_bins.p + c0;
+      A.n_levels = c0 == 0 ? n_levels : 0;                          // the levels once per batch: with its first chunk
+      for (int l = 0; l < gat::kEfdrLevels; ++l) A.levels[l] = l < A.n_levels ? levels_host[l] : -1;
+      hipLaunchKernelGGL(gat::k_efdr, dim3((unsigned)grid_x, (unsigned)((nb + rps - 1) / rps)), dim3(gat::kEfdrThreads),
+                         (size_t)nc * gat::kEfdrThresholdBytes, ctx->stream, A);
+      HIPCHK(ctx, hipGetLastError());
+    }
+    if (timed) { const int rc = T.add(ctx, ctx->efdr_ms); if (rc != GAT_OK) return rc; }
+  }
+  std::vector<unsigned long long> bins((size_t)(2 * n_thr));
+  HIPCHK(ctx, staged_d2h(ctx, bins.data(), d_bins.p, bins.size() * 8));
+  for (int64_t j = 1; j < n_thr; ++j) { bins[(size_t)j] += bins[(size_t)j - 1]; bins[(size_t)(n_thr + j)] += bins[(size_t)(n_thr + j) - 1]; }   // V_d(thr[j])
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const int64_t j = std::lower_bound(thr.begin(), thr.end(), kobs_host[r]) - thr.begin();
+    v_out_host[2 * r] = (int64_t)bins[(size_t)j];
+    v_out_host[2 * r + 1] = (int64_t)bins[(size_t)(n_thr + j)];
+  }
+  if (ps_words) HIPCHK(ctx, staged_d2h(ctx, per_sample_out_host, d_ps.p, ps_words * 4));
+  return GAT_OK;
+}
+
+extern "C" int gat_efdr_times(const gat_ctx* ctx, float* ms_rank, float* ms_efdr) {
+  if (!ctx || !ms_rank || !ms_efdr) return set_err(nullptr, GAT_ERR_ARG, "gat_efdr_times: NULL argument");
+  *ms_rank = ctx->efdr_ms[0];
+  *ms_efdr = ctx->efdr_ms[1];
   return GAT_OK;
 }

@@ -1734,10 +1734,14 @@ def getQValues(pvalues, method="storey", **kwargs):
 
 def updateQValues(annotator_results, method="storey", **kwargs):
     """gat/Engine.pyx:2044-2054.  method "minp" (not in the reference): step-down minP from the rows' own samples, on the
-    device (gat_amd/minp.py); getQValues, a function of p-values alone, does not know it."""
+    device (gat_amd/minp.py), and "efdr", the resampling-based false discovery rate from the same samples (gat_amd/efdr.py);
+    getQValues, a function of p-values alone, does not know them."""
     if method == "minp":
         from . import minp
         qvalues = minp.adjust(annotator_results)
+    elif method == "efdr":
+        from . import efdr
+        qvalues = efdr.adjust(annotator_results)
     else:
         qvalues = getQValues([r.pvalue for r in annotator_results], method, **kwargs)
     for r, qvalue in zip(annotator_results, qvalues):

@@ -406,8 +406,22 @@ def readDescriptions(options):
 
 def outputResults(results, options, header, description_header=(), description_width=0, descriptions=None,
                   format_observed="%i"):
-    """gat/IO.py:457-539: q-values, one table per counter, rows ordered by --order."""
-    if options.qvalue_method == "minp":
+    """gat/IO.py:457-539: q-values, one table per counter, rows ordered by --order; behind the tables the false discovery
+    summary (--output-stats=fdr_summary, gat_amd/efdr.py)."""
+    fdr_summary = "fdr_summary" in (getattr(options, "output_stats", None) or [])
+    summary_rows = None
+    if options.qvalue_method == "efdr" or fdr_summary:
+        # the resampling-based FDR (gat_amd/efdr.py): like minP from the rows' samples, scored with the empirical p-value;
+        # q-values and summary come out of one upload and one pass on the device
+        if getattr(options, "pvalue_method", "empirical") != "empirical":
+            raise ValueError("--%s needs --pvalue-method=empirical (got %s)"
+                             % ("qvalue-method=efdr" if options.qvalue_method == "efdr" else "output-stats=fdr_summary", options.pvalue_method))
+        from . import efdr
+        cutoffs = (getattr(options, "fdr_summary_pvalues", None) or [0.05]) if fdr_summary else []
+        efdr_qvalues, summary_rows = efdr.compute(results, cutoffs)
+    if options.qvalue_method == "efdr":
+        qvalues = efdr_qvalues
+    elif options.qvalue_method == "minp":
         # step-down minP (gat_amd/minp.py): from the rows' samples, not from their p-values -- and those samples are scored
         # with the empirical p-value, so the rows' own p-values have to be empirical too
         if getattr(options, "pvalue_method", "empirical") != "empirical":
@@ -444,5 +458,11 @@ def outputResults(results, options, header, description_header=(), description_w
             if descriptions:
                 outfile.write("\t" + "\t".join(descriptions.get(result.annotation, [""] * description_width)))
             outfile.write("\n")
+        if outfile is not options.stdout:
+            outfile.close()
+    if fdr_summary:
+        from . import efdr
+        outfile = openOutputFile("fdr_summary", options)
+        outfile.write(efdr.format_summary(summary_rows))
         if outfile is not options.stdout:
             outfile.close()

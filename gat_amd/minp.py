@@ -34,22 +34,22 @@ def adjusted(k_obs, c, nsamples):
     return out
 
 
-def _rows(results):
+def _rows(results, method="minp"):
     """(nsamples, k_obs, means, the float64 matrix) of a list of AnnotatorResult; ValueError where the procedure does not
-    apply"""
+    apply (`method`: the name the message gives it; gat_amd/efdr.py reads its rows here too)"""
     nsamples = None
     k_obs, means, rows = [], [], []
     for x in results:
         if not hasattr(x, "_two_sided") or not hasattr(x, "samples"):
-            raise ValueError("qvalue method minp: row (%s, %s) holds no samples (a results table read back has none; start "
-                             "from the run or from its counts file)" % (getattr(x, "track", "?"), getattr(x, "annotation", "?")))
+            raise ValueError("qvalue method %s: row (%s, %s) holds no samples (a results table read back has none; start "
+                             "from the run or from its counts file)" % (method, getattr(x, "track", "?"), getattr(x, "annotation", "?")))
         if getattr(x, "_has_reference", False):
-            raise ValueError("qvalue method minp: row (%s, %s) was built with a reference: its expected value is not the "
-                             "mean of its samples" % (x.track, x.annotation))
+            raise ValueError("qvalue method %s: row (%s, %s) was built with a reference: its expected value is not the "
+                             "mean of its samples" % (method, x.track, x.annotation))
         if nsamples is None:
             nsamples = x.nsamples
         elif x.nsamples != nsamples:
-            raise ValueError("qvalue method minp: rows of %d and %d samples (one family shares its samples)" % (nsamples, x.nsamples))
+            raise ValueError("qvalue method %s: rows of %d and %d samples (one family shares its samples)" % (method, nsamples, x.nsamples))
         k_obs.append(int(round(x._two_sided(x.observed) * x.nsamples)))
         means.append(x.expected)
         rows.append(x.samples)

@@ -562,6 +562,34 @@ int gat_minp_counts(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_
  * batches; measured only after gat_ctx_set_kernel_times(ctx, 1) (or GAT_KERNEL_TIMES), else 0 */
 int gat_minp_times(const gat_ctx* ctx, float* ms_rank, float* ms_step);
 
+/* ---- resampling-based FDR: the expected number of false calls from the joint null distribution --------
+ * The FDR counterpart of step-down minP, and what the Annotator's "False Discovery summary" estimates: the number of rows of
+ * column i that would be called at a threshold is one draw of the number of false calls there.  counts_dev, is_double, means,
+ * kobs, T and K[r][i] = T(r, row_r[i]) are those of gat_minp_counts (S = n_samples).  With
+ *     D[r][i] = 1 if row_r[i] > means[r] else 0        (the comparison T branches on: 1 = the over-represented tail)
+ *     V_d(t)  = #{(r, i) : K[r][i] <= t and D[r][i] == d},  d in {1, 0}
+ *     N_d[i]  = #{r : K[r][i] <= L and D[r][i] == d}   for a level L
+ * v_out[r] = { V_1(kobs[r]), V_0(kobs[r]) } in the order of the input rows, and per_sample_out[l] = { N_1[0..S), N_0[0..S) }
+ * for L = levels[l].  A sample counts as significant at t exactly when an observed value equal to it would.  The caller
+ * forms Rn(t) = #{r : kobs[r] <= t}, fdr(t) = (V_1(t) + V_0(t)) / (S * Rn(t)) and, along the rows o_1 .. o_R ordered by
+ * (kobs, r) ascending, q[o_j] = min(1, max(1 / S, min over j' >= j of fdr(kobs[o_j']))); and from N the summary per level
+ * (mean, median, 95 % limit over the samples).  All of it is integer arithmetic; a level 0 gives zeros (K >= 1).
+ * The rows are ranked into K as gat_minp_counts does it (k_minp_rank, batches of GAT_MINP_SCRATCH_MB, GAT_MINP_LDS_SAMPLES,
+ * GAT_MINP_ALL_PASSES); k_efdr then makes one pass over a batch's K and the matrix (D is recomputed from it) per chunk of at
+ * most GAT_EFDR_LDS_THRESHOLDS distinct kobs (default and upper limit: what a workgroup's LDS holds at 12 bytes a threshold,
+ * 13653 with 160 KiB), counting into LDS bins and from there into 64-bit bins on the device, whose prefix sums are V.  All
+ * are context options read once at the top of the call; none changes a result.  n_rows <= 0: GAT_OK, nothing written.
+ * GAT_ERR_ARG: a NULL argument (levels_host and per_sample_out_host may be NULL when n_levels == 0), n_samples < 1 or
+ * >= 2^31, a kobs outside [1, n_samples], n_levels outside [0, 8], a level outside [0, n_samples], an option out of range. */
+int gat_efdr_counts(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t n_samples,
+                    const uint8_t* is_double_host, const double* means_host, const int32_t* kobs_host,
+                    const int32_t* levels_host, int32_t n_levels,
+                    int64_t* v_out_host          /* [n_rows][2]: V_1(kobs[r]), V_0(kobs[r]), input row order */,
+                    int32_t* per_sample_out_host /* [n_levels][2][n_samples]: N_1, N_0; may be NULL when n_levels == 0 */);
+/* device time in milliseconds the context's last gat_efdr_counts spent in k_minp_rank and in k_efdr (all its chunks), summed
+ * over its batches; measured only after gat_ctx_set_kernel_times(ctx, 1) (or GAT_KERNEL_TIMES), else 0 */
+int gat_efdr_times(const gat_ctx* ctx, float* ms_rank, float* ms_efdr);
+
 /* ---- multi-GPU: the one collective of the path ---------------------------------------------
  * Replaces the result collation of the reference's process pool (gat/__init__.py:681-700, :770-774):
  * every rank has computed the columns of its own contiguous sample range (gat_sample_and_count with
