@@ -35,6 +35,7 @@ SYMBOLS = [
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
     "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics", "gat_list_distances",
     "gat_sample_distances", "gat_minp_counts", "gat_minp_times", "gat_efdr_counts", "gat_efdr_times",
+    "gat_list_bin_overlaps", "gat_sample_bin_enrichment",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -214,6 +215,10 @@ def lib():
     L.gat_list_distances.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, C.c_int, i64, vp]
     L.gat_sample_distances.restype = C.c_int
     L.gat_sample_distances.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, C.c_int, i64, vp, C.POINTER(Stats)]
+    L.gat_list_bin_overlaps.restype = C.c_int
+    L.gat_list_bin_overlaps.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, i64, vp, vp]
+    L.gat_sample_bin_enrichment.restype = C.c_int
+    L.gat_sample_bin_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, i64, vp, vp, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -471,7 +476,36 @@ class Context(object):
                 for k, c in enumerate(counters)]
 
 
+    def list_bin_overlaps(self, lists, list_off, n_lists, annos, anno_off, n_tracks, n_groups, bin_size, n_bins):
+        """the bases every one of n_lists x n_groups caller-provided normalized lists -- list l of group g is
+        lists[list_off[l * n_groups + g]:list_off[l * n_groups + g + 1]] -- shares with every one of n_tracks x n_groups
+        normalized annotation lists, track t of group g at index t * n_groups + g, per bin of bin_size bases
+        (gat_list_bin_overlaps): n_bins[g] bins for group g.  Returns (values, bin_off): int64 [n_lists, n_tracks, total_bins],
+        group g's bins at [bin_off[g], bin_off[g + 1])."""
+        lists = np.ascontiguousarray(lists, dtype=SEG)
+        annos = np.ascontiguousarray(annos, dtype=SEG)
+        list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+        anno_off = np.ascontiguousarray(anno_off, dtype=np.int64)
+        n_lists, n_tracks, n_groups = int(n_lists), int(n_tracks), int(n_groups)
+        assert len(list_off) == n_lists * n_groups + 1 and len(anno_off) == n_tracks * n_groups + 1
+        bin_off = _bin_offsets(n_bins, n_groups)
+        out = np.zeros((n_lists, n_tracks, max(0, int(bin_off[-1]))), dtype=np.int64)
+        _check(lib().gat_list_bin_overlaps(self._h, _p(lists), _p(list_off), n_lists, _p(annos), _p(anno_off), n_tracks, n_groups,
+                                           int(bin_size), _p(bin_off), _p(out)), self._h)
+        return out, bin_off
+
+
+def _bin_offsets(n_bins, n_groups):
+    """bin_off of gat_sample_coverage and the per-bin overlaps: n_groups + 1 entries, the running sum of n_bins"""
+    n_bins = np.ascontiguousarray(n_bins, dtype=np.int64)
+    assert n_bins.shape == (n_groups,)
+    bin_off = np.zeros(n_groups + 1, dtype=np.int64)
+    np.cumsum(n_bins, out=bin_off[1:])
+    return bin_off
+
+
 METRICS_WORDS = ("n", "bases", "pairs", "inter", "touched", "outside_pieces", "tail_n", "tail_bases")
+LOCAL_WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")
 
 
 def list_metrics(ctx, lists, list_off, n_lists, ws, ws_off, n_groups):
@@ -859,3 +893,25 @@ class Problem(object):
         self.last_stats = st.asdict()
         _check(rc, self.ctx._h)
         return out
+
+    def sample_bin_enrichment(self, seed, sample_begin, sample_end, annos, anno_off, n_tracks, bin_size, n_bins, obs):
+        """per (track, bin) the five sums (LOCAL_WORDS; gat_sample_bin_enrichment) over the sampled contig-level lists of
+        [sample_begin, sample_end) of v = the bases a list shares with the track inside the bin, against obs[track, bin] --
+        track t of contig c is annos[anno_off[t * n_contigs + c]:anno_off[t * n_contigs + c + 1]], n_bins[c] bins of bin_size
+        bases for contig c, contigs in the problem's order.  Returns (words, bin_off): int64 [n_tracks, total_bins, 5]."""
+        annos = np.ascontiguousarray(annos, dtype=SEG)
+        anno_off = np.ascontiguousarray(anno_off, dtype=np.int64)
+        n_tracks = int(n_tracks)
+        assert anno_off.shape == (n_tracks * self.n_contigs + 1,)
+        bin_off = _bin_offsets(n_bins, self.n_contigs)
+        total = max(0, int(bin_off[-1]))
+        obs = np.ascontiguousarray(obs, dtype=np.int64)
+        assert obs.shape == (n_tracks, total)
+        out = np.zeros((n_tracks, total, len(LOCAL_WORDS)), dtype=np.int64)
+        st = Stats()
+        rc = lib().gat_sample_bin_enrichment(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
+                                             _p(annos), _p(anno_off), n_tracks, int(bin_size), _p(bin_off), _p(obs), _p(out),
+                                             C.byref(st))
+        self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
+        return out, bin_off

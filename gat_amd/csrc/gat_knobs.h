@@ -84,7 +84,10 @@ struct gat_ctx;
   INT(minp_lds_samples, "GAT_MINP_LDS_SAMPLES", 4096) /* gat_minp_counts: samples per row up to which k_minp_rank sorts in LDS */   \
   REAL(minp_scratch_mb, "GAT_MINP_SCRATCH_MB", 1024.0) /* ... megabytes of K (4 bytes a sample) per batch of rows */                \
   FLAG(minp_all_passes, "GAT_MINP_ALL_PASSES") /* ... the sort runs all 16 digit passes (measuring what the skip is worth) */      \
-  INT(efdr_lds_thresholds, "GAT_EFDR_LDS_THRESHOLDS", 0) /* gat_efdr_counts: thresholds per pass of k_efdr; default: what a workgroup's LDS holds */
+  INT(efdr_lds_thresholds, "GAT_EFDR_LDS_THRESHOLDS", 0) /* gat_efdr_counts: thresholds per pass of k_efdr; default: what a workgroup's LDS holds */ \
+  INT(local_window_bins, "GAT_LOCAL_WINDOW_BINS", 256) /* gat_*_bin_*: bins of a workgroup's LDS window in k_local */          \
+  INT(local_samples_per_block, "GAT_LOCAL_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */            \
+  INT(local_lds_pieces, "GAT_LOCAL_LDS_PIECES", 256) /* ... annotation intervals of a window its search finds in LDS */
 
 struct Knobs {
 #define GAT_KNOB_FLAG(field, name) bool field = false;

@@ -39,6 +39,7 @@
 #include "gat_coverage.h"
 #include "gat_metrics.h"
 #include "gat_distance.h"
+#include "gat_local.h"
 
 
 #include "gat_host.h"
@@ -1628,8 +1629,8 @@ extern "C" void gat_mt19937_seed(uint32_t seed, uint32_t* mt_state) {
 }
 
 // ---- the entry points that read the sampled lists where they are: gat_sample / gat_sample_units copy them out, and
-// gat_sample_coverage, gat_sample_metrics and gat_sample_distances put a kernel (gat_coverage.h, gat_metrics.h,
-// gat_distance.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
+// gat_sample_coverage, gat_sample_metrics, gat_sample_distances and gat_sample_bin_enrichment put a kernel (gat_coverage.h,
+// gat_metrics.h, gat_distance.h, gat_local.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
 
 // A synchronous call's frame: refused while a call is in flight on the problem (P == nullptr: a call over the caller's own
 // lists); the knobs are read once; body(kn, local) does the work.  Whatever the body returns, the stream is drained behind it:
@@ -1970,14 +1971,15 @@ struct DistanceBufs {
 };
 // the searched side: every one of n_entities x n_groups lists sorted, disjoint, without an empty interval
 static int distance_check_normalized(gat_ctx* ctx, const char* who, const char* what, const gat_segment* a, const int64_t* off,
-                                     int64_t n_entities, int32_t n_groups) {
+                                     int64_t n_entities, int32_t n_groups,
+                                     const char* why = "the nearest interval is searched for in it") {
   for (int64_t i = 0; i < n_entities; ++i)
     for (int32_t g = 0; g < n_groups; ++g) {
       const int64_t b = off[i * n_groups + g], e = off[i * n_groups + g + 1];
       for (int64_t j = b; j < e; ++j)
         if (a[j].end <= a[j].start || (j > b && a[j].start < a[j - 1].end))
           return set_err(ctx, GAT_ERR_ARG, "%s: %s %lld, group %d is not normalized at interval %lld (sorted, disjoint, none empty: "
-                         "the nearest interval is searched for in it)", who, what, (long long)i, g, (long long)(j - b));
+                         "%s)", who, what, (long long)i, g, (long long)(j - b), why);
     }
   return GAT_OK;
 }
@@ -2099,6 +2101,159 @@ extern "C" int gat_sample_distances(gat_ctx* ctx, gat_problem* P, uint32_t seed,
     if (sample_end == sample_begin) return GAT_OK;  // (no batch runs: nothing is written)
     return sample_distances_body(ctx, P, kn, seed, sample_begin, sample_end - sample_begin, annos, anno_off, n_tracks, direction,
                                  max_distance, out_host, local, B);
+  });
+}
+
+// gat_list_bin_overlaps / gat_sample_bin_enrichment: k_local (gat_local.h) over caller-provided lists, or behind every batch.
+// The tracks go up once per call (uint2, from anno_off[0]); the windows -- W bins of one (track, contig) and the slice of the
+// track that reaches into them -- are made on the host per call, and only those a track reaches into: everywhere else v is
+// 0.  The device buffers live for the call.
+struct LocalBufs {
+  DevBuf<uint2> d_anno, d_seg;
+  DevBuf<int64_t> d_anno_csr, d_csr;
+  DevBuf<gat::LocalWindow> d_win;
+  DevBuf<long long> d_obs;
+  DevBuf<unsigned long long> d_out;
+  std::vector<gat::LocalWindow> win;
+  int64_t W = 0, L = 0;
+};
+static const char* const kLocalWhy = "the overlap per bin is formed from disjoint pieces";
+// what both entry points ask of the tracks and the bins
+static int local_check_common(gat_ctx* ctx, const char* who, const gat_segment* annos, const int64_t* anno_off, int64_t n_tracks,
+                              int64_t n_groups, int64_t bin_size, const int64_t* bin_off) {
+  if (bin_size < 1 || bin_size > (int64_t)1 << 31) return set_err(ctx, GAT_ERR_ARG, "%s: bin_size %lld outside [1, 2^31]", who, (long long)bin_size);
+  if (bin_off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: bin_off[0] < 0", who);
+  for (int64_t c = 0; c < n_groups; ++c)
+    if (bin_off[c + 1] < bin_off[c]) return set_err(ctx, GAT_ERR_ARG, "%s: bin_off decreases at group %lld", who, (long long)c);
+  if (n_tracks < 0 || n_tracks > (int64_t)INT32_MAX || n_tracks * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_tracks %lld", who, (long long)n_tracks);
+  const int64_t n = n_tracks * n_groups;
+  int rc;
+  if ((rc = check_list_offsets(ctx, who, "anno_off", "intervals", anno_off, n))) return rc;
+  if (anno_off[n] > anno_off[0] && !annos) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  return distance_check_normalized(ctx, who, "annotation track", annos, anno_off, n_tracks, (int32_t)n_groups, kLocalWhy);
+}
+// the windows of a call (gat_local_windows.h) and the tracks, on the device
+static int local_windows(gat_ctx* ctx, const char* who, const Knobs& kn, const gat_segment* annos, const int64_t* anno_off,
+                         int32_t n_tracks, int32_t C, int64_t bin_size, const int64_t* bin_off, LocalBufs& B) {
+  B.L = std::max<int64_t>(1, std::min<int64_t>(kn.local_lds_pieces, 8192));
+  B.W = std::max<int64_t>(1, std::min<int64_t>(kn.local_window_bins, gat::local_max_window(ctx->max_lds, B.L)));
+  if (!gat::local_build_windows(annos, anno_off, n_tracks, C, bin_size, bin_off, B.W, B.win))
+    return set_err(ctx, GAT_ERR_CAPACITY, "%s: more than 2^31 windows of %lld bins", who, (long long)B.W);
+  int rc;
+  if ((rc = upload_csr_lists(ctx, annos, anno_off, (int64_t)n_tracks * C, B.d_anno, B.d_anno_csr))) return rc;
+  HIPCHK(ctx, B.d_win.upload(B.win, ctx));
+  return GAT_OK;
+}
+// one launch over n_lists x windows; store: the raw values per list, else the fold into B.d_out's five words
+static int launch_local(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists, int64_t n_lists, int32_t n_groups, int64_t bin_size,
+                        bool store, int64_t list_stride, const LocalBufs& B) {
+  if (B.win.empty() || n_lists == 0) return GAT_OK;
+  gat::LocalArgs A;
+  memset(&A, 0, sizeof(A));
+  A.lists = lists;
+  A.n_lists = (int32_t)n_lists;
+  A.n_groups = n_groups;
+  A.window_bins = (int32_t)B.W;
+  A.lds_pieces = (int32_t)B.L;
+  A.span32 = B.W * bin_size <= (int64_t)1 << 32 ? 1 : 0;
+  A.bin_size = bin_size;
+  A.list_stride = list_stride;
+  A.win = B.d_win.p;
+  A.annos = B.d_anno.p;
+  A.obs = B.d_obs.p;
+  A.out = B.d_out.p;
+  const int64_t n_win = (int64_t)B.win.size();
+  const int64_t lpb = kn.local_samples_per_block > 0 ? gat::run_per_block(n_lists, n_win, 0, kn.local_samples_per_block)
+                                                     : gat::run_per_block(n_lists, n_win, 1024, gat::kNoRunCap);
+  A.lists_per_block = (int32_t)lpb;
+  const size_t lds = gat::local_lds_bytes(B.W, B.L, store);
+  const dim3 grid((unsigned)n_win, (unsigned)((n_lists + lpb - 1) / lpb));
+  if (store) {
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_local<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(gat::k_local<true>, grid, dim3(gat::kLocalThreads), lds, ctx->stream, A);
+  } else {
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_local<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(gat::k_local<false>, grid, dim3(gat::kLocalThreads), lds, ctx->stream, A);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return GAT_OK;
+}
+
+extern "C" int gat_list_bin_overlaps(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                                     const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups,
+                                     int64_t bin_size, const int64_t* bin_off, int64_t* out_host) {
+  const char* who = "gat_list_bin_overlaps";
+  if (!ctx || !list_off || !anno_off || !bin_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
+  int rc;
+  if ((rc = local_check_common(ctx, who, annos, anno_off, n_tracks, n_groups, bin_size, bin_off))) return rc;
+  const int64_t n = n_lists * n_groups;
+  if ((rc = check_list_offsets(ctx, who, "list_off", "intervals", list_off, n))) return rc;
+  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = distance_check_normalized(ctx, who, "segment list", lists, list_off, n_lists, n_groups, kLocalWhy))) return rc;
+  const int64_t list_stride = (int64_t)n_tracks * bin_off[n_groups];
+  const size_t words = (size_t)(n_lists * list_stride);
+  if (words == 0) return GAT_OK;
+  LocalBufs B;
+  return call_frame(ctx, nullptr, nullptr, [&](const Knobs& kn, gat_stats&) {
+    int brc;
+    if ((brc = local_windows(ctx, who, kn, annos, anno_off, n_tracks, n_groups, bin_size, bin_off, B))) return brc;
+    if ((brc = upload_csr_lists(ctx, lists, list_off, n, B.d_seg, B.d_csr))) return brc;
+    HIPCHK(ctx, B.d_out.alloc(words));
+    HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, words * 8, ctx->stream));
+    if ((brc = launch_local(ctx, kn, csr_lists(B.d_seg, B.d_csr), n_lists, n_groups, bin_size, true, list_stride, B))) return brc;
+    HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, words * 8));
+    return GAT_OK;
+  });
+}
+
+static int sample_bin_enrichment_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                                      const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int64_t bin_size,
+                                      const int64_t* bin_off, const int64_t* obs_host, int64_t* out_host, gat_stats& local, LocalBufs& B) {
+  const int C = P->n_contigs;
+  const int64_t cells = (int64_t)n_tracks * bin_off[C];
+  int rc;
+  if ((rc = local_windows(ctx, "gat_sample_bin_enrichment", kn, annos, anno_off, n_tracks, C, bin_size, bin_off, B))) return rc;
+  HIPCHK(ctx, B.d_obs.alloc((size_t)cells));
+  HIPCHK(ctx, staged_h2d(ctx, B.d_obs.p, obs_host, (size_t)cells * 8));
+  HIPCHK(ctx, B.d_out.alloc((size_t)cells * gat::kLocalWords));
+  HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, (size_t)cells * gat::kLocalWords * 8, ctx->stream));
+  rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t, int64_t nb) {
+    return launch_local(ctx, kn, sampled_lists(P), nb, C, bin_size, false, 0, B);
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(gat::k_local_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out.p, B.d_obs.p, cells, (unsigned long long)S);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, (size_t)cells * gat::kLocalWords * 8));
+  return GAT_OK;
+}
+
+extern "C" int gat_sample_bin_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                         const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks,
+                                         int64_t bin_size, const int64_t* bin_off, const int64_t* obs_host,
+                                         int64_t* out_host, gat_stats* stats) {
+  const char* who = "gat_sample_bin_enrichment";
+  if (!ctx || !P || !anno_off || !bin_off || !obs_host || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
+  int rc;
+  if ((rc = local_check_common(ctx, who, annos, anno_off, n_tracks, P->n_contigs, bin_size, bin_off))) return rc;
+  const int64_t S = sample_end - sample_begin, cells = (int64_t)n_tracks * bin_off[P->n_contigs];
+  if ((unsigned __int128)((uint64_t)bin_size * (uint64_t)bin_size) * (unsigned __int128)(uint64_t)S >> 64)
+    return set_err(ctx, GAT_ERR_ARG, "%s: bin_size^2 * samples = %lld^2 * %lld does not fit 64 bits (sumsq): a smaller bin_size or fewer samples per call",
+                   who, (long long)bin_size, (long long)S);
+  for (int64_t k = 0; k < cells; ++k)
+    if (obs_host[k] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: obs[%lld] = %lld is negative", who, (long long)k, (long long)obs_host[k]);
+  if (!sampled_lists_normalized(P))
+    return set_err(ctx, GAT_ERR_ARG, "%s: the sampled segment lists are not normalized (SamplerSegments without isochore keys leaves them "
+                   "neither sorted nor disjoint): the overlap per bin needs normalized lists", who);
+  LocalBufs B;
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    if (cells == 0) return GAT_OK;
+    if (S == 0) { memset(out_host, 0, (size_t)cells * gat::kLocalWords * 8); return GAT_OK; }   // (no batch runs: the sums are empty)
+    return sample_bin_enrichment_body(ctx, P, kn, seed, sample_begin, S, annos, anno_off, n_tracks, bin_size, bin_off, obs_host,
+                                      out_host, local, B);
   });
 }
 

@@ -1529,6 +1529,21 @@ def getTwoSidedPValue(sorted_samples, expected, val):
     return max(min_pval, float(idx) / l)
 
 
+def twoSidedPValueFromCounts(n_less, n_eq, above_expected, l):  # noqa: E741
+    """getTwoSidedPValue from two counts: n_less of the l sample values lie below val and n_eq equal it; above_expected:
+    val > expected.  (AnnotatorResult._two_sided has the derivation; gat_amd/local.py gets the counts per bin.)"""
+    idx = n_less
+    if idx == l:
+        idx = 1
+    elif above_expected:
+        if n_eq > 0 and idx > 0:
+            idx -= 1
+        idx = l - (idx + 1)
+    else:
+        idx += n_eq
+    return max(1.0 / l, float(idx) / l)
+
+
 class AnnotatorResult(object):
     """gat/Engine.pyx:1725 / makeEnrichmentStatistics :1635-1718 (numpy on the host; identical
     IEEE arithmetic: numpy.mean/std, sorted-value lookups)."""
@@ -1599,16 +1614,7 @@ class AnnotatorResult(object):
         else:
             n_less = int(np.count_nonzero(self._samples < val))
             n_eq = int(np.count_nonzero(self._samples == val))
-        idx = n_less
-        if idx == l:
-            idx = 1
-        elif val > self.expected:
-            if n_eq > 0 and idx > 0:
-                idx -= 1
-            idx = l - (idx + 1)
-        else:
-            idx += n_eq
-        return max(1.0 / l, float(idx) / l)
+        return twoSidedPValueFromCounts(n_less, n_eq, val > self.expected, l)
 
     @property
     def _samples(self):

@@ -446,6 +446,56 @@ int gat_sample_distances(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                          int direction, int64_t max_distance,
                          int64_t* out_host, gat_stats* stats /* nullable */);
 
+/* Where along the genome a segment list overlaps an annotation track, per bin, formed on the device by k_local (the reference
+ * has nothing like it: gat-run gives one number per annotation over the whole workspace).  Bin b of group (contig) c is
+ * [b * bin_size, (b + 1) * bin_size), b < n_bins[c] = bin_off[c + 1] - bin_off[c] -- the layout of gat_sample_coverage:
+ * bin_size in [1, 2^31], bin_off with n_groups + 1 non-decreasing entries.  For a normalized segment list L and a normalized
+ * annotation list A of the same group (sorted by start, pairwise disjoint, every interval with end > start; adjacent
+ * intervals allowed)
+ *     v(L, A, b) = |L n A n bin b|        bases; 0 <= v <= bin_size
+ * Overlap at or beyond n_bins[c] * bin_size is not counted.  Over a range of S samples and against an observed value
+ * obs[t][bin] >= 0 given by the caller, every (track t, bin) gets five int64 words (GAT_LOCAL_WORDS), in this order:
+ *     n_pos    samples with v > 0
+ *     sum      of v
+ *     sumsq    of v * v   (below 2^64, to be read as unsigned where it passes 2^63)
+ *     n_less   samples with v < obs   (all S samples count here and in n_eq, those with v == 0 too)
+ *     n_eq     samples with v == obs
+ * All arithmetic is 64-bit and exact.  Every word is additive over the samples: a partial sum has one owner on the device and
+ * is added once with a 64-bit integer add, so results are reproducible and do not depend on how the range is cut into
+ * batches, workgroups or calls -- the words of calls over [0, k) and [k, S) add up to those of the call over [0, S).
+ * Context options, none of which changes a result: GAT_LOCAL_WINDOW_BINS -- the bins of a workgroup's window in LDS (clamped
+ * to what a workgroup's LDS holds); GAT_LOCAL_SAMPLES_PER_BLOCK -- the run of lists a workgroup takes (default: by the
+ * launch); GAT_LOCAL_LDS_PIECES -- how many annotation intervals of a window the kernel's search finds in LDS before it goes
+ * to global memory.
+ *
+ * gat_list_bin_overlaps: the raw v of caller-provided lists (the observed values of the input segments with n_lists == 1).
+ * lists / list_off, annos / anno_off, n_tracks, n_groups: as in gat_list_distances.  out_host: [n_lists][n_tracks]
+ * [bin_off[n_groups]].  Synchronous.  GAT_ERR_ARG: a NULL ctx / list_off / anno_off / bin_off / out_host (lists / annos may
+ * be NULL where they hold nothing), negative counts, a decreasing offset, bin_size outside [1, 2^31], bin_off[0] < 0 or a
+ * decreasing bin_off, a segment list or a track that is not normalized or holds an empty interval: gat_last_error names the
+ * list (or track) and the group.  Never a wrong number. */
+#define GAT_LOCAL_WORDS 5
+int gat_list_bin_overlaps(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                          const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups,
+                          int64_t bin_size, const int64_t* bin_off, int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop shared with gat_sample, k_local behind every batch that passed its checks, reading
+ * the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed and
+ * range (per-unit streams only).  The groups are the problem's contigs in the problem's order: anno_off has n_tracks *
+ * n_contigs + 1 entries, bin_off n_contigs + 1; obs_host: [n_tracks][total_bins], total_bins = bin_off[n_contigs];
+ * out_host: [n_tracks][total_bins][5].  Synchronous, like gat_sample.  An empty sample range writes zeros.  GAT_ERR_ARG: a
+ * NULL ctx / p / anno_off / bin_off / obs_host / out_host, sample_end < sample_begin, a negative n_tracks, a decreasing
+ * anno_off, bin_size outside [1, 2^31], bin_off[0] < 0 or a decreasing bin_off, a negative obs, bin_size^2 * samples >= 2^64
+ * (sumsq would not fit), a track that is not normalized (gat_last_error names the track and the contig), a sampler whose
+ * lists are not normalized (SamplerSegments on a problem without isochore keys; the message says so), a call in flight on
+ * the problem.  The sampler's errors pass through (GAT_ERR_ASSERT; SamplerBruteForce's GAT_ERR_VALUE "sampling did not
+ * converge"). */
+int gat_sample_bin_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                              int64_t sample_begin, int64_t sample_end,
+                              const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks,
+                              int64_t bin_size, const int64_t* bin_off, const int64_t* obs_host,
+                              int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
