@@ -35,7 +35,7 @@ SYMBOLS = [
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
     "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics", "gat_list_distances",
     "gat_sample_distances", "gat_minp_counts", "gat_minp_times", "gat_efdr_counts", "gat_efdr_times",
-    "gat_list_bin_overlaps", "gat_sample_bin_enrichment",
+    "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -52,6 +52,26 @@ def mt19937_seed(seed):
 
 
 COUNT_KERNELS = {0: "none", 1: "k_count_seg", 2: "k_count_swap", 3: "k_count_merged"}
+
+
+COUNT_ANNO_KERNELS = {0: "none", 1: "k_count_anno_idx", 2: "k_count_anno"}
+
+
+class CountReport(C.Structure):
+    """gat_count_report: what the count stage launched last on a context (gat_count_last_launch)"""
+    _fields_ = [
+        ("kernel", C.c_int32),
+        ("staged", C.c_int32),
+        ("hits", C.c_int32),
+        ("patch", C.c_int32),
+        ("tracks_per_block", C.c_int32),
+        ("samples_per_block", C.c_int32),
+        ("merged_form", C.c_int32),
+        ("anno_kernel", C.c_int32),
+    ]
+
+    def asdict(self):
+        return dict((f, getattr(self, f)) for f, _ in self._fields_)
 
 
 class GatError(RuntimeError):
@@ -223,6 +243,8 @@ def lib():
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
     L.gat_count_list_ranges.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, vp, i32, vp, i32, vp]
+    L.gat_count_last_launch.restype = C.c_int
+    L.gat_count_last_launch.argtypes = [vp, C.POINTER(CountReport)]
     L.gat_call_lane_for.restype = C.c_int
     L.gat_call_lane_for.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.gat_intersection_sizes.restype = C.c_int
@@ -475,6 +497,12 @@ class Context(object):
         return [out[k].view(np.float64).copy() if c == "nucleotide-density" else out[k].copy()
                 for k, c in enumerate(counters)]
 
+    def count_report(self):
+        """what the count stage launched last on this context, as a dict of gat_count_report's fields: the newest batch of a
+        sample_and_count, or the last list of a count_lists (COUNT_KERNELS / COUNT_ANNO_KERNELS name the kernels)"""
+        r = CountReport()
+        _check(lib().gat_count_last_launch(self._h, C.byref(r)), self._h)
+        return r.asdict()
 
     def list_bin_overlaps(self, lists, list_off, n_lists, annos, anno_off, n_tracks, n_groups, bin_size, n_bins):
         """the bases every one of n_lists x n_groups caller-provided normalized lists -- list l of group g is

@@ -310,6 +310,8 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
                         int swap_capx, int list_cap, CountLaunch& L) {
   L.main_recorded = false;
   L.count_kernel = GAT_COUNT_KERNEL_NONE;
+  gat_count_report& R = ctx->count_report;      // (what is launched below, for gat_count_last_launch: no launch depends on it)
+  R = gat_count_report();
   for (int i = 0; i < GAT_NUM_COUNTERS; ++i) A.counter_slot[i] = C.slot[i];
   A.a_start = annos.start.p; A.a_end = annos.end.p; A.a_cumx = annos.cumx.p; A.a_off = annos.off.p;
   A.a_grid = annos.grid.p; A.g_off = annos.goff.p; A.c_shift = annos.shift.p; A.c_cells = annos.cells.p;
@@ -394,6 +396,8 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
       HIPCHK(ctx, hipEventRecord(L.ev_main[1], L.stream));
       L.main_recorded = true;
       L.count_kernel = GAT_COUNT_KERNEL_MERGED;
+      R.kernel = GAT_COUNT_KERNEL_MERGED; R.patch = patch ? 1 : 0; R.samples_per_block = SG;
+      R.merged_form = blk == 8 ? 8 : blk == 1 ? 1 : 2;
       const int64_t tiles = (int64_t)((A.n_tracks + 15) / 16) * ((A.n_samples + 15) / 16);
       hipLaunchKernelGGL(gat::k_count_merged_finish, dim3((unsigned)tiles), dim3(256), 0, L.stream, A);
       HIPCHK(ctx, hipGetLastError());
@@ -414,6 +418,7 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
       HIPCHK(ctx, hipEventRecord(L.ev_main[1], L.stream));
       L.main_recorded = true;
       L.count_kernel = GAT_COUNT_KERNEL_SWAP;
+      R.kernel = GAT_COUNT_KERNEL_SWAP;
     } else
     if (A.n_contigs > 0) {
     const bool hits = C.slot[GAT_COUNTER_SEGMENT_OVERLAP] >= 0 || C.slot[GAT_COUNTER_SEGMENT_MIDOVERLAP] >= 0;
@@ -430,6 +435,8 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
     HIPCHK(ctx, hipEventRecord(L.ev_main[1], L.stream));
     L.main_recorded = true;
     L.count_kernel = GAT_COUNT_KERNEL_SEG;
+    R.kernel = GAT_COUNT_KERNEL_SEG; R.staged = staged ? 1 : 0; R.hits = hits ? 1 : 0; R.patch = A.seg_merged != nullptr ? 1 : 0;
+    R.tracks_per_block = TT; R.samples_per_block = SC;
     }
     {
       const int64_t nfin = (int64_t)A.n_tracks * A.n_samples;
@@ -457,10 +464,12 @@ static int launch_count(gat_ctx* ctx, const Knobs& kn, const AnnoDev& annos, con
       const int64_t nfin = (int64_t)A.n_tracks * A.n_samples;
       hipLaunchKernelGGL(gat::k_count_anno_finish, dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, L.stream, B);
       HIPCHK(ctx, hipGetLastError());
+      R.anno_kernel = GAT_COUNT_ANNO_IDX;
     } else {
       const int64_t waves = (int64_t)A.n_samples * A.n_tracks;
       hipLaunchKernelGGL(gat::k_count_anno, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, L.stream, A);
       HIPCHK(ctx, hipGetLastError());
+      R.anno_kernel = GAT_COUNT_ANNO_PLAIN;
     }
   }
   return GAT_OK;
@@ -2288,7 +2297,9 @@ static int count_lists_body(gat_ctx* ctx, const Knobs& kn, const CountListsIn& i
   for (int64_t l = 0; l < n_lists * n_groups; ++l)
     if ((rc = check_list(ctx, in.lists + in.list_off[l], in.list_off[l + 1] - in.list_off[l], "segment", l))) return rc;
   const int64_t total = in.list_off[n_lists * n_groups];
-  std::vector<uint2> h_seg((size_t)total);
+  // (+1: k_count_seg issues the load of a list's element 0 whatever its length and turns it into padding afterwards -- an
+  //  empty list behind the last segment read 8 bytes beyond the buffer)
+  std::vector<uint2> h_seg((size_t)total + 1, make_uint2(0u, 0u));
   for (int64_t i = 0; i < total; ++i) h_seg[(size_t)i] = make_uint2(in.lists[i].start, in.lists[i].end);
   HIPCHK(ctx, B.d_seg.upload(h_seg, ctx));
   std::vector<int64_t> h_nseg(in.ws_nseg, in.ws_nseg + n_groups);
@@ -2349,7 +2360,9 @@ static int count_lists_impl(gat_ctx* ctx, const CountListsIn& in) {
   }
   gat_ctx* x = ctx->aux_ctx;
   const Knobs kn = read_knobs(ctx);                 // (the caller's: the auxiliary context has no options of its own)
+  x->count_report = gat_count_report();             // (a call without a list launches nothing)
   const int rc = count_lists_on(x, kn, in);
+  ctx->count_report = x->count_report;
   x->stage_used = 0;                                // (count_lists_on has drained the stream before its buffers went back to the pool)
   if (rc) return set_err(ctx, rc, "%s", x->err.c_str());
   return GAT_OK;
@@ -2361,6 +2374,12 @@ extern "C" int gat_count_lists(gat_ctx* ctx, const int32_t* counter_ids, int n_c
                                const int64_t* ws_nseg, int32_t n_groups, void* counts_host) {
   if (!anno_off) return set_err(ctx, GAT_ERR_ARG, "gat_count_lists: NULL argument");
   return count_lists_impl(ctx, {counter_ids, n_counters, lists, list_off, n_lists, annos, anno_off, anno_off + 1, n_tracks, ws_nseg, n_groups, counts_host});
+}
+
+extern "C" int gat_count_last_launch(const gat_ctx* ctx, gat_count_report* out) {
+  if (!ctx || !out) return set_err(nullptr, GAT_ERR_ARG, "gat_count_last_launch: NULL argument");
+  *out = ctx->count_report;
+  return GAT_OK;
 }
 
 extern "C" int gat_count_list_ranges(gat_ctx* ctx, const int32_t* counter_ids, int n_counters,

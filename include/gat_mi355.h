@@ -207,6 +207,23 @@ typedef struct {
 #define GAT_COUNT_KERNEL_SWAP 2     /* k_count_swap: sample list indexed in LDS, annotation tracks streamed */
 #define GAT_COUNT_KERNEL_MERGED 3   /* k_count_merged: one look-up per sample segment in a merged index of all tracks */
 
+/* What the count stage launched last on a context: the newest batch of a gat_sample_and_count* call, or the LAST list of a
+ * gat_count_lists / gat_count_list_ranges call (one launch per list).  For tests and diagnosis: which of the kernels the sizes
+ * and the GAT_COUNT_* / GAT_MERGED_* options led to.  All zero when nothing was launched. */
+typedef struct gat_count_report {
+  int32_t kernel;             /* GAT_COUNT_KERNEL_*: what served the segment-side counters                              */
+  int32_t staged;             /* k_count_seg: 1 the track tile's lists staged in LDS, 0 read from global memory         */
+  int32_t hits;               /* k_count_seg: 1 the variant that also counts segment-overlap / segment-midoverlap        */
+  int32_t patch;              /* k_count_seg / k_count_merged: 1 the lists read as (merged list, k_tail's record)         */
+  int32_t tracks_per_block;   /* k_count_seg: tracks of a tile as launched, else 0                                       */
+  int32_t samples_per_block;  /* k_count_seg / k_count_merged: samples of a workgroup as launched, else 0                */
+  int32_t merged_form;        /* k_count_merged: how a scan fetches the index, 8, 2 or 1; 0: it did not run              */
+  int32_t anno_kernel;        /* the annotation-side counters: 0 none, 1 k_count_anno_idx, 2 k_count_anno               */
+} gat_count_report;
+#define GAT_COUNT_ANNO_NONE 0
+#define GAT_COUNT_ANNO_IDX 1
+#define GAT_COUNT_ANNO_PLAIN 2
+
 /* ---- context ---------------------------------------------------------------------------- */
 /* device_id: HIP device ordinal.  stream: a hipStream_t to run on (e.g. a torch stream's handle; the default stream is
  * named by hipStreamLegacy, (hipStream_t)1 -- its own handle is NULL) or NULL to create a private non-blocking one. */
@@ -513,6 +530,10 @@ int gat_count_list_ranges(gat_ctx* ctx, const int32_t* counter_ids, int n_counte
                           const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
                           const gat_segment* annos, const int64_t* anno_begin, const int64_t* anno_end, int32_t n_tracks,
                           const int64_t* ws_nseg, int32_t n_groups, void* counts_host);
+
+/* Read-only: the record of the context's last count launch (gat_count_report above).  A gat_count_lists call runs on a
+ * stream of its own inside the library; its record is copied to the context it was called on. */
+int gat_count_last_launch(const gat_ctx* ctx, gat_count_report* out);
 
 /* Sizes of the intersection of two interval dictionaries, for the overlap_* columns of a result row: replaces
  * `overlap = track_segments.clone(); overlap.intersect(annotation_segments); overlap.counts(), overlap.sum()`
