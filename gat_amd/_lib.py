@@ -36,6 +36,7 @@ SYMBOLS = [
     "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics", "gat_list_distances",
     "gat_sample_distances", "gat_minp_counts", "gat_minp_times", "gat_efdr_counts", "gat_efdr_times",
     "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch",
+    "gat_list_pair_hits", "gat_sample_pair_enrichment",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -239,6 +240,10 @@ def lib():
     L.gat_list_bin_overlaps.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, i64, vp, vp]
     L.gat_sample_bin_enrichment.restype = C.c_int
     L.gat_sample_bin_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, i64, vp, vp, vp, C.POINTER(Stats)]
+    L.gat_list_pair_hits.restype = C.c_int
+    L.gat_list_pair_hits.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, vp]
+    L.gat_sample_pair_enrichment.restype = C.c_int
+    L.gat_sample_pair_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, vp, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -521,6 +526,32 @@ class Context(object):
         _check(lib().gat_list_bin_overlaps(self._h, _p(lists), _p(list_off), n_lists, _p(annos), _p(anno_off), n_tracks, n_groups,
                                            int(bin_size), _p(bin_off), _p(out)), self._h)
         return out, bin_off
+
+    def list_pair_hits(self, lists, list_off, n_lists, annos, anno_off, n_tracks, n_groups):
+        """how many segments of every one of n_lists caller-provided lists -- list l of group g is
+        lists[list_off[l * n_groups + g]:list_off[l * n_groups + g + 1]], in any order -- hit both tracks of every pair
+        (i, j), i <= j, of n_tracks x n_groups normalized annotation lists, track t of group g at index t * n_groups + g
+        (gat_list_pair_hits).  Returns int64 [n_lists, P], P = n_tracks * (n_tracks + 1) / 2, pair (i, j) at
+        i * n_tracks - i * (i - 1) / 2 + (j - i)."""
+        lists = np.ascontiguousarray(lists, dtype=SEG)
+        annos = np.ascontiguousarray(annos, dtype=SEG)
+        list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+        anno_off = np.ascontiguousarray(anno_off, dtype=np.int64)
+        n_lists, n_tracks, n_groups = int(n_lists), int(n_tracks), int(n_groups)
+        assert len(list_off) == n_lists * n_groups + 1 and len(anno_off) == n_tracks * n_groups + 1
+        out = np.zeros((n_lists, pair_count(n_tracks)), dtype=np.int64)
+        _check(lib().gat_list_pair_hits(self._h, _p(lists), _p(list_off), n_lists, _p(annos), _p(anno_off), n_tracks, n_groups,
+                                        _p(out)), self._h)
+        return out
+
+
+PAIR_WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")
+PAIR_MAX_TRACKS = 2048        # GAT_PAIR_MAX_TRACKS
+
+
+def pair_count(n_tracks):
+    """the pairs (i, j), i <= j, of n_tracks tracks (0 where n_tracks is out of range: the library refuses the call)"""
+    return n_tracks * (n_tracks + 1) // 2 if 0 <= n_tracks <= PAIR_MAX_TRACKS else 0
 
 
 def _bin_offsets(n_bins, n_groups):
@@ -943,3 +974,22 @@ class Problem(object):
         self.last_stats = st.asdict()
         _check(rc, self.ctx._h)
         return out, bin_off
+
+    def sample_pair_enrichment(self, seed, sample_begin, sample_end, annos, anno_off, n_tracks, obs):
+        """per pair (i, j), i <= j, of n_tracks tracks the five sums (PAIR_WORDS; gat_sample_pair_enrichment) over the sampled
+        contig-level lists of [sample_begin, sample_end) of c = the segments of a list that hit track i and track j, against
+        obs[pair] -- track t of contig c is annos[anno_off[t * n_contigs + c]:anno_off[t * n_contigs + c + 1]], contigs in
+        the problem's order.  Returns int64 [P, 5]."""
+        annos = np.ascontiguousarray(annos, dtype=SEG)
+        anno_off = np.ascontiguousarray(anno_off, dtype=np.int64)
+        n_tracks = int(n_tracks)
+        assert anno_off.shape == (max(0, n_tracks) * self.n_contigs + 1,)
+        obs = np.ascontiguousarray(obs, dtype=np.int64)
+        assert not 0 <= n_tracks <= PAIR_MAX_TRACKS or obs.shape == (pair_count(n_tracks),)
+        out = np.zeros((pair_count(n_tracks), len(PAIR_WORDS)), dtype=np.int64)
+        st = Stats()
+        rc = lib().gat_sample_pair_enrichment(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
+                                              _p(annos), _p(anno_off), n_tracks, _p(obs), _p(out), C.byref(st))
+        self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
+        return out

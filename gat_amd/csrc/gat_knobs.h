@@ -87,7 +87,9 @@ struct gat_ctx;
   INT(efdr_lds_thresholds, "GAT_EFDR_LDS_THRESHOLDS", 0) /* gat_efdr_counts: thresholds per pass of k_efdr; default: what a workgroup's LDS holds */ \
   INT(local_window_bins, "GAT_LOCAL_WINDOW_BINS", 256) /* gat_*_bin_*: bins of a workgroup's LDS window in k_local */          \
   INT(local_samples_per_block, "GAT_LOCAL_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */            \
-  INT(local_lds_pieces, "GAT_LOCAL_LDS_PIECES", 256) /* ... annotation intervals of a window its search finds in LDS */
+  INT(local_lds_pieces, "GAT_LOCAL_LDS_PIECES", 256) /* ... annotation intervals of a window its search finds in LDS */       \
+  INT(pairs_lds_pieces, "GAT_PAIRS_LDS_PIECES", 32) /* gat_*_pair_*: intervals of a (track, group) k_pairs' search finds in LDS; 0: none */ \
+  INT(pairs_samples_per_block, "GAT_PAIRS_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */
 
 struct Knobs {
 #define GAT_KNOB_FLAG(field, name) bool field = false;

@@ -40,6 +40,7 @@
 #include "gat_metrics.h"
 #include "gat_distance.h"
 #include "gat_local.h"
+#include "gat_pairs.h"
 
 
 #include "gat_host.h"
@@ -1638,8 +1639,8 @@ extern "C" void gat_mt19937_seed(uint32_t seed, uint32_t* mt_state) {
 }
 
 // ---- the entry points that read the sampled lists where they are: gat_sample / gat_sample_units copy them out, and
-// gat_sample_coverage, gat_sample_metrics, gat_sample_distances and gat_sample_bin_enrichment put a kernel (gat_coverage.h,
-// gat_metrics.h, gat_distance.h, gat_local.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
+// gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_bin_enrichment and gat_sample_pair_enrichment put a
+// kernel (gat_coverage.h, gat_metrics.h, gat_distance.h, gat_local.h, gat_pairs.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
 
 // A synchronous call's frame: refused while a call is in flight on the problem (P == nullptr: a call over the caller's own
 // lists); the knobs are read once; body(kn, local) does the work.  Whatever the body returns, the stream is drained behind it:
@@ -2263,6 +2264,139 @@ extern "C" int gat_sample_bin_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t 
     if (S == 0) { memset(out_host, 0, (size_t)cells * gat::kLocalWords * 8); return GAT_OK; }   // (no batch runs: the sums are empty)
     return sample_bin_enrichment_body(ctx, P, kn, seed, sample_begin, S, annos, anno_off, n_tracks, bin_size, bin_off, obs_host,
                                       out_host, local, B);
+  });
+}
+
+// gat_list_pair_hits / gat_sample_pair_enrichment: k_pairs (gat_pairs.h) over caller-provided lists, or behind every batch.
+// The tracks go up once per call (CSR, uint2); the device buffers live for the call.
+struct PairsBufs {
+  DevBuf<uint2> d_anno, d_seg;
+  DevBuf<int64_t> d_anno_csr, d_csr;
+  DevBuf<long long> d_obs;
+  DevBuf<unsigned long long> d_out;
+};
+static const char* const kPairsWhy = "the first interval that reaches a segment is searched for in it";
+// what both entry points ask of the tracks
+static int pairs_check_common(gat_ctx* ctx, const char* who, const gat_segment* annos, const int64_t* anno_off, int64_t n_tracks, int64_t n_groups) {
+  if (n_tracks < 0 || n_tracks > gat::kPairsMaxTracks)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_tracks %lld outside [0, %d]", who, (long long)n_tracks, gat::kPairsMaxTracks);
+  if (n_tracks * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_ARG, "%s: n_tracks %lld x %lld groups", who, (long long)n_tracks, (long long)n_groups);
+  const int64_t n = n_tracks * n_groups;
+  int rc;
+  if ((rc = check_list_offsets(ctx, who, "anno_off", "intervals", anno_off, n))) return rc;
+  if (anno_off[n] > anno_off[0] && !annos) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  return distance_check_normalized(ctx, who, "annotation track", annos, anno_off, n_tracks, (int32_t)n_groups, kPairsWhy);
+}
+// one launch over tiles x runs of n_lists lists; store: the raw counts per list, else the fold into B.d_out's five words.
+// The run: the knob's where it is set, else as long as leaves 4 096 workgroups -- three rounds of the five a compute unit holds: the
+// tiles of a call are not equally long, and a last round that is half empty costs as much as a full one -- but at least 8 lists
+static int launch_pairs(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists, int64_t n_lists, int32_t n_tracks, int32_t n_groups,
+                        bool store, const PairsBufs& B) {
+  if (n_lists == 0 || n_tracks == 0 || n_groups == 0) return GAT_OK;
+  gat::PairsArgs A;
+  memset(&A, 0, sizeof(A));
+  A.lists = lists;
+  A.n_lists = (int32_t)n_lists;
+  A.n_groups = n_groups;
+  A.n_tracks = n_tracks;
+  const int64_t L = gat::pairs_lds_pieces(std::max<int64_t>(0, kn.pairs_lds_pieces), n_groups);
+  A.lds_pieces = (int32_t)L;
+  A.annos = B.d_anno.p;
+  A.anno_csr = B.d_anno_csr.p;
+  A.obs = B.d_obs.p;
+  A.out = B.d_out.p;
+  const int64_t n_tiles = gat::pairs_tiles(n_tracks);
+  const int64_t lpb = kn.pairs_samples_per_block > 0 ? gat::run_per_block(n_lists, n_tiles, 0, kn.pairs_samples_per_block)
+                                                     : gat::run_per_block(n_lists, n_tiles, 4096, gat::kNoRunCap);
+  A.lists_per_block = (int32_t)lpb;
+  const size_t lds = (size_t)gat::pairs_lds_bytes(L, n_groups);
+  const dim3 grid((unsigned)n_tiles, (unsigned)((n_lists + lpb - 1) / lpb));
+  if (store) {
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(gat::k_pairs<true>, grid, dim3(gat::kPairsThreads), lds, ctx->stream, A);
+  } else {
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_pairs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(gat::k_pairs<false>, grid, dim3(gat::kPairsThreads), lds, ctx->stream, A);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return GAT_OK;
+}
+
+extern "C" int gat_list_pair_hits(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                                  const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups,
+                                  int64_t* out_host) {
+  const char* who = "gat_list_pair_hits";
+  if (!ctx || !list_off || !anno_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
+  int rc;
+  if ((rc = pairs_check_common(ctx, who, annos, anno_off, n_tracks, n_groups))) return rc;
+  const int64_t n = n_lists * n_groups;
+  if ((rc = check_list_offsets(ctx, who, "list_off", "segments", list_off, n))) return rc;
+  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  for (int64_t l = 0; l < n_lists; ++l)           // (a list's count of a pair is a 32-bit word on the device)
+    if (list_off[(l + 1) * n_groups] - list_off[l * n_groups] > (int64_t)INT32_MAX)
+      return set_err(ctx, GAT_ERR_CAPACITY, "%s: list %lld holds more than 2^31 - 1 segments", who, (long long)l);
+  const size_t words = (size_t)(n_lists * gat::pairs_count(n_tracks));
+  if (words == 0) return GAT_OK;
+  PairsBufs B;
+  return call_frame(ctx, nullptr, nullptr, [&](const Knobs& kn, gat_stats&) {
+    int brc;
+    if ((brc = upload_csr_lists(ctx, annos, anno_off, (int64_t)n_tracks * n_groups, B.d_anno, B.d_anno_csr))) return brc;
+    if ((brc = upload_csr_lists(ctx, lists, list_off, n, B.d_seg, B.d_csr))) return brc;
+    HIPCHK(ctx, B.d_out.alloc(words));
+    HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, words * 8, ctx->stream));
+    if ((brc = launch_pairs(ctx, kn, csr_lists(B.d_seg, B.d_csr), n_lists, n_tracks, n_groups, true, B))) return brc;
+    HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, words * 8));
+    return GAT_OK;
+  });
+}
+
+static int sample_pair_enrichment_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                                       const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, const int64_t* obs_host,
+                                       int64_t* out_host, gat_stats& local, PairsBufs& B) {
+  const int C = P->n_contigs;
+  const int64_t pairs = gat::pairs_count(n_tracks);
+  int rc;
+  if ((rc = upload_csr_lists(ctx, annos, anno_off, (int64_t)n_tracks * C, B.d_anno, B.d_anno_csr))) return rc;
+  HIPCHK(ctx, B.d_obs.alloc((size_t)pairs));
+  HIPCHK(ctx, staged_h2d(ctx, B.d_obs.p, obs_host, (size_t)pairs * 8));
+  HIPCHK(ctx, B.d_out.alloc((size_t)pairs * gat::kPairsWords));
+  HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, (size_t)pairs * gat::kPairsWords * 8, ctx->stream));
+  rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t, int64_t nb) {
+    return launch_pairs(ctx, kn, sampled_lists(P), nb, n_tracks, C, false, B);
+  });
+  if (rc) return rc;
+  // the samples whose count is 0: the five words are k_local's, and so is their last step
+  static_assert(gat::kPairsWords == gat::kLocalWords, "k_local_finish reads five words");
+  hipLaunchKernelGGL(gat::k_local_finish, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out.p, B.d_obs.p, pairs, (unsigned long long)S);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, (size_t)pairs * gat::kPairsWords * 8));
+  return GAT_OK;
+}
+
+extern "C" int gat_sample_pair_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                          const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks,
+                                          const int64_t* obs_host, int64_t* out_host, gat_stats* stats) {
+  const char* who = "gat_sample_pair_enrichment";
+  if (!ctx || !P || !anno_off) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
+  int rc;
+  if ((rc = pairs_check_common(ctx, who, annos, anno_off, n_tracks, P->n_contigs))) return rc;
+  const int64_t S = sample_end - sample_begin, pairs = gat::pairs_count(n_tracks);
+  if (pairs > 0 && (!obs_host || !out_host)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  const int64_t n_max = P->slab_stride;           // the most segments one sample can hold
+  if (n_max > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_CAPACITY, "%s: a sample can hold %lld segments, more than 2^31 - 1", who, (long long)n_max);
+  if ((unsigned __int128)((uint64_t)n_max * (uint64_t)n_max) * (unsigned __int128)(uint64_t)S >> 64)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_max^2 * samples = %lld^2 * %lld does not fit 64 bits (sumsq): fewer samples per call",
+                   who, (long long)n_max, (long long)S);
+  for (int64_t k = 0; k < pairs; ++k)
+    if (obs_host[k] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: obs[%lld] = %lld is negative", who, (long long)k, (long long)obs_host[k]);
+  PairsBufs B;
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    if (pairs == 0) return GAT_OK;
+    if (S == 0) { memset(out_host, 0, (size_t)pairs * gat::kPairsWords * 8); return GAT_OK; }   // (no batch runs: the sums are empty)
+    return sample_pair_enrichment_body(ctx, P, kn, seed, sample_begin, S, annos, anno_off, n_tracks, obs_host, out_host, local, B);
   });
 }
 

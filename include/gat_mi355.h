@@ -513,6 +513,55 @@ int gat_sample_bin_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                               int64_t bin_size, const int64_t* bin_off, const int64_t* obs_host,
                               int64_t* out_host, gat_stats* stats /* nullable */);
 
+/* Which annotation tracks the segments hit TOGETHER, counted on the device by k_pairs (the reference has nothing like it: a
+ * user intersects tracks pairwise and runs one job per pair).  The groups are contigs.  A_t is track t, normalized per group
+ * (sorted by start, pairwise disjoint, every interval with end > start; adjacent intervals allowed); q = [s, e), e > s, is a
+ * segment of group g:
+ *     hit(q, t) = 1  iff  q shares a base with an interval of A_t on g
+ *               iff  j < K and A_t[j].start < e,  j = the first index with A_t[j].end > s
+ * -- bookended is no hit, one shared base is one, a segment over several intervals of one track hits once.  For a segment
+ * list L (all its groups) and tracks i <= j
+ *     c(L, i, j) = the segments q of L (e > s) with hit(q, i) and hit(q, j)
+ * The segment lists need be neither sorted nor disjoint: every segment counts on its own; segments with e <= s are skipped.
+ * For a normalized L, c(L, t, t) is CounterSegmentOverlap (intersectionWithSegments, mode "base").  The P = T (T + 1) / 2 pairs
+ * of T tracks are ordered (0,0), (0,1), .., (0,T-1), (1,1), ..:  k(i, j) = i * T - i (i - 1) / 2 + (j - i).
+ * Over a range of S samples and against an observed value obs[k] >= 0 given by the caller, every pair gets five int64 words
+ * (GAT_PAIR_WORDS) -- those of GAT_LOCAL_WORDS, in the same order and with the same meaning, of c in place of v: n_pos, sum,
+ * sumsq (unsigned where it passes 2^63), n_less, n_eq; all S samples count in n_less / n_eq, those with c == 0 too.  All
+ * arithmetic is 64-bit and exact.  Every word is additive over the samples: a partial sum has one owner on the device and is
+ * added once with a 64-bit integer add, so results do not depend on batches, workgroups, the tile, the run, or how the range is
+ * cut into calls -- the words of calls over [0, k) and [k, S) add up to those of the call over [0, S).
+ * Context options, none of which changes a result: GAT_PAIRS_LDS_PIECES -- how many interval ends of a (track, group) the
+ * kernel's search finds in LDS before it goes to global memory (clamped to what fits beside the counts; 0: none);
+ * GAT_PAIRS_SAMPLES_PER_BLOCK -- the run of lists a workgroup takes (default: by the launch).
+ *
+ * gat_list_pair_hits: the raw c of caller-provided lists (the observed values of the input segments with n_lists == 1).
+ * lists / list_off, annos / anno_off, n_tracks, n_groups: as in gat_list_distances.  out_host: [n_lists][P].  Synchronous.
+ * n_tracks == 0 or n_lists == 0 writes nothing.  GAT_ERR_ARG: a NULL ctx / list_off / anno_off / out_host (lists / annos may
+ * be NULL where they hold nothing), negative counts, n_tracks above GAT_PAIR_MAX_TRACKS (2.1 M pairs, 84 MB of words: a
+ * contract number), a decreasing offset, a track that is not normalized or holds an empty interval: gat_last_error names the
+ * track and the group.  GAT_ERR_CAPACITY: a list of more than 2^31 - 1 segments.  Never a wrong number. */
+#define GAT_PAIR_WORDS 5
+#define GAT_PAIR_MAX_TRACKS 2048
+int gat_list_pair_hits(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                       const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks, int32_t n_groups,
+                       int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop shared with gat_sample, k_pairs behind every batch that passed its checks, reading
+ * the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed and
+ * range (per-unit streams only), for every sampler, SamplerSegments without isochore keys included.  The groups are the
+ * problem's contigs in the problem's order: anno_off has n_tracks * n_contigs + 1 entries; obs_host: [P]; out_host: [P][5].
+ * Synchronous, like gat_sample.  An empty sample range writes zeros; n_tracks == 0 writes nothing.  GAT_ERR_ARG: a NULL ctx /
+ * p / anno_off, a NULL obs_host / out_host with n_tracks > 0, sample_end < sample_begin, a negative n_tracks or one above
+ * GAT_PAIR_MAX_TRACKS, a decreasing anno_off, a negative obs, n_max^2 * samples >= 2^64 with n_max the most segments one
+ * sample can hold (sumsq would not fit), a track that is not normalized (gat_last_error names the track and the contig), a
+ * call in flight on the problem.  The sampler's errors pass through (GAT_ERR_ASSERT; SamplerBruteForce's GAT_ERR_VALUE
+ * "sampling did not converge"). */
+int gat_sample_pair_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                               int64_t sample_begin, int64_t sample_end,
+                               const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks,
+                               const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
