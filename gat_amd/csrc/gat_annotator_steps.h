@@ -28,14 +28,19 @@ __host__ __device__ __forceinline__ PlaceRange place_range(uint32_t cs, uint32_t
   sampling_start = prev_end > sampling_start ? prev_end : sampling_start;
   return {sampling_start, ce - 1u - (uint32_t)sampling_start};
 }
-// ... and q = sampling_start + offset gives the segment [max(0, q), q + length) and the bases of it inside the piece
+// ... and q = sampling_start + offset gives the segment [max(0, q), q + length) and the bases of it inside the piece.
+// The domain (gat_problem_create refuses a unit outside it: unit_lmax, gat_prep_units.h): ce + length - 1 <= 2^31 - 1, so
+// q + length <= 2^31 - 1 for every q a placement can draw (q <= ce - 1), and q + length >= 1 (q >= cs - length + 1).  No
+// signed operation here can overflow inside it: the end is an unsigned sum, the overlap an unsigned difference of two
+// values below 2^31.
 struct Placed { uint32_t start, end; int32_t overlap; };
 __host__ __device__ __forceinline__ Placed place_at(uint32_t cs, uint32_t ce, int32_t q, int32_t length) {
   const uint32_t start = (uint32_t)(q > 0 ? q : 0);
-  const uint32_t end = (uint32_t)(q + length);
+  const uint32_t end = (uint32_t)q + (uint32_t)length;
   const int32_t omin = (int32_t)ce < (int32_t)end ? (int32_t)ce : (int32_t)end;
   const int32_t omax = (int32_t)cs > (int32_t)start ? (int32_t)cs : (int32_t)start;
-  return {start, end, omin - omax > 0 ? omin - omax : 0};
+  const int32_t overlap = (int32_t)((uint32_t)omin - (uint32_t)omax);
+  return {start, end, overlap > 0 ? overlap : 0};
 }
 
 // HistogramSampler.sample (gat/Engine.pyx:413-435) on the unit's compressed cdf: rank_len[r] is the bucket searchsorted(cdf, r)

@@ -476,7 +476,8 @@ __device__ __forceinline__ void place_body(const SamplerArgs& A) {
   // placed << 9 (the ring slot's byte offset is nS9 & 0x1e00: the ring is 8 KB-aligned), used_lo = 1 + the row within the
   // current trip of 32 rows at which the lane last placed or triggered (an inline constant; folded into `used` per trip).
   // overlap = min(ws.end, end) - max(ws.start, start) is at least 1 for an accepted offset (q in [ws.start + 1 - len,
-  // ws.end - 1], coordinates below 2^31: gat_problem_create), so the reference's max(0, .) (gat/Engine.pyx:340-342) is not taken.
+  // ws.end - 1], and end = q + len stays below 2^31: the placement domain, last workspace end + Lmax - 1 <= 2^31 - 1, which
+  // gat_problem_create enforces -- prepare_unit, gat_prep_units.h), so the reference's max(0, .) (gat/Engine.pyx:340-342) is not taken.
   uint64_t mL = 0, mP = 0, mO = 0;
   uint32_t nS9 = 0, used_lo = 0;
   const uint32_t lane_ring = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)&l_out[0][lane];

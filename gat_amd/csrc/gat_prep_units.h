@@ -24,6 +24,24 @@ inline bool sampler_draws_lengths(int32_t s) {
   return s == GAT_SAMPLER_ANNOTATOR || s == GAT_SAMPLER_SEGMENTS || s == GAT_SAMPLER_BRUTE_FORCE;
 }
 
+// Lmax: the largest value length_draw (gat_annotator_steps.h) can return on a unit's rank table {0, the buckets of its
+// hist_total working segments in ascending order}.  The rank drawn is 1 + [0, hist_total - 2] (the reference's
+// randint(1, total_size) excludes total_size, gat/Engine.pyx:420; rank 1 when hist_total is 1), so the largest bucket
+// that can be drawn is rank[hist_total - 1] -- the table's last entry is never drawn when it has two or more; the length
+// is that bucket times the bucket size, plus the largest draw inside the bucket: with bucket > 1 a drawn length can
+// exceed every segment of the unit.
+inline uint64_t unit_lmax(const std::vector<uint32_t>& rank, uint32_t bucket) {
+  if (rank.size() < 2) return 0;
+  const size_t top = std::max<size_t>(1, rank.size() - 2);
+  return (uint64_t)rank[top] * bucket + (bucket > 1 ? bucket - 1u : 0u);
+}
+
+// The placement domain of those samplers: a placed segment starts at ce - 1 at the latest (ce: the end of the workspace's
+// last piece) and so ends at ce + Lmax - 1 at the most; that end has to stay a coordinate (< 2^31).  Beyond it the
+// reference computes on wrapped int32 values ("The placement domain") and nothing is defined.
+constexpr uint64_t kMaxCoordinate = 0x7fffffffull;
+inline bool placement_in_domain(uint32_t last_ws_end, uint64_t lmax) { return (uint64_t)last_ws_end + lmax <= kMaxCoordinate + 1; }
+
 // everything a unit needs by itself, in a record of its own; the offsets into the shared tables are dealt out in unit
 // order behind it (gat_prep.hip: gather_unit_tables)
 struct UnitPrep {
@@ -42,6 +60,7 @@ struct UnitPrep {
   std::vector<uint4> lperm;            // GAT_SAMPLER_LOCAL_PERMUTATION: the active pieces, the sum and maximum of their n
   int64_t lperm_sum_n = 0, lperm_max_n = 0;
   int64_t nwork = 0;
+  uint64_t lmax = 0;                   // unit_lmax of the rank table (the samplers that draw lengths)
   double cv2 = 0.0;
 };
 
@@ -330,6 +349,12 @@ inline void prepare_unit(const gat_problem_desc& d, const Knobs& kn, int u, Unit
   std::sort(R.rank.begin() + 1, R.rank.end());                    // ranks (cum-count, cum] of a bucket hold it
   U.hist_total = (uint32_t)lens.size();
   U.bucket = (uint32_t)bucket;
+  R.lmax = unit_lmax(R.rank, (uint32_t)bucket);
+  if (sampler_draws_lengths(d.sampler) && !placement_in_domain(uw[nuw - 1].end, R.lmax))
+    return fail_unit(R, GAT_ERR_ARG, "unit %d: workspace end %u + longest drawn length %llu - 1 > 2^31 - 1: a placed segment could end at "
+                     "or beyond 2^31, where nothing is defined (limit: workspace end + Lmax - 1 <= 2147483647; Lmax = largest "
+                     "bucket the histogram can draw x bucket_size %lld, + bucket_size - 1 when it is > 1)", u, uw[nuw - 1].end, (unsigned long long)R.lmax,
+                     (long long)bucket);
   R.cv2 = length_cv2(lens);
   // SegmentListSampler(workspace) (gat/Engine.pyx:261-277)
   U.n_ws = (int32_t)nuw;

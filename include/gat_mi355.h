@@ -78,6 +78,12 @@ typedef struct gat_annotations gat_annotations;
  * only read during gat_problem_create.  Every list must be normalized (sorted, disjoint,
  * non-empty segments: gat/SegmentList.pyx:697) and all coordinates must be < 2^31 (the
  * reference's int32 lmin/lmax, gat/SegmentList.pyx:68-77, are order-preserving only there).
+ * The samplers that draw lengths (GAT_SAMPLER_ANNOTATOR, _SEGMENTS, _BRUTE_FORCE) also need the END of every segment they
+ * can place to be a coordinate: for every active unit, last workspace end + Lmax - 1 <= 2^31 - 1, Lmax = the longest
+ * length the unit's histogram can return (the largest bucket it can draw x bucket size, + bucket size - 1 when the
+ * bucket size is > 1: with buckets a drawn length can exceed every segment of the unit; of two or more working segments
+ * the last rank is never drawn, gat/Engine.pyx:420, so that bucket is the second longest segment's).  gat_problem_create refuses a unit outside this
+ * domain with GAT_ERR_ARG; past it the reference itself computes on wrapped int32 values.
  */
 typedef struct {
   int32_t n_units;              /* isochore keys, reference order                               */
@@ -273,7 +279,10 @@ int gat_memcpy_h2d(gat_ctx* ctx, void* dst_dev, const void* src_host, size_t byt
  * Returns GAT_ERR_VALUE where the reference's first sample() would raise ValueError.
  * Limits (GAT_ERR_CAPACITY beyond them): 2^24 workspace segments per unit, 2^31 segments per sample; no limit on
  * the number of units or contigs.  There is no limit on the segments of a unit: lists that do not fit
- * on-chip memory are worked on in device memory. */
+ * on-chip memory are worked on in device memory.  GAT_ERR_ARG: a coordinate >= 2^31, or -- SamplerAnnotator,
+ * SamplerSegments, SamplerBruteForce; the per-unit and the serial stream alike -- an active unit whose last workspace
+ * end + Lmax - 1 exceeds 2^31 - 1 (see gat_problem_desc; gat_last_error names the unit, the workspace end and Lmax).
+ * Units without a working segment or a workspace are not looked at. */
 int gat_problem_create(gat_ctx* ctx, const gat_problem_desc* desc, gat_problem** out);
 void gat_problem_destroy(gat_problem* p);
 

@@ -9,6 +9,11 @@
  * cites it as file:line into /root/reference.  Parity of this restatement is PINNED:
  * tests/golden/ holds vectors produced by the reference itself (scratch build, see
  * tests/golden/make_goldens.py) and tests/test_oracle_*.py check this file against them.
+ *
+ * DOMAIN of the samplers: last workspace end + Lmax - 1 <= 2^31 - 1 per unit (Lmax: the longest
+ * length the unit's histogram can return).  Outside it this file is NOT the
+ * reference: that computes on wrapped int32 values there and asserts at gat/Engine.pyx:596 on some
+ * streams, which nothing here restates (tests/golden/coordinate_range.json records such streams).
  */
 #ifndef GAT_ORACLE_H
 #define GAT_ORACLE_H

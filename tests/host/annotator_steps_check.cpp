@@ -68,7 +68,15 @@ static void check_place(int64_t cs, int64_t ce, bool has_prev, int64_t prev_end,
         "piece [%lld, %lld) prev %d %lld length %lld: start %d range %u, want %lld %lld", (long long)cs, (long long)ce, (int)has_prev,
         (long long)prev_end, (long long)length, pr.sampling_start, pr.range, (long long)ss, (long long)range);
   std::vector<int64_t> offsets;
-  if (all_offsets) for (int64_t o = 0; o <= range; ++o) offsets.push_back(o);
+  constexpr int64_t kEdge = 4096;
+  if (all_offsets && range <= 4 * kEdge) for (int64_t o = 0; o <= range; ++o) offsets.push_back(o);
+  else if (all_offsets) {
+    // a range of up to 2^31 offsets: the first and the last 4 096, the 4 096 around q == 0 (where the start clamps) and
+    // 4 096 spread evenly -- the placement is piecewise linear in the offset with its kinks at those three places
+    for (int64_t o = 0; o < kEdge; ++o) { offsets.push_back(o); offsets.push_back(range - o); }
+    for (int64_t o = std::max<int64_t>(0, -ss - kEdge / 2); o <= std::min(range, -ss + kEdge / 2); ++o) offsets.push_back(o);
+    for (int64_t i = 1; i < kEdge; ++i) offsets.push_back((int64_t)((unsigned __int128)range * (unsigned)i / kEdge));
+  }
   else offsets = {0, range / 3, range / 2, range > 0 ? range - 1 : 0, range};
   for (int64_t o : offsets) {
     const int64_t q = ss + o;
@@ -106,6 +114,30 @@ static void check_placements() {
   check_place(top - 1000, top - 1, true, top - 5000, 2, false);
   check_place(0, top - 1, false, 0, 2, false);
   check_place(5, top - 10, true, 3, 11, false);
+  // the exact border of the placement domain: ce + length - 1 == 2^31 - 1, so the last offset's segment ends AT 2^31 - 1
+  // (gat_problem_create refuses a unit one base further up).  Every offset (for a range beyond 16 384: both ends, the
+  // clamp at q == 0 and a spread); the piece first in its workspace, and behind a piece that ends at its start, one base
+  // before, exactly at cs - length + 1, and further down than the segment reaches
+  for (int64_t length : {(int64_t)1, (int64_t)2, (int64_t)64, (int64_t)1 << 30}) {
+    const int64_t ce = top - length + 1;
+    for (int64_t width : {(int64_t)1, (int64_t)2, (int64_t)63, (int64_t)64, (int64_t)1000}) {
+      const int64_t cs = ce - width;
+      check_place(cs, ce, false, 0, length, true);
+      for (int64_t pe : {cs, cs - 1, cs - length + 1, cs - length, cs - length - 7, (int64_t)0, (int64_t)1})
+        if (pe >= 0 && pe <= cs) check_place(cs, ce, true, pe, length, true);
+    }
+    // ... and the piece from near 0 up to the border: q < 0 at the low offsets, the end at 2^31 - 1 at the last
+    check_place(0, ce, false, 0, length, true);
+    check_place(5, ce, false, 0, length, true);
+    check_place(5, ce, true, 3, length, true);
+  }
+  // q < 0 on a piece near 0 under a length near 2^30 (the start clamps to 0, the end does not)
+  for (int64_t length : {((int64_t)1 << 30) - 1, (int64_t)1 << 30, ((int64_t)1 << 30) + 1}) {
+    check_place(0, 1, false, 0, length, true);
+    check_place(3, 20, false, 0, length, true);
+    check_place(3, 20, true, 2, length, true);
+    check_place(7, top - length + 1, false, 0, length, true);
+  }
   std::mt19937_64 g(2);
   for (int t = 0; t < 200000; ++t) {
     const int64_t length = 1 + (int64_t)(g() % (t % 2 ? 100000 : 60));

@@ -2,6 +2,7 @@
 // plain loops.  Host only: tests/test_prep_units_host.py compiles it with the address and undefined-behaviour sanitizers
 // and runs it; exit status 0 = every check held, else the failed checks are on stderr.
 #include "gat_prep_units.h"
+#include "gat_annotator_steps.h"
 
 #include <random>
 
@@ -229,7 +230,135 @@ static void check_prepare_unit(const std::vector<gat_segment>& w, int merge_cont
   if (want_cgrid) CHECK(R.cgrid == build_cdf_grid(cdf, nuw, cdf.back() + 1u, 2), "cgrid is not build_cdf_grid's at two segments per cell");
 }
 
+// one unit (segments, workspace) through prepare_unit under a sampler kind and a bucket size
+static void prepare_one(const std::vector<gat_segment>& segs, const std::vector<gat_segment>& w, int32_t sampler, uint32_t bucket_size,
+                        UnitDev& U, UnitPrep& R) {
+  const int64_t seg_off[2] = {0, (int64_t)segs.size()}, ws_off[2] = {0, (int64_t)w.size()};
+  const int32_t unit_contig[1] = {0};
+  gat_problem_desc d = {};
+  d.n_units = 1; d.segs = segs.data(); d.seg_off = seg_off; d.ws = w.data(); d.ws_off = ws_off;
+  d.unit_contig = unit_contig; d.n_contigs = 1; d.nbuckets = 100000; d.bucket_size = bucket_size; d.sampler = sampler;
+  d.shift_radius = 2.0;
+  const Knobs kn;
+  prepare_unit(d, kn, 0, U, R);
+}
+
+// Lmax against the definition: the largest value length_draw returns over every rank and every draw inside the bucket
+static void check_lmax() {
+  const std::vector<std::vector<uint32_t>> length_sets = {
+      {1u}, {4u, 4u, 4u, 4u}, {1u, 2u, 3u, 64u, 65u}, {7u, 130u, 129u, 128u}, {90u}, {40u, 48u, 41u}, {250001u, 3u}, {6350000u, 1u, 63u}};
+  for (const std::vector<uint32_t>& lens : length_sets)
+    for (uint32_t bucket_size : {0u, 1u, 3u, 64u}) {
+      char name[96];
+      snprintf(name, sizeof(name), "lmax: %zu lengths from %u, bucket_size %u", lens.size(), lens[0], bucket_size);
+      g_case = name;
+      std::vector<gat_segment> segs;
+      uint32_t x = 10u, longest = 0u;
+      for (uint32_t l : lens) { segs.push_back(gat_segment{x, x + l}); x += l + 5u; longest = std::max(longest, l); }
+      const std::vector<gat_segment> w{{0u, x + 100u}};
+      UnitDev U = {};
+      UnitPrep R;
+      prepare_one(segs, w, GAT_SAMPLER_ANNOTATOR, bucket_size, U, R);
+      if (bucket_size && (longest + bucket_size - 1u) / bucket_size >= 100000u) {        // (beyond nbuckets: the reference's ValueError)
+        CHECK(R.rc == GAT_ERR_VALUE, "a length beyond the buckets: rc %d", R.rc);
+        continue;
+      }
+      CHECK(R.rc == 0 && R.active, "rc %d (%s)", R.rc, R.err.c_str());
+      if (R.rc || !R.active) continue;
+      const uint32_t want_bucket = bucket_size ? bucket_size : (uint32_t)std::ceil((double)longest / 100000.0);
+      CHECK(U.bucket == want_bucket, "bucket %u, want %u", U.bucket, want_bucket);
+      // every rank the first draw can name (1 + [0, hist_total - 2]; rank 1 alone for one segment), every second draw
+      uint64_t brute = 0;
+      const uint32_t last_d0 = U.hist_total > 1 ? U.hist_total - 2u : 0u;
+      for (uint32_t d0 = 0; d0 <= last_d0; ++d0)
+        for (uint32_t d1 = 0; d1 < std::max(U.bucket, 1u); ++d1) {
+          int call = 0;
+          const uint32_t got = gat::length_draw(U.hist_total, R.rank.data(), U.bucket, [&](uint32_t range) -> uint32_t {
+            const bool first = call++ == 0 && U.hist_total > 1;
+            CHECK((first ? d0 : d1) <= range, "draw beyond its range %u", range);
+            return first ? d0 : d1;
+          });
+          brute = std::max<uint64_t>(brute, got);
+        }
+      CHECK(R.lmax == brute && unit_lmax(R.rank, U.bucket) == brute, "Lmax %llu, the largest length_draw %llu", (unsigned long long)R.lmax,
+            (unsigned long long)brute);
+      // ... which is the unit's second longest segment (its only one) rounded up to its bucket, plus the bucket's last base: the
+      // reference's randint(1, total_size) never reaches the last rank
+      std::vector<uint32_t> sorted = lens;
+      std::sort(sorted.begin(), sorted.end());
+      const uint64_t top = sorted.size() > 1 ? sorted[sorted.size() - 2] : sorted[0];
+      const uint64_t want = (top + U.bucket - 1) / U.bucket * U.bucket + (U.bucket > 1 ? U.bucket - 1u : 0u);
+      CHECK(brute == want, "largest draw %llu, want %llu", (unsigned long long)brute, (unsigned long long)want);
+    }
+}
+
+// accept at the border (last workspace end + Lmax - 1 == 2^31 - 1), refuse one base further up: per sampler kind
+static void check_domain() {
+  const uint32_t T = 0x7fffffffu;
+  const int32_t drawing[] = {GAT_SAMPLER_ANNOTATOR, GAT_SAMPLER_SEGMENTS, GAT_SAMPLER_BRUTE_FORCE};
+  const int32_t others[] = {GAT_SAMPLER_SHIFT, GAT_SAMPLER_GLOBAL_PERMUTATION, GAT_SAMPLER_LOCAL_PERMUTATION};
+  for (uint32_t bucket_size : {1u, 3u, 0u}) {
+    // four segments of 4 bases (bucket 3: Lmax = 2 * 3 + 2 = 8; bucket 0 -> 1: Lmax 4), or one of 250 001 (bucket 0 -> 3)
+    for (uint32_t seg_len : {4u, 250001u}) {
+      if (bucket_size == 1u && seg_len > 99999u) continue;                                // (beyond nbuckets: another error)
+      UnitDev U0 = {};
+      UnitPrep R0;
+      const uint32_t base = T - 2000000u;
+      std::vector<gat_segment> segs;
+      for (uint32_t i = 0; i < (seg_len == 4u ? 4u : 1u); ++i) segs.push_back(gat_segment{base + 10u * i, base + 10u * i + seg_len});
+      prepare_one(segs, {{base, base + 300000u}}, GAT_SAMPLER_ANNOTATOR, bucket_size, U0, R0);
+      const uint64_t lmax = R0.lmax;
+      CHECK(R0.rc == 0 && lmax >= seg_len, "probe: rc %d Lmax %llu", R0.rc, (unsigned long long)lmax);
+      const uint32_t ce_border = (uint32_t)((uint64_t)T - lmax + 1);                       // ce + Lmax - 1 == T
+      for (uint32_t up : {0u, 1u}) {
+        const uint32_t ce = ce_border + up;
+        if (ce > T) continue;
+        const std::vector<gat_segment> w{{base, base + 300000u}, {ce - 1u, ce}};
+        char name[96];
+        snprintf(name, sizeof(name), "domain: bucket_size %u segments of %u, last end border + %u", bucket_size, seg_len, up);
+        g_case = name;
+        for (int32_t s : drawing) {
+          UnitDev U = {};
+          UnitPrep R;
+          prepare_one(segs, w, s, bucket_size, U, R);
+          if (up == 0) CHECK(R.rc == 0 && R.active && R.lmax == lmax, "sampler %d at the border: rc %d (%s)", s, R.rc, R.err.c_str());
+          else {
+            char want_unit[32], want_end[32], want_lmax[32];
+            snprintf(want_unit, sizeof(want_unit), "unit 0"); snprintf(want_end, sizeof(want_end), "%u", ce);
+            snprintf(want_lmax, sizeof(want_lmax), "%llu", (unsigned long long)lmax);
+            CHECK(R.rc == GAT_ERR_ARG && !R.active, "sampler %d one base past the border: rc %d active %d", s, R.rc, (int)R.active);
+            CHECK(R.err.find(want_unit) != std::string::npos && R.err.find(want_end) != std::string::npos &&
+                  R.err.find(want_lmax) != std::string::npos && R.err.find("2^31 - 1") != std::string::npos, "message: %s", R.err.c_str());
+          }
+        }
+        for (int32_t s : others) {                             // their own rules: this one is not theirs
+          UnitDev U = {};
+          UnitPrep R;
+          prepare_one(segs, w, s, bucket_size, U, R);
+          CHECK(R.rc != GAT_ERR_ARG, "sampler %d: rc %d (%s)", s, R.rc, R.err.c_str());
+        }
+        // a unit without a working segment, or without a workspace, is not looked at
+        UnitDev U = {};
+        UnitPrep R;
+        prepare_one({{5u, 9u}}, w, GAT_SAMPLER_ANNOTATOR, bucket_size, U, R);
+        CHECK(R.rc == 0 && !R.active, "no working segment: rc %d active %d", R.rc, (int)R.active);
+        UnitPrep R2;
+        prepare_one(segs, {}, GAT_SAMPLER_ANNOTATOR, bucket_size, U, R2);
+        CHECK(R2.rc == 0 && !R2.active, "no workspace: rc %d active %d", R2.rc, (int)R2.active);
+      }
+    }
+  }
+  // the helpers by themselves
+  g_case = "domain helpers";
+  CHECK(placement_in_domain(T, 1) && !placement_in_domain(T, 2) && placement_in_domain(T - 3u, 4) && !placement_in_domain(T - 3u, 5) &&
+        placement_in_domain(1u, (uint64_t)T) && !placement_in_domain(2u, (uint64_t)T) && !placement_in_domain(T, 0xffffffffull * 3), "placement_in_domain");
+  CHECK(unit_lmax({0u}, 5u) == 0 && unit_lmax({0u, 2u, 9u}, 1u) == 2 && unit_lmax({0u, 2u, 9u}, 4u) == 11 && unit_lmax({0u, 2u, 5u, 9u}, 4u) == 23 &&
+        unit_lmax({0u, 9u}, 1u) == 9 && unit_lmax({0u, 0x7fffffffu}, 3u) == 3ull * 0x7fffffffull + 2, "unit_lmax");
+}
+
 int main() {
+  check_lmax();
+  check_domain();
   std::mt19937 rng(20240607u);
   int most_steps = 0;
   for (int n : kSizes)
