@@ -36,7 +36,7 @@ SYMBOLS = [
     "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics", "gat_list_distances",
     "gat_sample_distances", "gat_minp_counts", "gat_minp_times", "gat_efdr_counts", "gat_efdr_times",
     "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch",
-    "gat_list_pair_hits", "gat_sample_pair_enrichment",
+    "gat_list_pair_hits", "gat_sample_pair_enrichment", "gat_list_geneset_hits", "gat_sample_geneset_enrichment",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -244,6 +244,10 @@ def lib():
     L.gat_list_pair_hits.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, vp]
     L.gat_sample_pair_enrichment.restype = C.c_int
     L.gat_sample_pair_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, vp, vp, C.POINTER(Stats)]
+    L.gat_list_geneset_hits.restype = C.c_int
+    L.gat_list_geneset_hits.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp]
+    L.gat_sample_geneset_enrichment.restype = C.c_int
+    L.gat_sample_geneset_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -544,14 +548,43 @@ class Context(object):
                                         _p(out)), self._h)
         return out
 
+    def list_geneset_hits(self, lists, list_off, n_lists, pieces, piece_off, member_off, members, n_genes, term_off, term_genes,
+                          n_terms, n_groups):
+        """c(L, t) = the genes of term t hit by any segment of list L, for every one of n_lists caller-provided lists -- list l
+        of group g is lists[list_off[l * n_groups + g]:list_off[l * n_groups + g + 1]], in any order -- and n_terms terms
+        (gat_list_geneset_hits): pieces / piece_off the genes' pieces per group, member_off / members the genes that cover
+        every piece, term_off / term_genes the genes of every term.  Returns int64 [n_lists, n_terms]."""
+        lists = np.ascontiguousarray(lists, dtype=SEG)
+        list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+        n_lists, n_genes, n_terms, n_groups = int(n_lists), int(n_genes), int(n_terms), int(n_groups)
+        assert len(list_off) == n_lists * n_groups + 1
+        g = _geneset_arrays(pieces, piece_off, member_off, members, term_off, term_genes, n_terms, n_groups)
+        out = np.zeros((n_lists, max(0, n_terms)), dtype=np.int64)
+        _check(lib().gat_list_geneset_hits(self._h, _p(lists), _p(list_off), n_lists, _p(g[0]), _p(g[1]), _p(g[2]), _p(g[3]), n_genes,
+                                           _p(g[4]), _p(g[5]), n_terms, n_groups, _p(out)), self._h)
+        return out
 
-PAIR_WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")
+
+PAIR_WORDS =("n_pos", "sum", "sumsq", "n_less", "n_eq")
 PAIR_MAX_TRACKS = 2048        # GAT_PAIR_MAX_TRACKS
 
 
 def pair_count(n_tracks):
     """the pairs (i, j), i <= j, of n_tracks tracks (0 where n_tracks is out of range: the library refuses the call)"""
     return n_tracks * (n_tracks + 1) // 2 if 0 <= n_tracks <= PAIR_MAX_TRACKS else 0
+
+
+GENESET_WORDS = PAIR_WORDS    # GAT_GENESET_WORDS
+
+
+def _geneset_arrays(pieces, piece_off, member_off, members, term_off, term_genes, n_terms, n_groups):
+    """the gene and term arguments of the two geneset calls as the library takes them"""
+    pieces = np.ascontiguousarray(pieces, dtype=SEG)
+    piece_off, member_off, term_off = (np.ascontiguousarray(x, dtype=np.int64) for x in (piece_off, member_off, term_off))
+    members, term_genes = (np.ascontiguousarray(x, dtype=np.int32) for x in (members, term_genes))
+    assert len(piece_off) == max(0, n_groups) + 1 and len(term_off) == max(0, n_terms) + 1
+    assert len(member_off) == max(0, int(piece_off[-1] - piece_off[0])) + 1
+    return pieces, piece_off, member_off, members, term_off, term_genes
 
 
 def _bin_offsets(n_bins, n_groups):
@@ -990,6 +1023,25 @@ class Problem(object):
         st = Stats()
         rc = lib().gat_sample_pair_enrichment(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
                                               _p(annos), _p(anno_off), n_tracks, _p(obs), _p(out), C.byref(st))
+        self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
+        return out
+
+    def sample_geneset_enrichment(self, seed, sample_begin, sample_end, pieces, piece_off, member_off, members, n_genes, term_off,
+                                  term_genes, n_terms, obs):
+        """per term the five sums (GENESET_WORDS; gat_sample_geneset_enrichment) over the sampled contig-level lists of
+        [sample_begin, sample_end) of c = the genes of the term hit by any segment of a list, against obs[term] -- the genes'
+        pieces of contig c are pieces[piece_off[c]:piece_off[c + 1]], contigs in the problem's order; the other arguments as
+        in Context.list_geneset_hits.  Returns int64 [n_terms, 5]."""
+        n_genes, n_terms = int(n_genes), int(n_terms)
+        g = _geneset_arrays(pieces, piece_off, member_off, members, term_off, term_genes, n_terms, self.n_contigs)
+        obs = np.ascontiguousarray(obs, dtype=np.int64)
+        assert obs.shape == (max(0, n_terms),)
+        out = np.zeros((max(0, n_terms), len(GENESET_WORDS)), dtype=np.int64)
+        st = Stats()
+        rc = lib().gat_sample_geneset_enrichment(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
+                                                 _p(g[0]), _p(g[1]), _p(g[2]), _p(g[3]), n_genes, _p(g[4]), _p(g[5]), n_terms,
+                                                 _p(obs), _p(out), C.byref(st))
         self.last_stats = st.asdict()
         _check(rc, self.ctx._h)
         return out

@@ -89,7 +89,10 @@ struct gat_ctx;
   INT(local_samples_per_block, "GAT_LOCAL_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */            \
   INT(local_lds_pieces, "GAT_LOCAL_LDS_PIECES", 256) /* ... annotation intervals of a window its search finds in LDS */       \
   INT(pairs_lds_pieces, "GAT_PAIRS_LDS_PIECES", 32) /* gat_*_pair_*: intervals of a (track, group) k_pairs' search finds in LDS; 0: none */ \
-  INT(pairs_samples_per_block, "GAT_PAIRS_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */
+  INT(pairs_samples_per_block, "GAT_PAIRS_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */            \
+  INT(geneset_lds_pieces, "GAT_GENESET_LDS_PIECES", 1024) /* gat_*_geneset_*: piece ends of a group k_geneset_hits' searches find in LDS; 0: none */ \
+  INT(geneset_samples_per_block, "GAT_GENESET_SAMPLES_PER_BLOCK", 0) /* ... the run of lists of both kernels; default: by the launch */ \
+  INT(geneset_term_tile, "GAT_GENESET_TERM_TILE", 256) /* ... terms a workgroup of k_geneset_terms owns, 1 .. 256 */
 
 struct Knobs {
 #define GAT_KNOB_FLAG(field, name) bool field = false;

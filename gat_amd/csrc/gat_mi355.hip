@@ -41,6 +41,7 @@
 #include "gat_distance.h"
 #include "gat_local.h"
 #include "gat_pairs.h"
+#include "gat_geneset.h"
 
 
 #include "gat_host.h"
@@ -1639,8 +1640,9 @@ extern "C" void gat_mt19937_seed(uint32_t seed, uint32_t* mt_state) {
 }
 
 // ---- the entry points that read the sampled lists where they are: gat_sample / gat_sample_units copy them out, and
-// gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_bin_enrichment and gat_sample_pair_enrichment put a
-// kernel (gat_coverage.h, gat_metrics.h, gat_distance.h, gat_local.h, gat_pairs.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
+// gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_bin_enrichment, gat_sample_pair_enrichment and
+// gat_sample_geneset_enrichment put a kernel (gat_coverage.h, gat_metrics.h, gat_distance.h, gat_local.h, gat_pairs.h,
+// gat_geneset.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
 
 // A synchronous call's frame: refused while a call is in flight on the problem (P == nullptr: a call over the caller's own
 // lists); the knobs are read once; body(kn, local) does the work.  Whatever the body returns, the stream is drained behind it:
@@ -2397,6 +2399,207 @@ extern "C" int gat_sample_pair_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t
     if (pairs == 0) return GAT_OK;
     if (S == 0) { memset(out_host, 0, (size_t)pairs * gat::kPairsWords * 8); return GAT_OK; }   // (no batch runs: the sums are empty)
     return sample_pair_enrichment_body(ctx, P, kn, seed, sample_begin, S, annos, anno_off, n_tracks, obs_host, out_host, local, B);
+  });
+}
+
+// gat_list_geneset_hits / gat_sample_geneset_enrichment: k_geneset_hits and k_geneset_terms (gat_geneset.h) over caller-provided
+// lists, or behind every batch.  The pieces, their members and the terms go up once per call; the device buffers live for the call.
+struct GenesetBufs {
+  DevBuf<uint2> d_piece, d_seg;
+  DevBuf<int64_t> d_piece_csr, d_csr, d_member_off, d_term_off;
+  DevBuf<int32_t> d_members, d_term_genes;
+  DevBuf<long long> d_obs;
+  DevBuf<uint32_t> d_bitmaps;
+  DevBuf<unsigned long long> d_out;
+  int64_t chunk = 0;          // lists whose bitmaps d_bitmaps holds
+};
+struct GenesetIn {
+  const gat_segment* pieces; const int64_t* piece_off; const int64_t* member_off; const int32_t* members; int32_t n_genes;
+  const int64_t* term_off; const int32_t* term_genes; int32_t n_terms;
+};
+static const char* const kGenesetWhy = "the pieces a segment reaches are searched for in it";
+// ids[b .. e) within [0, n_genes) and strictly ascending
+static bool geneset_ids_ok(const int32_t* ids, int64_t b, int64_t e, int32_t n_genes) {
+  for (int64_t m = b; m < e; ++m)
+    if (ids[m] < 0 || ids[m] >= n_genes || (m > b && ids[m] <= ids[m - 1])) return false;
+  return true;
+}
+// what both entry points ask of the genes and the terms
+static int geneset_check_common(gat_ctx* ctx, const char* who, const GenesetIn& in, int64_t n_groups) {
+  if (in.n_genes < 0 || in.n_genes > gat::kGenesetMaxGenes)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_genes %d outside [0, %d]", who, in.n_genes, gat::kGenesetMaxGenes);
+  if (in.n_terms < 0) return set_err(ctx, GAT_ERR_ARG, "%s: n_terms %d is negative", who, in.n_terms);
+  int rc;
+  if ((rc = check_list_offsets(ctx, who, "piece_off", "pieces", in.piece_off, n_groups))) return rc;
+  const int64_t n_pieces = in.piece_off[n_groups] - in.piece_off[0];
+  if (n_pieces > 0 && !in.pieces) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = distance_check_normalized(ctx, who, "gene pieces", in.pieces, in.piece_off, 1, (int32_t)n_groups, kGenesetWhy))) return rc;
+  if (in.member_off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: member_off[0] < 0", who);
+  for (int64_t j = 0; j < n_pieces; ++j) {
+    if (in.member_off[j + 1] < in.member_off[j]) return set_err(ctx, GAT_ERR_ARG, "%s: member_off decreases at piece %lld", who, (long long)j);
+    if (in.member_off[j + 1] == in.member_off[j]) return set_err(ctx, GAT_ERR_ARG, "%s: piece %lld has no member", who, (long long)j);
+  }
+  if (in.member_off[n_pieces] > in.member_off[0] && !in.members) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  for (int64_t j = 0; j < n_pieces; ++j)
+    if (!geneset_ids_ok(in.members, in.member_off[j], in.member_off[j + 1], in.n_genes))
+      return set_err(ctx, GAT_ERR_ARG, "%s: the members of piece %lld are not strictly ascending gene ids in [0, %d)", who, (long long)j, in.n_genes);
+  if (in.term_off[0] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: term_off[0] < 0", who);
+  for (int64_t t = 0; t < in.n_terms; ++t)
+    if (in.term_off[t + 1] < in.term_off[t]) return set_err(ctx, GAT_ERR_ARG, "%s: term_off decreases at term %lld", who, (long long)t);
+  if (in.term_off[in.n_terms] > in.term_off[0] && !in.term_genes) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  for (int64_t t = 0; t < in.n_terms; ++t)
+    if (!geneset_ids_ok(in.term_genes, in.term_off[t], in.term_off[t + 1], in.n_genes))
+      return set_err(ctx, GAT_ERR_ARG, "%s: the genes of term %lld are not strictly ascending gene ids in [0, %d)", who, (long long)t, in.n_genes);
+  return GAT_OK;
+}
+// n + 1 offsets from 0, and the ids they index
+static int geneset_upload_csr(gat_ctx* ctx, const int64_t* off, int64_t n, const int32_t* ids, DevBuf<int64_t>& d_off, DevBuf<int32_t>& d_ids) {
+  const int64_t base = off[0], total = off[n] - base;
+  HIPCHK(ctx, d_off.upload_built((size_t)n + 1, ctx, [&](int64_t* h) { for (int64_t k = 0; k <= n; ++k) h[k] = off[k] - base; }));
+  HIPCHK(ctx, d_ids.upload_built((size_t)total, ctx, [&](int32_t* h) { memcpy(h, ids + base, (size_t)total * 4); }));
+  return GAT_OK;
+}
+// the genes and the terms on the device, and the bitmaps of as many lists as a quarter of GAT_SLAB_BYTES holds -- at most
+// 256 MB, at least one list's, no more than the call's n_lists
+static int geneset_upload(gat_ctx* ctx, const Knobs& kn, const GenesetIn& in, int64_t n_groups, int64_t n_lists, GenesetBufs& B) {
+  int rc;
+  if ((rc = upload_csr_lists(ctx, in.pieces, in.piece_off, n_groups, B.d_piece, B.d_piece_csr))) return rc;
+  const int64_t n_pieces = in.piece_off[n_groups] - in.piece_off[0];
+  if ((rc = geneset_upload_csr(ctx, in.member_off, n_pieces, in.members, B.d_member_off, B.d_members))) return rc;
+  if ((rc = geneset_upload_csr(ctx, in.term_off, in.n_terms, in.term_genes, B.d_term_off, B.d_term_genes))) return rc;
+  const int64_t row = gat::geneset_bitmap_words(in.n_genes) * 4;
+  const double budget = std::min(kn.slab_bytes / 4.0, 256.0 * 1024 * 1024);
+  B.chunk = std::max<int64_t>(1, std::min<int64_t>(n_lists, (int64_t)(budget / (double)row)));
+  HIPCHK(ctx, B.d_bitmaps.alloc((size_t)(B.chunk * row / 4)));
+  return GAT_OK;
+}
+// n_lists lists in chunks of B.chunk: k_geneset_hits writes a chunk's bitmaps, k_geneset_terms reads them.  store: the raw counts
+// per list (row `first + i` of B.d_out), else the fold into B.d_out's five words.  The runs: the knob's where it is set, else
+// as long as leaves 2 048 workgroups (eight for each of 256 compute units) but at least 16 lists
+static int launch_geneset(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists, int64_t n_lists, const GenesetIn& in, int32_t n_groups,
+                          bool store, const GenesetBufs& B) {
+  if (n_lists == 0 || in.n_terms == 0) return GAT_OK;
+  const int64_t W = gat::geneset_bitmap_words(in.n_genes);
+  const int64_t L = gat::geneset_lds_pieces(kn.geneset_lds_pieces, n_groups);
+  const int64_t tile = std::min<int64_t>(gat::kGenesetMaxTermTile, std::max<int64_t>(1, kn.geneset_term_tile));
+  const int64_t n_tiles = (in.n_terms + tile - 1) / tile;
+  const int64_t knob_run = kn.geneset_samples_per_block;
+  for (int64_t first = 0; first < n_lists; first += B.chunk) {
+    const int64_t n = std::min(B.chunk, n_lists - first);
+    gat::GenesetHitsArgs H;
+    memset(&H, 0, sizeof(H));
+    H.lists = lists;
+    H.list_begin = (int32_t)first;
+    H.n_lists = (int32_t)n;
+    H.n_groups = n_groups;
+    H.lds_pieces = (int32_t)L;
+    H.bm_words = (int32_t)W;
+    H.pieces = B.d_piece.p;
+    H.piece_csr = B.d_piece_csr.p;
+    H.member_off = B.d_member_off.p;
+    H.members = B.d_members.p;
+    H.bitmaps = B.d_bitmaps.p;
+    const int64_t run_h = knob_run > 0 ? gat::run_per_block(n, 1, 0, knob_run) : gat::run_per_block(n, 1, 2048, gat::kNoRunCap);
+    H.lists_per_block = (int32_t)run_h;
+    const size_t lds_h = (size_t)(W + (int64_t)n_groups * L) * 4;
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_geneset_hits, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
+    hipLaunchKernelGGL(gat::k_geneset_hits, dim3((unsigned)((n + run_h - 1) / run_h)), dim3(gat::kGenesetThreads), lds_h, ctx->stream, H);
+    HIPCHK(ctx, hipGetLastError());
+
+    gat::GenesetTermsArgs T;
+    memset(&T, 0, sizeof(T));
+    T.bitmaps = B.d_bitmaps.p;
+    T.list_begin = (int32_t)first;
+    T.n_lists = (int32_t)n;
+    T.bm_words = (int32_t)W;
+    T.term_tile = (int32_t)tile;
+    T.n_terms = in.n_terms;
+    T.term_off = B.d_term_off.p;
+    T.term_genes = B.d_term_genes.p;
+    T.obs = B.d_obs.p;
+    T.out = B.d_out.p;
+    const int64_t run_t = knob_run > 0 ? gat::run_per_block(n, n_tiles, 0, knob_run) : gat::run_per_block(n, n_tiles, 2048, gat::kNoRunCap);
+    T.lists_per_block = (int32_t)run_t;
+    const dim3 grid((unsigned)n_tiles, (unsigned)((n + run_t - 1) / run_t));
+    if (store) hipLaunchKernelGGL(gat::k_geneset_terms<true>, grid, dim3(gat::kGenesetThreads), (size_t)W * 4, ctx->stream, T);
+    else hipLaunchKernelGGL(gat::k_geneset_terms<false>, grid, dim3(gat::kGenesetThreads), (size_t)W * 4, ctx->stream, T);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  return GAT_OK;
+}
+
+extern "C" int gat_list_geneset_hits(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                                     const gat_segment* pieces, const int64_t* piece_off, const int64_t* member_off, const int32_t* members,
+                                     int32_t n_genes, const int64_t* term_off, const int32_t* term_genes, int32_t n_terms,
+                                     int32_t n_groups, int64_t* out_host) {
+  const char* who = "gat_list_geneset_hits";
+  if (!ctx || !list_off || !piece_off || !member_off || !term_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
+  const GenesetIn in = {pieces, piece_off, member_off, members, n_genes, term_off, term_genes, n_terms};
+  int rc;
+  if ((rc = geneset_check_common(ctx, who, in, n_groups))) return rc;
+  const int64_t n = n_lists * n_groups;
+  if ((rc = check_list_offsets(ctx, who, "list_off", "segments", list_off, n))) return rc;
+  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  const size_t words = (size_t)(n_lists * (int64_t)n_terms);
+  if (words == 0) return GAT_OK;
+  GenesetBufs B;
+  return call_frame(ctx, nullptr, nullptr, [&](const Knobs& kn, gat_stats&) {
+    int brc;
+    if ((brc = geneset_upload(ctx, kn, in, n_groups, n_lists, B))) return brc;
+    if ((brc = upload_csr_lists(ctx, lists, list_off, n, B.d_seg, B.d_csr))) return brc;
+    HIPCHK(ctx, B.d_out.alloc(words));
+    HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, words * 8, ctx->stream));
+    if ((brc = launch_geneset(ctx, kn, csr_lists(B.d_seg, B.d_csr), n_lists, in, n_groups, true, B))) return brc;
+    HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, words * 8));
+    return GAT_OK;
+  });
+}
+
+static int sample_geneset_enrichment_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                                          const GenesetIn& in, const int64_t* obs_host, int64_t* out_host, gat_stats& local, GenesetBufs& B) {
+  const int64_t T = in.n_terms;
+  int rc;
+  if ((rc = geneset_upload(ctx, kn, in, P->n_contigs, S, B))) return rc;
+  HIPCHK(ctx, B.d_obs.alloc((size_t)T));
+  HIPCHK(ctx, staged_h2d(ctx, B.d_obs.p, obs_host, (size_t)T * 8));
+  HIPCHK(ctx, B.d_out.alloc((size_t)T * gat::kGenesetWords));
+  HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, (size_t)T * gat::kGenesetWords * 8, ctx->stream));
+  rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t, int64_t nb) {
+    return launch_geneset(ctx, kn, sampled_lists(P), nb, in, P->n_contigs, false, B);
+  });
+  if (rc) return rc;
+  // the samples whose count is 0: the five words are k_local's, and so is their last step
+  static_assert(gat::kGenesetWords == gat::kLocalWords, "k_local_finish reads five words");
+  hipLaunchKernelGGL(gat::k_local_finish, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out.p, B.d_obs.p, T, (unsigned long long)S);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, (size_t)T * gat::kGenesetWords * 8));
+  return GAT_OK;
+}
+
+extern "C" int gat_sample_geneset_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                             const gat_segment* pieces, const int64_t* piece_off, const int64_t* member_off,
+                                             const int32_t* members, int32_t n_genes, const int64_t* term_off, const int32_t* term_genes,
+                                             int32_t n_terms, const int64_t* obs_host, int64_t* out_host, gat_stats* stats) {
+  const char* who = "gat_sample_geneset_enrichment";
+  if (!ctx || !P || !piece_off || !member_off || !term_off) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
+  const GenesetIn in = {pieces, piece_off, member_off, members, n_genes, term_off, term_genes, n_terms};
+  int rc;
+  if ((rc = geneset_check_common(ctx, who, in, P->n_contigs))) return rc;
+  const int64_t S = sample_end - sample_begin;
+  if (n_terms > 0 && (!obs_host || !out_host)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if ((unsigned __int128)((uint64_t)n_genes * (uint64_t)n_genes) * (unsigned __int128)(uint64_t)S >> 64)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_genes^2 * samples = %d^2 * %lld does not fit 64 bits (sumsq): fewer samples per call",
+                   who, n_genes, (long long)S);
+  for (int64_t t = 0; t < n_terms; ++t)
+    if (obs_host[t] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: obs[%lld] = %lld is negative", who, (long long)t, (long long)obs_host[t]);
+  GenesetBufs B;
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    if (n_terms == 0) return GAT_OK;
+    if (S == 0) { memset(out_host, 0, (size_t)n_terms * gat::kGenesetWords * 8); return GAT_OK; }   // (no batch runs: the sums are empty)
+    return sample_geneset_enrichment_body(ctx, P, kn, seed, sample_begin, S, in, obs_host, out_host, local, B);
   });
 }
 

@@ -571,6 +571,62 @@ int gat_sample_pair_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                                const gat_segment* annos, const int64_t* anno_off, int32_t n_tracks,
                                const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
 
+/* Gene-set enrichment against the sampled null, counted on the device by k_geneset_hits and k_geneset_terms (the reference's
+ * gat-geneset.py tests with a hypergeometric draw, which takes every gene to be hit equally often).
+ * GENES.  G genes, 0 .. G-1; gene g owns a set of intervals on the groups (contigs); genes may overlap, nest or coincide.  The
+ * host flattens a group's genes into PIECES: the elementary intervals between consecutive gene boundaries that at least one
+ * gene covers -- normalized (sorted, pairwise disjoint, end > start; adjacent pieces allowed).  Piece j carries members(j),
+ * the ascending, duplicate-free ids of the genes that cover it: a CSR (member_off, members) over the pieces of all groups in
+ * the groups' order.  For q = [s, e), e > s, a segment of group g:
+ *     hit(q, g') iff q shares a base with a piece that has g' among its members
+ *                = g' in members(j0 .. j1 - 1),  j0 = the first piece with end > s,  j1 = the first piece with start >= e
+ * -- bookended is no hit, one shared base is one.
+ *     H(L)    = the genes hit by any segment of list L, over all its groups: a gene hit by three segments, through four
+ *               pieces or on two contigs is in H once
+ *     c(L, t) = |H(L) n M_t|,  M_t the genes of term t: a CSR (term_off, term_genes) of ascending, duplicate-free gene ids; a
+ *               term may be empty
+ * The segment lists need be neither sorted nor disjoint (every sampler, SamplerSegments without isochore keys included);
+ * segments with e <= s are skipped.  Over a range of S samples and against an observed value obs[t] >= 0 given by the caller,
+ * every term gets five int64 words (GAT_GENESET_WORDS) -- those of GAT_LOCAL_WORDS, in the same order and with the same
+ * meaning, of c in place of v: n_pos, sum, sumsq, n_less, n_eq; all S samples count in n_less / n_eq, those with c == 0 too.
+ * All arithmetic is 64-bit integer and exact.  A partial sum has one owner on the device and is added once, so the words do
+ * not depend on batches, workgroups, tiles, runs or knobs, and the words of calls over [0, k) and [k, S) add up to those of
+ * the call over [0, S).  Context options, none of which changes a result: GAT_GENESET_LDS_PIECES -- piece ends of a group the
+ * searches find in LDS before they go to global memory (clamped to 32 KB over all groups; 0: none);
+ * GAT_GENESET_SAMPLES_PER_BLOCK -- the run of lists a workgroup of either kernel takes (default: by the launch);
+ * GAT_GENESET_TERM_TILE -- the terms a workgroup of k_geneset_terms owns (1 .. 256).  GAT_GENESET_MAX_GENES is a contract
+ * number: 262 144 bits are a bitmap of 32 KB per list, which leaves half of a 64 KB workgroup for the searches' first level
+ * and holds every GENCODE gene and transcript set.
+ *
+ * gat_list_geneset_hits: the raw c of caller-provided lists (the observed values of the input segments with n_lists == 1).
+ * lists / list_off, n_groups: as in gat_list_pair_hits.  pieces / piece_off[n_groups + 1]; member_off[n_pieces + 1], n_pieces
+ * = piece_off[n_groups] - piece_off[0], indexed by piece from piece_off[0]; term_off[n_terms + 1].  out_host:
+ * [n_lists][n_terms].  Synchronous.  n_terms == 0 or n_lists == 0 writes nothing.  GAT_ERR_ARG, nothing written: a NULL ctx /
+ * list_off / piece_off / member_off / term_off / out_host (lists / pieces / members / term_genes may be NULL where they hold
+ * nothing), negative counts, a decreasing offset array, pieces that are not normalized (gat_last_error names the group and
+ * the piece), a piece with no member, members or term genes outside [0, n_genes) or not strictly ascending (it names the
+ * piece or the term), n_genes above GAT_GENESET_MAX_GENES.  Never a wrong number. */
+#define GAT_GENESET_WORDS 5
+#define GAT_GENESET_MAX_GENES 262144
+int gat_list_geneset_hits(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                          const gat_segment* pieces, const int64_t* piece_off, const int64_t* member_off, const int32_t* members,
+                          int32_t n_genes, const int64_t* term_off, const int32_t* term_genes, int32_t n_terms,
+                          int32_t n_groups, int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop shared with gat_sample, the two kernels behind every batch that passed its checks,
+ * reading the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed
+ * and range (per-unit streams only), for every sampler.  The groups are the problem's contigs in the problem's order:
+ * piece_off has n_contigs + 1 entries; obs_host: [n_terms]; out_host: [n_terms][5].  Synchronous, like gat_sample.  An empty
+ * sample range writes zeros; n_terms == 0 writes nothing.  GAT_ERR_ARG, nothing written: as above, and a NULL p, a NULL
+ * obs_host / out_host with n_terms > 0, sample_end < sample_begin, a negative obs, n_genes^2 * samples >= 2^64 (sumsq would
+ * not fit), a call in flight on the problem.  The sampler's errors pass through (GAT_ERR_ASSERT; SamplerBruteForce's
+ * GAT_ERR_VALUE "sampling did not converge"). */
+int gat_sample_geneset_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                                  int64_t sample_begin, int64_t sample_end,
+                                  const gat_segment* pieces, const int64_t* piece_off, const int64_t* member_off,
+                                  const int32_t* members, int32_t n_genes, const int64_t* term_off, const int32_t* term_genes,
+                                  int32_t n_terms, const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
