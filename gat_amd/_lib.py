@@ -565,16 +565,14 @@ class Context(object):
         return out
 
 
-PAIR_WORDS =("n_pos", "sum", "sumsq", "n_less", "n_eq")
+NULL_WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")      # the sampled null of one cell against obs: include/gat_mi355.h
+LOCAL_WORDS = PAIR_WORDS = GENESET_WORDS = NULL_WORDS     # GAT_LOCAL_WORDS, GAT_PAIR_WORDS, GAT_GENESET_WORDS
 PAIR_MAX_TRACKS = 2048        # GAT_PAIR_MAX_TRACKS
 
 
 def pair_count(n_tracks):
     """the pairs (i, j), i <= j, of n_tracks tracks (0 where n_tracks is out of range: the library refuses the call)"""
     return n_tracks * (n_tracks + 1) // 2 if 0 <= n_tracks <= PAIR_MAX_TRACKS else 0
-
-
-GENESET_WORDS = PAIR_WORDS    # GAT_GENESET_WORDS
 
 
 def _geneset_arrays(pieces, piece_off, member_off, members, term_off, term_genes, n_terms, n_groups):
@@ -597,7 +595,6 @@ def _bin_offsets(n_bins, n_groups):
 
 
 METRICS_WORDS = ("n", "bases", "pairs", "inter", "touched", "outside_pieces", "tail_n", "tail_bases")
-LOCAL_WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")
 
 
 def list_metrics(ctx, lists, list_off, n_lists, ws, ws_off, n_groups):
@@ -986,6 +983,16 @@ class Problem(object):
         _check(rc, self.ctx._h)
         return out
 
+    def _sample_null_words(self, call, seed, sample_begin, sample_end, args, obs, cells):
+        """the tail of the three calls below: call(ctx, problem, seed, the range, *args, obs, out, stats) fills NULL_WORDS per
+        cell of an int64 array of shape `cells`, which is returned"""
+        out = np.zeros(tuple(cells) + (len(NULL_WORDS),), dtype=np.int64)
+        st = Stats()
+        rc = call(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end), *args, _p(obs), _p(out), C.byref(st))
+        self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
+        return out
+
     def sample_bin_enrichment(self, seed, sample_begin, sample_end, annos, anno_off, n_tracks, bin_size, n_bins, obs):
         """per (track, bin) the five sums (LOCAL_WORDS; gat_sample_bin_enrichment) over the sampled contig-level lists of
         [sample_begin, sample_end) of v = the bases a list shares with the track inside the bin, against obs[track, bin] --
@@ -999,14 +1006,8 @@ class Problem(object):
         total = max(0, int(bin_off[-1]))
         obs = np.ascontiguousarray(obs, dtype=np.int64)
         assert obs.shape == (n_tracks, total)
-        out = np.zeros((n_tracks, total, len(LOCAL_WORDS)), dtype=np.int64)
-        st = Stats()
-        rc = lib().gat_sample_bin_enrichment(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
-                                             _p(annos), _p(anno_off), n_tracks, int(bin_size), _p(bin_off), _p(obs), _p(out),
-                                             C.byref(st))
-        self.last_stats = st.asdict()
-        _check(rc, self.ctx._h)
-        return out, bin_off
+        return self._sample_null_words(lib().gat_sample_bin_enrichment, seed, sample_begin, sample_end,
+                                       (_p(annos), _p(anno_off), n_tracks, int(bin_size), _p(bin_off)), obs, (n_tracks, total)), bin_off
 
     def sample_pair_enrichment(self, seed, sample_begin, sample_end, annos, anno_off, n_tracks, obs):
         """per pair (i, j), i <= j, of n_tracks tracks the five sums (PAIR_WORDS; gat_sample_pair_enrichment) over the sampled
@@ -1019,13 +1020,8 @@ class Problem(object):
         assert anno_off.shape == (max(0, n_tracks) * self.n_contigs + 1,)
         obs = np.ascontiguousarray(obs, dtype=np.int64)
         assert not 0 <= n_tracks <= PAIR_MAX_TRACKS or obs.shape == (pair_count(n_tracks),)
-        out = np.zeros((pair_count(n_tracks), len(PAIR_WORDS)), dtype=np.int64)
-        st = Stats()
-        rc = lib().gat_sample_pair_enrichment(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
-                                              _p(annos), _p(anno_off), n_tracks, _p(obs), _p(out), C.byref(st))
-        self.last_stats = st.asdict()
-        _check(rc, self.ctx._h)
-        return out
+        return self._sample_null_words(lib().gat_sample_pair_enrichment, seed, sample_begin, sample_end,
+                                       (_p(annos), _p(anno_off), n_tracks), obs, (pair_count(n_tracks),))
 
     def sample_geneset_enrichment(self, seed, sample_begin, sample_end, pieces, piece_off, member_off, members, n_genes, term_off,
                                   term_genes, n_terms, obs):
@@ -1037,11 +1033,5 @@ class Problem(object):
         g = _geneset_arrays(pieces, piece_off, member_off, members, term_off, term_genes, n_terms, self.n_contigs)
         obs = np.ascontiguousarray(obs, dtype=np.int64)
         assert obs.shape == (max(0, n_terms),)
-        out = np.zeros((max(0, n_terms), len(GENESET_WORDS)), dtype=np.int64)
-        st = Stats()
-        rc = lib().gat_sample_geneset_enrichment(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
-                                                 _p(g[0]), _p(g[1]), _p(g[2]), _p(g[3]), n_genes, _p(g[4]), _p(g[5]), n_terms,
-                                                 _p(obs), _p(out), C.byref(st))
-        self.last_stats = st.asdict()
-        _check(rc, self.ctx._h)
-        return out
+        return self._sample_null_words(lib().gat_sample_geneset_enrichment, seed, sample_begin, sample_end,
+                                       (_p(g[0]), _p(g[1]), _p(g[2]), _p(g[3]), n_genes, _p(g[4]), _p(g[5]), n_terms), obs, (max(0, n_terms),))

@@ -7,8 +7,8 @@
 //   hit(q, .) = the members of pieces j0 .. j1 - 1 = members[member_off[j0] .. member_off[j1])  -- ONE contiguous range
 //   H(L) = the genes hit by any segment of L, all its groups;   c(L, t) = |H(L) n M_t|
 //
-// and over the samples of a range, per term, five 64-bit words against the caller's obs: n_pos (c > 0), sum, sumsq, n_less
-// (c < obs), n_eq (c == obs).  The lists are taken in any order and may overlap themselves; segments with e <= s are skipped.
+// and over the samples of a range, per term, the five words of gat_null_words.h against the caller's obs.  The lists are taken
+// in any order and may overlap themselves; segments with e <= s are skipped.
 //
 // TWO KERNELS, a bitmap of n_genes bits per list between them (global scratch, [list][words]):
 //
@@ -27,17 +27,16 @@
 // terms dealt round-robin to the four waves, reduced with shuffles.  The thread that owns the term then has c: STORED (one
 // owner per (list, term)) or FOLDED into the thread's five partial words, kept in registers over the run and added to the
 // result once at its end with 64-bit integer atomics: one owner per (run, term); integer adds commute, so neither the tile,
-// nor the run, nor the batches, nor the order of arrival can change a bit.  The lists with c == 0 are counted at the very end
-// from n_pos and the number of samples (k_local_finish, gat_local.h: the same five words).
+// nor the run, nor the batches, nor the order of arrival can change a bit.
 #pragma once
 #include "gat_device.h"
 #include "gat_lists.h"
+#include "gat_null_words.h"
 
 namespace gat {
 
 constexpr int kGenesetThreads = 256;
 constexpr int kGenesetWaves = kGenesetThreads / kWave;
-constexpr int kGenesetWords = 5;                         // GAT_GENESET_WORDS: those of GAT_LOCAL_WORDS
 constexpr int kGenesetMaxGenes = 262144;                 // GAT_GENESET_MAX_GENES: a bitmap of 32 KB
 constexpr int kGenesetMaxTermTile = kGenesetThreads;     // a thread owns a term of the tile
 constexpr int kGenesetLaneRange = 16;                    // member entries a lane walks on its own
@@ -78,7 +77,7 @@ struct GenesetTermsArgs {
   const int64_t* term_off;    // [n_terms + 1], from 0
   const int32_t* term_genes;
   const long long* obs;       // FOLD: [n_terms]
-  unsigned long long* out;    // STORE: [all lists][n_terms]; FOLD: [n_terms][kGenesetWords]
+  unsigned long long* out;    // STORE: [all lists][n_terms]; FOLD: [n_terms][kNullWords]
 };
 
 // first j in [0, K) with end(j) > x (UPPER) / >= x, K: none; nl == 0: no first level in LDS
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(kGenesetThreads) void k_geneset_terms(GenesetTermsA
     const unsigned long long v = (unsigned long long)c;
     if constexpr (STORE) {
       A.out[((int64_t)A.list_begin + i) * A.n_terms + t] = v;
-    } else {
+    } else {                                        // (null_words_count's step, spelled out: through a callable the five leave the registers)
       n_pos += 1ull;
       sum += v;
       sumsq += v * v;
@@ -223,12 +222,7 @@ __global__ __launch_bounds__(kGenesetThreads) void k_geneset_terms(GenesetTermsA
   }
   if constexpr (!STORE) {
     if (n_pos == 0ull) return;
-    unsigned long long* w = A.out + t * kGenesetWords;
-    atomicAdd(w + 0, n_pos);
-    atomicAdd(w + 1, sum);
-    atomicAdd(w + 2, sumsq);
-    if (n_less != 0ull) atomicAdd(w + 3, n_less);
-    if (n_eq != 0ull) atomicAdd(w + 4, n_eq);
+    null_words_flush(A.out + t * kNullWords, n_pos, sum, sumsq, n_less, n_eq);
   }
 }
 

@@ -4,8 +4,8 @@
 //
 //   v(L, A, b) = |L n A n [b * bin, (b + 1) * bin)|        0 <= v <= bin <= 2^31
 //
-// and over the samples of a range, per (track, bin), five 64-bit words against the caller's obs: n_pos (v > 0), sum (of v),
-// sumsq (of v * v), n_less (v < obs), n_eq (v == obs).  The (samples x tracks x bins) matrix is never formed.
+// and over the samples of a range, per (track, bin), the five words of gat_null_words.h against the caller's obs.  The
+// (samples x tracks x bins) matrix is never formed.
 //
 // A workgroup (256 threads, 4 waves) owns a WINDOW of W consecutive bins of one (track, contig) and a run of the lists of
 // that contig.  It stages what the search for the first annotation interval starts in -- the window's slice of the track (the
@@ -25,15 +25,13 @@
 // the words behind it, and either STORES v (one owner per (list, track, bin): a plain store into an output the caller zeroed)
 // or FOLDS it into the workgroup's per-bin accumulators in LDS: n_pos, n_less, n_eq (32 bits: at most one a list, the run is
 // below 2^31) and sum, sumsq (64 bits) -- for v > 0 only.  At the end the workgroup adds the bins with n_pos > 0 to the
-// result: consecutive lanes, consecutive bins, 64-bit integer atomicAdd.  A partial sum has one owner and integer adds
-// commute, so neither the window, nor the run, nor the batches, nor the order of arrival can change a bit.
-// The samples with v == 0 are counted at the very end, k_local_finish, from n_pos and the number of samples S:
-// n_less += (S - n_pos) * [0 < obs], n_eq += (S - n_pos) * [obs == 0].
+// result: consecutive lanes, consecutive bins.
 #pragma once
 #include "gat_device.h"
 #include "gat_lists.h"
 #include "gat_coverage.h"     // coverage_first_reaching
 #include "gat_local_windows.h"
+#include "gat_null_words.h"
 
 namespace gat {
 
@@ -50,7 +48,7 @@ struct LocalArgs {
   const LocalWindow* win;     // gridDim.x of them
   const uint2* annos;
   const long long* obs;       // FOLD: [n_tracks][total_bins]
-  unsigned long long* out;    // STORE: [n_lists][n_tracks][total_bins]; FOLD: [n_tracks][total_bins][kLocalWords]
+  unsigned long long* out;    // STORE: [n_lists][n_tracks][total_bins]; FOLD: [n_tracks][total_bins][kNullWords]
 };
 
 template <bool STORE>
@@ -175,12 +173,11 @@ __global__ __launch_bounds__(kLocalThreads) void k_local(LocalArgs A) {
       if constexpr (STORE) {
         A.out[(int64_t)i * A.list_stride + win.out + b] = v;
       } else {
-        const unsigned long long o = (unsigned long long)l_obs[b];
-        atomicAdd(&l_pos[b], 1u);
-        atomicAdd(&l_sum[b], v);
-        atomicAdd(&l_sumsq[b], v * v);
-        if (v < o) atomicAdd(&l_less[b], 1u);
-        else if (v == o) atomicAdd(&l_eq[b], 1u);
+        null_words_count(v, (unsigned long long)l_obs[b], [&](NullWord w, unsigned long long x) {
+          if (w == kNullSum) atomicAdd(&l_sum[b], x);
+          else if (w == kNullSumsq) atomicAdd(&l_sumsq[b], x);
+          else atomicAdd(&(w == kNullPos ? l_pos : w == kNullLess ? l_less : l_eq)[b], (uint32_t)x);
+        });
       }
     }
     wave_fence();
@@ -191,25 +188,9 @@ __global__ __launch_bounds__(kLocalThreads) void k_local(LocalArgs A) {
     for (int b = tid; b < nb; b += kLocalThreads) {
       const uint32_t np = l_pos[b];
       if (np == 0u) continue;
-      unsigned long long* o = A.out + (win.out + b) * kLocalWords;
-      atomicAdd(o + 0, (unsigned long long)np);
-      atomicAdd(o + 1, l_sum[b]);
-      atomicAdd(o + 2, l_sumsq[b]);
-      if (l_less[b]) atomicAdd(o + 3, (unsigned long long)l_less[b]);
-      if (l_eq[b]) atomicAdd(o + 4, (unsigned long long)l_eq[b]);
+      null_words_flush(A.out + (win.out + b) * kNullWords, np, l_sum[b], l_sumsq[b], l_less[b], l_eq[b]);
     }
   }
-}
-
-// the samples whose value is 0, which k_local never counted: S - n_pos of them per (track, bin)
-__global__ __launch_bounds__(256) void k_local_finish(unsigned long long* out, const long long* __restrict__ obs, int64_t n, unsigned long long S) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= n) return;
-  unsigned long long* o = out + k * kLocalWords;
-  const unsigned long long zeros = S - o[0];
-  const long long ob = obs[k];
-  if (ob > 0) o[3] += zeros;
-  else if (ob == 0) o[4] += zeros;
 }
 
 }  // namespace gat

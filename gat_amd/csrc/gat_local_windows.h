@@ -11,7 +11,6 @@ namespace gat {
 
 constexpr int kLocalThreads = 256;
 constexpr int kLocalWaves = kLocalThreads / kWave;
-constexpr int kLocalWords = 5;                  // GAT_LOCAL_WORDS
 constexpr int kLocalFoldBinBytes = 32;          // sum, sumsq (8 each), n_pos, n_less, n_eq, obs (4 each)
 constexpr int kLocalWaveBinBytes = 8;           // part, diff
 

@@ -1722,6 +1722,70 @@ static gat::ListSet csr_lists(const DevBuf<uint2>& d_seg, const DevBuf<int64_t>&
   S.csr = d_csr.p;
   return S;
 }
+// what a call over n_lists x n_groups caller-provided lists asks of the two counts (before anything is indexed with them) ...
+static int check_list_counts(gat_ctx* ctx, const char* who, int64_t n_lists, int32_t n_groups) {
+  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
+  return GAT_OK;
+}
+// ... and of the n = n_lists * n_groups lists themselves, once the other side of the call is checked
+static int check_caller_lists(gat_ctx* ctx, const char* who, const char* noun, const gat_segment* lists, const int64_t* list_off, int64_t n) {
+  const int rc = check_list_offsets(ctx, who, "list_off", noun, list_off, n);
+  if (rc) return rc;
+  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  return GAT_OK;
+}
+// k_store (the raw values per list) or k_fold (the fold into the five words), with `lds` bytes of dynamic LDS
+template <class Args>
+static int launch_store_or_fold(gat_ctx* ctx, bool store, void (*k_store)(Args), void (*k_fold)(Args), dim3 grid, int threads, size_t lds, const Args& A) {
+  void (*const k)(Args) = store ? k_store : k_fold;
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k, grid, dim3(threads), lds, ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  return GAT_OK;
+}
+
+// ---- the fold of the sampled null to five words per cell (gat_null_words.h), as gat_sample_bin_enrichment,
+// gat_sample_pair_enrichment and gat_sample_geneset_enrichment share it: obs up and the words zeroed before the first batch,
+// k_null_finish and the words down behind the last
+struct NullWordsOut {
+  DevBuf<long long> d_obs;
+  DevBuf<unsigned long long> d_out;         // (the calls over caller-provided lists keep their raw values here)
+  int begin(gat_ctx* ctx, const int64_t* obs_host, int64_t n) {
+    HIPCHK(ctx, d_obs.alloc((size_t)n));
+    HIPCHK(ctx, staged_h2d(ctx, d_obs.p, obs_host, (size_t)n * 8));
+    HIPCHK(ctx, d_out.alloc((size_t)n * gat::kNullWords));
+    HIPCHK(ctx, hipMemsetAsync(d_out.p, 0, (size_t)n * gat::kNullWords * 8, ctx->stream));
+    return GAT_OK;
+  }
+  int finish(gat_ctx* ctx, int64_t n, int64_t S, int64_t* out_host) {
+    hipLaunchKernelGGL(gat::k_null_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_out.p, d_obs.p, n, (unsigned long long)S);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, staged_d2h(ctx, out_host, d_out.p, (size_t)n * gat::kNullWords * 8));
+    return GAT_OK;
+  }
+};
+// what the three ask of the range and of obs: a value is at most `bound` (`bound_name` and `advice`: the caller's words for
+// it), so sumsq <= bound^2 * S has to fit 64 bits; obs[0 .. n) >= 0
+static int check_null_words(gat_ctx* ctx, const char* who, const char* bound_name, int64_t bound, const char* advice, int64_t S,
+                            const int64_t* obs_host, int64_t n) {
+  if ((unsigned __int128)((uint64_t)bound * (uint64_t)bound) * (unsigned __int128)(uint64_t)S >> 64)
+    return set_err(ctx, GAT_ERR_ARG, "%s: %s^2 * samples = %lld^2 * %lld does not fit 64 bits (sumsq): %s", who, bound_name,
+                   (long long)bound, (long long)S, advice);
+  for (int64_t k = 0; k < n; ++k)
+    if (obs_host[k] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: obs[%lld] = %lld is negative", who, (long long)k, (long long)obs_host[k]);
+  return GAT_OK;
+}
+// the call's frame around the fold of n cells over S samples: no cell -- nothing is written; no sample -- no batch runs, the
+// sums are empty; else body(kn, local)
+template <class Body>
+static int null_words_frame(gat_ctx* ctx, gat_problem* P, gat_stats* stats, int64_t n, int64_t S, int64_t* out_host, Body body) {
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    if (n == 0) return GAT_OK;
+    if (S == 0) { memset(out_host, 0, (size_t)n * gat::kNullWords * 8); return GAT_OK; }
+    return body(kn, local);
+  });
+}
 
 // gat_sample / gat_sample_units: the lists of every (sample, contig) after fromIsochores, or of every (sample, unit)
 // as the sampler returned them
@@ -2064,13 +2128,10 @@ extern "C" int gat_list_distances(gat_ctx* ctx, const gat_segment* lists, const 
                                   int direction, int64_t max_distance, int64_t* out_host) {
   const char* who = "gat_list_distances";
   if (!ctx || !list_off || !anno_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
-  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
-    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
   int rc;
+  if ((rc = check_list_counts(ctx, who, n_lists, n_groups))) return rc;
   if ((rc = distance_check_common(ctx, who, annos, anno_off, n_tracks, n_groups, direction, max_distance))) return rc;
-  const int64_t n = n_lists * n_groups;
-  if ((rc = check_list_offsets(ctx, who, "list_off", "intervals", list_off, n))) return rc;
-  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = check_caller_lists(ctx, who, "intervals", lists, list_off, n_lists * n_groups))) return rc;
   if (direction == GAT_DISTANCE_ANNOTATION_TO_SEGMENT && (rc = distance_check_normalized(ctx, who, "segment list", lists, list_off, n_lists, n_groups))) return rc;
   if (n_lists == 0 || n_tracks == 0) return GAT_OK;
   DistanceBufs B;
@@ -2124,8 +2185,7 @@ struct LocalBufs {
   DevBuf<uint2> d_anno, d_seg;
   DevBuf<int64_t> d_anno_csr, d_csr;
   DevBuf<gat::LocalWindow> d_win;
-  DevBuf<long long> d_obs;
-  DevBuf<unsigned long long> d_out;
+  NullWordsOut out;
   std::vector<gat::LocalWindow> win;
   int64_t W = 0, L = 0;
 };
@@ -2173,23 +2233,15 @@ static int launch_local(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists
   A.list_stride = list_stride;
   A.win = B.d_win.p;
   A.annos = B.d_anno.p;
-  A.obs = B.d_obs.p;
-  A.out = B.d_out.p;
+  A.obs = B.out.d_obs.p;
+  A.out = B.out.d_out.p;
   const int64_t n_win = (int64_t)B.win.size();
   const int64_t lpb = kn.local_samples_per_block > 0 ? gat::run_per_block(n_lists, n_win, 0, kn.local_samples_per_block)
                                                      : gat::run_per_block(n_lists, n_win, 1024, gat::kNoRunCap);
   A.lists_per_block = (int32_t)lpb;
   const size_t lds = gat::local_lds_bytes(B.W, B.L, store);
   const dim3 grid((unsigned)n_win, (unsigned)((n_lists + lpb - 1) / lpb));
-  if (store) {
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_local<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(gat::k_local<true>, grid, dim3(gat::kLocalThreads), lds, ctx->stream, A);
-  } else {
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_local<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(gat::k_local<false>, grid, dim3(gat::kLocalThreads), lds, ctx->stream, A);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  return GAT_OK;
+  return launch_store_or_fold(ctx, store, gat::k_local<true>, gat::k_local<false>, grid, gat::kLocalThreads, lds, A);
 }
 
 extern "C" int gat_list_bin_overlaps(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
@@ -2197,13 +2249,11 @@ extern "C" int gat_list_bin_overlaps(gat_ctx* ctx, const gat_segment* lists, con
                                      int64_t bin_size, const int64_t* bin_off, int64_t* out_host) {
   const char* who = "gat_list_bin_overlaps";
   if (!ctx || !list_off || !anno_off || !bin_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
-  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
-    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
   int rc;
+  if ((rc = check_list_counts(ctx, who, n_lists, n_groups))) return rc;
   if ((rc = local_check_common(ctx, who, annos, anno_off, n_tracks, n_groups, bin_size, bin_off))) return rc;
   const int64_t n = n_lists * n_groups;
-  if ((rc = check_list_offsets(ctx, who, "list_off", "intervals", list_off, n))) return rc;
-  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = check_caller_lists(ctx, who, "intervals", lists, list_off, n))) return rc;
   if ((rc = distance_check_normalized(ctx, who, "segment list", lists, list_off, n_lists, n_groups, kLocalWhy))) return rc;
   const int64_t list_stride = (int64_t)n_tracks * bin_off[n_groups];
   const size_t words = (size_t)(n_lists * list_stride);
@@ -2213,10 +2263,10 @@ extern "C" int gat_list_bin_overlaps(gat_ctx* ctx, const gat_segment* lists, con
     int brc;
     if ((brc = local_windows(ctx, who, kn, annos, anno_off, n_tracks, n_groups, bin_size, bin_off, B))) return brc;
     if ((brc = upload_csr_lists(ctx, lists, list_off, n, B.d_seg, B.d_csr))) return brc;
-    HIPCHK(ctx, B.d_out.alloc(words));
-    HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, words * 8, ctx->stream));
+    HIPCHK(ctx, B.out.d_out.alloc(words));
+    HIPCHK(ctx, hipMemsetAsync(B.out.d_out.p, 0, words * 8, ctx->stream));
     if ((brc = launch_local(ctx, kn, csr_lists(B.d_seg, B.d_csr), n_lists, n_groups, bin_size, true, list_stride, B))) return brc;
-    HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, words * 8));
+    HIPCHK(ctx, staged_d2h(ctx, out_host, B.out.d_out.p, words * 8));
     return GAT_OK;
   });
 }
@@ -2228,18 +2278,11 @@ static int sample_bin_enrichment_body(gat_ctx* ctx, gat_problem* P, const Knobs&
   const int64_t cells = (int64_t)n_tracks * bin_off[C];
   int rc;
   if ((rc = local_windows(ctx, "gat_sample_bin_enrichment", kn, annos, anno_off, n_tracks, C, bin_size, bin_off, B))) return rc;
-  HIPCHK(ctx, B.d_obs.alloc((size_t)cells));
-  HIPCHK(ctx, staged_h2d(ctx, B.d_obs.p, obs_host, (size_t)cells * 8));
-  HIPCHK(ctx, B.d_out.alloc((size_t)cells * gat::kLocalWords));
-  HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, (size_t)cells * gat::kLocalWords * 8, ctx->stream));
+  if ((rc = B.out.begin(ctx, obs_host, cells))) return rc;
   rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t, int64_t nb) {
     return launch_local(ctx, kn, sampled_lists(P), nb, C, bin_size, false, 0, B);
   });
-  if (rc) return rc;
-  hipLaunchKernelGGL(gat::k_local_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out.p, B.d_obs.p, cells, (unsigned long long)S);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, (size_t)cells * gat::kLocalWords * 8));
-  return GAT_OK;
+  return rc ? rc : B.out.finish(ctx, cells, S, out_host);
 }
 
 extern "C" int gat_sample_bin_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
@@ -2252,18 +2295,12 @@ extern "C" int gat_sample_bin_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t 
   int rc;
   if ((rc = local_check_common(ctx, who, annos, anno_off, n_tracks, P->n_contigs, bin_size, bin_off))) return rc;
   const int64_t S = sample_end - sample_begin, cells = (int64_t)n_tracks * bin_off[P->n_contigs];
-  if ((unsigned __int128)((uint64_t)bin_size * (uint64_t)bin_size) * (unsigned __int128)(uint64_t)S >> 64)
-    return set_err(ctx, GAT_ERR_ARG, "%s: bin_size^2 * samples = %lld^2 * %lld does not fit 64 bits (sumsq): a smaller bin_size or fewer samples per call",
-                   who, (long long)bin_size, (long long)S);
-  for (int64_t k = 0; k < cells; ++k)
-    if (obs_host[k] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: obs[%lld] = %lld is negative", who, (long long)k, (long long)obs_host[k]);
+  if ((rc = check_null_words(ctx, who, "bin_size", bin_size, "a smaller bin_size or fewer samples per call", S, obs_host, cells))) return rc;
   if (!sampled_lists_normalized(P))
     return set_err(ctx, GAT_ERR_ARG, "%s: the sampled segment lists are not normalized (SamplerSegments without isochore keys leaves them "
                    "neither sorted nor disjoint): the overlap per bin needs normalized lists", who);
   LocalBufs B;
-  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
-    if (cells == 0) return GAT_OK;
-    if (S == 0) { memset(out_host, 0, (size_t)cells * gat::kLocalWords * 8); return GAT_OK; }   // (no batch runs: the sums are empty)
+  return null_words_frame(ctx, P, stats, cells, S, out_host, [&](const Knobs& kn, gat_stats& local) {
     return sample_bin_enrichment_body(ctx, P, kn, seed, sample_begin, S, annos, anno_off, n_tracks, bin_size, bin_off, obs_host,
                                       out_host, local, B);
   });
@@ -2274,8 +2311,7 @@ extern "C" int gat_sample_bin_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t 
 struct PairsBufs {
   DevBuf<uint2> d_anno, d_seg;
   DevBuf<int64_t> d_anno_csr, d_csr;
-  DevBuf<long long> d_obs;
-  DevBuf<unsigned long long> d_out;
+  NullWordsOut out;
 };
 static const char* const kPairsWhy = "the first interval that reaches a segment is searched for in it";
 // what both entry points ask of the tracks
@@ -2305,23 +2341,15 @@ static int launch_pairs(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists
   A.lds_pieces = (int32_t)L;
   A.annos = B.d_anno.p;
   A.anno_csr = B.d_anno_csr.p;
-  A.obs = B.d_obs.p;
-  A.out = B.d_out.p;
+  A.obs = B.out.d_obs.p;
+  A.out = B.out.d_out.p;
   const int64_t n_tiles = gat::pairs_tiles(n_tracks);
   const int64_t lpb = kn.pairs_samples_per_block > 0 ? gat::run_per_block(n_lists, n_tiles, 0, kn.pairs_samples_per_block)
                                                      : gat::run_per_block(n_lists, n_tiles, 4096, gat::kNoRunCap);
   A.lists_per_block = (int32_t)lpb;
   const size_t lds = (size_t)gat::pairs_lds_bytes(L, n_groups);
   const dim3 grid((unsigned)n_tiles, (unsigned)((n_lists + lpb - 1) / lpb));
-  if (store) {
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(gat::k_pairs<true>, grid, dim3(gat::kPairsThreads), lds, ctx->stream, A);
-  } else {
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_pairs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(gat::k_pairs<false>, grid, dim3(gat::kPairsThreads), lds, ctx->stream, A);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  return GAT_OK;
+  return launch_store_or_fold(ctx, store, gat::k_pairs<true>, gat::k_pairs<false>, grid, gat::kPairsThreads, lds, A);
 }
 
 extern "C" int gat_list_pair_hits(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
@@ -2329,14 +2357,12 @@ extern "C" int gat_list_pair_hits(gat_ctx* ctx, const gat_segment* lists, const 
                                   int64_t* out_host) {
   const char* who = "gat_list_pair_hits";
   if (!ctx || !list_off || !anno_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
-  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
-    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
   int rc;
+  if ((rc = check_list_counts(ctx, who, n_lists, n_groups))) return rc;
   if ((rc = pairs_check_common(ctx, who, annos, anno_off, n_tracks, n_groups))) return rc;
   const int64_t n = n_lists * n_groups;
-  if ((rc = check_list_offsets(ctx, who, "list_off", "segments", list_off, n))) return rc;
-  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
-  for (int64_t l = 0; l < n_lists; ++l)           // (a list's count of a pair is a 32-bit word on the device)
+  if ((rc = check_caller_lists(ctx, who, "segments", lists, list_off, n))) return rc;
+  for (int64_t l = 0; l < n_lists; ++l)          // (a list's count of a pair is a 32-bit word on the device)
     if (list_off[(l + 1) * n_groups] - list_off[l * n_groups] > (int64_t)INT32_MAX)
       return set_err(ctx, GAT_ERR_CAPACITY, "%s: list %lld holds more than 2^31 - 1 segments", who, (long long)l);
   const size_t words = (size_t)(n_lists * gat::pairs_count(n_tracks));
@@ -2346,10 +2372,10 @@ extern "C" int gat_list_pair_hits(gat_ctx* ctx, const gat_segment* lists, const 
     int brc;
     if ((brc = upload_csr_lists(ctx, annos, anno_off, (int64_t)n_tracks * n_groups, B.d_anno, B.d_anno_csr))) return brc;
     if ((brc = upload_csr_lists(ctx, lists, list_off, n, B.d_seg, B.d_csr))) return brc;
-    HIPCHK(ctx, B.d_out.alloc(words));
-    HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, words * 8, ctx->stream));
+    HIPCHK(ctx, B.out.d_out.alloc(words));
+    HIPCHK(ctx, hipMemsetAsync(B.out.d_out.p, 0, words * 8, ctx->stream));
     if ((brc = launch_pairs(ctx, kn, csr_lists(B.d_seg, B.d_csr), n_lists, n_tracks, n_groups, true, B))) return brc;
-    HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, words * 8));
+    HIPCHK(ctx, staged_d2h(ctx, out_host, B.out.d_out.p, words * 8));
     return GAT_OK;
   });
 }
@@ -2361,20 +2387,11 @@ static int sample_pair_enrichment_body(gat_ctx* ctx, gat_problem* P, const Knobs
   const int64_t pairs = gat::pairs_count(n_tracks);
   int rc;
   if ((rc = upload_csr_lists(ctx, annos, anno_off, (int64_t)n_tracks * C, B.d_anno, B.d_anno_csr))) return rc;
-  HIPCHK(ctx, B.d_obs.alloc((size_t)pairs));
-  HIPCHK(ctx, staged_h2d(ctx, B.d_obs.p, obs_host, (size_t)pairs * 8));
-  HIPCHK(ctx, B.d_out.alloc((size_t)pairs * gat::kPairsWords));
-  HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, (size_t)pairs * gat::kPairsWords * 8, ctx->stream));
+  if ((rc = B.out.begin(ctx, obs_host, pairs))) return rc;
   rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t, int64_t nb) {
     return launch_pairs(ctx, kn, sampled_lists(P), nb, n_tracks, C, false, B);
   });
-  if (rc) return rc;
-  // the samples whose count is 0: the five words are k_local's, and so is their last step
-  static_assert(gat::kPairsWords == gat::kLocalWords, "k_local_finish reads five words");
-  hipLaunchKernelGGL(gat::k_local_finish, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out.p, B.d_obs.p, pairs, (unsigned long long)S);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, (size_t)pairs * gat::kPairsWords * 8));
-  return GAT_OK;
+  return rc ? rc : B.out.finish(ctx, pairs, S, out_host);
 }
 
 extern "C" int gat_sample_pair_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
@@ -2389,15 +2406,9 @@ extern "C" int gat_sample_pair_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t
   if (pairs > 0 && (!obs_host || !out_host)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
   const int64_t n_max = P->slab_stride;           // the most segments one sample can hold
   if (n_max > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_CAPACITY, "%s: a sample can hold %lld segments, more than 2^31 - 1", who, (long long)n_max);
-  if ((unsigned __int128)((uint64_t)n_max * (uint64_t)n_max) * (unsigned __int128)(uint64_t)S >> 64)
-    return set_err(ctx, GAT_ERR_ARG, "%s: n_max^2 * samples = %lld^2 * %lld does not fit 64 bits (sumsq): fewer samples per call",
-                   who, (long long)n_max, (long long)S);
-  for (int64_t k = 0; k < pairs; ++k)
-    if (obs_host[k] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: obs[%lld] = %lld is negative", who, (long long)k, (long long)obs_host[k]);
+  if ((rc = check_null_words(ctx, who, "n_max", n_max, "fewer samples per call", S, obs_host, pairs))) return rc;
   PairsBufs B;
-  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
-    if (pairs == 0) return GAT_OK;
-    if (S == 0) { memset(out_host, 0, (size_t)pairs * gat::kPairsWords * 8); return GAT_OK; }   // (no batch runs: the sums are empty)
+  return null_words_frame(ctx, P, stats, pairs, S, out_host, [&](const Knobs& kn, gat_stats& local) {
     return sample_pair_enrichment_body(ctx, P, kn, seed, sample_begin, S, annos, anno_off, n_tracks, obs_host, out_host, local, B);
   });
 }
@@ -2408,10 +2419,9 @@ struct GenesetBufs {
   DevBuf<uint2> d_piece, d_seg;
   DevBuf<int64_t> d_piece_csr, d_csr, d_member_off, d_term_off;
   DevBuf<int32_t> d_members, d_term_genes;
-  DevBuf<long long> d_obs;
   DevBuf<uint32_t> d_bitmaps;
-  DevBuf<unsigned long long> d_out;
-  int64_t chunk = 0;          // lists whose bitmaps d_bitmaps holds
+  NullWordsOut out;
+  int64_t chunk = 0;         // lists whose bitmaps d_bitmaps holds
 };
 struct GenesetIn {
   const gat_segment* pieces; const int64_t* piece_off; const int64_t* member_off; const int32_t* members; int32_t n_genes;
@@ -2516,8 +2526,8 @@ static int launch_geneset(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lis
     T.n_terms = in.n_terms;
     T.term_off = B.d_term_off.p;
     T.term_genes = B.d_term_genes.p;
-    T.obs = B.d_obs.p;
-    T.out = B.d_out.p;
+    T.obs = B.out.d_obs.p;
+    T.out = B.out.d_out.p;
     const int64_t run_t = knob_run > 0 ? gat::run_per_block(n, n_tiles, 0, knob_run) : gat::run_per_block(n, n_tiles, 2048, gat::kNoRunCap);
     T.lists_per_block = (int32_t)run_t;
     const dim3 grid((unsigned)n_tiles, (unsigned)((n + run_t - 1) / run_t));
@@ -2534,14 +2544,12 @@ extern "C" int gat_list_geneset_hits(gat_ctx* ctx, const gat_segment* lists, con
                                      int32_t n_groups, int64_t* out_host) {
   const char* who = "gat_list_geneset_hits";
   if (!ctx || !list_off || !piece_off || !member_off || !term_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
-  if (n_lists < 0 || n_groups < 0 || n_lists > (int64_t)INT32_MAX || n_lists * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
-    return set_err(ctx, GAT_ERR_ARG, "%s: n_lists %lld, n_groups %d", who, (long long)n_lists, n_groups);
   const GenesetIn in = {pieces, piece_off, member_off, members, n_genes, term_off, term_genes, n_terms};
   int rc;
+  if ((rc = check_list_counts(ctx, who, n_lists, n_groups))) return rc;
   if ((rc = geneset_check_common(ctx, who, in, n_groups))) return rc;
   const int64_t n = n_lists * n_groups;
-  if ((rc = check_list_offsets(ctx, who, "list_off", "segments", list_off, n))) return rc;
-  if (list_off[n] > list_off[0] && !lists) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = check_caller_lists(ctx, who, "segments", lists, list_off, n))) return rc;
   const size_t words = (size_t)(n_lists * (int64_t)n_terms);
   if (words == 0) return GAT_OK;
   GenesetBufs B;
@@ -2549,10 +2557,10 @@ extern "C" int gat_list_geneset_hits(gat_ctx* ctx, const gat_segment* lists, con
     int brc;
     if ((brc = geneset_upload(ctx, kn, in, n_groups, n_lists, B))) return brc;
     if ((brc = upload_csr_lists(ctx, lists, list_off, n, B.d_seg, B.d_csr))) return brc;
-    HIPCHK(ctx, B.d_out.alloc(words));
-    HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, words * 8, ctx->stream));
+    HIPCHK(ctx, B.out.d_out.alloc(words));
+    HIPCHK(ctx, hipMemsetAsync(B.out.d_out.p, 0, words * 8, ctx->stream));
     if ((brc = launch_geneset(ctx, kn, csr_lists(B.d_seg, B.d_csr), n_lists, in, n_groups, true, B))) return brc;
-    HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, words * 8));
+    HIPCHK(ctx, staged_d2h(ctx, out_host, B.out.d_out.p, words * 8));
     return GAT_OK;
   });
 }
@@ -2562,20 +2570,11 @@ static int sample_geneset_enrichment_body(gat_ctx* ctx, gat_problem* P, const Kn
   const int64_t T = in.n_terms;
   int rc;
   if ((rc = geneset_upload(ctx, kn, in, P->n_contigs, S, B))) return rc;
-  HIPCHK(ctx, B.d_obs.alloc((size_t)T));
-  HIPCHK(ctx, staged_h2d(ctx, B.d_obs.p, obs_host, (size_t)T * 8));
-  HIPCHK(ctx, B.d_out.alloc((size_t)T * gat::kGenesetWords));
-  HIPCHK(ctx, hipMemsetAsync(B.d_out.p, 0, (size_t)T * gat::kGenesetWords * 8, ctx->stream));
+  if ((rc = B.out.begin(ctx, obs_host, T))) return rc;
   rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t, int64_t nb) {
     return launch_geneset(ctx, kn, sampled_lists(P), nb, in, P->n_contigs, false, B);
   });
-  if (rc) return rc;
-  // the samples whose count is 0: the five words are k_local's, and so is their last step
-  static_assert(gat::kGenesetWords == gat::kLocalWords, "k_local_finish reads five words");
-  hipLaunchKernelGGL(gat::k_local_finish, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out.p, B.d_obs.p, T, (unsigned long long)S);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, staged_d2h(ctx, out_host, B.d_out.p, (size_t)T * gat::kGenesetWords * 8));
-  return GAT_OK;
+  return rc ? rc : B.out.finish(ctx, T, S, out_host);
 }
 
 extern "C" int gat_sample_geneset_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
@@ -2590,15 +2589,9 @@ extern "C" int gat_sample_geneset_enrichment(gat_ctx* ctx, gat_problem* P, uint3
   if ((rc = geneset_check_common(ctx, who, in, P->n_contigs))) return rc;
   const int64_t S = sample_end - sample_begin;
   if (n_terms > 0 && (!obs_host || !out_host)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
-  if ((unsigned __int128)((uint64_t)n_genes * (uint64_t)n_genes) * (unsigned __int128)(uint64_t)S >> 64)
-    return set_err(ctx, GAT_ERR_ARG, "%s: n_genes^2 * samples = %d^2 * %lld does not fit 64 bits (sumsq): fewer samples per call",
-                   who, n_genes, (long long)S);
-  for (int64_t t = 0; t < n_terms; ++t)
-    if (obs_host[t] < 0) return set_err(ctx, GAT_ERR_ARG, "%s: obs[%lld] = %lld is negative", who, (long long)t, (long long)obs_host[t]);
+  if ((rc = check_null_words(ctx, who, "n_genes", n_genes, "fewer samples per call", S, obs_host, n_terms))) return rc;
   GenesetBufs B;
-  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
-    if (n_terms == 0) return GAT_OK;
-    if (S == 0) { memset(out_host, 0, (size_t)n_terms * gat::kGenesetWords * 8); return GAT_OK; }   // (no batch runs: the sums are empty)
+  return null_words_frame(ctx, P, stats, n_terms, S, out_host, [&](const Knobs& kn, gat_stats& local) {
     return sample_geneset_enrichment_body(ctx, P, kn, seed, sample_begin, S, in, obs_host, out_host, local, B);
   });
 }

@@ -5,9 +5,9 @@
 //   hit(q, t) = 1 iff j < K and A_t[j].start < e,  j = the first index with A_t[j].end > s       (bookended: no hit)
 //   c(L, i, j) = the segments q of L, over all its groups, with hit(q, i) and hit(q, j)            i <= j
 //
-// and over the samples of a range, per pair, five 64-bit words against the caller's obs: n_pos (c > 0), sum (of c), sumsq
-// (of c * c), n_less (c < obs), n_eq (c == obs).  The (samples x pairs) matrix is never formed.  The lists are taken in any
-// order and may overlap themselves: every segment counts on its own; segments with e <= s are skipped.
+// and over the samples of a range, per pair, the five words of gat_null_words.h against the caller's obs.  The (samples x
+// pairs) matrix is never formed.  The lists are taken in any order and may overlap themselves: every segment counts on its
+// own; segments with e <= s are skipped.
 //
 // A workgroup (256 threads, 4 waves) owns a TILE of 64 x 64 tracks -- blocks (I, J), I <= J (gat_pairs_tiles.h) -- and a run
 // of lists.  It takes one list at a time, all its groups; its waves stride over the list's segments in chunks of 64.
@@ -28,12 +28,11 @@
 // once; integer adds commute, so neither the tile, nor the run, nor the batches, nor the order of arrival can change a bit.
 // (Partial sums of a run kept in registers -- 16 slots x five words a thread, 190 VGPRs -- were measured and gained nothing: the
 // adds are as many as the pairs a list touches, few beside its searches.)
-// The samples with c == 0 are counted at the very end, from n_pos and the number of samples (k_local_finish, gat_local.h:
-// the same five words).
 #pragma once
 #include "gat_device.h"
 #include "gat_lists.h"
 #include "gat_pairs_tiles.h"
+#include "gat_null_words.h"
 
 namespace gat {
 
@@ -47,7 +46,7 @@ struct PairsArgs {
   const uint2* annos;
   const int64_t* anno_csr;    // [n_tracks * n_groups + 1], track-major, from 0
   const long long* obs;       // FOLD: [P]
-  unsigned long long* out;    // STORE: [n_lists][P]; FOLD: [P][kPairsWords]
+  unsigned long long* out;    // STORE: [n_lists][P]; FOLD: [P][kNullWords]
 };
 
 // a track of one group: its K intervals and where the search for them starts (level: the track's row of the table)
@@ -174,13 +173,9 @@ __global__ __launch_bounds__(kPairsThreads) void k_pairs(PairsArgs A) {
       if constexpr (STORE) {
         A.out[(int64_t)i * P + pk] = (unsigned long long)c;
       } else {
-        const unsigned long long v = (unsigned long long)c, o = (unsigned long long)A.obs[pk];      // (obs >= 0)
-        unsigned long long* w = A.out + pk * kPairsWords;
-        atomicAdd(w + 0, 1ull);
-        atomicAdd(w + 1, v);
-        atomicAdd(w + 2, v * v);
-        if (v < o) atomicAdd(w + 3, 1ull);
-        else if (v == o) atomicAdd(w + 4, 1ull);
+        const unsigned long long o = (unsigned long long)A.obs[pk];
+        unsigned long long* cell = A.out + pk * kNullWords;
+        null_words_count((unsigned long long)c, o, [&](NullWord w, unsigned long long x) { atomicAdd(cell + w, x); });
       }
     }
     __syncthreads();

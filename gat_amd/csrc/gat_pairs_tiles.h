@@ -16,7 +16,6 @@ namespace gat {
 constexpr int kPairsBlock = 64;                 // tracks of a block: a lane each
 constexpr int kPairsThreads = 256;
 constexpr int kPairsWaves = kPairsThreads / kPairsBlock;
-constexpr int kPairsWords = 5;                  // GAT_PAIR_WORDS
 constexpr int kPairsMaxTracks = 2048;           // the contract's cap: 2 098 176 pairs
 constexpr int kPairsTileSlots = kPairsBlock * kPairsBlock;
 constexpr int kPairsSlotsPerThread = kPairsTileSlots / kPairsThreads;

@@ -25,11 +25,11 @@ sharding.
 """
 import numpy as np
 
-from . import intervals as iv
+from . import enrichment
 from . import problem
-from .coverage import SAMPLERS, flatten, make_sampler  # noqa: F401  (make_sampler: what scripts/gat-distance.py builds its sampler with)
 from .engine import AnnotatorResult, get_context
 
+flatten, make_sampler, build_inputs, contig_lists = enrichment.flatten, enrichment.make_sampler, enrichment.build_inputs, enrichment.contig_lists
 WORDS = ("n", "sum", "near", "none")
 SEGMENT_TO_ANNOTATION, ANNOTATION_TO_SEGMENT = 0, 1
 # counter -> (direction, which value of a list's words)
@@ -57,24 +57,9 @@ def rows(track, annotations, counter, observed_words, sample_words, pseudo_count
             for t, a in enumerate(annotations)]
 
 
-def contig_lists(per_entity, contigs):
-    """(SEG array, CSR offsets) of len(per_entity) x len(contigs) lists, entity-major: per_entity[i] is a dict contig -> SEG
-    array (contig level); a contig it lacks is an empty list"""
-    lists = [per.get(c, iv.EMPTY) for per in per_entity for c in contigs]
-    off = np.zeros(len(lists) + 1, dtype=np.int64)
-    if lists:
-        np.cumsum([len(a) for a in lists], out=off[1:])
-    return (np.concatenate(lists) if off[-1] else iv.EMPTY.copy()), off
-
-
 def check_options(options):
     """what the distance counters do not do, refused before anything is read"""
-    if getattr(options, "conditional", "unconditional") != "unconditional":
-        raise NotImplementedError("gat-distance: only --conditional=unconditional (the samples of a generated workspace are not measured)")
-    if getattr(options, "annotations_to_points", None):
-        raise NotImplementedError("gat-distance: --annotations-to-points is not supported (a position list is not an interval list)")
-    if getattr(options, "reference_stream", False):
-        raise NotImplementedError("gat-distance: per-unit streams only, not --reference-stream")
+    enrichment.check_options(options, "gat-distance")
 
 
 def track_distances(track, segs, annotations, workspace, sampler, counters, num_samples, max_distance=MAX_DISTANCE, random_seed=None,
@@ -82,25 +67,17 @@ def track_distances(track, segs, annotations, workspace, sampler, counters, num_
     """the rows of one segment track: `segs` and `workspace` IntervalDictionaries at isochore level as sample_counts takes
     them, `annotations` the IntervalCollection.  Returns (rows by counter in `counters`' order, the problem's unit count)."""
     from . import _lib
-    if not isinstance(sampler, SAMPLERS):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation and SamplerBruteForce run on the GPU path")
     for c in counters:
         if c not in COUNTERS:
             raise ValueError("unknown counter '%s'" % c)
-    max_distance, num_samples = int(max_distance), int(num_samples)
+    max_distance = int(max_distance)
     if not 0 <= max_distance <= 2 ** 32:
         raise ValueError("max_distance %d outside [0, 2^32]" % max_distance)
-    if num_samples < 1:
-        raise ValueError("num_samples < 1")
-    seed = int(np.random.randint(0, 2 ** 32)) if random_seed is None else int(random_seed)
-    flat, sa, _ = flatten(segs, workspace, sampler)
-    contigs = list(flat["contig_names"])
+    num_samples, seed, flat, _, contigs, lists, list_off = enrichment.track_start(segs, workspace, sampler, num_samples, random_seed)
     names = list(annotations.tracks)
     if not contigs or not names:
         return [[] for _ in counters], flat["n_units"]
     annos, anno_off = contig_lists([problem.from_isochores(annotations[t].asArrays()) for t in names], contigs)
-    lists, list_off = contig_lists([problem.from_isochores(sa)], contigs)
     ctx = ctx or get_context()
     observed, null = {}, {}
     P = _lib.Problem(ctx, flat)
@@ -127,17 +104,6 @@ def run(segments, annotations, workspace, sampler, counters, num_samples, max_di
         for k, r in enumerate(per):
             by_counter[k].extend(r)
     return [r for per in by_counter for r in per]
-
-
-def build_inputs(options):
-    """segments, annotations and the workspace of a run as gat-run.py prepares them (IO.buildSegments / IO.applyIsochores)"""
-    from . import io as IO
-    segments, annotations, workspaces, isochores = IO.buildSegments(options)
-    workspace = IO.applyIsochores(segments, annotations, workspaces, options, isochores,
-                                  truncate_segments_to_workspace=options.truncate_segments_to_workspace,
-                                  truncate_workspace_to_annotations=options.truncate_workspace_to_annotations,
-                                  restrict_workspace=options.restrict_workspace)
-    return segments, annotations, workspace
 
 
 def observed_format(counters):

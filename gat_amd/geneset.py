@@ -11,7 +11,7 @@ against the same count of every sampled segment list.  The genes are flattened o
 genes that cover it (flatten_genes); the device finds the pieces a segment reaches with one search per segment, marks the genes
 in a bitmap per list and counts every term from the bitmap (k_geneset_hits, k_geneset_terms: gat_sample_geneset_enrichment).
 The (samples x terms) matrix is never formed: five integers per term come back -- n_pos, sum, sumsq, n_less, n_eq;
-include/gat_mi355.h has the definition -- and the row's statistics are made from those with local.bin_statistics.  A pseudo-term
+include/gat_mi355.h has the definition -- and the row's statistics are made from those with enrichment.bin_statistics.  A pseudo-term
 of all genes rides along in every call: its words are the null of n = the genes hit at all.  The hypergeometric columns of the
 reference are written beside the sampled ones, so that the bias the sampled null removes can be seen.
 
@@ -23,14 +23,14 @@ import math
 
 import numpy as np
 
+from . import enrichment
 from . import intervals as iv
 from . import problem
-from . import stats
-from .coverage import SAMPLERS, flatten, make_sampler  # noqa: F401  (make_sampler: what scripts/gat-geneset.py builds its sampler with)
-from .distance import build_inputs, contig_lists  # noqa: F401  (build_inputs: the script reads its inputs as gat-distance does)
 from .engine import AnnotatorResult, get_context
-from .local import QVALUE_METHODS, WORDS, bin_statistics  # noqa: F401  (the five words and their arithmetic are gat-local's)
 
+TOOL = "gat-geneset"
+WORDS, QVALUE_METHODS, bin_statistics = enrichment.WORDS, enrichment.QVALUE_METHODS, enrichment.bin_statistics
+flatten, make_sampler, build_inputs = enrichment.flatten, enrichment.make_sampler, enrichment.build_inputs
 MAX_GENES = 262144                        # genes of one call (GAT_GENESET_MAX_GENES)
 HEADER = ("track", "annotation", "genes_in_workspace", "genes_with_annotation", "genes_with_segments",
           "genes_with_annotation_and_segments", "expected", "fold", "pvalue", "qvalue", "stddev", "l2fold", "samples_with_hit",
@@ -199,24 +199,12 @@ def rows(track, terms, term_off, n_genes, observed, words, num_samples, pseudo_c
 
 def set_qvalues(results, method="BH"):
     """q-values over the rows written, per segment track"""
-    if method not in QVALUE_METHODS:
-        raise ValueError("gat-geneset: --qvalue-method=%s is not one of %s (stats.adjustPValues)" % (method, ", ".join(QVALUE_METHODS)))
-    by_track = {}
-    for x in results:
-        by_track.setdefault(x.track, []).append(x)
-    for family in by_track.values():
-        for x, q in zip(family, stats.adjustPValues([x.pvalue for x in family], method=method)):
-            x.qvalue = float(q)
+    enrichment.set_qvalues(results, method, TOOL)
 
 
 def check_options(options):
     """what gat-geneset does not do, refused before anything is read"""
-    if getattr(options, "conditional", "unconditional") != "unconditional":
-        raise NotImplementedError("gat-geneset: only --conditional=unconditional (the samples of a generated workspace are not measured)")
-    if getattr(options, "annotations_to_points", None):
-        raise NotImplementedError("gat-geneset: --annotations-to-points is not supported (a gene is an interval list, not a position)")
-    if getattr(options, "reference_stream", False):
-        raise NotImplementedError("gat-geneset: per-unit streams only, not --reference-stream")
+    enrichment.check_options(options, TOOL, "a gene is an interval list, not a position")
 
 
 def track_geneset(track, segs, ids, genes, terms, term_off, term_genes, workspace, sampler, num_samples, random_seed=None,
@@ -224,23 +212,14 @@ def track_geneset(track, segs, ids, genes, terms, term_off, term_genes, workspac
     """the rows of one segment track: `segs` and `workspace` IntervalDictionaries at isochore level as sample_counts takes
     them; ids / genes from gene_table, terms / term_off / term_genes from term_table.  Returns (rows, the problem's unit count)."""
     from . import _lib
-    if not isinstance(sampler, SAMPLERS):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation and SamplerBruteForce run on the GPU path")
-    num_samples = int(num_samples)
-    if num_samples < 1:
-        raise ValueError("num_samples < 1")
     if len(ids) > MAX_GENES:
         raise ValueError("gat-geneset: %d genes are more than %d" % (len(ids), MAX_GENES))
-    seed = int(np.random.randint(0, 2 ** 32)) if random_seed is None else int(random_seed)
-    flat, sa, wa = flatten(segs, workspace, sampler)
-    contigs = list(flat["contig_names"])
+    num_samples, seed, flat, _, contigs, lists, list_off = enrichment.track_start(segs, workspace, sampler, num_samples, random_seed)
     if not contigs or not terms:
         return [], flat["n_units"]
     G, T = len(ids), len(terms) + 1
     pieces, piece_off, member_off, members = flatten_genes(genes, contigs)
     all_off, all_genes = with_all_genes(term_off, term_genes, G)
-    lists, list_off = contig_lists([problem.from_isochores(sa)], contigs)
     ctx = ctx or get_context()
     observed = ctx.list_geneset_hits(lists, list_off, 1, pieces, piece_off, member_off, members, G, all_off, all_genes, T, len(contigs))[0]
     P = _lib.Problem(ctx, flat)
@@ -257,30 +236,17 @@ def run(segments, annotations, gene_sets, workspace, sampler, num_samples, rando
     collection (gene_table); gene_sets: read_gene_sets' map.  random_seed: base of the per-unit streams (None: drawn from
     numpy's global RandomState); every track takes the next num_samples * n_units streams, as gat.run hands them out.  log: a
     callable that takes a line about the genes dropped and the ids ignored."""
-    if qvalue_method not in QVALUE_METHODS:
-        raise ValueError("gat-geneset: --qvalue-method=%s is not one of %s (stats.adjustPValues)" % (qvalue_method, ", ".join(QVALUE_METHODS)))
-    seed = int(np.random.randint(0, 2 ** 32)) if random_seed is None else int(random_seed)
+    enrichment.check_qvalue_method(qvalue_method, TOOL)
     ids, genes, dropped = gene_table(annotations)
     terms, term_off, term_genes, unknown = term_table(gene_sets, ids)
     if log:
         log("gat-geneset: %d genes in the workspace, %d genes without a base in it dropped" % (len(ids), dropped))
         log("gat-geneset: %d terms, %d gene ids of the map not in the gene file ignored" % (len(terms), unknown))
-    results = []
-    for track in segments.tracks:
-        per, n_units = track_geneset(track, segments[track], ids, genes, terms, term_off, term_genes, workspace, sampler, num_samples,
-                                     seed, pseudo_count, min_term_genes, ctx)
-        seed = (seed + int(num_samples) * int(n_units)) & 0xFFFFFFFF
-        results.extend(per)
-    set_qvalues(results, qvalue_method)
-    return results
+    return enrichment.run_tracks(segments, lambda track, segs, seed: track_geneset(
+        track, segs, ids, genes, terms, term_off, term_genes, workspace, sampler, num_samples, seed, pseudo_count, min_term_genes, ctx),
+        num_samples, random_seed, qvalue_method, TOOL)
 
 
 def write_results(outfile, results, order="track"):
     """the table, rows ordered by --order (ties in the terms' order)"""
-    keys = {"track": lambda x: (x.track, x.position), "annotation": lambda x: (x.position, x.track),
-            "observed": lambda x: x.observed, "fold": lambda x: x.fold, "pvalue": lambda x: x.pvalue, "qvalue": lambda x: x.qvalue}
-    if order not in keys:
-        raise ValueError("unknown sort order %s" % order)
-    outfile.write("\t".join(HEADER) + "\n")
-    for x in sorted(results, key=keys[order]):
-        outfile.write(str(x) + "\n")
+    enrichment.write_results(outfile, results, HEADER, {"track": lambda x: (x.track, x.position), "annotation": lambda x: (x.position, x.track)}, order)

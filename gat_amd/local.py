@@ -23,32 +23,18 @@ import math
 
 import numpy as np
 
+from . import enrichment
 from . import problem
-from . import stats
-from .coverage import SAMPLERS, flatten, make_sampler  # noqa: F401  (make_sampler: what scripts/gat-local.py builds its sampler with)
-from .distance import build_inputs, contig_lists  # noqa: F401  (build_inputs: the script reads its inputs as gat-distance does)
-from .engine import AnnotatorResult, get_context, twoSidedPValueFromCounts
+from .engine import AnnotatorResult, get_context
 
-WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")
+TOOL = "gat-local"
+WORDS, QVALUE_METHODS, bin_statistics = enrichment.WORDS, enrichment.QVALUE_METHODS, enrichment.bin_statistics
+flatten, make_sampler, build_inputs = enrichment.flatten, enrichment.make_sampler, enrichment.build_inputs
 BIN_SIZE = 100000
 MAX_CELLS = 2 ** 27                       # tracks x bins of one call: five int64 words each on the device and on the host
-QVALUE_METHODS = ("BH", "bonferroni", "holm", "hommel", "hochberg", "BY", "none")      # what stats.adjustPValues offers
 HEADER = ("track", "annotation", "contig", "start", "end", "observed", "expected", "stddev", "fold", "l2fold", "pvalue", "qvalue",
           "samples_with_overlap")
 ORDERS = ("track", "annotation", "fold", "pvalue", "qvalue", "observed")
-
-
-def bin_statistics(observed, words, num_samples, pseudo_count=1.0):
-    """(expected, stddev, fold, pvalue) of one (annotation, bin) from its five words over num_samples samples: the numbers
-    AnnotatorResult makes from the row of sample values, without the row.  The radicand of the standard deviation is formed
-    in Python integers: S * sumsq and sum * sum pass 2^64."""
-    n_pos, total, sumsq, n_less, n_eq = (int(w) for w in words)
-    sumsq %= 2 ** 64                          # (the one word that may pass 2^63: it comes in an int64)
-    S, observed = int(num_samples), int(observed)
-    expected = total / S
-    stddev = math.sqrt(S * sumsq - total * total) / S
-    fold = (observed + pseudo_count) / (expected + pseudo_count) if expected != 0 else 1.0
-    return expected, stddev, fold, twoSidedPValueFromCounts(n_less, n_eq, observed > expected, S)
 
 
 class LocalResult(object):
@@ -95,24 +81,12 @@ def rows(track, annotations, contigs, bin_off, bin_size, observed, words, num_sa
 
 def set_qvalues(results, method="BH"):
     """q-values over the rows written, per segment track"""
-    if method not in QVALUE_METHODS:
-        raise ValueError("gat-local: --qvalue-method=%s is not one of %s (stats.adjustPValues)" % (method, ", ".join(QVALUE_METHODS)))
-    by_track = {}
-    for x in results:
-        by_track.setdefault(x.track, []).append(x)
-    for family in by_track.values():
-        for x, q in zip(family, stats.adjustPValues([x.pvalue for x in family], method=method)):
-            x.qvalue = float(q)
+    enrichment.set_qvalues(results, method, TOOL)
 
 
 def check_options(options):
     """what gat-local does not do, refused before anything is read"""
-    if getattr(options, "conditional", "unconditional") != "unconditional":
-        raise NotImplementedError("gat-local: only --conditional=unconditional (the samples of a generated workspace are not measured)")
-    if getattr(options, "annotations_to_points", None):
-        raise NotImplementedError("gat-local: --annotations-to-points is not supported (a position list is not an interval list)")
-    if getattr(options, "reference_stream", False):
-        raise NotImplementedError("gat-local: per-unit streams only, not --reference-stream")
+    enrichment.check_options(options, TOOL)
 
 
 def bins_per_contig(contig_ws, contigs, bin_size):
@@ -130,17 +104,10 @@ def track_local(track, segs, annotations, workspace, sampler, num_samples, bin_s
     """the rows of one segment track: `segs` and `workspace` IntervalDictionaries at isochore level as sample_counts takes
     them, `annotations` the IntervalCollection.  Returns (rows, the problem's unit count)."""
     from . import _lib
-    if not isinstance(sampler, SAMPLERS):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation and SamplerBruteForce run on the GPU path")
-    bin_size, num_samples = int(bin_size), int(num_samples)
+    bin_size = int(bin_size)
     if not 1 <= bin_size <= 2 ** 31:
         raise ValueError("bin_size %d outside [1, 2^31]" % bin_size)
-    if num_samples < 1:
-        raise ValueError("num_samples < 1")
-    seed = int(np.random.randint(0, 2 ** 32)) if random_seed is None else int(random_seed)
-    flat, sa, wa = flatten(segs, workspace, sampler)
-    contigs = list(flat["contig_names"])
+    num_samples, seed, flat, wa, contigs, lists, list_off = enrichment.track_start(segs, workspace, sampler, num_samples, random_seed)
     names = list(annotations.tracks)
     if not contigs or not names:
         return [], flat["n_units"]
@@ -148,8 +115,7 @@ def track_local(track, segs, annotations, workspace, sampler, num_samples, bin_s
     if len(names) * sum(n_bins) > MAX_CELLS:
         raise ValueError("gat-local: %d annotations x %d bins of %d bases are more than 2^27 (annotation, bin) pairs: choose a larger "
                          "--bin-size" % (len(names), sum(n_bins), bin_size))
-    annos, anno_off = contig_lists([problem.from_isochores(annotations[t].asArrays()) for t in names], contigs)
-    lists, list_off = contig_lists([problem.from_isochores(sa)], contigs)
+    annos, anno_off = enrichment.contig_lists([problem.from_isochores(annotations[t].asArrays()) for t in names], contigs)
     ctx = ctx or get_context()
     observed, bin_off = ctx.list_bin_overlaps(lists, list_off, 1, annos, anno_off, len(names), len(contigs), bin_size, n_bins)
     P = _lib.Problem(ctx, flat)
@@ -165,24 +131,11 @@ def run(segments, annotations, workspace, sampler, num_samples, bin_size=BIN_SIZ
     """every segment track against every annotation track, bin by bin: the LocalResults track by track.  random_seed: base of
     the per-unit streams (None: drawn from numpy's global RandomState); every track takes the next num_samples * n_units
     streams, as gat.run hands them out."""
-    if qvalue_method not in QVALUE_METHODS:
-        raise ValueError("gat-local: --qvalue-method=%s is not one of %s (stats.adjustPValues)" % (qvalue_method, ", ".join(QVALUE_METHODS)))
-    seed = int(np.random.randint(0, 2 ** 32)) if random_seed is None else int(random_seed)
-    results = []
-    for track in segments.tracks:
-        per, n_units = track_local(track, segments[track], annotations, workspace, sampler, num_samples, bin_size, seed, pseudo_count, ctx)
-        seed = (seed + int(num_samples) * int(n_units)) & 0xFFFFFFFF
-        results.extend(per)
-    set_qvalues(results, qvalue_method)
-    return results
+    return enrichment.run_tracks(segments, lambda track, segs, seed: track_local(
+        track, segs, annotations, workspace, sampler, num_samples, bin_size, seed, pseudo_count, ctx), num_samples, random_seed, qvalue_method, TOOL)
 
 
 def write_results(outfile, results, order="track"):
     """the table, rows ordered by --order (ties along the genome)"""
-    keys = {"track": lambda x: (x.track, x.annotation, x.position), "annotation": lambda x: (x.annotation, x.track, x.position),
-            "observed": lambda x: x.observed, "fold": lambda x: x.fold, "pvalue": lambda x: x.pvalue, "qvalue": lambda x: x.qvalue}
-    if order not in keys:
-        raise ValueError("unknown sort order %s" % order)
-    outfile.write("\t".join(HEADER) + "\n")
-    for x in sorted(results, key=keys[order]):
-        outfile.write(str(x) + "\n")
+    enrichment.write_results(outfile, results, HEADER, {"track": lambda x: (x.track, x.annotation, x.position),
+                                                        "annotation": lambda x: (x.annotation, x.track, x.position)}, order)

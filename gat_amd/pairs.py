@@ -10,7 +10,7 @@ Here every pair of annotation tracks (i, j), i <= j, gets gat-run's test of the 
 against the same count of every sampled segment list (i == j: the segments that hit the track, CounterSegmentOverlap).  The
 (samples x pairs) matrix is never formed: the null is reduced on the device where the sampler leaves its lists (k_pairs
 behind every batch, gat_sample_pair_enrichment) to five integers per pair -- n_pos, sum, sumsq, n_less, n_eq;
-include/gat_mi355.h has the definition -- and the row's statistics are made from those with local.bin_statistics.  The observed
+include/gat_mi355.h has the definition -- and the row's statistics are made from those with enrichment.bin_statistics.  The observed
 values come from gat_list_pair_hits on the input segments.  Segments and annotations are both taken to contig level
 (problem.from_isochores).  A row is written for every pair i < j that holds an observed or a sampled hit (--include-single:
 the pairs (i, i) too); q-values are over the rows written, per segment track.
@@ -22,13 +22,13 @@ import math
 
 import numpy as np
 
+from . import enrichment
 from . import problem
-from . import stats
-from .coverage import SAMPLERS, flatten, make_sampler  # noqa: F401  (make_sampler: what scripts/gat-pairs.py builds its sampler with)
-from .distance import build_inputs, contig_lists  # noqa: F401  (build_inputs: the script reads its inputs as gat-distance does)
 from .engine import AnnotatorResult, get_context
-from .local import QVALUE_METHODS, WORDS, bin_statistics  # noqa: F401  (the five words and their arithmetic are gat-local's)
 
+TOOL = "gat-pairs"
+WORDS, QVALUE_METHODS, bin_statistics = enrichment.WORDS, enrichment.QVALUE_METHODS, enrichment.bin_statistics
+flatten, make_sampler, build_inputs = enrichment.flatten, enrichment.make_sampler, enrichment.build_inputs
 MAX_TRACKS = 2048                         # annotation tracks of one call (GAT_PAIR_MAX_TRACKS): 2 098 176 pairs
 HEADER = ("track", "annotation_a", "annotation_b", "observed", "expected", "stddev", "fold", "l2fold", "pvalue", "qvalue",
           "samples_with_hit", "observed_a", "observed_b")
@@ -89,24 +89,12 @@ def rows(track, annotations, observed, words, num_samples, pseudo_count=1.0, inc
 
 def set_qvalues(results, method="BH"):
     """q-values over the rows written, per segment track"""
-    if method not in QVALUE_METHODS:
-        raise ValueError("gat-pairs: --qvalue-method=%s is not one of %s (stats.adjustPValues)" % (method, ", ".join(QVALUE_METHODS)))
-    by_track = {}
-    for x in results:
-        by_track.setdefault(x.track, []).append(x)
-    for family in by_track.values():
-        for x, q in zip(family, stats.adjustPValues([x.pvalue for x in family], method=method)):
-            x.qvalue = float(q)
+    enrichment.set_qvalues(results, method, TOOL)
 
 
 def check_options(options):
     """what gat-pairs does not do, refused before anything is read"""
-    if getattr(options, "conditional", "unconditional") != "unconditional":
-        raise NotImplementedError("gat-pairs: only --conditional=unconditional (the samples of a generated workspace are not measured)")
-    if getattr(options, "annotations_to_points", None):
-        raise NotImplementedError("gat-pairs: --annotations-to-points is not supported (a position list is not an interval list)")
-    if getattr(options, "reference_stream", False):
-        raise NotImplementedError("gat-pairs: per-unit streams only, not --reference-stream")
+    enrichment.check_options(options, TOOL)
 
 
 def track_pairs(track, segs, annotations, workspace, sampler, num_samples, random_seed=None, pseudo_count=1.0, include_single=False,
@@ -114,22 +102,13 @@ def track_pairs(track, segs, annotations, workspace, sampler, num_samples, rando
     """the rows of one segment track: `segs` and `workspace` IntervalDictionaries at isochore level as sample_counts takes
     them, `annotations` the IntervalCollection.  Returns (rows, the problem's unit count)."""
     from . import _lib
-    if not isinstance(sampler, SAMPLERS):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation and SamplerBruteForce run on the GPU path")
-    num_samples = int(num_samples)
-    if num_samples < 1:
-        raise ValueError("num_samples < 1")
-    seed = int(np.random.randint(0, 2 ** 32)) if random_seed is None else int(random_seed)
-    flat, sa, wa = flatten(segs, workspace, sampler)
-    contigs = list(flat["contig_names"])
+    num_samples, seed, flat, _, contigs, lists, list_off = enrichment.track_start(segs, workspace, sampler, num_samples, random_seed)
     names = list(annotations.tracks)
     if not contigs or not names:
         return [], flat["n_units"]
     if len(names) > MAX_TRACKS:
         raise ValueError("gat-pairs: %d annotation tracks are more than %d (%d pairs)" % (len(names), MAX_TRACKS, MAX_TRACKS * (MAX_TRACKS + 1) // 2))
-    annos, anno_off = contig_lists([problem.from_isochores(annotations[t].asArrays()) for t in names], contigs)
-    lists, list_off = contig_lists([problem.from_isochores(sa)], contigs)
+    annos, anno_off = enrichment.contig_lists([problem.from_isochores(annotations[t].asArrays()) for t in names], contigs)
     ctx = ctx or get_context()
     observed = ctx.list_pair_hits(lists, list_off, 1, annos, anno_off, len(names), len(contigs))[0]
     P = _lib.Problem(ctx, flat)
@@ -145,25 +124,10 @@ def run(segments, annotations, workspace, sampler, num_samples, random_seed=None
     """every segment track against every pair of annotation tracks: the PairResults track by track.  random_seed: base of
     the per-unit streams (None: drawn from numpy's global RandomState); every track takes the next num_samples * n_units
     streams, as gat.run hands them out."""
-    if qvalue_method not in QVALUE_METHODS:
-        raise ValueError("gat-pairs: --qvalue-method=%s is not one of %s (stats.adjustPValues)" % (qvalue_method, ", ".join(QVALUE_METHODS)))
-    seed = int(np.random.randint(0, 2 ** 32)) if random_seed is None else int(random_seed)
-    results = []
-    for track in segments.tracks:
-        per, n_units = track_pairs(track, segments[track], annotations, workspace, sampler, num_samples, seed, pseudo_count,
-                                   include_single, ctx)
-        seed = (seed + int(num_samples) * int(n_units)) & 0xFFFFFFFF
-        results.extend(per)
-    set_qvalues(results, qvalue_method)
-    return results
+    return enrichment.run_tracks(segments, lambda track, segs, seed: track_pairs(
+        track, segs, annotations, workspace, sampler, num_samples, seed, pseudo_count, include_single, ctx), num_samples, random_seed, qvalue_method, TOOL)
 
 
 def write_results(outfile, results, order="track"):
     """the table, rows ordered by --order (ties in the pairs' order)"""
-    keys = {"track": lambda x: (x.track, x.position), "annotation": lambda x: (x.position, x.track),
-            "observed": lambda x: x.observed, "fold": lambda x: x.fold, "pvalue": lambda x: x.pvalue, "qvalue": lambda x: x.qvalue}
-    if order not in keys:
-        raise ValueError("unknown sort order %s" % order)
-    outfile.write("\t".join(HEADER) + "\n")
-    for x in sorted(results, key=keys[order]):
-        outfile.write(str(x) + "\n")
+    enrichment.write_results(outfile, results, HEADER, {"track": lambda x: (x.track, x.position), "annotation": lambda x: (x.position, x.track)}, order)

@@ -27,12 +27,11 @@ columns are the reference's test on the same counts.  The null is reduced on the
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 import gat_amd as gat  # noqa: E402
-from gat_amd import geneset as Geneset  # noqa: E402
+from gat_amd import enrichment, geneset as Geneset  # noqa: E402
 
 
 def buildParser(usage=None):
@@ -57,40 +56,18 @@ def buildParser(usage=None):
 
 def main(argv=None):
     argv = argv or sys.argv
-    parser = buildParser(usage=__doc__)
-    options, args = parser.parse_args(argv[1:])
+    options, args = buildParser(usage=__doc__).parse_args(argv[1:])
     Geneset.check_options(options)
     if not options.gene_sets:
         raise ValueError("please specify the gene sets (--gene-sets)")
-    tstart = time.time()
-    close_out = False
-    if options.stdout and options.stdout != "-":
-        options.stdout = open(options.stdout, "w")
-        close_out = True
-    else:
-        options.stdout = sys.stdout
-    log = open(options.stdlog, "a") if options.stdlog else options.stdout
-    if options.loglevel >= 1:
-        log.write("# output generated by %s\n# job started at %s\n" % (" ".join(argv), time.asctime()))
-    if options.random_seed is not None:
-        import numpy
-        numpy.random.seed(options.random_seed)
-    gene_sets = Geneset.read_gene_sets(options.gene_sets)
-    segments, annotations, workspace = Geneset.build_inputs(options)
-    sampler = Geneset.make_sampler(options)
-    gat.set_device(options.device)
-    results = Geneset.run(segments, annotations, gene_sets, workspace, sampler, options.num_samples, random_seed=options.random_seed,
-                          pseudo_count=options.pseudo_count, qvalue_method=options.qvalue_method,
-                          min_term_genes=options.min_term_genes,
-                          log=(lambda line: log.write("# %s\n" % line)) if options.loglevel >= 1 else None)
-    Geneset.write_results(options.stdout, results, options.output_order)
-    if options.loglevel >= 1:
-        log.write("# job finished in %i seconds at %s\n" % (time.time() - tstart, time.asctime()))
-    if close_out:
-        options.stdout.close()
-    if options.stdlog:
-        log.close()
-    return 0
+
+    def run(options, log):
+        gene_sets = Geneset.read_gene_sets(options.gene_sets)
+        segments, annotations, workspace, sampler = enrichment.read_inputs(options)
+        return Geneset.run(segments, annotations, gene_sets, workspace, sampler, options.num_samples, random_seed=options.random_seed,
+                           pseudo_count=options.pseudo_count, qvalue_method=options.qvalue_method,
+                           min_term_genes=options.min_term_genes, log=log)
+    return enrichment.main(Geneset, argv, options, run)
 
 
 if __name__ == "__main__":

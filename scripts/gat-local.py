@@ -21,12 +21,11 @@ bin.  The null is reduced on the GPU where the sampler leaves its lists (gat_amd
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 import gat_amd as gat  # noqa: E402
-from gat_amd import local as Local  # noqa: E402
+from gat_amd import enrichment, local as Local  # noqa: E402
 
 
 def buildParser(usage=None):
@@ -43,35 +42,14 @@ def buildParser(usage=None):
 
 def main(argv=None):
     argv = argv or sys.argv
-    parser = buildParser(usage=__doc__)
-    options, args = parser.parse_args(argv[1:])
+    options, args = buildParser(usage=__doc__).parse_args(argv[1:])
     Local.check_options(options)
-    tstart = time.time()
-    close_out = False
-    if options.stdout and options.stdout != "-":
-        options.stdout = open(options.stdout, "w")
-        close_out = True
-    else:
-        options.stdout = sys.stdout
-    log = open(options.stdlog, "a") if options.stdlog else options.stdout
-    if options.loglevel >= 1:
-        log.write("# output generated by %s\n# job started at %s\n" % (" ".join(argv), time.asctime()))
-    if options.random_seed is not None:
-        import numpy
-        numpy.random.seed(options.random_seed)
-    segments, annotations, workspace = Local.build_inputs(options)
-    sampler = Local.make_sampler(options)
-    gat.set_device(options.device)
-    results = Local.run(segments, annotations, workspace, sampler, options.num_samples, bin_size=options.bin_size,
-                        random_seed=options.random_seed, pseudo_count=options.pseudo_count, qvalue_method=options.qvalue_method)
-    Local.write_results(options.stdout, results, options.output_order)
-    if options.loglevel >= 1:
-        log.write("# job finished in %i seconds at %s\n" % (time.time() - tstart, time.asctime()))
-    if close_out:
-        options.stdout.close()
-    if options.stdlog:
-        log.close()
-    return 0
+
+    def run(options, log):
+        segments, annotations, workspace, sampler = enrichment.read_inputs(options)
+        return Local.run(segments, annotations, workspace, sampler, options.num_samples, bin_size=options.bin_size,
+                         random_seed=options.random_seed, pseudo_count=options.pseudo_count, qvalue_method=options.qvalue_method)
+    return enrichment.main(Local, argv, options, run)
 
 
 if __name__ == "__main__":

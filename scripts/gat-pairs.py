@@ -24,12 +24,11 @@ per annotation on its own (annotation_b == annotation_a).  The null is reduced o
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 import gat_amd as gat  # noqa: E402
-from gat_amd import pairs as Pairs  # noqa: E402
+from gat_amd import enrichment, pairs as Pairs  # noqa: E402
 
 
 def buildParser(usage=None):
@@ -47,36 +46,15 @@ def buildParser(usage=None):
 
 def main(argv=None):
     argv = argv or sys.argv
-    parser = buildParser(usage=__doc__)
-    options, args = parser.parse_args(argv[1:])
+    options, args = buildParser(usage=__doc__).parse_args(argv[1:])
     Pairs.check_options(options)
-    tstart = time.time()
-    close_out = False
-    if options.stdout and options.stdout != "-":
-        options.stdout = open(options.stdout, "w")
-        close_out = True
-    else:
-        options.stdout = sys.stdout
-    log = open(options.stdlog, "a") if options.stdlog else options.stdout
-    if options.loglevel >= 1:
-        log.write("# output generated by %s\n# job started at %s\n" % (" ".join(argv), time.asctime()))
-    if options.random_seed is not None:
-        import numpy
-        numpy.random.seed(options.random_seed)
-    segments, annotations, workspace = Pairs.build_inputs(options)
-    sampler = Pairs.make_sampler(options)
-    gat.set_device(options.device)
-    results = Pairs.run(segments, annotations, workspace, sampler, options.num_samples, random_seed=options.random_seed,
-                        pseudo_count=options.pseudo_count, qvalue_method=options.qvalue_method,
-                        include_single=options.include_single)
-    Pairs.write_results(options.stdout, results, options.output_order)
-    if options.loglevel >= 1:
-        log.write("# job finished in %i seconds at %s\n" % (time.time() - tstart, time.asctime()))
-    if close_out:
-        options.stdout.close()
-    if options.stdlog:
-        log.close()
-    return 0
+
+    def run(options, log):
+        segments, annotations, workspace, sampler = enrichment.read_inputs(options)
+        return Pairs.run(segments, annotations, workspace, sampler, options.num_samples, random_seed=options.random_seed,
+                         pseudo_count=options.pseudo_count, qvalue_method=options.qvalue_method,
+                         include_single=options.include_single)
+    return enrichment.main(Pairs, argv, options, run)
 
 
 if __name__ == "__main__":

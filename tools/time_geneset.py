@@ -4,7 +4,7 @@ segment per contig), SamplerAnnotator, against --genes synthetic genes of mixed 
 --terms (a term holds --per-gene * genes / terms genes on average, sizes drawn log-uniformly around that):
 
   (a) the call end to end (wall clock around Problem.sample_geneset_enrichment: the pieces, members, terms and obs up, the
-      sampler, k_geneset_hits and k_geneset_terms behind every batch, k_local_finish, the five words per term down),
+      sampler, k_geneset_hits and k_geneset_terms behind every batch, k_null_finish, the five words per term down),
   (b) gat_stats::ms_sampler of the same call -- the sampler's kernels alone,
   (c) the same call over ONE sample -- the fixed cost of a call, so (a) - (b) - (c) is close to what the two kernels cost over
       the samples,

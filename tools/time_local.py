@@ -4,7 +4,7 @@ segment per contig), SamplerAnnotator, against --tracks synthetic annotation tra
 --bin-size:
 
   (a) the call end to end (wall clock around Problem.sample_bin_enrichment: the windows made on the host, obs up, the sampler,
-      k_local behind every batch, k_local_finish, the five words per (track, bin) down),
+      k_local behind every batch, k_null_finish, the five words per (track, bin) down),
   (b) gat_stats::ms_sampler of the same call -- the sampler's kernels alone,
   (c) the same call over ONE sample -- the fixed cost of a call (windows, obs up, words down), so (a) - (b) - (c) is close to
       what k_local costs over the samples,

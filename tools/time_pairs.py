@@ -3,7 +3,7 @@
 segment per contig), SamplerAnnotator, against synthetic annotation tracks of --intervals intervals each, for every --tracks:
 
   (a) the call end to end (wall clock around Problem.sample_pair_enrichment: the tracks and obs up, the sampler, k_pairs behind
-      every batch, k_local_finish, the five words per pair down),
+      every batch, k_null_finish, the five words per pair down),
   (b) gat_stats::ms_sampler of the same call -- the sampler's kernels alone,
   (c) the same call over ONE sample -- the fixed cost of a call, so (a) - (b) - (c) is close to what k_pairs costs over the
       samples,
