@@ -35,7 +35,7 @@ SYMBOLS = [
     "gat_isochore_split", "gat_comm_library_preloaded", "gat_ctx_set_option", "gat_ctx_get_option", "gat_compare_stats",
     "gat_call_lane_for", "gat_sample_coverage", "gat_list_metrics", "gat_sample_metrics", "gat_list_distances",
     "gat_sample_distances", "gat_minp_counts", "gat_minp_times", "gat_efdr_counts", "gat_efdr_times",
-    "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch",
+    "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch", "gat_sampler_last_launch",
     "gat_list_pair_hits", "gat_sample_pair_enrichment", "gat_list_geneset_hits", "gat_sample_geneset_enrichment",
 ]
 
@@ -73,6 +73,46 @@ class CountReport(C.Structure):
 
     def asdict(self):
         return dict((f, getattr(self, f)) for f, _ in self._fields_)
+
+
+SAMPLER_REPORT_CLASSES = 8    # GAT_SAMPLER_REPORT_CLASSES
+
+
+class SamplerClassReport(C.Structure):
+    """gat_sampler_class_report: what the long-list chain and the split path were launched with for one size class"""
+    _fields_ = [
+        ("first", C.c_int32),
+        ("merge_ccap", C.c_int32),
+        ("merge_buckets", C.c_int32),
+        ("merge_form", C.c_int32),
+        ("consolidate_ccap", C.c_int32),
+    ]
+
+
+class SamplerReport(C.Structure):
+    """gat_sampler_report: what the sampler stage planned for the newest batch of a call (gat_sampler_last_launch)"""
+    _fields_ = [
+        ("huge", C.c_int32),
+        ("split", C.c_int32),
+        ("long_lists", C.c_int32),
+        ("merge_big", C.c_int32),
+        ("tail_big", C.c_int32),
+        ("resume_big", C.c_int32),
+        ("long_queue", C.c_int32),
+        ("resume_virtual", C.c_int32),
+        ("tree", C.c_int32),
+        ("big_buckets", C.c_int32),
+        ("n_long", C.c_int32),
+        ("sampler_variant", C.c_int32),
+        ("n_classes", C.c_int32),
+        ("cls", SamplerClassReport * SAMPLER_REPORT_CLASSES),
+    ]
+
+    def asdict(self):
+        d = dict((f, getattr(self, f)) for f, _ in self._fields_ if f != "cls")
+        d["classes"] = [dict((f, getattr(c, f)) for f, _ in SamplerClassReport._fields_)
+                        for c in self.cls[:min(self.n_classes, SAMPLER_REPORT_CLASSES)]]
+        return d
 
 
 class GatError(RuntimeError):
@@ -254,6 +294,8 @@ def lib():
     L.gat_count_list_ranges.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, vp, i32, vp, i32, vp]
     L.gat_count_last_launch.restype = C.c_int
     L.gat_count_last_launch.argtypes = [vp, C.POINTER(CountReport)]
+    L.gat_sampler_last_launch.restype = C.c_int
+    L.gat_sampler_last_launch.argtypes = [vp, C.POINTER(SamplerReport)]
     L.gat_call_lane_for.restype = C.c_int
     L.gat_call_lane_for.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.gat_intersection_sizes.restype = C.c_int
@@ -511,6 +553,13 @@ class Context(object):
         sample_and_count, or the last list of a count_lists (COUNT_KERNELS / COUNT_ANNO_KERNELS name the kernels)"""
         r = CountReport()
         _check(lib().gat_count_last_launch(self._h, C.byref(r)), self._h)
+        return r.asdict()
+
+    def sampler_report(self):
+        """what the sampler stage planned for the newest batch of this context's last sampling call, as a dict of
+        gat_sampler_report's fields; "classes": one dict per size class of the launch order (the first SAMPLER_REPORT_CLASSES)"""
+        r = SamplerReport()
+        _check(lib().gat_sampler_last_launch(self._h, C.byref(r)), self._h)
         return r.asdict()
 
     def list_bin_overlaps(self, lists, list_off, n_lists, annos, anno_off, n_tracks, n_groups, bin_size, n_bins):

@@ -121,6 +121,7 @@ struct gat_ctx {
                                                 // its kernels and read after the batch's ONE synchronisation
   std::string err;
   gat_count_report count_report = {};           // what launch_count launched last on this context (gat_count_last_launch)
+  gat_sampler_report sampler_report = {};       // what the sampler stage planned for the newest batch (gat_sampler_last_launch)
   int max_lds = 65536;
   // gat_ctx_set_option: the context's own values of the tuning / testing knobs (GAT_*), in front of the process's -- the
   // environment as it was when the library was first asked.  Only read_knobs (gat_knobs.h) and the two option calls touch the

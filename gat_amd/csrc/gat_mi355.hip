@@ -553,6 +553,22 @@ static BatchPlan plan_batch(const gat_ctx* ctx, const Knobs& kn, const gat_probl
   return B;
 }
 
+// The plan as gat_sampler_last_launch reports it: the stages below add what they launch per size class.  No launch reads it.
+static void record_plan(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B) {
+  gat_sampler_report& R = ctx->sampler_report;
+  R = gat_sampler_report();
+  R.sampler_variant = -1;
+  if (sampler_runs_wave_per_unit(P->sampler)) return;      // (one kernel, no stages: nothing of the plan applies)
+  R.huge = B.huge; R.split = B.split; R.long_lists = B.long_lists; R.tree = B.tree;
+  R.merge_big = B.merge_big; R.tail_big = B.tail_big; R.resume_big = B.resume_big; R.long_queue = B.long_queue;
+  R.big_buckets = B.big_buckets; R.n_long = (int32_t)B.n_long;
+  R.n_classes = (int32_t)P->h_class_start.size() - 1;
+  for (int c = 0; c < R.n_classes && c < GAT_SAMPLER_REPORT_CLASSES; ++c) {
+    R.cls[c].first = P->h_class_start[(size_t)c];
+    R.cls[c].merge_form = -1;
+  }
+}
+
 // The wave-per-unit samplers that write the units' final (normalized) lists -- no front end, no split path, no records: what
 // their argument structs share, the grid and the launch.  H comes with the sampler's own tables and lds_cap.
 template <typename Args>
@@ -796,6 +812,10 @@ static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
       lds_k = ((size_t)ccap + (size_t)std::max(ccap, cnbk + gat::kMergeThreads + 1)) * 4;   // (short lists: the 1 024 buckets and their padding need their own words)
     }
     M.a_base = a0; M.a_end = a1; M.lds_cap = ccap; M.big_buckets = cnbk;
+    if (c < GAT_SAMPLER_REPORT_CLASSES) {
+      gat_sampler_class_report& rc_ = ctx->sampler_report.cls[c];
+      rc_.merge_ccap = ccap; rc_.merge_buckets = cnbk; rc_.merge_form = form == 0 ? 0 : 8 * form;
+    }
     hipLaunchKernelGGL(fns[form], grid_yz((unsigned)B.nb, (unsigned)(a1 - a0)), dim3(gat::kMergeThreads), lds_k, call_stream(ctx, P), M);
     HIPCHK(ctx, hipGetLastError());
   }
@@ -819,6 +839,7 @@ static int enqueue_long_lists(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
     // (a reader that takes the segments one by one in any order -- k_count_merged on the units' lists, no contig lists
     //  in between --: the log stays behind the merged list, the trim works on virtual indices)
     const bool virt = TB.loose_ok && !P->merge_contigs && !B.kn.resume_insert;
+    ctx->sampler_report.resume_virtual = virt;
     hipLaunchKernelGGL(virt ? gat::k_resume_big<true> : gat::k_resume_big<false>, grid_yz((unsigned)B.nb, n_long), dim3(64), 0, call_stream(ctx, P), TB);
     HIPCHK(ctx, hipGetLastError());
   }
@@ -869,6 +890,8 @@ static int enqueue_split_path(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
     const int ccap = std::min(std::min(P->h_units[(size_t)P->h_order[(size_t)a0]].slab_cap, T.S.lds_cap), tight);
     gat::TailArgs C = T;
     C.S.a_base = a0; C.S.a_end = a1; C.S.lds_cap = ccap;
+    for (size_t k = c; k + 1 < P->h_class_start.size() && k < GAT_SAMPLER_REPORT_CLASSES && P->h_class_start[k] < a1; ++k)
+      ctx->sampler_report.cls[k].consolidate_ccap = ccap;
     const size_t lds_c = (size_t)(gat::kSortScratchWords + 2 * (size_t)ccap) * 4;
     hipLaunchKernelGGL(consolidate, grid_yz((unsigned)nb, (unsigned)(a1 - a0)), dim3(64), lds_c, call_stream(ctx, P), C);
     HIPCHK(ctx, hipGetLastError());
@@ -914,6 +937,7 @@ static int enqueue_sampler(gat_ctx* ctx, const gat_problem* P, const BatchPlan& 
               : B.huge ? (B.tree ? 7 : 6) : (B.long_lists ? 2 : 0) + (B.tree ? 1 : 0);
   // short lists only (20 waves of this kernel fit a CU's LDS): the instantiation with registers for 5 waves per SIMD
   if (variant == 0 && (int64_t)B.lds * 20 <= ctx->max_lds && !B.kn.no_wpe5) variant = 8;
+  ctx->sampler_report.sampler_variant = variant;
   HIPCHK(ctx, hipFuncSetAttribute((const void*)kSamplerFns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.lds));
   auto launch_sampler = [&](const dim3& gs, size_t lds_, const gat::SamplerArgs& K) {
     hipLaunchKernelGGL(kSamplerFns[variant], gs, dim3(64), lds_, call_stream(ctx, P), K);
@@ -1220,6 +1244,7 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
     if (timed) ctx->k_recorded = ctx->t_recorded = false;     // (the timed call's: another problem's call beside it leaves them)
     P->split_ran = P->patched_contigs = P->patched_counts = false;
     const BatchPlan B = plan_batch(ctx, kn, P, nb, timed, o);
+    record_plan(ctx, P, B);
     if (P->sampler == GAT_SAMPLER_SHIFT) rc = enqueue_shift(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) rc = enqueue_permute(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) rc = enqueue_permute_local(ctx, P, B, seed, begin);
@@ -2709,6 +2734,12 @@ extern "C" int gat_count_lists(gat_ctx* ctx, const int32_t* counter_ids, int n_c
 extern "C" int gat_count_last_launch(const gat_ctx* ctx, gat_count_report* out) {
   if (!ctx || !out) return set_err(nullptr, GAT_ERR_ARG, "gat_count_last_launch: NULL argument");
   *out = ctx->count_report;
+  return GAT_OK;
+}
+
+extern "C" int gat_sampler_last_launch(const gat_ctx* ctx, gat_sampler_report* out) {
+  if (!ctx || !out) return set_err(nullptr, GAT_ERR_ARG, "gat_sampler_last_launch: NULL argument");
+  *out = ctx->sampler_report;
   return GAT_OK;
 }
 

@@ -230,6 +230,38 @@ typedef struct gat_count_report {
 #define GAT_COUNT_ANNO_IDX 1
 #define GAT_COUNT_ANNO_PLAIN 2
 
+/* What the sampler stage planned for the newest batch of a call on a context: the plan's flags, and per size class of the
+ * launch order what the long-list chain and the split path were launched with (SamplerAnnotator / SamplerSegments; the
+ * samplers that run one kernel per unit report sampler_variant -1 and nothing else).  Host bookkeeping for tests and
+ * diagnosis: no launch depends on it, and what the kernels decided per (sample, unit) is in gat_stats.  All zero before the
+ * first batch. */
+#define GAT_SAMPLER_REPORT_CLASSES 8
+typedef struct gat_sampler_class_report {
+  int32_t first;              /* the class's first launch position                                                      */
+  int32_t merge_ccap;         /* k_merge_big: segments its LDS holds for the class, 0: not launched for the class      */
+  int32_t merge_buckets;      /* k_merge_big: the counting sort's buckets at most, 0: not launched                     */
+  int32_t merge_form;         /* k_merge_big: list elements per thread in registers, 8, 16 or 24; 0 the two-pass form; */
+                              /* -1: not launched for the class                                                        */
+  int32_t consolidate_ccap;   /* k_consolidate: segments the LDS of the launch that covers the class holds, 0: none    */
+} gat_sampler_class_report;
+typedef struct gat_sampler_report {
+  int32_t huge;               /* lists beyond LDS: worked on in global memory                                           */
+  int32_t split;              /* the split path ran: k_consolidate, k_tail (, k_finalize) in front of k_sampler          */
+  int32_t long_lists;         /* k_sampler's code for lists beyond the wave's bucket sorts                               */
+  int32_t merge_big;          /* k_merge_big launched over the long units ...                                            */
+  int32_t tail_big;           /* ... k_tail_big behind it ...                                                            */
+  int32_t resume_big;         /* ... k_resume_big behind that ...                                                        */
+  int32_t long_queue;         /* ... and k_sampler working off k_queue_rest's queue                                      */
+  int32_t resume_virtual;     /* k_resume_big<true>: the log left behind the merged list (counts through the merged index) */
+  int32_t tree;               /* the TREE instantiations: some workspace has more segments than the register loop takes  */
+  int32_t big_buckets;        /* no k_merge_big: buckets of k_sampler's own counting sort of lists above 1 024, 0: none  */
+  int32_t n_long;             /* launch positions [0, n_long) are long units                                             */
+  int32_t sampler_variant;    /* k_sampler / k_serial: 0..3 SamplerAnnotator (+1 trees, +2 long lists), 4 / 5            */
+                              /* SamplerSegments, 6 / 7 lists in global memory, 8 variant 0 at five waves per SIMD       */
+  int32_t n_classes;          /* size classes of the launch order (the first GAT_SAMPLER_REPORT_CLASSES are recorded)    */
+  gat_sampler_class_report cls[GAT_SAMPLER_REPORT_CLASSES];
+} gat_sampler_report;
+
 /* ---- context ---------------------------------------------------------------------------- */
 /* device_id: HIP device ordinal.  stream: a hipStream_t to run on (e.g. a torch stream's handle; the default stream is
  * named by hipStreamLegacy, (hipStream_t)1 -- its own handle is NULL) or NULL to create a private non-blocking one. */
@@ -648,6 +680,10 @@ int gat_count_list_ranges(gat_ctx* ctx, const int32_t* counter_ids, int n_counte
 /* Read-only: the record of the context's last count launch (gat_count_report above).  A gat_count_lists call runs on a
  * stream of its own inside the library; its record is copied to the context it was called on. */
 int gat_count_last_launch(const gat_ctx* ctx, gat_count_report* out);
+
+/* Read-only: what the sampler stage planned for the newest batch of the context's last sampling call (gat_sampler_report
+ * above). */
+int gat_sampler_last_launch(const gat_ctx* ctx, gat_sampler_report* out);
 
 /* Sizes of the intersection of two interval dictionaries, for the overlap_* columns of a result row: replaces
  * `overlap = track_segments.clone(); overlap.intersect(annotation_segments); overlap.counts(), overlap.sum()`

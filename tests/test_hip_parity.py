@@ -307,7 +307,8 @@ def test_robustness_paths_vs_oracle(ctx, case, monkeypatch):
         flat = _big_problem(rs, 900, 150)
     elif case in ("large_units", "large_units_swapped_count"):
         flat = _big_problem(rs, 6000, 3)
-    elif case == "very_large_unit":                       # one list of 13 500: beyond k_merge_big's registers (its round-3 form), within LDS
+    elif case == "very_large_unit":                       # 13 500 segments drawn, 11 722 after normalization: one list beyond k_merge_big's
+        #                                                   registers (ccap 12 800 > 12 288: its two-pass form), within LDS (asserted below)
         flat = _big_problem(rs, 13500, 1, n_contigs=1, mean_len=30)
     elif case == "rows_run_out":
         monkeypatch.setitem(ctx.options, "GAT_RNG_SLACK", "0.6")
@@ -329,10 +330,14 @@ def test_robustness_paths_vs_oracle(ctx, case, monkeypatch):
     P = _lib.Problem(ctx, flat)
     got = P.sample_and_count(counters, 99, 3, 3 + S)
     st = P.last_stats
+    planned = ctx.sampler_report()
     for k, c in enumerate(counters):
         assert np.array_equal(got[k], want[k]), (case, c)
     seg, off = P.sample(99, 3, 3 + S)
     assert np.array_equal(off, wsamples[1]) and np.array_equal(seg, wsamples[0])
+    if case == "very_large_unit":
+        assert (planned["long_lists"], planned["merge_big"], planned["huge"], planned["big_buckets"]) == (1, 1, 0, 0), planned
+        assert planned["classes"][0]["merge_form"] == 0 and planned["classes"][0]["merge_ccap"] > 12288, planned
     if case == "rows_run_out":
         # (a stream that runs out of pre-generated rows goes on from the generator moved up to its position; only SamplerSegments
         #  and long lists behind k_tail_big are still run in full)
