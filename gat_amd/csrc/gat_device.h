@@ -733,6 +733,9 @@ __device__ __forceinline__ bool wave_sort_bucket_global(uint2* dst, const uint2*
   return true;
 }
 
+// (-DGAT_CONS_SORT1024_OLD: k_consolidate's sort of 513..1 024 segments before wave_sort_bucket_sparse<16, 1024> took them, kept for
+//  the comparison of the two; no other caller)
+#ifdef GAT_CONS_SORT1024_OLD
 // The same counting sort with the list in registers (E rounds of 64, all loaded in ONE round trip by the caller) instead
 // of three passes over the slab, each a round trip or two of its own: for a kernel lean enough to hold 2 E registers more.
 template <int E>
@@ -779,8 +782,9 @@ __device__ __forceinline__ bool wave_sort_bucket_regs(uint2* dst, const uint2 (&
   wave_sync();
   return true;
 }
+#endif
 
-// k_consolidate's bucket sort for a list of 65..512 segments (its only caller; ONE wave per workgroup): wave_sort_bucket with
+// k_consolidate's bucket sort for a list of 65..1 024 segments (its only caller; ONE wave per workgroup): wave_sort_bucket with
 // what the result does not need taken out.  The list comes from the registers it was loaded into (v: E rounds of 64), every
 // element is written ONCE, to base + its arrival slot -- an element alone in its bucket is final there -- and only the buckets
 // with two or more members are looked at again: the element that arrived first in such a bucket hands (base, count) to a dense
@@ -789,12 +793,21 @@ __device__ __forceinline__ bool wave_sort_bucket_regs(uint2* dst, const uint2 (&
 // buckets (one or two rounds of 64), not E x the wave's largest bucket.  The counters are packed two to a word (an LDS atomic adds
 // 1 or 1 << 16 and returns the slot), so NB = 1 024 buckets fit the 512 words that held 512: a third of the elements of a list of
 // 400 share a bucket instead of half, the largest bucket is ~4 instead of ~6, and a workgroup's LDS does not grow.  After the
-// prefix a bucket's halfword is base | count << 9 (base < 512, count <= 16): one 16-bit read per element gives both.
+// prefix a bucket's halfword is base | count << BB (count <= 16): one 16-bit read per element gives both.  BB = 9 for lists of up
+// to 512 (E <= 8), 10 for lists of up to 1 024 (E = 16): a bucket WITH members has base < n <= 2^BB.  An EMPTY bucket behind the
+// last element has base = n, which is 2^BB for a full list -- one bit into the count's field; the halfword still fits its half
+// (1 024 | 16 << 10 < 2^16) and no element reads an empty bucket's halfword.
 // Returns false, seg untouched, where wave_sort_bucket does (all starts equal, a bucket beyond 16): the caller takes the network.
+// E = 16 (lists of 513..1 024, still 1 024 buckets: about one element per bucket where the shorter lists have one in two or
+// three).  A bucket of five or more members --
+// one or two per list here, one list in ten there -- still takes the insertion loop: ordering up to eight in registers (an
+// odd-even transposition, 28 exchanges) measured the same and is not kept.
 template <int E, int NB, int EV>
 __device__ __forceinline__ bool wave_sort_bucket_sparse(uint2* seg, const uint2 (&v)[EV], int n, uint32_t* scratch, int lane) {
-  static_assert(E <= EV && E * kWave <= 512 && NB % (8 * kWave) == 0 && NB / 2 <= 512, "base in 9 bits, the packed counters in 512 words");
+  static_assert(E <= EV && E * kWave <= 1024 && NB % (8 * kWave) == 0 && NB / 2 <= 512, "base in 9 or 10 bits, the packed counters in 512 words");
   constexpr int Q = NB / 2 / kWave / 4;                           // 16-byte pieces of the packed histogram per lane
+  constexpr int BB = E * kWave <= 512 ? 9 : 10;                   // bits of a bucket's base in its halfword (the count: the 5 above them)
+  constexpr uint32_t BMASK = (1u << BB) - 1u;
   uint32_t lo = 0xffffffffu, hi = 0u;
 #pragma unroll
   for (int r = 0; r < E; ++r)
@@ -811,13 +824,25 @@ __device__ __forceinline__ bool wave_sort_bucket_sparse(uint2* seg, const uint2 
 #pragma unroll
   for (int q = 0; q < Q; ++q) hist4[q * kWave + lane] = make_uint4(0u, 0u, 0u, 0u);
   wave_sync();
-  uint32_t aux[E];                                               // the arrival slot, then what a bucket's first arrival hands on
+  // the arrival slot, then what a bucket's first arrival hands on: 15 bits either -- sixteen rounds keep two to a register (AP),
+  // or list (32 registers), slots and the prefix's words together do not fit the 64 registers of eight waves per SIMD
+  constexpr int AP = E > 8 ? 2 : 1;
+  uint32_t aux[E / AP];
 #pragma unroll
   for (int r = 0; r < E; ++r) {
-    aux[r] = 0;
-    if (r * kWave + lane < n) {
-      const uint32_t d = v[r].x - lo, bk = direct ? d : __umulhi(d, scale), sh = (bk & 1u) << 4;
-      aux[r] = (atomicAdd(&scratch[bk >> 1], 1u << sh) >> sh) & 0xffffu;
+    if constexpr (AP == 1) {
+      aux[r] = 0;
+      if (r * kWave + lane < n) {
+        const uint32_t d = v[r].x - lo, bk = direct ? d : __umulhi(d, scale), sh = (bk & 1u) << 4;
+        aux[r] = (atomicAdd(&scratch[bk >> 1], 1u << sh) >> sh) & 0xffffu;
+      }
+    } else {
+      uint32_t slot = 0;
+      if (r * kWave + lane < n) {
+        const uint32_t d = v[r].x - lo, bk = direct ? d : __umulhi(d, scale), sh = (bk & 1u) << 4;
+        slot = (atomicAdd(&scratch[bk >> 1], 1u << sh) >> sh) & 0xffffu;
+      }
+      aux[r / 2] = (r & 1) ? aux[r / 2] | (slot << 16) : slot;
     }
   }
   wave_sync();
@@ -833,12 +858,21 @@ __device__ __forceinline__ bool wave_sort_bucket_sparse(uint2* seg, const uint2 
   const uint32_t sum = (acc & 0xffffu) + (acc >> 16);
   uint32_t run = wave_incl_sum_u32(sum, lane) - sum;
   if (__ballot((over & 0x80008000u) != 0u) != 0ull) return false;
+  if constexpr (AP > 1) {
+    // (sixteen rounds: the words are read again instead of held across the scan -- eight registers at the kernel's fullest point)
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const uint4 x = hist4[lane * Q + q];
+      w[4 * q] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w;
+    }
+  }
 #pragma unroll
   for (int q = 0; q < 4 * Q; ++q) {
     const uint32_t c0 = w[q] & 0xffffu, c1 = w[q] >> 16;
-    uint32_t o = run | (c0 << 9);
+    uint32_t o = run | (c0 << BB);
     run += c0;
-    o |= (run | (c1 << 9)) << 16;
+    o |= (run | (c1 << BB)) << 16;
     run += c1;
     w[q] = o;
   }
@@ -850,24 +884,32 @@ __device__ __forceinline__ bool wave_sort_bucket_sparse(uint2* seg, const uint2 
   for (int r = 0; r < E; ++r) {
     if (r * kWave + lane < n) {
       const uint32_t d = v[r].x - lo, bk = direct ? d : __umulhi(d, scale);
-      const uint32_t h = hist16[bk], slot = aux[r];
-      seg[(h & 511u) + slot] = v[r];
-      aux[r] = (slot == 0u && h >= (2u << 9)) ? h : 0u;          // first arrival of a bucket of two or more
+      if constexpr (AP == 1) {
+        const uint32_t h = hist16[bk], slot = aux[r];
+        seg[(h & BMASK) + slot] = v[r];
+        aux[r] = (slot == 0u && h >= (2u << BB)) ? h : 0u;       // first arrival of a bucket of two or more
+      } else {
+        const uint32_t h = hist16[bk], slot = (r & 1) ? aux[r / 2] >> 16 : aux[r / 2] & 0xffffu;
+        seg[(h & BMASK) + slot] = v[r];
+        const uint32_t first = (slot == 0u && h >= (2u << BB)) ? h : 0u;
+        aux[r / 2] = (r & 1) ? (aux[r / 2] & 0xffffu) | (first << 16) : (aux[r / 2] & 0xffff0000u) | first;
+      }
     }
   }
   wave_sync();                                                   // (the histogram has been read: its words take the list)
   int nl = 0;
 #pragma unroll
   for (int r = 0; r < E; ++r) {
-    const uint64_t b = __ballot(aux[r] != 0u);
-    if (aux[r] != 0u) scratch[nl + __popcll(b & lanemask_lt(lane))] = aux[r];
+    const uint32_t first = AP == 1 ? aux[r / AP] : ((r & 1) ? aux[r / AP] >> 16 : aux[r / AP] & 0xffffu);
+    const uint64_t b = __ballot(first != 0u);
+    if (first != 0u) scratch[nl + __popcll(b & lanemask_lt(lane))] = first;
     nl += __popcll(b);
   }
   wave_sync();
   for (int t0 = 0; t0 < nl; t0 += kWave) {                        // (wave-uniform: one or two rounds)
     const uint32_t h = t0 + lane < nl ? scratch[t0 + lane] : 0u;
-    const int s0 = (int)(h & 511u), cnt = (int)(h >> 9);
-    if (cnt > 4) {                                                // rare (one list in ten has such a bucket): insertion in place
+    const int s0 = (int)(h & BMASK), cnt = (int)(h >> BB);
+    if (cnt > 4) {                                                // rare (one list in ten has such a bucket; E = 16: one or two a list): insertion in place
       for (int i = s0 + 1; i < s0 + cnt; ++i) {
         const uint2 x = seg[i];
         int j = i - 1;

@@ -874,8 +874,11 @@ static int enqueue_split_path(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
   T.todo = P->d_todo.p;
   T.todo_count = P->todo_count_dev();                         // (zeroed with the statistics at the batch's start)
   const size_t lds_max = (size_t)(gat::kSortScratchWords + 2 * (size_t)T.S.lds_cap) * 4;
+  // (two kernels: classes whose lists end at 512 segments run the one without the branches -- and registers -- of longer lists)
   void (*const consolidate)(gat::TailArgs) = B.tree ? gat::k_consolidate<true> : gat::k_consolidate<false>;
+  void (*const consolidate_long)(gat::TailArgs) = B.tree ? gat::k_consolidate_long<true> : gat::k_consolidate_long<false>;
   HIPCHK(ctx, hipFuncSetAttribute((const void*)consolidate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)consolidate_long, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
   // (a call of a few hundred tiles does not fill the chip whatever the LDS of a workgroup: one launch for all classes,
   //  each launch less is a tail less -- config 2 at 1 250 samples: k_consolidate 0.121 -> 0.101 ms)
   const bool one_class = (int64_t)((nb + 63) / 64) * (int64_t)B.n_act <= 1024 && !B.kn.size_classes_set;
@@ -893,7 +896,7 @@ static int enqueue_split_path(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, 
     for (size_t k = c; k + 1 < P->h_class_start.size() && k < GAT_SAMPLER_REPORT_CLASSES && P->h_class_start[k] < a1; ++k)
       ctx->sampler_report.cls[k].consolidate_ccap = ccap;
     const size_t lds_c = (size_t)(gat::kSortScratchWords + 2 * (size_t)ccap) * 4;
-    hipLaunchKernelGGL(consolidate, grid_yz((unsigned)nb, (unsigned)(a1 - a0)), dim3(64), lds_c, call_stream(ctx, P), C);
+    hipLaunchKernelGGL(ccap > 512 ? consolidate_long : consolidate, grid_yz((unsigned)nb, (unsigned)(a1 - a0)), dim3(64), lds_c, call_stream(ctx, P), C);
     HIPCHK(ctx, hipGetLastError());
   }
   if (B.timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k[2], call_stream(ctx, P)));

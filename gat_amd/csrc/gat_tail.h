@@ -76,8 +76,11 @@ struct TailArgs {
 
 // ------------------------------------------------------------------------------------------------------------------
 // k_consolidate: sort + merge(0) + coverage of what k_place placed (gat/Engine.pyx:582-606, first time round).
-template <bool TREE>
-__global__ __launch_bounds__(64) void k_consolidate(TailArgs T) {
+// Two kernels over one body: k_consolidate for the size classes whose lists end at 512 segments (LONG = false: the branches for
+// longer lists are not compiled in, registers and code are what the classes of short lists need), k_consolidate_long for the
+// classes beyond (every branch: such a class holds short lists too).  The host picks by the class's ccap (enqueue_split_path).
+template <bool TREE, bool LONG>
+__device__ __forceinline__ void consolidate_unit(const TailArgs& T) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const SamplerArgs& A = T.S;
   const int lane = threadIdx.x;
@@ -93,6 +96,7 @@ __global__ __launch_bounds__(64) void k_consolidate(TailArgs T) {
   else if (lane == 0) A.st2[sa] = make_int4(0, 0, 0, 0);
   const int n = pre.x;
   if (pre.z < 0 || n <= 0 || n > A.lds_cap) return;               // not handed over by k_place / beyond this kernel's LDS: k_sampler's
+  if (!LONG && n > 512) return;                                   // (never: this kernel is launched with lds_cap <= 512)
 #ifdef GAT_DIAG_CONS
   // (tools/diag_consolidate.sh: cycles of a unit per phase -- 0 record + workspace, 1 list in registers, 2 sort, 3 merge(0),
   //  4 coverage + write-back; the stamps fence the schedule: shares, not a timing)
@@ -168,18 +172,26 @@ __global__ __launch_bounds__(64) void k_consolidate(TailArgs T) {
 #endif
     return;
   }
-  if (n > 1024) {
+  if (LONG && n > 1024) {
     if (!wave_sort_bucket_global(seg, out, n, scratch, 512, lane)) {
       for (int i = lane; i < n; i += kWave) seg[i] = out[i];
       wave_sort_auto(seg, n, lane);
     }
-  } else if (n > 512) {
-    // 513..1 024 segments: the counting sort with the list in registers (one round trip instead of the six of the three
-    // passes over the slab; this kernel has the registers: the old k_sampler did not)
+  } else if (LONG && n > 512) {
+    // 513..1 024 segments: the list in registers in one round trip, then the sort of the shorter lists at sixteen rounds and
+    // a 10-bit base (wave_sort_bucket_sparse: written once, only the collided buckets looked at again).
+    // -DGAT_CONS_SORT1024_OLD: the counting sort these lists had before (512 buckets, two passes of atomics, a lane walking
+    // every bucket), for the comparison; a crowded list leaves it at 48 a bucket, the new one at 16 -- the network either way
     uint2 v[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { const int i = r * kWave + lane; v[r] = i < n ? out[i] : make_uint2(0u, 0u); }
-    if (!wave_sort_bucket_regs<16>(seg, v, n, scratch, 512, lane)) {
+    GAT_CPHASE(1)
+#ifdef GAT_CONS_SORT1024_OLD
+    const bool sorted = wave_sort_bucket_regs<16>(seg, v, n, scratch, 512, lane);
+#else
+    const bool sorted = wave_sort_bucket_sparse<16, 1024>(seg, v, n, scratch, lane);
+#endif
+    if (!sorted) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) { const int i = r * kWave + lane; if (i < n) seg[i] = v[r]; }
       wave_sort_auto(seg, n, lane);
@@ -238,6 +250,13 @@ __global__ __launch_bounds__(64) void k_consolidate(TailArgs T) {
 #undef GAT_CPHASE
 #undef GAT_CSTAMP
 }
+template <bool TREE>
+__global__ __launch_bounds__(64) void k_consolidate(TailArgs T) { consolidate_unit<TREE, false>(T); }
+// (the sixteen rounds of the 513..1 024 sort, scheduled for themselves, take 231 registers -- two waves per SIMD.  Six waves
+//  per SIMD is the bound; the 70 / 72 registers it compiles to fit seven, and a class of such lists holds no more by its LDS:
+//  528 scratch words + 8 bytes a segment is 25 workgroups a CU at a ccap of 544, 17 at config 2's 928)
+template <bool TREE>
+__global__ __launch_bounds__(64, 6) void k_consolidate_long(TailArgs T) { consolidate_unit<TREE, true>(T); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // k_tail: the loop of gat/Engine.pyx:572-635 from behind the first consolidation to its end, one stream per lane.
