@@ -37,6 +37,7 @@ SYMBOLS = [
     "gat_sample_distances", "gat_minp_counts", "gat_minp_times", "gat_efdr_counts", "gat_efdr_times",
     "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch", "gat_sampler_last_launch",
     "gat_list_pair_hits", "gat_sample_pair_enrichment", "gat_list_geneset_hits", "gat_sample_geneset_enrichment",
+    "gat_list_profile", "gat_sample_profile_enrichment",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -288,6 +289,10 @@ def lib():
     L.gat_list_geneset_hits.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp]
     L.gat_sample_geneset_enrichment.restype = C.c_int
     L.gat_sample_geneset_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, C.POINTER(Stats)]
+    L.gat_list_profile.restype = C.c_int
+    L.gat_list_profile.argtypes = [vp, vp, vp, i64, vp, vp, vp, i32, i32, i64, i32, C.c_int, vp]
+    L.gat_sample_profile_enrichment.restype = C.c_int
+    L.gat_sample_profile_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, vp, i32, i64, i32, C.c_int, vp, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -613,10 +618,44 @@ class Context(object):
                                            _p(g[4]), _p(g[5]), n_terms, n_groups, _p(out)), self._h)
         return out
 
+    def list_profile(self, lists, list_off, n_lists, anchor_pos, anchor_minus, anchor_off, n_tracks, n_groups, bin_size, half_bins,
+                     mode=0):
+        """the profile of every one of n_lists x n_groups caller-provided normalized lists -- list l of group g is
+        lists[list_off[l * n_groups + g]:list_off[l * n_groups + g + 1]] -- around the anchors of n_tracks tracks, track t of
+        group g at anchor_pos / anchor_minus[anchor_off[t * n_groups + g]:anchor_off[t * n_groups + g + 1]], in 2 * half_bins
+        offset bins of bin_size bases (gat_list_profile; mode: PROFILE_BASES or PROFILE_MIDPOINTS).  Returns int64
+        [n_lists, n_tracks, 2 * half_bins]."""
+        lists = np.ascontiguousarray(lists, dtype=SEG)
+        list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+        n_lists, n_tracks, n_groups = int(n_lists), int(n_tracks), int(n_groups)
+        assert len(list_off) == n_lists * n_groups + 1
+        pos, minus, anchor_off = _profile_arrays(anchor_pos, anchor_minus, anchor_off, n_tracks, n_groups)
+        out = np.zeros((n_lists, n_tracks, profile_bins(half_bins)), dtype=np.int64)
+        _check(lib().gat_list_profile(self._h, _p(lists), _p(list_off), n_lists, _p(pos), _p(minus), _p(anchor_off), n_tracks, n_groups,
+                                      int(bin_size), int(half_bins), int(mode), _p(out)), self._h)
+        return out
+
 
 NULL_WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")      # the sampled null of one cell against obs: include/gat_mi355.h
-LOCAL_WORDS = PAIR_WORDS = GENESET_WORDS = NULL_WORDS     # GAT_LOCAL_WORDS, GAT_PAIR_WORDS, GAT_GENESET_WORDS
+# GAT_LOCAL_WORDS, GAT_PAIR_WORDS, GAT_GENESET_WORDS, GAT_PROFILE_WORDS
+LOCAL_WORDS = PAIR_WORDS = GENESET_WORDS = PROFILE_WORDS = NULL_WORDS
 PAIR_MAX_TRACKS = 2048        # GAT_PAIR_MAX_TRACKS
+PROFILE_MAX_BINS = 1024       # GAT_PROFILE_MAX_BINS
+PROFILE_BASES, PROFILE_MIDPOINTS = 0, 1       # GAT_PROFILE_BASES, GAT_PROFILE_MIDPOINTS
+
+
+def profile_bins(half_bins):
+    """the bins of a profile (0 where half_bins is out of range: the library refuses the call)"""
+    return 2 * int(half_bins) if 1 <= int(half_bins) <= PROFILE_MAX_BINS // 2 else 0
+
+
+def _profile_arrays(anchor_pos, anchor_minus, anchor_off, n_tracks, n_groups):
+    """the anchor arguments of the two profile calls as the library takes them"""
+    pos = np.ascontiguousarray(anchor_pos, dtype=np.uint32)
+    minus = np.ascontiguousarray(anchor_minus, dtype=np.uint8)
+    anchor_off = np.ascontiguousarray(anchor_off, dtype=np.int64)
+    assert len(anchor_off) == max(0, n_tracks) * max(0, n_groups) + 1 and len(pos) == len(minus)
+    return pos, minus, anchor_off
 
 
 def pair_count(n_tracks):
@@ -1084,3 +1123,17 @@ class Problem(object):
         assert obs.shape == (max(0, n_terms),)
         return self._sample_null_words(lib().gat_sample_geneset_enrichment, seed, sample_begin, sample_end,
                                        (_p(g[0]), _p(g[1]), _p(g[2]), _p(g[3]), n_genes, _p(g[4]), _p(g[5]), n_terms), obs, (max(0, n_terms),))
+
+    def sample_profile_enrichment(self, seed, sample_begin, sample_end, anchor_pos, anchor_minus, anchor_off, n_tracks, bin_size,
+                                  half_bins, mode, obs):
+        """per (track, offset bin) the five sums (PROFILE_WORDS; gat_sample_profile_enrichment) over the sampled contig-level
+        lists of [sample_begin, sample_end) of v = the bases (mode PROFILE_BASES) or segment midpoints (PROFILE_MIDPOINTS) of
+        a list in the bin around the track's anchors, against obs[track, bin] -- the anchors as in Context.list_profile, the
+        groups the problem's contigs in the problem's order.  Returns int64 [n_tracks, 2 * half_bins, 5]."""
+        n_tracks = int(n_tracks)
+        pos, minus, anchor_off = _profile_arrays(anchor_pos, anchor_minus, anchor_off, n_tracks, self.n_contigs)
+        cells = (max(0, n_tracks), profile_bins(half_bins))
+        obs = np.ascontiguousarray(obs, dtype=np.int64)
+        assert obs.shape == cells
+        return self._sample_null_words(lib().gat_sample_profile_enrichment, seed, sample_begin, sample_end,
+                                       (_p(pos), _p(minus), _p(anchor_off), n_tracks, int(bin_size), int(half_bins), int(mode)), obs, cells)

@@ -42,6 +42,7 @@
 #include "gat_local.h"
 #include "gat_pairs.h"
 #include "gat_geneset.h"
+#include "gat_profile.h"
 
 
 #include "gat_host.h"
@@ -1668,9 +1669,9 @@ extern "C" void gat_mt19937_seed(uint32_t seed, uint32_t* mt_state) {
 }
 
 // ---- the entry points that read the sampled lists where they are: gat_sample / gat_sample_units copy them out, and
-// gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_bin_enrichment, gat_sample_pair_enrichment and
-// gat_sample_geneset_enrichment put a kernel (gat_coverage.h, gat_metrics.h, gat_distance.h, gat_local.h, gat_pairs.h,
-// gat_geneset.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
+// gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_bin_enrichment, gat_sample_pair_enrichment,
+// gat_sample_geneset_enrichment and gat_sample_profile_enrichment put a kernel (gat_coverage.h, gat_metrics.h, gat_distance.h,
+// gat_local.h, gat_pairs.h, gat_geneset.h, gat_profile.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
 
 // A synchronous call's frame: refused while a call is in flight on the problem (P == nullptr: a call over the caller's own
 // lists); the knobs are read once; body(kn, local) does the work.  Whatever the body returns, the stream is drained behind it:
@@ -1774,7 +1775,7 @@ static int launch_store_or_fold(gat_ctx* ctx, bool store, void (*k_store)(Args),
 }
 
 // ---- the fold of the sampled null to five words per cell (gat_null_words.h), as gat_sample_bin_enrichment,
-// gat_sample_pair_enrichment and gat_sample_geneset_enrichment share it: obs up and the words zeroed before the first batch,
+// gat_sample_pair_enrichment, gat_sample_geneset_enrichment and gat_sample_profile_enrichment share it: obs up and the words zeroed before the first batch,
 // k_null_finish and the words down behind the last
 struct NullWordsOut {
   DevBuf<long long> d_obs;
@@ -2621,6 +2622,184 @@ extern "C" int gat_sample_geneset_enrichment(gat_ctx* ctx, gat_problem* P, uint3
   GenesetBufs B;
   return null_words_frame(ctx, P, stats, n_terms, S, out_host, [&](const Knobs& kn, gat_stats& local) {
     return sample_geneset_enrichment_body(ctx, P, kn, seed, sample_begin, S, in, obs_host, out_host, local, B);
+  });
+}
+
+// gat_list_profile / gat_sample_profile_enrichment: k_profile (gat_profile.h) over caller-provided lists, or behind every batch.
+// The anchors go up once per call (positions, strands, offsets from anchor_off[0]); the device buffers live for the call.
+struct ProfileIn {
+  const uint32_t* pos; const uint8_t* minus; const int64_t* off;
+  int32_t n_tracks; int64_t bin_size; int32_t half_bins; int mode;
+};
+struct ProfileBufs {
+  DevBuf<uint32_t> d_pos;
+  DevBuf<uint8_t> d_minus;
+  DevBuf<int64_t> d_off, d_csr;
+  DevBuf<uint2> d_seg;
+  NullWordsOut out;
+  int64_t longest = 0;        // the most anchors of a (track, group)
+};
+static const char* const kProfileWhy = "a base counts once per anchor: the profile is formed from disjoint segments";
+// what both entry points ask of the bins and the anchors; most_bases: the largest K_t * bin_size of a track, what a value can reach
+static int profile_check_common(gat_ctx* ctx, const char* who, const ProfileIn& in, int64_t n_groups, int64_t& most_bases) {
+  if (in.bin_size < 1 || in.bin_size > (int64_t)1 << 31) return set_err(ctx, GAT_ERR_ARG, "%s: bin_size %lld outside [1, 2^31]", who, (long long)in.bin_size);
+  if (in.half_bins < 1 || 2 * (int64_t)in.half_bins > GAT_PROFILE_MAX_BINS)
+    return set_err(ctx, GAT_ERR_ARG, "%s: half_bins %d outside [1, %d]", who, in.half_bins, GAT_PROFILE_MAX_BINS / 2);
+  if (in.half_bins * in.bin_size > (int64_t)1 << 31)
+    return set_err(ctx, GAT_ERR_ARG, "%s: half_bins * bin_size = %d * %lld is more than 2^31", who, in.half_bins, (long long)in.bin_size);
+  if (in.mode != GAT_PROFILE_BASES && in.mode != GAT_PROFILE_MIDPOINTS)
+    return set_err(ctx, GAT_ERR_ARG, "%s: mode %d is neither GAT_PROFILE_BASES nor GAT_PROFILE_MIDPOINTS", who, in.mode);
+  if (in.n_tracks < 0 || (int64_t)in.n_tracks * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+    return set_err(ctx, GAT_ERR_ARG, "%s: n_tracks %d", who, in.n_tracks);
+  const int64_t n = (int64_t)in.n_tracks * n_groups;
+  int rc;
+  if ((rc = check_list_offsets(ctx, who, "anchor_off", "anchors", in.off, n))) return rc;
+  if (in.off[n] > in.off[0] && (!in.pos || !in.minus)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  most_bases = 0;
+  for (int64_t t = 0; t < in.n_tracks; ++t) {
+    for (int64_t g = 0; g < n_groups; ++g) {
+      const int64_t b = in.off[t * n_groups + g], e = in.off[t * n_groups + g + 1];
+      for (int64_t k = b; k < e; ++k) {
+        if (in.minus[k] > 1)
+          return set_err(ctx, GAT_ERR_ARG, "%s: anchor track %lld, group %lld: anchor_minus %d at anchor %lld is neither 0 nor 1", who,
+                         (long long)t, (long long)g, (int)in.minus[k], (long long)(k - b));
+        if (k == b) continue;
+        const int64_t before = (int64_t)in.pos[k - 1] * 2 + in.minus[k - 1], here = (int64_t)in.pos[k] * 2 + in.minus[k];
+        if (here == before)
+          return set_err(ctx, GAT_ERR_ARG, "%s: anchor track %lld, group %lld repeats an anchor (position, strand) at anchor %lld", who,
+                         (long long)t, (long long)g, (long long)(k - b));
+        if (here < before)
+          return set_err(ctx, GAT_ERR_ARG, "%s: anchor track %lld, group %lld is out of order at anchor %lld (ascending by position, "
+                         "plus before minus at one position)", who, (long long)t, (long long)g, (long long)(k - b));
+      }
+    }
+    most_bases = std::max<int64_t>(most_bases, (in.off[(t + 1) * n_groups] - in.off[t * n_groups]) * in.bin_size);
+  }
+  return GAT_OK;
+}
+// K_t * bin_size of every track below 2^32 -- a value is a 32-bit word on the device -- and its square times S below 2^64
+static int profile_check_words(gat_ctx* ctx, const char* who, int64_t most_bases, int64_t S, const int64_t* obs_host, int64_t cells) {
+  if (most_bases >= (int64_t)1 << 32)
+    return set_err(ctx, GAT_ERR_ARG, "%s: anchors * bin_size = %lld of a track does not fit 32 bits: fewer anchors per track or a smaller bin_size",
+                   who, (long long)most_bases);
+  return check_null_words(ctx, who, "anchors * bin_size", most_bases, "fewer anchors per track, a smaller bin_size or fewer samples per call",
+                          S, obs_host, cells);
+}
+static int profile_upload(gat_ctx* ctx, const ProfileIn& in, int64_t n_groups, ProfileBufs& B) {
+  const int64_t n = (int64_t)in.n_tracks * n_groups, base = in.off[0], total = in.off[n] - base;
+  std::vector<int64_t> h_off((size_t)n + 1);
+  B.longest = 0;
+  for (int64_t l = 0; l <= n; ++l) {
+    h_off[(size_t)l] = in.off[l] - base;
+    if (l) B.longest = std::max(B.longest, in.off[l] - in.off[l - 1]);
+  }
+  HIPCHK(ctx, B.d_pos.alloc((size_t)total));
+  HIPCHK(ctx, B.d_minus.alloc((size_t)total));
+  if (total > 0) {
+    HIPCHK(ctx, staged_h2d(ctx, B.d_pos.p, in.pos + base, (size_t)total * 4));
+    HIPCHK(ctx, staged_h2d(ctx, B.d_minus.p, in.minus + base, (size_t)total));
+  }
+  HIPCHK(ctx, B.d_off.upload(h_off, ctx));
+  HIPCHK(ctx, stage_flush(ctx));                    // (h_off goes away with this frame)
+  return GAT_OK;
+}
+// one launch over tracks x runs of n_lists lists; store: the raw values per list, else the fold into B.out's five words
+static int launch_profile(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists, int64_t n_lists, int32_t n_groups, const ProfileIn& in,
+                          bool store, const ProfileBufs& B) {
+  if (n_lists == 0 || in.n_tracks == 0 || n_groups == 0 || B.longest == 0) return GAT_OK;
+  gat::ProfileArgs A;
+  memset(&A, 0, sizeof(A));
+  const int64_t bins = 2 * (int64_t)in.half_bins;
+  const int64_t L = gat::profile_lds_anchors(std::max<int64_t>(0, kn.profile_lds_anchors), B.longest, ctx->max_lds, bins, n_groups);
+  A.lists = lists;
+  A.n_lists = (int32_t)n_lists;
+  A.n_groups = n_groups;
+  A.n_tracks = in.n_tracks;
+  A.bins = (int32_t)bins;
+  A.lds_anchors = (int32_t)L;
+  A.midpoints = in.mode == GAT_PROFILE_MIDPOINTS ? 1 : 0;
+  A.bin_size = in.bin_size;
+  A.reach = in.half_bins * in.bin_size;
+  A.pos = B.d_pos.p;
+  A.minus = B.d_minus.p;
+  A.anchor_off = B.d_off.p;
+  A.obs = B.out.d_obs.p;
+  A.out = B.out.d_out.p;
+  // the run: the knob's where it is set, else as long as leaves 8 192 workgroups -- four rounds of the eight a compute unit holds at
+  // 100 bins: the lists of a run are not equally long, and runs of 4 and 16 were measured faster than runs of 49 and 64 there
+  // (profiles/r22_profile.txt) -- but at least 8 lists: a workgroup's fixed cost is the flush of its bins; and a list for every
+  // wave in every round: a run of 10 is three rounds for two of the four waves and two for the others, measured 1.17 x a run of 16
+  const int64_t lpb = kn.profile_samples_per_block > 0
+                          ? gat::run_per_block(n_lists, in.n_tracks, 0, kn.profile_samples_per_block)
+                          : (gat::run_per_block(n_lists, in.n_tracks, 8192, gat::kNoRunCap) + gat::kProfileWaves - 1) / gat::kProfileWaves * gat::kProfileWaves;
+  A.lists_per_block = (int32_t)lpb;
+  const size_t lds = (size_t)gat::profile_lds_bytes(bins, L, n_groups, store);
+  const dim3 grid((unsigned)in.n_tracks, (unsigned)((n_lists + lpb - 1) / lpb));
+  return launch_store_or_fold(ctx, store, gat::k_profile<true>, gat::k_profile<false>, grid, gat::kProfileThreads, lds, A);
+}
+
+extern "C" int gat_list_profile(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                                const uint32_t* anchor_pos, const uint8_t* anchor_minus, const int64_t* anchor_off,
+                                int32_t n_tracks, int32_t n_groups, int64_t bin_size, int32_t half_bins, int mode, int64_t* out_host) {
+  const char* who = "gat_list_profile";
+  if (!ctx || !list_off || !anchor_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  const ProfileIn in = {anchor_pos, anchor_minus, anchor_off, n_tracks, bin_size, half_bins, mode};
+  int rc;
+  int64_t most_bases = 0;
+  if ((rc = check_list_counts(ctx, who, n_lists, n_groups))) return rc;
+  if ((rc = profile_check_common(ctx, who, in, n_groups, most_bases))) return rc;
+  if ((rc = profile_check_words(ctx, who, most_bases, 1, nullptr, 0))) return rc;
+  const int64_t n = n_lists * n_groups;
+  if ((rc = check_caller_lists(ctx, who, "intervals", lists, list_off, n))) return rc;
+  if ((rc = distance_check_normalized(ctx, who, "segment list", lists, list_off, n_lists, n_groups, kProfileWhy))) return rc;
+  const size_t words = (size_t)(n_lists * n_tracks * 2 * (int64_t)half_bins);
+  if (words == 0) return GAT_OK;
+  ProfileBufs B;
+  return call_frame(ctx, nullptr, nullptr, [&](const Knobs& kn, gat_stats&) {
+    int brc;
+    if ((brc = profile_upload(ctx, in, n_groups, B))) return brc;
+    if ((brc = upload_csr_lists(ctx, lists, list_off, n, B.d_seg, B.d_csr))) return brc;
+    HIPCHK(ctx, B.out.d_out.alloc(words));
+    HIPCHK(ctx, hipMemsetAsync(B.out.d_out.p, 0, words * 8, ctx->stream));
+    if ((brc = launch_profile(ctx, kn, csr_lists(B.d_seg, B.d_csr), n_lists, n_groups, in, true, B))) return brc;
+    HIPCHK(ctx, staged_d2h(ctx, out_host, B.out.d_out.p, words * 8));
+    return GAT_OK;
+  });
+}
+
+static int sample_profile_enrichment_body(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint32_t seed, int64_t sample_begin, int64_t S,
+                                          const ProfileIn& in, const int64_t* obs_host, int64_t* out_host, gat_stats& local, ProfileBufs& B) {
+  const int C = P->n_contigs;
+  const int64_t cells = (int64_t)in.n_tracks * 2 * in.half_bins;
+  int rc;
+  if ((rc = profile_upload(ctx, in, C, B))) return rc;
+  if ((rc = B.out.begin(ctx, obs_host, cells))) return rc;
+  rc = for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t, int64_t nb) {
+    return launch_profile(ctx, kn, sampled_lists(P), nb, C, in, false, B);
+  });
+  return rc ? rc : B.out.finish(ctx, cells, S, out_host);
+}
+
+extern "C" int gat_sample_profile_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                             const uint32_t* anchor_pos, const uint8_t* anchor_minus, const int64_t* anchor_off,
+                                             int32_t n_tracks, int64_t bin_size, int32_t half_bins, int mode,
+                                             const int64_t* obs_host, int64_t* out_host, gat_stats* stats) {
+  const char* who = "gat_sample_profile_enrichment";
+  if (!ctx || !P || !anchor_off) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (sample_end < sample_begin) return set_err(ctx, GAT_ERR_ARG, "sample_end < sample_begin");
+  const ProfileIn in = {anchor_pos, anchor_minus, anchor_off, n_tracks, bin_size, half_bins, mode};
+  int rc;
+  int64_t most_bases = 0;
+  if ((rc = profile_check_common(ctx, who, in, P->n_contigs, most_bases))) return rc;
+  const int64_t S = sample_end - sample_begin, cells = (int64_t)n_tracks * 2 * half_bins;
+  if (cells > 0 && (!obs_host || !out_host)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = profile_check_words(ctx, who, most_bases, S, obs_host, cells))) return rc;
+  if (!sampled_lists_normalized(P))
+    return set_err(ctx, GAT_ERR_ARG, "%s: the sampled segment lists are not normalized (SamplerSegments without isochore keys leaves them "
+                   "neither sorted nor disjoint): the profile needs normalized lists", who);
+  ProfileBufs B;
+  return null_words_frame(ctx, P, stats, cells, S, out_host, [&](const Knobs& kn, gat_stats& local) {
+    return sample_profile_enrichment_body(ctx, P, kn, seed, sample_begin, S, in, obs_host, out_host, local, B);
   });
 }
 

@@ -659,6 +659,64 @@ int gat_sample_geneset_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                                   const int32_t* members, int32_t n_genes, const int64_t* term_off, const int32_t* term_genes,
                                   int32_t n_terms, const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
 
+/* How the segments of a list are distributed around a class of points -- transcription start sites, motif centres, exon ends --
+ * formed on the device by k_profile (the reference has nothing like it).  The groups are contigs.  An anchor is (a, sigma): a
+ * position a in [0, 2^32 - 1] and a strand sigma in {+1, -1} (anchor_minus 0 / 1).  With w = bin_size in [1, 2^31],
+ * H = half_bins in [1, 512], R = H * w <= 2^31 and B = 2 H <= GAT_PROFILE_MAX_BINS offset bins, the offset of base x from the
+ * anchor is o = sigma * (x - a) in signed 64-bit arithmetic, x lies in the window iff -R <= o < R, and its bin is
+ * floor((o + R) / w): bin b covers the offsets [b * w - R, (b + 1) * w - R).  A plus anchor's window is [a - R, a + R), a minus
+ * anchor's (a - R, a + R].  For a normalized segment list L (per group sorted by start, pairwise disjoint, every interval with
+ * end > start; adjacent intervals allowed) and the anchors A_{t,g} of track t on group g
+ *     GAT_PROFILE_BASES      v(L, t, b) = sum over g, over (a, sigma) in A_{t,g}, over q = [s, e) in L_g of
+ *                                         #{ x in [s, e) : bin(x; a, sigma) = b }
+ *     GAT_PROFILE_MIDPOINTS  the same with q replaced by [m, m + 1), m = s + (e - s) / 2 in integer division
+ * A base counts once per anchor whose window holds it: overlapping windows count with multiplicity.  v sums over all groups:
+ * a cell is (track, bin).  With K_t the anchors of track t over all groups, 0 <= v <= K_t * w.  Example (w = 10, H = 2), the
+ * segment [85, 112): anchor (100, +) gives v = 5, 10, 10, 2; anchor (100, -) gives 1, 10, 10, 6; the midpoint 98 lands in bin
+ * 1 of the plus anchor and in bin 2 of the minus one.
+ * anchor_off has n_tracks * n_groups + 1 non-decreasing entries, track t of group g at index t * n_groups + g; within a
+ * (track, group) the anchors ascend by position, plus before minus at one position, no (position, strand) twice.
+ * Over a range of S samples and against an observed value obs[t][b] >= 0 given by the caller, every (track, bin) gets five
+ * int64 words (GAT_PROFILE_WORDS) -- those of GAT_LOCAL_WORDS, in the same order and with the same meaning: n_pos, sum, sumsq
+ * (unsigned where it passes 2^63), n_less, n_eq; all S samples count in n_less / n_eq, those with v == 0 too.  All arithmetic
+ * is integer and exact.  Every word is additive over the samples: a partial sum has one owner on the device and is added once
+ * with a 64-bit integer add, so results do not depend on batches, workgroups, the run, or how the range is cut into calls --
+ * the words of calls over [0, k) and [k, S) add up to those of the call over [0, S).  Context options, none of which changes a
+ * result: GAT_PROFILE_LDS_ANCHORS -- how many anchor positions of a (track, group) the kernel's search finds in LDS before it
+ * goes to global memory (clamped to what a workgroup's LDS holds beside the bins; 0: none);
+ * GAT_PROFILE_SAMPLES_PER_BLOCK -- the run of lists a workgroup takes (default: by the launch).
+ *
+ * gat_list_profile: the raw v of caller-provided lists (the observed values of the input segments with n_lists == 1).
+ * lists / list_off, n_groups: as in gat_list_distances.  out_host: [n_lists][n_tracks][B].  Synchronous.  n_lists == 0 or
+ * n_tracks == 0 writes nothing.  GAT_ERR_ARG, nothing written: a NULL ctx / list_off / anchor_off / out_host (lists /
+ * anchor_pos / anchor_minus may be NULL where they hold nothing), negative counts, a decreasing offset, bin_size, half_bins,
+ * half_bins * bin_size or mode out of range, K_t * bin_size >= 2^32 for some track (a value is a 32-bit word on the device),
+ * anchors that are out of order, a repeated (position, strand), an anchor_minus other than 0 or 1 (gat_last_error names the
+ * track and the group), a segment list that is not normalized (it names the list and the group).  Never a wrong number. */
+#define GAT_PROFILE_WORDS 5
+#define GAT_PROFILE_MAX_BINS 1024
+#define GAT_PROFILE_BASES 0
+#define GAT_PROFILE_MIDPOINTS 1
+int gat_list_profile(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                     const uint32_t* anchor_pos, const uint8_t* anchor_minus, const int64_t* anchor_off,
+                     int32_t n_tracks, int32_t n_groups, int64_t bin_size, int32_t half_bins, int mode,
+                     int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop shared with gat_sample, k_profile behind every batch that passed its checks,
+ * reading the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed
+ * and range (per-unit streams only).  The groups are the problem's contigs in the problem's order: anchor_off has n_tracks *
+ * n_contigs + 1 entries; obs_host: [n_tracks][B]; out_host: [n_tracks][B][5].  Synchronous, like gat_sample.  An empty sample
+ * range writes zeros; n_tracks == 0 writes nothing.  GAT_ERR_ARG, nothing written: as above, and a NULL p, a NULL obs_host /
+ * out_host with n_tracks > 0, sample_end < sample_begin, a negative obs, (K_t * bin_size)^2 * samples >= 2^64 for some track
+ * (sumsq would not fit), a sampler whose lists are not normalized (SamplerSegments on a problem without isochore keys; the
+ * message says so), a call in flight on the problem.  The sampler's errors pass through (GAT_ERR_ASSERT; SamplerBruteForce's
+ * GAT_ERR_VALUE "sampling did not converge"). */
+int gat_sample_profile_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                                  int64_t sample_begin, int64_t sample_end,
+                                  const uint32_t* anchor_pos, const uint8_t* anchor_minus, const int64_t* anchor_off,
+                                  int32_t n_tracks, int64_t bin_size, int32_t half_bins, int mode,
+                                  const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
