@@ -37,7 +37,7 @@ SYMBOLS = [
     "gat_sample_distances", "gat_minp_counts", "gat_minp_times", "gat_efdr_counts", "gat_efdr_times",
     "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch", "gat_sampler_last_launch",
     "gat_list_pair_hits", "gat_sample_pair_enrichment", "gat_list_geneset_hits", "gat_sample_geneset_enrichment",
-    "gat_list_profile", "gat_sample_profile_enrichment",
+    "gat_list_profile", "gat_sample_profile_enrichment", "gat_list_signal", "gat_sample_signal",
 ]
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
@@ -277,6 +277,10 @@ def lib():
     L.gat_list_distances.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, C.c_int, i64, vp]
     L.gat_sample_distances.restype = C.c_int
     L.gat_sample_distances.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, C.c_int, i64, vp, C.POINTER(Stats)]
+    L.gat_list_signal.restype = C.c_int
+    L.gat_list_signal.argtypes = [vp, vp, vp, i64, vp, vp, vp, i32, i32, vp]
+    L.gat_sample_signal.restype = C.c_int
+    L.gat_sample_signal.argtypes = [vp, vp, u32, i64, i64, vp, vp, vp, i32, vp, C.POINTER(Stats)]
     L.gat_list_bin_overlaps.restype = C.c_int
     L.gat_list_bin_overlaps.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, i64, vp, vp]
     L.gat_sample_bin_enrichment.restype = C.c_int
@@ -722,6 +726,27 @@ def list_distances(ctx, lists, list_off, n_lists, annos, anno_off, n_tracks, n_g
     return out
 
 
+SIGNAL_WORDS = ("n", "covered", "hit", "sum")
+
+
+def list_signal(ctx, lists, list_off, n_lists, pieces, values, piece_off, n_tracks, n_groups):
+    """the four sums (SIGNAL_WORDS; gat_list_signal) of n_tracks x n_groups signal tracks -- track t of group g is
+    pieces[piece_off[t * n_groups + g]:piece_off[t * n_groups + g + 1]], normalized, with the int32 values beside them -- over
+    n_lists x n_groups caller-provided segment lists (the layout of list_distances), summed over the groups.  Returns int64
+    [n_lists, n_tracks, 4]."""
+    lists = np.ascontiguousarray(lists, dtype=SEG)
+    pieces = np.ascontiguousarray(pieces, dtype=SEG)
+    values = np.ascontiguousarray(values, dtype=np.int32)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    piece_off = np.ascontiguousarray(piece_off, dtype=np.int64)
+    n_lists, n_tracks, n_groups = int(n_lists), int(n_tracks), int(n_groups)
+    assert len(list_off) == n_lists * n_groups + 1 and len(piece_off) == n_tracks * n_groups + 1 and len(values) == len(pieces)
+    out = np.zeros((n_lists, n_tracks, len(SIGNAL_WORDS)), dtype=np.int64)
+    _check(lib().gat_list_signal(ctx._h, _p(lists), _p(list_off), n_lists, _p(pieces), _p(values), _p(piece_off), n_tracks, n_groups,
+                                 _p(out)), ctx._h)
+    return out
+
+
 def call_lane_for(n_lanes, asynchronous, timed, serial_state, others_in_flight, lane_busy):
     """The lane (0..n_lanes-1) an enqueued call would take, or -1: the context's stream (gat_call_lane_for: the library's own rule)."""
     busy = np.ascontiguousarray(list(lane_busy) + [0] * 4, dtype=np.int32)
@@ -1067,6 +1092,24 @@ class Problem(object):
         st = Stats()
         rc = lib().gat_sample_distances(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
                                         _p(annos), _p(anno_off), n_tracks, int(direction), int(max_distance), _p(out), C.byref(st))
+        self.last_stats = st.asdict()
+        _check(rc, self.ctx._h)
+        return out
+
+    def sample_signal(self, seed, sample_begin, sample_end, pieces, values, piece_off, n_tracks):
+        """the four sums (SIGNAL_WORDS; gat_sample_signal) of n_tracks signal tracks -- track t of contig c is
+        pieces[piece_off[t * n_contigs + c]:piece_off[t * n_contigs + c + 1]] with the int32 values beside them, contigs in the
+        problem's order -- over every sampled contig-level list of [sample_begin, sample_end), summed over the contigs.
+        Returns int64 [samples, n_tracks, 4]."""
+        pieces = np.ascontiguousarray(pieces, dtype=SEG)
+        values = np.ascontiguousarray(values, dtype=np.int32)
+        piece_off = np.ascontiguousarray(piece_off, dtype=np.int64)
+        n_tracks = int(n_tracks)
+        assert piece_off.shape == (n_tracks * self.n_contigs + 1,) and len(values) == len(pieces)
+        out = np.zeros((max(0, int(sample_end) - int(sample_begin)), n_tracks, len(SIGNAL_WORDS)), dtype=np.int64)
+        st = Stats()
+        rc = lib().gat_sample_signal(self.ctx._h, self._h, int(seed) & 0xFFFFFFFF, int(sample_begin), int(sample_end),
+                                     _p(pieces), _p(values), _p(piece_off), n_tracks, _p(out), C.byref(st))
         self.last_stats = st.asdict()
         _check(rc, self.ctx._h)
         return out

@@ -81,6 +81,7 @@ struct gat_ctx;
   INT(coverage_samples_per_block, "GAT_COVERAGE_SAMPLES_PER_BLOCK", 0) /* ... its chunk of samples; default: by the launch */ \
   INT(metrics_lds_pieces, "GAT_METRICS_LDS_PIECES", 2048) /* gat_*_metrics: pieces of a group k_metrics' searches find in LDS */ \
   INT(distance_lds_pieces, "GAT_DISTANCE_LDS_PIECES", 2048) /* gat_*_distances: intervals of a list k_distance's search finds in LDS */ \
+  INT(signal_lds_pieces, "GAT_SIGNAL_LDS_PIECES", 2048) /* gat_*_signal: piece ends of a (track, group) k_signal's searches find in LDS */ \
   INT(minp_lds_samples, "GAT_MINP_LDS_SAMPLES", 4096) /* gat_minp_counts: samples per row up to which k_minp_rank sorts in LDS */   \
   REAL(minp_scratch_mb, "GAT_MINP_SCRATCH_MB", 1024.0) /* ... megabytes of K (4 bytes a sample) per batch of rows */                \
   FLAG(minp_all_passes, "GAT_MINP_ALL_PASSES") /* ... the sort runs all 16 digit passes (measuring what the skip is worth) */      \

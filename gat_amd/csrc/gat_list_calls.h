@@ -4,9 +4,9 @@
 #pragma once
 
 // ---- the entry points that read the sampled lists where they are: gat_sample / gat_sample_units copy them out, and
-// gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_bin_enrichment, gat_sample_pair_enrichment,
-// gat_sample_geneset_enrichment and gat_sample_profile_enrichment put a kernel (gat_coverage.h, gat_metrics.h, gat_distance.h,
-// gat_local.h, gat_pairs.h, gat_geneset.h, gat_profile.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
+// gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_signal, gat_sample_bin_enrichment,
+// gat_sample_pair_enrichment, gat_sample_geneset_enrichment and gat_sample_profile_enrichment put a kernel (gat_coverage.h,
+// gat_metrics.h, gat_distance.h, gat_signal.h, gat_local.h, gat_pairs.h, gat_geneset.h, gat_profile.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
 
 // A synchronous call's frame: refused while a call is in flight on the problem (P == nullptr: a call over the caller's own
 // lists); the knobs are read once; body(kn, local) does the work.  Whatever the body returns, the stream is drained behind it:
@@ -579,6 +579,169 @@ extern "C" int gat_sample_distances(gat_ctx* ctx, gat_problem* P, uint32_t seed,
       const int lrc = T.launch(ctx, kn, sampled_lists(P), nb, C, true);
       if (lrc) return lrc;
       HIPCHK(ctx, staged_d2h(ctx, out_host + done * n_tracks * gat::kDistanceWords, T.out.d_out.p, words * 8));
+      return GAT_OK;
+    });
+  });
+}
+
+// gat_list_signal / gat_sample_signal: k_signal (gat_signal.h) over caller-provided lists, or behind every batch.  The signal
+// tracks go up once per call as 32-byte records -- piece, value and the two prefix sums before it (gat_signal_sum.h) -- built
+// in upload; the device buffers live for the call.
+static const char* const kSignalWhy = "the pieces are searched and their prefix sums are formed over it";
+struct SignalCall {
+  const char* who;
+  const gat_segment* pieces; const int32_t* values; const int64_t* piece_off; int32_t n_tracks;
+  DevBuf<gat::SignalPiece> d_rec;
+  DevBuf<int64_t> d_off;
+  struct { DevBuf<unsigned long long> d_out; } out;      // (T.out.d_out: the store frame fills it)
+  std::vector<unsigned __int128> M;                      // [track][group]: sum_k |q_k| * (e_k - s_k)
+  // what both entry points ask of the tracks: normalized, no value of INT32_MIN, and sum_g M[t][g] < 2^63 -- the bound of
+  // normalized segment lists, and the least any list asks
+  int check(gat_ctx* ctx, int64_t n_groups) {
+    int rc;
+    if ((rc = check_tracks(ctx, who, pieces, piece_off, n_tracks, n_groups, kSignalWhy))) return rc;
+    const int64_t n = (int64_t)n_tracks * n_groups;
+    if (piece_off[n] > piece_off[0] && !values) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+    M.assign((size_t)n, 0);
+    for (int64_t t = 0; t < n_tracks; ++t) {
+      unsigned __int128 total = 0;
+      for (int64_t g = 0; g < n_groups; ++g) {
+        unsigned __int128 m = 0;
+        for (int64_t k = piece_off[t * n_groups + g]; k < piece_off[t * n_groups + g + 1]; ++k) {
+          if (values[k] == INT32_MIN)
+            return set_err(ctx, GAT_ERR_ARG, "%s: signal track %lld, group %lld: the value of piece %lld is INT32_MIN (|q| <= 2^31 - 1)", who,
+                           (long long)t, (long long)g, (long long)(k - piece_off[t * n_groups + g]));
+          m += (unsigned __int128)(uint64_t)std::llabs((long long)values[k]) * (uint64_t)(pieces[k].end - pieces[k].start);
+        }
+        M[(size_t)(t * n_groups + g)] = m;
+        total += m;
+      }
+      if (total >> 63) return refuse_bound(ctx, t, "the sum over its groups of |value| * length", nullptr);
+    }
+    return GAT_OK;
+  }
+  int refuse_bound(gat_ctx* ctx, int64_t t, const char* what, const char* advice) const {
+    return set_err(ctx, GAT_ERR_ARG, "%s: signal track %lld: %s reaches 2^63: a sum could leave 64 bits%s%s", who, (long long)t, what,
+                   advice ? ": " : "", advice ? advice : "");
+  }
+  // ... and of segment lists that are not normalized, n_g[g] of them at most on group g: a base counts once per segment that
+  // covers it, so sum_g n_g * M[t][g] < 2^63.  (M[t][g] < 2^63 and n_g < 2^31 after check: the products and their sum fit 128 bits)
+  int check_any_lists(gat_ctx* ctx, const int64_t* n_g, int64_t n_groups, const char* advice) const {
+    for (int64_t t = 0; t < n_tracks; ++t) {
+      unsigned __int128 total = 0;
+      for (int64_t g = 0; g < n_groups; ++g) total += (unsigned __int128)(uint64_t)n_g[g] * M[(size_t)(t * n_groups + g)];
+      if (total >> 63) return refuse_bound(ctx, t, "the sum over its groups of segments * |value| * length, for segment lists that are not normalized,", advice);
+    }
+    return GAT_OK;
+  }
+  int upload(gat_ctx* ctx, const Knobs&, int32_t n_groups, int64_t) {
+    const int64_t n = (int64_t)n_tracks * n_groups, base = piece_off[0], total = piece_off[n] - base;
+    HIPCHK(ctx, d_rec.upload_built((size_t)total, ctx, [&](gat::SignalPiece* h) {
+      for (int64_t i = 0; i < n; ++i) {
+        const int64_t b = piece_off[i];
+        gat::signal_fill(h + (b - base), piece_off[i + 1] - b, [&](int64_t k, uint32_t& s, uint32_t& e, int32_t& q) {
+          s = pieces[b + k].start; e = pieces[b + k].end; q = values[b + k];
+        });
+      }
+    }));
+    std::vector<int64_t> h_off((size_t)n + 1);
+    for (int64_t i = 0; i <= n; ++i) h_off[(size_t)i] = piece_off[i] - base;
+    HIPCHK(ctx, d_off.upload(h_off, ctx));
+    HIPCHK(ctx, stage_flush(ctx));                    // (h_off goes away with this frame)
+    return GAT_OK;
+  }
+  // the launch over n_lists x n_tracks x n_groups: a workgroup stages the ends of one (track, group) and takes a run of the
+  // lists: the run as long as leaves 2 048 workgroups (eight for each of 256 compute units) but at least 16 lists, within the
+  // grid's y.  out.d_out holds n_lists * n_tracks * 4 words, zeroed by the caller (the flag says nothing here).
+  int launch(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists, int64_t n_lists, int32_t n_groups, bool) const {
+    if (n_lists == 0 || n_tracks == 0 || n_groups == 0) return GAT_OK;
+    gat::SignalArgs A;
+    memset(&A, 0, sizeof(A));
+    A.q = lists;
+    A.rec = d_rec.p;
+    A.rec_off = d_off.p;
+    A.n_tracks = n_tracks;
+    A.n_q = (int32_t)n_lists;
+    A.n_groups = n_groups;
+    A.out = out.d_out.p;
+    const int64_t L = std::max<int64_t>(1, std::min<int64_t>(kn.signal_lds_pieces, ((int64_t)ctx->max_lds - 1024) / 4));
+    A.lds_pieces = (int32_t)L;
+    const int64_t qpb = gat::run_per_block(n_lists, (int64_t)n_tracks * n_groups, 2048, gat::kNoRunCap);
+    A.q_per_block = (int32_t)qpb;
+    const size_t lds = gat::signal_lds_bytes(L);
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)gat::k_signal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(gat::k_signal, dim3((unsigned)((int64_t)n_tracks * n_groups), (unsigned)((n_lists + qpb - 1) / qpb)), dim3(gat::kSignalThreads), lds, ctx->stream, A);
+    HIPCHK(ctx, hipGetLastError());
+    return GAT_OK;
+  }
+};
+
+extern "C" int gat_list_signal(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                               const gat_segment* pieces, const int32_t* values, const int64_t* piece_off,
+                               int32_t n_tracks, int32_t n_groups, int64_t* out_host) {
+  const char* who = "gat_list_signal";
+  if (!ctx || !list_off || !piece_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  SignalCall T = {who, pieces, values, piece_off, n_tracks};
+  int rc;
+  if ((rc = check_list_counts(ctx, who, n_lists, n_groups))) return rc;
+  if ((rc = T.check(ctx, n_groups))) return rc;
+  if ((rc = check_caller_lists(ctx, who, "segments", lists, list_off, n_lists, n_groups, nullptr))) return rc;
+  // the lists the host does not find normalized: the most segments one of them has on each group
+  std::vector<int64_t> n_g((size_t)n_groups, 0);
+  bool any = false;
+  for (int64_t l = 0; l < n_lists; ++l) {
+    bool normalized = true;
+    for (int64_t j = list_off[l * n_groups]; j < list_off[(l + 1) * n_groups] && normalized; ++j)
+      normalized = lists[j].end > lists[j].start;
+    for (int32_t g = 0; g < n_groups && normalized; ++g)
+      for (int64_t j = list_off[l * n_groups + g] + 1; j < list_off[l * n_groups + g + 1] && normalized; ++j)
+        normalized = lists[j].start >= lists[j - 1].end;
+    if (normalized) continue;
+    any = true;
+    for (int32_t g = 0; g < n_groups; ++g)
+      n_g[(size_t)g] = std::max(n_g[(size_t)g], list_off[l * n_groups + g + 1] - list_off[l * n_groups + g]);
+  }
+  if (any && (rc = T.check_any_lists(ctx, n_g.data(), n_groups, "normalized lists, shorter lists or a smaller scale"))) return rc;
+  return store_over_caller_lists(ctx, T, lists, list_off, n_lists, n_groups, (int64_t)n_tracks * gat::kSignalWords, out_host);
+}
+
+// (not the fold: the words of a batch are copied out behind it, and an empty range writes nothing)
+extern "C" int gat_sample_signal(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                 const gat_segment* pieces, const int32_t* values, const int64_t* piece_off,
+                                 int32_t n_tracks, int64_t* out_host, gat_stats* stats) {
+  const char* who = "gat_sample_signal";
+  if (!ctx || !P || !piece_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (int rc = check_sample_range(ctx, sample_begin, sample_end)) return rc;
+  SignalCall T = {who, pieces, values, piece_off, n_tracks};
+  int rc;
+  if ((rc = T.check(ctx, P->n_contigs))) return rc;
+  // lists that are not normalized (one unit a contig): as many segments on a contig as its region of the slab holds -- checked
+  // again behind a batch for which the slab had to grow, before that batch is reduced
+  int64_t checked_scale = 0;
+  const auto check_slab = [&]() {
+    if (sampled_lists_normalized(P) || checked_scale == P->cap_scale) return GAT_OK;
+    std::vector<int64_t> n_g((size_t)P->n_contigs);
+    for (int c = 0; c < P->n_contigs; ++c) n_g[(size_t)c] = P->h_units[(size_t)P->h_count_n_index[c]].slab_cap;
+    checked_scale = P->cap_scale;
+    return T.check_any_lists(ctx, n_g.data(), P->n_contigs, "n is what a contig's region of the sampler's slab holds; isochore keys "
+                             "(normalized lists) or a smaller scale");
+  };
+  if ((rc = check_slab())) return rc;
+  return call_frame(ctx, P, stats, [&](const Knobs& kn, gat_stats& local) {
+    const int C = P->n_contigs;
+    const int64_t S = sample_end - sample_begin;
+    if (S == 0) return GAT_OK;                        // (no batch runs: nothing is written)
+    const int urc = T.upload(ctx, kn, C, S);
+    if (urc) return urc;
+    return for_each_sampler_batch(ctx, P, kn, seed, sample_begin, S, local, BatchOpts(), [&](int64_t done, int64_t nb) {
+      const size_t words = (size_t)(nb * n_tracks * gat::kSignalWords);
+      if (words == 0) return GAT_OK;
+      if (const int brc = check_slab()) return brc;
+      if (T.out.d_out.n < words) HIPCHK(ctx, T.out.d_out.alloc(words));
+      HIPCHK(ctx, hipMemsetAsync(T.out.d_out.p, 0, words * 8, ctx->stream));
+      const int lrc = T.launch(ctx, kn, sampled_lists(P), nb, C, true);
+      if (lrc) return lrc;
+      HIPCHK(ctx, staged_d2h(ctx, out_host + done * n_tracks * gat::kSignalWords, T.out.d_out.p, words * 8));
       return GAT_OK;
     });
   });

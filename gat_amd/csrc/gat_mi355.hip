@@ -7,8 +7,8 @@
 //
 // In this file: the context, the scratch, the count launches, the sampler batch and the call seam (gat_sample_and_count*),
 // gat_count_lists, the RCCL entry points and the statistics.  gat_list_calls.h, included behind the call seam: gat_sample /
-// gat_sample_units and the list reductions (gat_sample_* / gat_list_* of coverage, metrics, distances, gat-local, gat-pairs,
-// gat-geneset and gat-profile).  One translation unit: the Makefile keeps its device assembly and checks it.
+// gat_sample_units and the list reductions (gat_sample_* / gat_list_* of coverage, metrics, distances, signal, gat-local,
+// gat-pairs, gat-geneset and gat-profile).  One translation unit: the Makefile keeps its device assembly and checks it.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <link.h>            // dl_iterate_phdr: the RCCL a host process has mapped already
@@ -44,6 +44,7 @@
 #include "gat_coverage.h"
 #include "gat_metrics.h"
 #include "gat_distance.h"
+#include "gat_signal.h"
 #include "gat_local.h"
 #include "gat_pairs.h"
 #include "gat_geneset.h"

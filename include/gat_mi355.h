@@ -504,6 +504,59 @@ int gat_sample_distances(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                          int direction, int64_t max_distance,
                          int64_t* out_host, gat_stats* stats /* nullable */);
 
+/* What a quantitative track -- conservation, GC content, a ChIP or ATAC signal, a methylation level -- amounts to over the
+ * segments of a list, formed on the device by k_signal (the reference has nothing like it: its annotations are interval sets).
+ * The groups are contigs.  A signal track t on group g is a list of K >= 0 pieces (s_k, e_k, q_k): the intervals normalized --
+ * sorted by start, pairwise disjoint, every e_k > s_k; adjacent pieces allowed -- and q_k a SIGNED 32-bit integer with
+ * |q_k| <= 2^31 - 1 (INT32_MIN is refused).  The caller quantises; the device never sees a float.  For a segment q = [s, e)
+ * with e > s:
+ *     c(q, t) = sum_k |[s, e) n [s_k, e_k)|            bases of q that carry a value
+ *     w(q, t) = sum_k q_k * |[s, e) n [s_k, e_k)|      signed
+ * A (segment list, track) pair gets four int64 words (GAT_SIGNAL_WORDS), summed over the groups and the list's segments, in
+ * this order:
+ *     n        segments with e > s; the same for every track
+ *     covered  sum of c(q, t)
+ *     hit      segments with c(q, t) > 0
+ *     sum      sum of w(q, t), signed
+ * Segments with e <= s are skipped.  The segment lists need be neither sorted nor disjoint (SamplerSegments without isochore
+ * keys returns neither): every segment counts on its own.  All arithmetic is integer and exact; a partial sum has one owner on
+ * the device and is added once with a 64-bit integer add, so results do not depend on batches, workgroups, the LDS limit or how
+ * a range is cut into calls.  GAT_SIGNAL_LDS_PIECES (context option): how many piece ends of a (track, group) the kernel's
+ * searches find in LDS before they go to global memory; it changes no result.
+ *
+ * Never a wrong number: with M[t][g] = sum_k |q_k| * (e_k - s_k), formed in 128 bits on the host, a call is refused
+ * (GAT_ERR_ARG; gat_last_error names the track) where it cannot show that every |sum| stays below 2^63.  The bound checked:
+ *   - normalized segment lists -- the sampled lists of every problem but SamplerSegments without isochore keys, and a caller's
+ *     lists that the host finds normalized: a base counts once, so sum_g M[t][g] < 2^63;
+ *   - any other lists: sum_g n_g * M[t][g] < 2^63 -- in gat_list_signal n_g is the most segments one of the call's lists that
+ *     are not normalized has on group g; in gat_sample_signal what the contig's region of the sampler's slab holds (where the
+ *     slab has to grow in mid-call the bound is checked again before the batch that needed it is reduced; the samples of
+ *     earlier batches are then written).
+ *
+ * gat_list_signal: caller-provided lists.  lists / list_off / n_lists / n_groups: as in gat_list_distances.  pieces / piece_off:
+ * n_tracks * n_groups piece lists (HOST, CSR, n_tracks * n_groups + 1 entries), track t of group g at index t * n_groups + g;
+ * values: parallel to pieces.  out_host: [n_lists][n_tracks][4].  Synchronous.  GAT_ERR_ARG, with nothing written: a NULL ctx /
+ * list_off / piece_off / out_host, a NULL pieces / values / lists where they would hold something, negative counts, a
+ * decreasing offset, a track that is not normalized (gat_last_error names the track, the group and the interval), a value of
+ * INT32_MIN, the bound above.  n_lists == 0 or n_tracks == 0 writes nothing; n_groups == 0 writes zeros. */
+#define GAT_SIGNAL_WORDS 4
+int gat_list_signal(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                    const gat_segment* pieces, const int32_t* values, const int64_t* piece_off,
+                    int32_t n_tracks, int32_t n_groups, int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop shared with gat_sample, k_signal behind every batch that passed its checks, reading
+ * the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed and range
+ * (per-unit streams only).  The groups are the problem's contigs in the problem's order: piece_off has n_tracks * n_contigs + 1
+ * entries; out_host: [sample][track][4], sample_end - sample_begin samples.  Synchronous, like gat_sample.  GAT_ERR_ARG: a NULL
+ * ctx / p / piece_off / out_host, a NULL pieces / values where they would hold something, sample_end < sample_begin, a negative
+ * n_tracks, a decreasing piece_off, a track that is not normalized, a value of INT32_MIN, the bound above, a call in flight on
+ * the problem.  An empty sample range or n_tracks == 0 writes nothing.  The sampler's errors pass through (GAT_ERR_ASSERT;
+ * SamplerBruteForce's GAT_ERR_VALUE "sampling did not converge"). */
+int gat_sample_signal(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                      int64_t sample_begin, int64_t sample_end,
+                      const gat_segment* pieces, const int32_t* values, const int64_t* piece_off,
+                      int32_t n_tracks, int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Where along the genome a segment list overlaps an annotation track, per bin, formed on the device by k_local (the reference
  * has nothing like it: gat-run gives one number per annotation over the whole workspace).  Bin b of group (contig) c is
  * [b * bin_size, (b + 1) * bin_size), b < n_bins[c] = bin_off[c + 1] - bin_off[c] -- the layout of gat_sample_coverage:
