@@ -119,14 +119,82 @@ def _device_stats_wanted(n_values):
     return n_values > 0 and _numpy_summation_model_holds()
 
 
+def check_null_round_options(null_round_size, counters=(), conditional="unconditional", reference_stream=False,
+                             output_counts_pattern=None, output_samples_pattern=None, output_stats=(), qvalue_method=None):
+    """run(null_round_size=R) / gat-run.py --null-round-size=R keep no sample: what needs the samples, or a null that is
+    not one range of per-unit streams on one device, is refused here -- while the options are checked, before anything is
+    read, allocated or sampled.  counters: their names; conditional: the --conditional choice."""
+    R = null_round_size
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)):
+        raise ValueError("--null-round-size: an integer number of samples per round (got %r)" % (R,))
+    if R < 0:
+        raise ValueError("--null-round-size: the samples per round cannot be negative (got %d); 0 holds the whole matrix" % R)
+    if R == 0:
+        return
+    what = "--null-round-size folds every round's counts into integer words and keeps no sample: "
+    if output_counts_pattern:
+        raise NotImplementedError(what + "--output-counts-pattern has no counts to write")
+    if output_samples_pattern:
+        raise NotImplementedError(what + "--output-samples-pattern has no sampled lists to write")
+    if "sample_metrics" in (output_stats or ()):
+        raise NotImplementedError(what + "--output-stats=sample_metrics is not written")
+    if "fdr_summary" in (output_stats or ()):
+        raise NotImplementedError(what + "--output-stats=fdr_summary needs rows that hold their samples")
+    if qvalue_method in ("minp", "efdr"):
+        raise NotImplementedError(what + "--qvalue-method=%s needs rows that hold their samples" % qvalue_method)
+    if conditional != "unconditional":
+        raise NotImplementedError("--null-round-size: only --conditional=unconditional (got %s: one sampling pass per "
+                                  "annotation)" % conditional)
+    if reference_stream:
+        raise NotImplementedError("--null-round-size: per-unit streams only, not --reference-stream (a run cut into rounds "
+                                  "is the same run only because sample s is the same sample whichever call draws it)")
+    if "nucleotide-density" in counters:
+        raise NotImplementedError("--null-round-size: the counter nucleotide-density has float rows, which have no exact "
+                                  "fold; its integer twin nucleotide-overlap gives the same p-values")
+    if _dist_state()[1] > 1:
+        raise NotImplementedError("--null-round-size: one process (the rounds are not sharded over the %d ranks of "
+                                  "torch.distributed)" % _dist_state()[1])
+
+
+def check_null_round_options_of(options):
+    """check_null_round_options on the parsed command line of gat-run.py"""
+    check_null_round_options(getattr(options, "null_round_size", 0) or 0, counters=list(getattr(options, "counters", None) or []),
+                             conditional=getattr(options, "conditional", "unconditional"),
+                             reference_stream=bool(getattr(options, "reference_stream", False)),
+                             output_counts_pattern=getattr(options, "output_counts_pattern", None),
+                             output_samples_pattern=getattr(options, "output_samples_pattern", None),
+                             output_stats=getattr(options, "output_stats", None) or [],
+                             qvalue_method=getattr(options, "qvalue_method", None))
+
+
+def _check_null_round_units(num_samples, n_units, workspace_bases):
+    """what a deep run is refused for once a track's work units are known, before it samples"""
+    if num_samples * n_units > (1 << 32):
+        raise ValueError("--null-round-size: %d samples x %d work units are more than the 2^32 unit streams there are (the "
+                         "streams are seeded modulo 2^32: beyond that samples repeat, and a deeper null would claim precision "
+                         "it does not have); this problem allows %d samples" % (num_samples, n_units, (1 << 32) // n_units))
+    if num_samples * workspace_bases >= (1 << 63):
+        raise ValueError("--null-round-size: %d samples of up to %d bases each: the sum of a row no longer fits its 64-bit "
+                         "word" % (num_samples, workspace_bases))
+
+
+class _NullWordsPerTrack(list):
+    """what a deep run keeps of a segment track's null distributions: [ {annotation: (the row's eight words, CI95 low value,
+    CI95 high value of the first round)} per counter ]"""
+
+
+_NOTHING_TO_PLACE = object()     # a deep job's result[0] where no unit has a contig: every sample counts 0
+
+
 class _TrackJob(object):
     """the sampling of one segment track between its two halves (_sample_start / _sample_finish): the problem on the device,
-    the count matrix there, and -- when the call could be enqueued -- the call in flight"""
+    the count matrix there, and -- when the call could be enqueued -- the call in flight.  round: the samples per round of a
+    deep run (_sample_finish_rounds), whose `dev` holds one round"""
     __slots__ = ("ctx", "P", "flat", "names", "tracks", "num_samples", "seed", "dev", "enqueued", "samples_outfile", "mt_state",
-                 "result", "metrics")
+                 "result", "metrics", "round")
 
     def __init__(self, **kw):
-        self.dev, self.enqueued, self.result, self.P, self.metrics = None, False, None, None, None
+        self.dev, self.enqueued, self.result, self.P, self.metrics, self.round = None, False, None, None, None, 0
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -144,12 +212,15 @@ class _TrackJob(object):
 
 
 def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, seed, ctx=None, samples_outfile=None,
-                  workspace_generator=None, only_tracks=None, mt_state=None, _aflat=None, _shared=None, _metrics=None):
+                  workspace_generator=None, only_tracks=None, mt_state=None, _aflat=None, _shared=None, _metrics=None,
+                  null_round_size=0):
     """First half of the batch seam (UnconditionalSampler.sample, gat/__init__.py:704-778): the inputs go to the device --
     the annotation tables only if no earlier track of this run() left them there (_shared) -- and, on the plain
     single-process path, the samples are ENQUEUED (gat_sample_and_count_enqueue): the caller computes observed counts and
     the sizes of its rows while the device samples, then calls _sample_finish.  Returns a _TrackJob; job.result is set
-    already where there is nothing to sample."""
+    already where there is nothing to sample.
+    null_round_size > 0 (a deep run: check_null_round_options has passed): the buffer holds ONE round of
+    min(null_round_size, num_samples) samples and only the first round is enqueued; _sample_finish_rounds draws the others."""
     from . import _lib
     job = _TrackJob(ctx=None, flat=None, names=[c.name for c in counters], tracks=None, num_samples=num_samples, seed=seed,
                     samples_outfile=samples_outfile, mt_state=mt_state)
@@ -190,6 +261,12 @@ def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, 
         flat["brute_ntries_inner"], flat["brute_ntries_outer"] = sampler.ntries_inner, sampler.ntries_outer
     job.flat = flat
     names = job.names
+    if null_round_size > 0:
+        _check_null_round_units(num_samples, flat["n_units"], workspace.sum())
+        job.round = max(1, min(int(null_round_size), num_samples))
+        if flat["n_contigs"] == 0:
+            job.result = (_NOTHING_TO_PLACE, flat["n_units"])       # (no zero rows of num_samples: the words are written down)
+            return job
     if flat["n_contigs"] == 0:
         # nothing to place (the generated workspace holds no segments): computeSample skips every unit
         # (gat/__init__.py:536-538) and each counter sums over no contigs
@@ -213,7 +290,16 @@ def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, 
                                                          nucleotide_only=all(n in ("nucleotide-overlap", "nucleotide-density") for n in names))
     job.P = _lib.Problem(ctx, flat, annotations=shared_annos)
     rank, world, _ = _dist_state()
-    if world == 1 and mt_state is None and num_samples > 0 and not _force_collective_path():
+    if job.round > 0:
+        if num_samples > 0:
+            try:
+                job.dev = ctx.alloc(len(names) * len(tracks) * job.round * 8)
+                job.P.enqueue(names, seed, 0, job.round, job.dev)
+                job.enqueued = True
+            except Exception:
+                job.abandon()
+                raise
+    elif world == 1 and mt_state is None and num_samples > 0 and not _force_collective_path():
         try:
             job.dev = ctx.alloc(len(names) * len(tracks) * num_samples * 8)
             job.P.enqueue(names, seed, 0, num_samples, job.dev)
@@ -301,6 +387,71 @@ def _sample_finish(job, stat_vals=None):
     out.stats = stats
     job.result = (out, flat["n_units"])
     return job.result
+
+
+def _sample_finish_rounds(job, stat_vals):
+    """_sample_finish's sibling for a deep run (run(null_round_size=R)): the samples are drawn in rounds of job.round into the
+    ONE buffer _sample_start allocated -- round [b, e) is Problem.enqueue + wait as the whole range is on the plain path, and
+    sample s is the same sample whichever call draws it -- and every round is folded where it lies into eight integer words
+    per (counter, track) row (gat_null_fold; stat_vals as for _sample_finish: the values whose p-values will be asked for).
+    The first round also gives the two order statistics behind CI95low / CI95high (gat_null_stats, or numpy where
+    _device_stats_wanted says so): the interval is the first round's.  Nothing here grows with num_samples: the buffer is a
+    round, the words are 64 bytes a row.  Returns (_NullWordsPerTrack, number of work units), or (None, 0)."""
+    from . import _lib
+    if job.result is not None and job.result[0] is not _NOTHING_TO_PLACE:
+        return job.result                                    # (None, 0): an empty workspace -- or this was called before
+    names, tracks, num_samples = job.names, job.tracks, job.num_samples
+    vals = np.array([[stat_vals[n][t] for t in tracks] for n in names], dtype=np.float64).ravel()
+    n_rows = len(vals)
+    if job.result is not None:                               # _NOTHING_TO_PLACE: num_samples values of 0 per row
+        words = [(num_samples, 0, 0, 0, num_samples if v > 0 else 0, num_samples if v == 0 else 0, 0, 0) for v in vals.tolist()]
+        interval = np.zeros((n_rows, 2))
+        n_units = job.result[1]
+    else:
+        ctx, P, seed, R = job.ctx, job.P, job.seed, job.round
+        n_units = job.flat["n_units"]
+        words_dev = None
+        try:
+            words_dev = ctx.alloc(max(1, n_rows) * _lib.NULL_FOLD_WORDS * 8)
+            ctx.null_fold_reset(words_dev, n_rows)
+            interval = np.zeros((n_rows, 2))
+            for b in range(0, num_samples, R):
+                e = min(b + R, num_samples)
+                if b > 0:
+                    P.enqueue(names, seed, b, e, job.dev)    # (round 0 was enqueued by _sample_start)
+                P.wait()
+                if n_rows == 0:
+                    continue
+                if b == 0:
+                    interval = _first_round_interval(ctx, job.dev, n_rows, e, vals)
+                ctx.null_fold(job.dev, n_rows, e - b, e - b, vals, words_dev)    # (a round's rows lie e - b slots apart)
+            words = ctx.null_fold_words(words_dev, n_rows)
+        finally:
+            if words_dev is not None:
+                try:
+                    ctx.free(words_dev)
+                except Exception:
+                    pass
+            job.abandon()
+    out = _NullWordsPerTrack()
+    A = len(tracks)
+    for k in range(len(names)):
+        out.append(collections.OrderedDict((t, (words[k * A + a], float(interval[k * A + a, 0]), float(interval[k * A + a, 1])))
+                                           for a, t in enumerate(tracks)))
+    job.result = (out, n_units)
+    return job.result
+
+
+def _first_round_interval(ctx, dev, n_rows, n, vals):
+    """[n_rows, 2]: the values at AnnotatorResult's two interval positions in the n samples of the round on the device"""
+    if _device_stats_wanted(n_rows * n):
+        return ctx.null_stats(dev, n_rows, n, np.zeros(n_rows, dtype=np.uint8), vals)[:, 2:4]
+    host = np.empty((n_rows, n), dtype=np.int64)
+    ctx.d2h(host, dev)
+    offset = int(0.05 * n)
+    lo_i, hi_i = (min(offset, n - 1), max(n - offset, 0)) if offset > 0 else (0, n - 1)       # gat/Engine.pyx:1689-1696
+    part = np.partition(host, sorted(set((lo_i, hi_i))), axis=1)
+    return part[:, [lo_i, hi_i]].astype(np.float64)
 
 
 class _DeviceCounts(object):
@@ -437,7 +588,12 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
     global RandomState, so numpy.random.seed() makes a run reproducible).  reference_stream=True: random_seed seeds ONE
     stream for the whole run, as the reference's gat-run.py --random-seed does (same numbers as an unpatched reference;
     one wave's speed).  num_threads is accepted
-    and ignored (the GPU replaces the process pool)."""
+    and ignored (the GPU replaces the process pool).
+    null_round_size=R > 0 (not in the reference): a null distribution deeper than a count matrix -- the samples are drawn in
+    rounds of R into one buffer and every round is folded into eight exact integer words per row (_sample_finish_rounds); the
+    same samples as the plain run of the same call, rows with `null_words` and no `.samples`, every column of the plain
+    table's except CI95low / CI95high, which are the interval of the first round's min(R, num_samples) samples (and stddev,
+    which may differ in its last bit: nullWordsStatistics).  check_null_round_options lists what such a run refuses."""
     num_samples = kwargs.get("num_samples", 10000)
     pseudo_count = kwargs.get("pseudo_count", 1.0)
     reference = kwargs.get("reference", None)
@@ -447,6 +603,15 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
     reference_stream = bool(kwargs.get("reference_stream", False))
     sample_files = kwargs.get("sample_files", None) or []
     outfiles = kwargs.get("outfiles", None) or {}
+    null_round_size = kwargs.get("null_round_size", 0) or 0
+    if null_round_size:
+        # a deep run (before anything is read or sampled, and before a context is made)
+        check_null_round_options(null_round_size, counters=[c.name for c in counters],
+                                 conditional="unconditional" if type(workspace_generator) is UnconditionalWorkspace else
+                                 getattr(workspace_generator, "name", type(workspace_generator).__name__),
+                                 reference_stream=reference_stream, output_counts_pattern=output_counts_pattern,
+                                 output_samples_pattern=output_samples_pattern, output_stats=list(outfiles.keys()),
+                                 qvalue_method=kwargs.get("qvalue_method", None))
     if "sample_metrics" in outfiles:
         # (before anything is read or sampled)
         if type(workspace_generator) is not UnconditionalWorkspace:
@@ -556,7 +721,7 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
                         v = v / f if f > 0 else v
                     stat_vals[c.name][annotation] = v
         try:
-            r, _ = _sample_finish(job, stat_vals)
+            r, _ = _sample_finish_rounds(job, stat_vals) if null_round_size else _sample_finish(job, stat_vals)
         finally:
             if outf:
                 outf.close()
@@ -582,13 +747,15 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
                 continue
             ref = reference[track][annotation] if reference else None
             dev_stats = getattr(sampled_counts[track], "stats", None)
+            deep = isinstance(sampled_counts[track], _NullWordsPerTrack)     # the row's words instead of its samples
             rows.append(AnnotatorResultExtended(
                 track=track, annotation=annotation, counter=counter.name, observed=observed_value,
-                samples=sampled_counts[track][counter_id][annotation], track_segments=temp_segs,
+                samples=None if deep else sampled_counts[track][counter_id][annotation], track_segments=temp_segs,
                 annotation_segments=temp_annos, workspace=temp_workspace, reference=ref,
                 pseudo_count=pseudo_count, _sizes=sizes,
                 _stats=dev_stats[counter_id][annotation] if dev_stats else None,
-                _overlap=overlaps[track].get(annotation) if overlaps.get(track) else None))
+                _overlap=overlaps[track].get(annotation) if overlaps.get(track) else None,
+                _words=sampled_counts[track][counter_id][annotation] if deep else None))
         return rows
 
     inflight = collections.deque()
@@ -621,7 +788,8 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
                 job = _sample_start(segments[track], annotations, workspace, sampler, counters, num_samples, seed,
                                     samples_outfile=outf, workspace_generator=workspace_generator, mt_state=mt_state,
                                     _aflat=aflat, _shared=shared,
-                                    _metrics=(outfiles["sample_metrics"], track) if "sample_metrics" in outfiles else None)
+                                    _metrics=(outfiles["sample_metrics"], track) if "sample_metrics" in outfiles else None,
+                                    null_round_size=null_round_size)
             except Exception:
                 observed()           # (the reference has counted before it samples: an error there comes first)
                 raise
@@ -755,6 +923,17 @@ def buildParser(usage=None, samplers=SAMPLERS):
                  help="if the sampling method is 'shift', the region a segment is shifted within is its length times this "
                       "[default=%default]")
     g.add_option("-n", "--num-samples", dest="num_samples", type="int")
+    g.add_option("--null-round-size", dest="null_round_size", type="int",
+                 help="(not in the reference) draw the samples in rounds of this many and fold each round, on the GPU, into "
+                      "eight exact integers per row (count, sum, sum of squares, samples below and equal to the observed "
+                      "value, minimum, maximum) instead of holding the count matrix: memory no longer grows with "
+                      "--num-samples, so p-values can go down to 1 / num_samples for 10^7 samples and more.  The samples, and "
+                      "every column made from them, are those of the plain run -- except CI95low and CI95high, which are the "
+                      "interval of the FIRST round's min(round size, num-samples) samples (exact quantiles of a stream need a "
+                      "second pass or memory per value).  Not with --output-counts-pattern, --output-samples-pattern, "
+                      "--output-stats=sample_metrics / fdr_summary, --qvalue-method=minp / efdr, --conditional other than "
+                      "unconditional, --reference-stream or the counter nucleotide-density.  0: hold the matrix "
+                      "[default=%default]")
     g.add_option("--bucket-size", dest="bucket_size", type="int")
     g.add_option("--nbuckets", dest="nbuckets", type="int")
     parser.add_option_group(g)
@@ -802,7 +981,7 @@ def buildParser(usage=None, samplers=SAMPLERS):
     parser.set_defaults(input_filename_counts=None, output_stats=[], output_bed=[], output_filename_pattern="%s", output_force=False,
                         input_filename_results=None, input_filename_descriptions=None, annotation_files=[], annotations_label=None, annotations_to_points=None, bucket_size=0,
                         counters=[], enable_split_tracks=False, ignore_segment_tracks=True, isochore_files=[],
-                        nbuckets=100000, num_samples=1000, num_threads=0, output_counts_pattern=None,
+                        nbuckets=100000, num_samples=1000, null_round_size=0, num_threads=0, output_counts_pattern=None,
                         output_order="fold", output_samples_pattern=None, output_tables_pattern="%s.tsv.gz",
                         overlapping_annotations=False, pseudo_count=1.0, pvalue_method="empirical", qvalue_method="BH",
                         qvalue_lambda=None, qvalue_pi0_method="smoother",
@@ -830,6 +1009,7 @@ def _open_metrics_files(options):
 
 def fromSegments(options, args=None):
     """run an analysis from BED files: scripts/gat-run.py:77-220 of the reference."""
+    check_null_round_options_of(options)                     # (--null-round-size: refused before a file is read)
     segments, annotations, workspaces, isochores = IO.buildSegments(options)
     outfiles = _open_metrics_files(options)
     try:
@@ -874,7 +1054,9 @@ def fromSegments(options, args=None):
                    output_samples_pattern=options.output_samples_pattern, pseudo_count=options.pseudo_count,
                    num_threads=options.num_threads, random_seed=options.random_seed,
                    reference_stream=getattr(options, "reference_stream", False),
-                   sample_files=getattr(options, "sample_files", []), outfiles=outfiles)
+                   sample_files=getattr(options, "sample_files", []), outfiles=outfiles,
+                   null_round_size=getattr(options, "null_round_size", 0),
+                   qvalue_method=getattr(options, "qvalue_method", None))
     finally:
         for f in outfiles.values():
             if f is not getattr(options, "stdout", None):

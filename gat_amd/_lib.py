@@ -38,7 +38,9 @@ SYMBOLS = [
     "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch", "gat_sampler_last_launch",
     "gat_list_pair_hits", "gat_sample_pair_enrichment", "gat_list_geneset_hits", "gat_sample_geneset_enrichment",
     "gat_list_profile", "gat_sample_profile_enrichment", "gat_list_signal", "gat_sample_signal",
+    "gat_null_fold_reset", "gat_null_fold",
 ]
+NULL_FOLD_WORDS = 8           # GAT_NULL_FOLD_WORDS: n, sum, sumsq_lo, sumsq_hi, n_less, n_eq, min, max
 
 MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's position
 # gat_problem_desc::sampler (GAT_SAMPLER_*)
@@ -319,6 +321,10 @@ def lib():
     L.gat_problem_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.gat_null_stats.restype = C.c_int
     L.gat_null_stats.argtypes = [vp, vp, i64, i64, vp, vp, i64, i64, vp]
+    L.gat_null_fold_reset.restype = C.c_int
+    L.gat_null_fold_reset.argtypes = [vp, vp, i64]
+    L.gat_null_fold.restype = C.c_int
+    L.gat_null_fold.argtypes = [vp, vp, i64, i64, i64, vp, vp]
     L.gat_compare_stats.restype = C.c_int
     L.gat_compare_stats.argtypes = COMPARE_STATS_ARGTYPES
     L.gat_minp_counts.restype = C.c_int
@@ -466,6 +472,26 @@ class Context(object):
                                     _p(out)), self._h)
         out[:, 1] = np.sqrt(out[:, 1] / l)                # numpy.std's last two steps (sum of squares from the device)
         return out
+
+    def null_fold_reset(self, words_dev_ptr, n_rows):
+        """the eight words (NULL_FOLD_WORDS) of n_rows rows before anything is folded into them: zeros, min = 2^64 - 1"""
+        _check(lib().gat_null_fold_reset(self._h, C.c_void_p(words_dev_ptr), int(n_rows)), self._h)
+
+    def null_fold(self, counts_dev_ptr, n_rows, n_samples, row_stride, vals, words_dev_ptr):
+        """a round of a device count matrix -- the first n_samples slots of rows row_stride slots apart -- added to the rows'
+        words (gat_null_fold): n, sum, the 128-bit sum of squares, the samples below and equal to vals[row], min, max; exact
+        integers, whatever the cut into rounds.  Returns when the kernel has completed."""
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        assert len(vals) == int(n_rows)
+        _check(lib().gat_null_fold(self._h, C.c_void_p(counts_dev_ptr), int(n_rows), int(n_samples), int(row_stride), _p(vals),
+                                   C.c_void_p(words_dev_ptr)), self._h)
+
+    def null_fold_words(self, words_dev_ptr, n_rows):
+        """the words read back: n_rows tuples of NULL_FOLD_WORDS Python ints"""
+        w = np.zeros((int(n_rows), NULL_FOLD_WORDS), dtype=np.uint64)
+        if n_rows:
+            self.d2h(w, words_dev_ptr)
+        return [tuple(int(x) for x in row) for row in w.tolist()]
 
     def h2d(self, dev_ptr, host_array):
         host_array = np.ascontiguousarray(host_array)

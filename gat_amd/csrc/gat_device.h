@@ -355,6 +355,25 @@ __device__ __forceinline__ long long wave_max_i64(long long v) {
   for (int d = 32; d > 0; d >>= 1) { const long long o = __shfl_xor(v, d); v = o > v ? o : v; }
   return v;
 }
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_xor(v, d); v = o > v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_xor(v, d); v = o < v ? o : v; }
+  return v;
+}
+// the 128-bit sum (lo, hi) over the lanes, the carry of the low word taken into the high one at every step
+__device__ __forceinline__ void wave_sum_u128(unsigned long long& lo, unsigned long long& hi) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned long long ol = __shfl_xor(lo, d), oh = __shfl_xor(hi, d);
+    lo += ol;
+    hi += oh + (lo < ol ? 1ull : 0ull);
+  }
+}
 // all-lanes reduction on the DPP path (result broadcast from lane 63); id = identity of op
 template <typename Op>
 __device__ __forceinline__ int wave_reduce_dpp(int v, int id, Op op) {

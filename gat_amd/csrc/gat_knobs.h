@@ -76,6 +76,7 @@ struct gat_ctx;
   INT(count_staged, "GAT_COUNT_STAGED", 1)                                                                                   \
   INT(merged_samples_per_block, "GAT_MERGED_SAMPLES_PER_BLOCK", 4)                                                           \
   FLAG(count_lists_merged, "GAT_COUNT_LISTS_MERGED")                                                                         \
+  INT(null_fold_parts, "GAT_NULL_FOLD_PARTS", 0) /* gat_null_fold: workgroups a row is cut over, 1 .. 1024; default: by the launch */ \
   REAL(compare_scratch_mb, "GAT_COMPARE_SCRATCH_MB", 1024.0) /* gat_compare_stats: megabytes of transformed rows per batch */ \
   INT(coverage_window_bins, "GAT_COVERAGE_WINDOW_BINS", 1920) /* gat_sample_coverage: bins of a workgroup's LDS window */      \
   INT(coverage_samples_per_block, "GAT_COVERAGE_SAMPLES_PER_BLOCK", 0) /* ... its chunk of samples; default: by the launch */ \

@@ -38,6 +38,7 @@
 #include "gat_local_permute.h"
 #include "gat_brute_force.h"
 #include "gat_stats.h"
+#include "gat_null_fold.h"
 #include "gat_compare.h"
 #include "gat_minp.h"
 #include "gat_efdr.h"
@@ -1991,6 +1992,59 @@ extern "C" int gat_null_stats(gat_ctx* ctx, const void* counts_dev, int64_t n_ro
     HIPCHK(ctx, hipGetLastError());
   }
   HIPCHK(ctx, staged_d2h(ctx, out_host, d_out.p, (size_t)n_rows * 64));
+  return GAT_OK;
+}
+
+// A round of a count matrix folded into the rows' eight integer words (include/gat_mi355.h, gat_null_fold.h).
+static_assert(gat::kNullFoldWords == GAT_NULL_FOLD_WORDS, "gat_null_fold.h and gat_mi355.h disagree on the words of a row");
+extern "C" int gat_null_fold_reset(gat_ctx* ctx, uint64_t* words_dev, int64_t n_rows) {
+  if (!ctx || !words_dev || n_rows < 0) return set_err(ctx, GAT_ERR_ARG, "gat_null_fold_reset: bad argument");
+  if (n_rows == 0) return GAT_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int64_t n_words = n_rows * gat::kNullFoldWords;
+  hipLaunchKernelGGL(gat::k_null_fold_reset, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, ctx->stream,
+                     (unsigned long long*)words_dev, n_words);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return GAT_OK;
+}
+
+extern "C" int gat_null_fold(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t n_samples, int64_t row_stride,
+                             const double* vals_host, uint64_t* words_dev) {
+  if (!ctx || !counts_dev || !vals_host || !words_dev) return set_err(ctx, GAT_ERR_ARG, "gat_null_fold: NULL argument");
+  if (n_rows < 0 || n_samples < 1 || row_stride < n_samples)
+    return set_err(ctx, GAT_ERR_ARG, "gat_null_fold: bad row count / sample count / row stride");
+  if (n_rows == 0) return GAT_OK;
+  // val as two integers: v < val is v < lt, v == val is v == eq (gat_null_fold.h)
+  std::vector<unsigned long long> lt((size_t)n_rows), eq((size_t)n_rows);
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const double val = vals_host[r];
+    if (!std::isfinite(val)) return set_err(ctx, GAT_ERR_ARG, "gat_null_fold: the value of row %lld is not finite", (long long)r);
+    const double c = std::ceil(val);
+    lt[(size_t)r] = c <= 0.0 ? 0ull : c >= 9223372036854775808.0 ? 1ull << 63 : (unsigned long long)c;
+    eq[(size_t)r] = (c == val && c >= 0.0 && c < 9223372036854775808.0) ? (unsigned long long)c : gat::kNullFoldNoEq;
+  }
+  const Knobs kn = read_knobs(ctx);                 // the call's
+  if (kn.null_fold_parts < 0 || kn.null_fold_parts > 1024) return set_err(ctx, GAT_ERR_ARG, "gat_null_fold: GAT_NULL_FOLD_PARTS must be 0 .. 1024");
+  // a row is cut over several workgroups when the rows alone do not fill the device, down to 4 096 samples a workgroup
+  int64_t parts = kn.null_fold_parts;
+  if (parts == 0) parts = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(1024, 2048 / n_rows), n_samples / 4096));
+  const int64_t chunk = (n_samples + parts - 1) / parts;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  DevBuf<unsigned long long> d_lt, d_eq;
+  HIPCHK(ctx, d_lt.upload(lt, ctx));
+  HIPCHK(ctx, d_eq.upload(eq, ctx));
+  gat::NullFoldArgs A;
+  A.row_stride = row_stride; A.S = n_samples; A.chunk = chunk;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += 1 << 20) {                // (grid x: rows)
+    const int64_t nr = std::min<int64_t>(n_rows - r0, 1 << 20);
+    A.counts = (const unsigned long long*)counts_dev + r0 * row_stride; A.lt = d_lt.p + r0; A.eq = d_eq.p + r0;
+    A.words = (unsigned long long*)words_dev + r0 * gat::kNullFoldWords;
+    hipLaunchKernelGGL(gat::k_null_fold, dim3((unsigned)nr, (unsigned)parts), dim3(gat::kNullFoldThreads), 0, ctx->stream, A);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  HIPCHK(ctx, stage_flush(ctx));                    // (the two uploads have left the staging buffer)
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return GAT_OK;
 }
 

@@ -1544,9 +1544,42 @@ def twoSidedPValueFromCounts(n_less, n_eq, above_expected, l):  # noqa: E741
     return max(1.0 / l, float(idx) / l)
 
 
+class _NoSamples(object):
+    """stands where a row's samples would be when the row was built from its null words: it has their number, and asking
+    for the samples themselves (.samples, getSample, a p-value for another value, minp / efdr) says why there are none"""
+    __slots__ = ("n",)
+
+    def __init__(self, n):
+        self.n = int(n)
+
+    def __len__(self):
+        return self.n
+
+    def error(self):
+        return ValueError("this row was built from the integer words of a null distribution folded in rounds "
+                          "(null_round_size / --null-round-size): its %d samples were never kept" % self.n)
+
+    def __array__(self, dtype=None, copy=None):
+        raise self.error()
+
+
+def nullWordsStatistics(words):
+    """(n, mean, stddev) of a null distribution from its eight integer words (gat_null_fold: n, sum, sumsq_lo, sumsq_hi,
+    n_less, n_eq, min, max), in Python ints: mean = sum / n, the division of two ints, correctly rounded -- numpy.mean's
+    number whenever sum < 2^53, where sums of integer-valued doubles are exact; stddev = sqrt((n * sumsq - sum^2) / n^2),
+    one rounding for the division and one for the root."""
+    n, total = int(words[0]), int(words[1])
+    sumsq = int(words[2]) + (int(words[3]) << 64)
+    if n < 1:
+        raise ValueError("no samples")
+    return n, total / n, math.sqrt((n * sumsq - total * total) / (n * n))
+
+
 class AnnotatorResult(object):
     """gat/Engine.pyx:1725 / makeEnrichmentStatistics :1635-1718 (numpy on the host; identical
     IEEE arithmetic: numpy.mean/std, sorted-value lookups)."""
+
+    null_words = None          # the row's eight words when it was built from them instead of from samples (_words)
 
     format_observed = "%i"
     format_expected = "%6.4f"
@@ -1557,10 +1590,18 @@ class AnnotatorResult(object):
     headers = ["track", "annotation", "observed", "expected", "CI95low", "CI95high", "stddev", "fold", "l2fold",
                "pvalue", "qvalue"]
 
-    def __init__(self, track, annotation, counter, observed, samples, reference=None, pseudo_count=1.0, _stats=None):
+    def __init__(self, track, annotation, counter, observed, samples, reference=None, pseudo_count=1.0, _stats=None, _words=None):
         """_stats: (mean, std, value at the lower / upper interval position, samples < val, samples == val) of `samples`
-        as gat_null_stats computed them on the device (val = observed, or observed / reference.fold); None = numpy here."""
+        as gat_null_stats computed them on the device (val = observed, or observed / reference.fold); None = numpy here.
+        _words: (the row's eight words, lower interval value, upper interval value) of a run that folded its samples in
+        rounds (run(null_round_size=...)): `samples` is None, the row holds no samples -- nsamples = n, null_words = the words,
+        the statistics come from nullWordsStatistics, the counts behind the p-value are the words' own."""
         self.track, self.annotation, self.counter = track, annotation, counter
+        if _words is not None:
+            self.null_words = tuple(int(w) for w in _words[0])
+            n, mean, std = nullWordsStatistics(self.null_words)
+            _stats = (mean, std, _words[1], _words[2], self.null_words[4], self.null_words[5])
+            samples = _NoSamples(n)
         # the reference builds a Python list of floats and sorts it; the same numbers come out of array operations
         # without the sort (two order statistics by selection, the p-value from two counts), which is what keeps
         # 1000 tracks x 100 000 samples from spending longer here than on the GPU
@@ -1618,6 +1659,8 @@ class AnnotatorResult(object):
 
     @property
     def _samples(self):
+        if isinstance(self._raw, _NoSamples):
+            raise self._raw.error()
         if self._samples_cache is None:
             self._samples_cache = np.array(self._raw, dtype=np.float64)
             self._raw = None
@@ -1661,11 +1704,11 @@ class AnnotatorResultExtended(AnnotatorResult):
         "percent_overlap_nsegments_annotation", "percent_overlap_size_annotation"]
 
     def __init__(self, track, annotation, counter, observed, samples, track_segments, annotation_segments,
-                 workspace, reference=None, pseudo_count=1.0, _sizes=None, _stats=None, _overlap=None):
+                 workspace, reference=None, pseudo_count=1.0, _sizes=None, _stats=None, _overlap=None, _words=None):
         """_overlap: (segments, bases) of the intersection of the two dictionaries when the caller has them already
         (overlap_sizes: every annotation of a run in one call)."""
         AnnotatorResult.__init__(self, track, annotation, counter, observed, samples, reference=reference,
-                                 pseudo_count=pseudo_count, _stats=_stats)
+                                 pseudo_count=pseudo_count, _stats=_stats, _words=_words)
         sizes = _sizes if _sizes is not None else {}
 
         def cached(obj):                               # (counts, sum) of a dictionary, once per object and run()

@@ -850,6 +850,26 @@ int gat_null_stats(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t
                    const uint8_t* is_double_host, const double* vals_host, int64_t lo_index, int64_t hi_index,
                    double* out_host);
 
+/* ---- a null distribution deeper than a count matrix: rounds folded into integer words --------
+ * gat_null_stats needs the whole null distribution of a row in one matrix.  A run that draws more samples than a matrix
+ * holds draws them in rounds into ONE buffer (sample s is the same sample whichever call draws it: the per-unit contract)
+ * and folds every round, where gat_sample_and_count left it, into GAT_NULL_FOLD_WORDS uint64 words per row:
+ *     n   sum of v   sumsq_lo, sumsq_hi: the sum of v * v modulo 2^128   n_less = #{v < val}   n_eq = #{v == val}   min   max
+ * counts_dev: n_rows rows of non-negative int64 (0 <= v < 2^63; not the IEEE rows of nucleotide-density), of which the
+ * first n_samples slots are used; rows lie row_stride >= n_samples slots apart (a run's last, short round reuses the
+ * buffer).  vals_host[r]: the value the row's p-value will be asked for.  Integer arithmetic only: the host turns val into
+ * ceil(val) clamped to [0, 2^63] (for an integer v, v < val is v < ceil(val)) and into the integer v has to equal, none when
+ * val is not an integer a slot can hold; v * v is the full 128-bit product, added with its carry; sum is modulo 2^64 (a
+ * caller that wants it keeps n * max below that).  words_dev += this round: the words of disjoint sample ranges add, in
+ * any order and under any launch shape -- GAT_NULL_FOLD_PARTS (a context option, default 0: by the launch, else 1 .. 1024)
+ * is the number of workgroups a row is cut over and changes no word.  gat_null_fold_reset: all words 0, min = 2^64 - 1.
+ * Both return after their kernel has completed.  n_rows == 0: GAT_OK, nothing touched.  GAT_ERR_ARG: a NULL argument,
+ * n_rows < 0, n_samples < 1, row_stride < n_samples, a val that is NaN or infinite, the option out of range. */
+#define GAT_NULL_FOLD_WORDS 8   /* n, sum, sumsq_lo, sumsq_hi, n_less, n_eq, min, max -- uint64 each */
+int gat_null_fold_reset(gat_ctx* ctx, uint64_t* words_dev, int64_t n_rows);
+int gat_null_fold(gat_ctx* ctx, const void* counts_dev, int64_t n_rows, int64_t n_samples, int64_t row_stride,
+                  const double* vals_host, uint64_t* words_dev);
+
 /* ---- gat-compare: the null distribution of a fold-change difference, and its statistics -------
  * What scripts/gat-compare.py:214-231 of the reference forms for a pair (data1, data2) of result rows read from counts
  * files, and what AnnotatorResult then takes from it, without the row ever existing on the host.  a_dev / b_dev: DEVICE
