@@ -10,7 +10,7 @@ import numpy as np
 from . import intervals, problem, synthetic            # noqa: F401
 from . import io as IO                                   # noqa: F401
 from . import stats as Stats                             # noqa: F401
-from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerBruteForce,  # noqa: F401
+from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerBruteForce, SamplerCircular,  # noqa: F401
                      Counter, computeCountsAll, overlap_sizes, CounterNucleotideOverlap, CounterNucleotideDensity, CounterSegmentOverlap,
                      CounterSegmentMidpointOverlap, CounterAnnotationOverlap, CounterAnnotationMidpointOverlap,
                      UnconditionalWorkspace, ConditionalWorkspaceCooccurance, ConditionalWorkspaceCentered,
@@ -647,9 +647,9 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
             seed = int(box[0])
     conditional = getattr(workspace_generator, "is_conditional", False)
     if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation,
-                                SamplerBruteForce)):
+                                SamplerBruteForce, SamplerCircular)):
         raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation and SamplerBruteForce run on the GPU path")
+                                  "SamplerLocalPermutation, SamplerBruteForce and SamplerCircular run on the GPU path")
     if _dist_state()[0] != 0:
         outfiles = {}                # (one writer: rank 0 computes and writes the metrics, all samples, no sharding)
     if "segment_metrics" in outfiles:
@@ -664,6 +664,8 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
         raise NotImplementedError("reference_stream: SamplerLocalPermutation runs on the per-unit streams only")
     if reference_stream and isinstance(sampler, SamplerBruteForce):
         raise NotImplementedError("reference_stream: SamplerBruteForce runs on the per-unit streams only")
+    if reference_stream and isinstance(sampler, SamplerCircular):
+        raise NotImplementedError("reference_stream: SamplerCircular runs on the per-unit streams only")
     if reference_stream:
         # the reference's own stream: numpy.random.seed(seed) once (scripts/gat-run.py:267-271), every work unit of every
         # segment track drawing from it in order -- an unpatched reference's table, number for number, at one stream's speed
@@ -856,12 +858,15 @@ ALL_SAMPLERS = SAMPLERS + ("local-permutation",)
 # builds SamplerUniform without its increment): what scripts/gat-run.py passes.  A run whose sampling does not converge
 # ends in the reference's ValueError (DESIGN §5 "k_brute_force").
 CLI_SAMPLERS = ALL_SAMPLERS + ("brute-force",)
+# ... and TOOL_SAMPLERS circular, the one sampler here that the reference does not have (DESIGN §5 "k_circular"): what
+# scripts/gat-run.py and the tool scripts pass.  The tuples above stay as they were, as before.
+TOOL_SAMPLERS = CLI_SAMPLERS + ("circular",)
 
 
 def buildParser(usage=None, samplers=SAMPLERS):
     """gat command line parser: the options of the reference's buildParser (gat/__init__.py:54-429)
     that concern the accelerated path, with the same names, destinations and defaults.  `samplers`: the choices of
-    --sampler (SAMPLERS, ALL_SAMPLERS, or CLI_SAMPLERS as scripts/gat-run.py passes)."""
+    --sampler (SAMPLERS, ALL_SAMPLERS, CLI_SAMPLERS, or TOOL_SAMPLERS as scripts/gat-run.py passes)."""
     import optparse
     parser = optparse.OptionParser(version="%prog (gat_amd " + __version__ + ")", usage=usage)
     g = optparse.OptionGroup(parser, "Input options")
@@ -1029,6 +1034,8 @@ def fromSegments(options, args=None):
             sampler = SamplerLocalPermutation()              # scripts/gat-run.py:135-136
         elif options.sampler == "brute-force":
             sampler = SamplerBruteForce()                    # scripts/gat-run.py:139-140 (no bucket arguments: bucket_size 1)
+        elif options.sampler == "circular":
+            sampler = SamplerCircular()
         else:
             raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
         counters = []

@@ -136,9 +136,10 @@ struct gat_ctx {
 inline bool count_lists_staged(const Knobs& kn, int64_t max_m) { return max_m > 0 && max_m + 4 <= kn.count_lds_entries; }
 
 // gat_problem_desc::sampler: the samplers there are; those whose kernel is a wave per work unit with its stream in LDS
-// (k_shift, k_permute, k_permute_local, k_brute_force: no k_rng + k_place in front).  sampler_draws_lengths: gat_prep_units.h
+// (k_shift, k_permute, k_permute_local, k_brute_force, k_circular: no k_rng + k_place in front).  sampler_draws_lengths: gat_prep_units.h
 inline bool sampler_runs_wave_per_unit(int32_t s) {
-  return s == GAT_SAMPLER_SHIFT || s == GAT_SAMPLER_GLOBAL_PERMUTATION || s == GAT_SAMPLER_LOCAL_PERMUTATION || s == GAT_SAMPLER_BRUTE_FORCE;
+  return s == GAT_SAMPLER_SHIFT || s == GAT_SAMPLER_GLOBAL_PERMUTATION || s == GAT_SAMPLER_LOCAL_PERMUTATION || s == GAT_SAMPLER_BRUTE_FORCE ||
+         s == GAT_SAMPLER_CIRCULAR;
 }
 inline bool sampler_is_known(int32_t s) { return s == GAT_SAMPLER_ANNOTATOR || s == GAT_SAMPLER_SEGMENTS || sampler_runs_wave_per_unit(s); }
 
@@ -339,7 +340,7 @@ struct PrepTimer {
   }
 };
 
-int check_list(gat_ctx* ctx, const gat_segment* s, int64_t n, const char* what, int64_t idx);
+int check_list(gat_ctx* ctx, const gat_segment* s, int64_t n, const char* what, int64_t idx, bool wide = false);
 
 // host threads for the per-list / per-contig preparation of gat_problem_create, the observed counts' tables and the input
 // statistics (GAT_HOST_THREADS, default min(16, cores)): ONE pool per process, created at the first use and kept -- a
@@ -404,6 +405,11 @@ struct gat_problem {
   DevBuf<uint32_t> d_lperm_len;
   int32_t lperm_max_n = 0;               // ... the most working segments of one piece, the longest raw list (sum of 2n) of a unit
   int64_t lperm_max_out = 0;
+  // GAT_SAMPLER_CIRCULAR: per unit {offset into d_circ_iv, n, |W|, Wsum}; the working list in linear workspace coordinates
+  // {linear start, length} (gat_prep_units.h: circular_intervals).  W and its cumulated lengths are the unit's part of d_ws and
+  // d_ws_cdf (cumulated - 1)
+  DevBuf<uint4> d_circ_unit;
+  DevBuf<uint2> d_circ_iv;
   // GAT_SAMPLER_BRUTE_FORCE: SamplerBruteForce(ntries_inner, ntries_outer) (the desc's 0 replaced by the reference's 100 / 10)
   int32_t brute_ntries_inner = 100, brute_ntries_outer = 10;
   gat_annotations* anno = nullptr;       // the annotation tables: its own (made from the lists of its desc) or a shared object

@@ -36,6 +36,7 @@
 #include "gat_shift.h"
 #include "gat_permute.h"
 #include "gat_local_permute.h"
+#include "gat_circular.h"
 #include "gat_brute_force.h"
 #include "gat_stats.h"
 #include "gat_null_fold.h"
@@ -639,6 +640,16 @@ static int enqueue_permute_local(gat_ctx* ctx, gat_problem* P, const BatchPlan& 
   H.no_normalize = B.kn.exp_lperm_no_normalize ? 1 : 0;
   return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_permute_local, H,
                               (size_t)(gat::kMtLdsWords + 2 * gat::kLpBatchDraws + words) * 4);
+}
+
+// SamplerCircular: k_circular
+static int enqueue_circular(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
+  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerCircular has no reference-stream mode");
+  gat::CircularArgs H;
+  memset(&H, 0, sizeof(H));
+  H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.circ_unit = P->d_circ_unit.p; H.circ_iv = P->d_circ_iv.p;
+  // (LDS for the generator's state alone: the intervals are read where they lie and the pieces go straight to the slab)
+  return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_circular, H, (size_t)gat::kMtLdsWords * 4);
 }
 
 // SamplerBruteForce: k_brute_force
@@ -1260,6 +1271,7 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
     else if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) rc = enqueue_permute(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) rc = enqueue_permute_local(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) rc = enqueue_brute_force(ctx, P, B, seed, begin);
+    else if (P->sampler == GAT_SAMPLER_CIRCULAR) rc = enqueue_circular(ctx, P, B, seed, begin);
     else rc = enqueue_placement_sampler(ctx, P, B, seed, begin, A);
     if (rc) return rc;
   }
@@ -1661,7 +1673,8 @@ extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const i
   const char* const per_unit_only = P->sampler == GAT_SAMPLER_SHIFT ? "SamplerShift"      // (the list samplers: no k_serial)
                                   : P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION ? "SamplerGlobalPermutation"
                                   : P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION ? "SamplerLocalPermutation"
-                                  : P->sampler == GAT_SAMPLER_BRUTE_FORCE ? "SamplerBruteForce" : nullptr;
+                                  : P->sampler == GAT_SAMPLER_BRUTE_FORCE ? "SamplerBruteForce"
+                                  : P->sampler == GAT_SAMPLER_CIRCULAR ? "SamplerCircular" : nullptr;
   if (per_unit_only) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: %s runs on the per-unit streams only", per_unit_only);
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
   const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state, false);

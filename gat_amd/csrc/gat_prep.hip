@@ -292,12 +292,12 @@ void host_pool_run(int64_t n, void (*fn)(void*, int64_t), void* arg) {
   P->run_mutex.unlock();
 }
 
-int check_list(gat_ctx* ctx, const gat_segment* s, int64_t n, const char* what, int64_t idx) {
+int check_list(gat_ctx* ctx, const gat_segment* s, int64_t n, const char* what, int64_t idx, bool wide) {
   for (int64_t i = 0; i < n; ++i) {
     if (s[i].start >= s[i].end)
       return set_err(ctx, GAT_ERR_ASSERT, "%s list %lld is not normalized: empty/invalid segment %u-%u", what,
                      (long long)idx, s[i].start, s[i].end);
-    if (s[i].end >= 0x80000000u)
+    if (!wide && s[i].end >= 0x80000000u)
       return set_err(ctx, GAT_ERR_ARG, "%s list %lld: coordinate %u >= 2^31 not supported", what, (long long)idx, s[i].end);
     if (i > 0 && s[i - 1].end > s[i].start)
       return set_err(ctx, GAT_ERR_ASSERT, "%s list %lld is not normalized: %u-%u overlaps/precedes %u-%u", what,
@@ -1029,8 +1029,11 @@ struct UnitTables {
   std::vector<uint2> perm_w;
   std::vector<uint4> lperm_unit, lperm_piece;      // GAT_SAMPLER_LOCAL_PERMUTATION: gat_problem::d_lperm_*
   std::vector<uint32_t> lperm_len;
+  std::vector<uint4> circ_unit;                    // GAT_SAMPLER_CIRCULAR: gat_problem::d_circ_*
+  std::vector<uint2> circ_iv;
   explicit UnitTables(size_t n)                    // (per-unit arrays: at least one element, for the upload)
-      : len_cv2(n, 0.0), shift_off(n, 0), perm_unit(n, make_uint4(0u, 0u, 0u, 0u)), lperm_unit(n, make_uint4(0u, 0u, 0u, 0u)) {}
+      : len_cv2(n, 0.0), shift_off(n, 0), perm_unit(n, make_uint4(0u, 0u, 0u, 0u)), lperm_unit(n, make_uint4(0u, 0u, 0u, 0u)),
+        circ_unit(n, make_uint4(0u, 0u, 0u, 0u)) {}
 };
 
 static int check_problem_desc(gat_ctx* ctx, const gat_problem_desc* d) {
@@ -1083,6 +1086,10 @@ static void append_sampler_tables(gat_problem* P, UnitTables& T, int u, const Un
     P->lperm_max_n = std::max<int32_t>(P->lperm_max_n, (int32_t)R.lperm_max_n);
     P->lperm_max_out = std::max<int64_t>(P->lperm_max_out, 2 * R.lperm_sum_n);
   }
+  if (P->sampler == GAT_SAMPLER_CIRCULAR) {
+    T.circ_unit[(size_t)u] = make_uint4((uint32_t)T.circ_iv.size(), (uint32_t)R.circ_iv.size(), (uint32_t)R.ws.size(), R.cdf.back() + 1u);
+    T.circ_iv.insert(T.circ_iv.end(), R.circ_iv.begin(), R.circ_iv.end());
+  }
   if (P->sampler == GAT_SAMPLER_SHIFT) {
     T.shift_off[(size_t)u] = (int32_t)(T.shift.size() / 2);
     T.shift.insert(T.shift.end(), R.shift.begin(), R.shift.end());
@@ -1105,8 +1112,9 @@ static int gather_unit_tables(gat_ctx* ctx, const gat_problem_desc* d, const Kno
     const int64_t nus = d->seg_off[u + 1] - d->seg_off[u];
     if (R.rc == GAT_ERR_ASSERT) {                    // (the first offender in unit order, with the reference's message)
       int rc;
-      if ((rc = check_list(ctx, d->segs + d->seg_off[u], nus, "segment", u))) return rc;                                   // gat/Engine.pyx:535
-      if ((rc = check_list(ctx, d->ws + d->ws_off[u], d->ws_off[u + 1] - d->ws_off[u], "workspace", u))) return rc;       // gat/Engine.pyx:536
+      const bool wide = sampler_takes_wide_coordinates(*d);
+      if ((rc = check_list(ctx, d->segs + d->seg_off[u], nus, "segment", u, wide))) return rc;                                   // gat/Engine.pyx:535
+      if ((rc = check_list(ctx, d->ws + d->ws_off[u], d->ws_off[u + 1] - d->ws_off[u], "workspace", u, wide))) return rc;       // gat/Engine.pyx:536
     }
     if (R.rc) return set_err(ctx, R.rc, "%s", R.err.c_str());
     if (!R.active) continue;
@@ -1268,7 +1276,7 @@ static int64_t rng_rows_for_unit(const gat_problem* P, const Knobs& kn, const Un
 }
 
 static void size_rng_rows(gat_problem* P, const gat_problem_desc* d, const Knobs& kn, const UnitTables& T) {
-  // (k_shift, k_permute, k_permute_local, k_brute_force: a wave per work unit, its stream in LDS)
+  // (k_shift, k_permute, k_permute_local, k_brute_force, k_circular: a wave per work unit, its stream in LDS)
   if (kn.sampler_mode == "wave" || sampler_runs_wave_per_unit(P->sampler)) P->sampler_mode = 0;
   for (int32_t u : P->h_order) {
     const int64_t rows = rng_rows_for_unit(P, kn, P->h_units[(size_t)u], d->ws + d->ws_off[u], d->ws_off[u + 1] - d->ws_off[u], T.len_cv2[(size_t)u]);
@@ -1291,6 +1299,11 @@ static int upload_sampler_tables(gat_ctx* ctx, gat_problem* P, UnitTables& T) {
     HIPCHK(ctx, P->d_perm_len.upload(T.perm_len, ctx));
     HIPCHK(ctx, P->d_perm_w.upload(T.perm_w, ctx));
     HIPCHK(ctx, P->d_perm_cum.upload(T.perm_cum, ctx));
+  }
+  if (P->sampler == GAT_SAMPLER_CIRCULAR) {
+    if (T.circ_iv.empty()) T.circ_iv.push_back(make_uint2(0u, 0u));
+    HIPCHK(ctx, P->d_circ_unit.upload(T.circ_unit, ctx));
+    HIPCHK(ctx, P->d_circ_iv.upload(T.circ_iv, ctx));
   }
   if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) {
     if (T.lperm_piece.empty()) T.lperm_piece.push_back(make_uint4(0u, 0u, 0u, 0u));

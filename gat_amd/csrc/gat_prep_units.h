@@ -24,6 +24,13 @@ inline bool sampler_draws_lengths(int32_t s) {
   return s == GAT_SAMPLER_ANNOTATOR || s == GAT_SAMPLER_SEGMENTS || s == GAT_SAMPLER_BRUTE_FORCE;
 }
 
+// SamplerCircular computes on 64-bit linear positions and never leaves the workspace, so a problem that only samples -- no
+// annotation tracks, no isochore keys: nothing is counted or merged -- takes the whole uint32 range; whatever counts or merges
+// compares coordinates as the reference's int32 lmin / lmax do and stays below 2^31
+inline bool sampler_takes_wide_coordinates(const gat_problem_desc& d) {
+  return d.sampler == GAT_SAMPLER_CIRCULAR && d.n_tracks == 0 && !d.merge_contigs;
+}
+
 // Lmax: the largest value length_draw (gat_annotator_steps.h) can return on a unit's rank table {0, the buckets of its
 // hist_total working segments in ascending order}.  The rank drawn is 1 + [0, hist_total - 2] (the reference's
 // randint(1, total_size) excludes total_size, gat/Engine.pyx:420; rank 1 when hist_total is 1), so the largest bucket
@@ -57,6 +64,7 @@ struct UnitPrep {
   std::vector<uint2> perm_w;
   std::vector<uint32_t> perm_cum;
   int64_t perm_free = 0;
+  std::vector<uint2> circ_iv;          // GAT_SAMPLER_CIRCULAR: the working list in linear workspace coordinates {start, length}
   std::vector<uint4> lperm;            // GAT_SAMPLER_LOCAL_PERMUTATION: the active pieces, the sum and maximum of their n
   int64_t lperm_sum_n = 0, lperm_max_n = 0;
   int64_t nwork = 0;
@@ -136,6 +144,26 @@ inline int64_t permute_tables(std::vector<uint2>& w, std::vector<uint32_t>& cum,
   return sum - total;
 }
 
+// SamplerCircular (no counterpart in the reference; DESIGN.md section 5, "k_circular"): the working list -- the unit's
+// segments cut to the workspace -- in LINEAR workspace coordinates: a base of piece j at genome position x has the linear
+// position x minus the gaps before it, cum(j - 1) + (x - start_j).  Pieces that touch in linear coordinates are united, so a
+// segment bridging a workspace gap is one interval; the workspace's own pieces stay apart, touching or not.  Appends the
+// intervals {linear start, length}, sorted, disjoint and non-touching.  cdf: the cumulated lengths - 1 (UnitPrep::cdf).
+inline void circular_intervals(std::vector<uint2>& out, const gat_segment* us, int64_t nus, const gat_segment* uw, int64_t nuw,
+                               const std::vector<uint32_t>& cdf) {
+  for (int64_t i = 0; i < nus; ++i) {
+    const uint32_t s = us[i].start, e = us[i].end;
+    const gat_segment* it = std::lower_bound(uw, uw + nuw, s, [](const gat_segment& a, uint32_t v) { return a.end <= v; });
+    for (; it != uw + nuw && it->start < e; ++it) {
+      const int64_t j = it - uw;
+      const uint32_t gs = std::max(s, it->start), ge = std::min(e, it->end);
+      const uint32_t ls = (j ? cdf[(size_t)j - 1] + 1u : 0u) + (gs - it->start);
+      if (!out.empty() && out.back().x + out.back().y == ls) out.back().y += ge - gs;
+      else out.push_back(make_uint2(ls, ge - gs));
+    }
+  }
+}
+
 // SamplerLocalPermutation (gat/Engine.pyx:1174-1188): per workspace piece (ws, we) the working segments are
 // getOverlappingSegments' set (gat/SegmentList.pyx:952-983) -- from the last segment with start <= ws (the first one when
 // there is none) on, every segment with start <= we, whether or not it reaches the piece --, a contiguous run of the
@@ -189,6 +217,8 @@ inline int64_t base_cap_for(int32_t sampler, const Knobs& kn, const UnitDev& U, 
     case GAT_SAMPLER_GLOBAL_PERMUTATION: return 2 * R.nwork + (int64_t)R.perm_w.size();
     // (exact: two slots per working segment of every piece -- a segment gives one piece, two where it wraps; a piece of
     //  more working segments than LDS holds keeps its lengths and points at the top of the region)
+    // (exact: an interval gives one piece and one more per border of the workspace or wrap it crosses, |W| over the list)
+    case GAT_SAMPLER_CIRCULAR: return (int64_t)R.circ_iv.size() + (int64_t)R.ws.size();
     case GAT_SAMPLER_LOCAL_PERMUTATION: return 2 * R.lperm_sum_n + (R.lperm_max_n > 2048 ? 2 * R.lperm_max_n : 0);
     default: return cap_for(kn, R.nwork);
   }
@@ -281,10 +311,10 @@ inline std::vector<uint32_t> build_cdf_grid(const std::vector<uint32_t>& cdf, in
   return grid;
 }
 
-// what check_list (gat_prep.hip) reports, as a yes or no
-inline bool list_is_normalized(const gat_segment* l, int64_t n) {
+// what check_list (gat_prep.hip) reports, as a yes or no.  wide: coordinates up to 2^32 - 1 (sampler_takes_wide_coordinates)
+inline bool list_is_normalized(const gat_segment* l, int64_t n, bool wide = false) {
   for (int64_t i = 0; i < n; ++i)
-    if (l[i].start >= l[i].end || l[i].end >= 0x80000000u || (i > 0 && l[i - 1].end > l[i].start)) return false;
+    if (l[i].start >= l[i].end || (!wide && l[i].end >= 0x80000000u) || (i > 0 && l[i - 1].end > l[i].start)) return false;
   return true;
 }
 
@@ -305,8 +335,9 @@ inline void prepare_unit(const gat_problem_desc& d, const Knobs& kn, int u, Unit
   const gat_segment* uw = d.ws + d.ws_off[u];
   const int64_t nuw = d.ws_off[u + 1] - d.ws_off[u];
   if (nus == 0 || nuw == 0) return;
-  if (!list_is_normalized(us, nus)) { R.rc = GAT_ERR_ASSERT; R.err = "segment"; return; }       // gat/Engine.pyx:535-536: both
-  if (!list_is_normalized(uw, nuw)) { R.rc = GAT_ERR_ASSERT; R.err = "workspace"; return; }     // lists normalized
+  const bool wide = sampler_takes_wide_coordinates(d);
+  if (!list_is_normalized(us, nus, wide)) { R.rc = GAT_ERR_ASSERT; R.err = "segment"; return; }       // gat/Engine.pyx:535-536: both
+  if (!list_is_normalized(uw, nuw, wide)) { R.rc = GAT_ERR_ASSERT; R.err = "workspace"; return; }     // lists normalized
   const bool local = d.sampler == GAT_SAMPLER_LOCAL_PERMUTATION;
   if (local) {
     // the unit is active when some piece has a working segment (the segment in front of a piece counts): not filter()'s rule
@@ -398,5 +429,10 @@ inline void prepare_unit(const gat_problem_desc& d, const Knobs& kn, int u, Unit
   }
   if (local || d.sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) R.lens = std::move(lens);
   R.nwork = local ? R.lperm_sum_n : nwork;       // (the launch order: the longest draw chain first)
+  if (d.sampler == GAT_SAMPLER_CIRCULAR) {
+    circular_intervals(R.circ_iv, us, nus, uw, nuw, R.cdf);
+    U.hist_total = (uint32_t)R.circ_iv.size();   // (n: the intervals the kernel maps, at most the working segments' pieces)
+    R.nwork = (int64_t)R.circ_iv.size();
+  }
   R.active = true;
 }

@@ -1333,6 +1333,38 @@ class SamplerBruteForce(Sampler):
         return r
 
 
+class SamplerCircular(Sampler):
+    """The circular-shift null (regioneR's circularRandomizeRegions, GenometriCorr's permutations; the reference has no such
+    sampler): the working list -- the segments cut to the workspace -- is rotated as a whole by one offset r = randint(0,
+    workspace bases) along the workspace with its gaps taken out, wrapping at its end.  Every length and every gap between
+    segments stays as it is; only the position relative to the annotations changes.  The rotated intervals are cut at the
+    workspace borders they cross and at the wrap, and nothing is united afterwards: the list is sorted and free of overlap,
+    touching pieces are kept apart.  Same per-unit stream convention as SamplerAnnotator.sample (numpy's).  No parameters."""
+
+    kind = 6
+
+    def __init__(self):
+        pass
+
+    def sample(self, segments, workspace, seed=None):
+        assert workspace.isNormalized, "workspace is not normalized"
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 32))
+        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
+            return SegmentList()
+        s, w = segments.asArray(), workspace.asArray()
+        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
+                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], sampler=self.kind)
+        P = _lib.Problem(get_context(), flat)
+        try:
+            seg, _ = P.sample(seed, 0, 1)
+        finally:
+            P.close()
+        r = SegmentList(array=seg)
+        r.isNormalized = 1
+        return r
+
+
 class Counter(object):
     name = None
 
