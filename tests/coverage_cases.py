@@ -1,6 +1,7 @@
 """Problems of the gat_sample_coverage tests (tests/test_coverage_gpu.py).  TEST INFRASTRUCTURE ONLY.
 
-Unit problems (one contig per unit, no annotations: sampler_edges.units_flat) for every sampler, the hand-built problem of the
+Unit problems (one contig per unit, no annotations: sampler_edges.units_flat) for every sampler (SIX: the six samplers the name
+is from, and SamplerCircular's three problems, tests/circular_cases.py), the hand-built problem of the
 window-edge test, the one whose bins pass 2^32, and what the tests need of a problem: its contigs' workspace extents.
 """
 import random
@@ -8,6 +9,7 @@ import random
 import numpy as np
 
 import brute_force_edges as BF
+import circular_cases as CIRC
 import local_permutation_edges as LP
 import sampler_edges as E
 from gat_amd import problem, synthetic
@@ -70,7 +72,11 @@ SIX = {
     "segments-genome-isochores": lambda: genome_problem(SEGMENTS, True),
     "shift-genome-isochores": lambda: genome_problem(E.SHIFT, True),
     "global-permutation-genome-isochores": lambda: genome_problem(E.PERM, True),
+    "circular-units": lambda: CIRC.units_flat(CIRC.consumer_units()),            # touching pieces, lists longer than the unit
+    "circular-genome": lambda: genome_problem(CIRC.CIRCULAR, False),
+    "circular-genome-isochores": lambda: genome_problem(CIRC.CIRCULAR, True),    # k_contig merges the touching pieces
 }
+CIRCULAR_NAMES = ("circular-units", "circular-genome", "circular-genome-isochores")
 
 
 def extents(flat):

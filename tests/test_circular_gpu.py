@@ -8,9 +8,12 @@ import random
 import numpy as np
 import pytest
 
+import circular_cases as CIRC
 import circular_model as M
+import coverage_cases as CC
 import coverage_model
 import gat_amd
+from circular_cases import EDGE_SEGS, EDGE_WS, rand_norm, unit_of_n, units_flat
 from gat_amd import _lib, problem, synthetic
 from oracle import oracle as O
 
@@ -28,36 +31,6 @@ def ctx():
 
 
 # ------------------------------------------------------------------------------------------------ helpers
-def rand_norm(r, n, span, maxlen, start=0):
-    """up to n separated, sorted pieces in [start, span) of length at most maxlen."""
-    pts = sorted(r.sample(range(start, span), 2 * n))
-    return [(pts[2 * i], min(pts[2 * i + 1], pts[2 * i] + maxlen)) for i in range(n) if pts[2 * i + 1] > pts[2 * i]]
-
-
-def units_flat(units):
-    """one contig per unit, no isochores, no annotations: the sampler alone.  A unit without segments or workspace is
-    skipped: it carries contig -1."""
-    def cat(lists):
-        out = np.zeros(sum(len(x) for x in lists), dtype=O.SEG)
-        k = 0
-        for x in lists:
-            for s, e in x:
-                out[k] = (s, e)
-                k += 1
-        return out
-
-    def off(lists):
-        return np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int64)
-
-    segs, ws = [s for s, _ in units], [w for _, w in units]
-    live = [len(s) > 0 and len(w) > 0 for s, w in units]
-    contig = np.where(live, np.cumsum(live) - 1, -1).astype(np.int32)
-    return dict(n_units=len(units), segs=cat(segs), seg_off=off(segs), ws=cat(ws), ws_off=off(ws), unit_contig=contig,
-                n_contigs=int(sum(live)), merge_contigs=0, n_tracks=0, annos=np.zeros(0, dtype=O.SEG),
-                anno_off=np.zeros(1, np.int64), cws_nseg=np.array([len(w) for w, k in zip(ws, live) if k], np.int64),
-                sampler=CIRCULAR)
-
-
 def as_lists(seg, off):
     s, e = seg["start"].tolist(), seg["end"].tolist()
     return [list(zip(s[off[i]:off[i + 1]], e[off[i]:off[i + 1]])) for i in range(len(off) - 1)]
@@ -119,22 +92,6 @@ def test_split_sample_range(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ wave-step carries
-def unit_of_n(r, n, frag):
-    """a unit of exactly n working intervals; frag: a workspace of short pieces, so that intervals are cut"""
-    segs = [(10 + 7 * i, 10 + 7 * i + r.choice((1, 2, 5))) for i in range(n)]
-    top = 10 + 7 * n + 20
-    if frag:
-        ws, x = [], 0
-        while x < top:
-            ln = r.choice((3, 9, 16, 40))
-            ws.append((x, min(top, x + ln)))
-            x += ln + r.choice((0, 0, 1))          # (gaps of one base never swallow a whole segment start..end run)
-    else:
-        ws = [(0, top)]
-    n_iv = len(M.linear_intervals(segs, ws))
-    return (segs, ws), n_iv
-
-
 @pytest.mark.parametrize("frag", [False, True])
 def test_wave_step_sizes(ctx, frag):
     r = random.Random(64 + frag)
@@ -154,10 +111,6 @@ def test_long_unit_beside_a_short_one(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ edges
-EDGE_WS = [(10, 20), (25, 30), (30, 31), (40, 60)]               # Wsum 36, touching pieces, a piece of one base
-EDGE_SEGS = [(12, 15), (18, 27), (50, 60)]                       # linear [2, 5), [8, 12), [26, 36): the last ends at Wsum
-
-
 def _edge(ctx, units, seed, unit=0):
     """sample 0 of the units under `seed`: the model's stats of `unit` and its list, after the device agreed"""
     info = []
@@ -284,6 +237,33 @@ def test_problem_lists_and_counts(ctx, isochores):
     for k, c in enumerate(INT_COUNTERS):
         assert np.array_equal(got[k], want[k]), c
         assert np.array_equal(np.concatenate([p[k] for p in parts], axis=1), want[k]), c
+
+
+CONSUMER_PROBLEMS = dict({name: CC.SIX[name] for name in CC.CIRCULAR_NAMES}, **{"dense-isochores": CIRC.dense_isochore_problem})
+
+
+@pytest.mark.parametrize("name", sorted(CONSUMER_PROBLEMS))
+def test_consumer_problems_sample_is_the_models(ctx, name):
+    """what every list consumer reads, for the problems their tests run on (tests/coverage_cases.py: SIX) under their seed and
+    samples: the unit lists, and the contig lists -- with isochore keys k_contig's merged lists (d_cslab): the model's unit
+    lists of a contig one after the other and merge(0)d"""
+    flat = CONSUMER_PROBLEMS[name]()
+    want_units, want_off = CIRC.model_sample(flat, CIRC.SEED, 0, CIRC.SAMPLES, unit_level=True)
+    want, off = CIRC.model_sample(flat, CIRC.SEED, 0, CIRC.SAMPLES)
+    P = _lib.Problem(ctx, flat)
+    try:
+        got_units, got_unit_off = P.sample(CIRC.SEED, 0, CIRC.SAMPLES, unit_level=True)
+        got, got_off = P.sample(CIRC.SEED, 0, CIRC.SAMPLES)
+        part, part_off = P.sample(CIRC.SEED, 5, CIRC.SAMPLES)
+    finally:
+        P.close()
+    assert got_unit_off.tolist() == want_off.tolist() and got_units.tolist() == want_units.tolist()
+    assert got_off.tolist() == off.tolist() and got.tolist() == want.tolist()
+    at = 5 * int(flat["n_contigs"])
+    assert (part_off + off[at]).tolist() == off[at:].tolist() and part.tolist() == want[off[at]:].tolist()
+    if int(flat["merge_contigs"]):
+        assert int(flat["n_units"]) > int(flat["n_contigs"])
+        assert (len(want) < len(want_units)) == (name == "dense-isochores")         # (touching unit pieces, united)
 
 
 def test_run_counts(ctx, monkeypatch):

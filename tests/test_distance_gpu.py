@@ -347,8 +347,9 @@ CLI_SEED, CLI_SAMPLES, CLI_BOUND = 11, 50, 300
 ALL_COUNTERS = ["--counter=segment-distance", "--counter=segment-nearby", "--counter=annotation-distance", "--counter=annotation-nearby"]
 
 
-@pytest.mark.parametrize("extra", [["--isochores=%s" % os.path.join(CLI, "isochores.bed")], ["--with-segment-tracks"] + ALL_COUNTERS],
-                         ids=["isochores", "tracks-four-counters"])
+@pytest.mark.parametrize("extra", [["--isochores=%s" % os.path.join(CLI, "isochores.bed")], ["--with-segment-tracks"] + ALL_COUNTERS,
+                                   ["--sampler=circular"] + ALL_COUNTERS],
+                         ids=["isochores", "tracks-four-counters", "circular-four-counters"])
 def test_script(ctx, tmp_path, extra):
     """the printed tables are the ones built here: Problem.sample of the same inputs and seeds, the model, engine.AnnotatorResult,
     IO.outputResults"""

@@ -451,7 +451,8 @@ CLI_SEED, CLI_SAMPLES = 11, 30
 
 
 @pytest.mark.parametrize("extra", [["--isochores=%s" % os.path.join(CLI, "isochores.bed"), "--order=track"],
-                                   ["--with-segment-tracks", "--qvalue-method=holm", "--order=pvalue"]], ids=["isochores", "tracks"])
+                                   ["--with-segment-tracks", "--qvalue-method=holm", "--order=pvalue"], ["--sampler=circular"]],
+                         ids=["isochores", "tracks", "circular"])
 def test_script(ctx, tmp_path, extra):
     """the printed table is the one built here: Problem.sample of the same inputs and seeds, the model's counts and words"""
     from gat_amd import geneset, problem

@@ -151,7 +151,7 @@ def test_list_arguments(ctx):
 # ---- 2. gat_sample_bin_enrichment -----------------------------------------------------------------------------------------------------
 SEED, SAMPLES = 77, 12
 PROBLEMS = ("annotator-units", "shift-units", "global-permutation-units", "local-permutation-units", "brute-force-units",
-            "annotator-genome-isochores", "segments-genome-isochores")
+            "annotator-genome-isochores", "segments-genome-isochores") + CC.CIRCULAR_NAMES
 BIN_SIZES = (1, 64, 1000)
 
 
@@ -364,7 +364,8 @@ CLI_SEED, CLI_SAMPLES, CLI_BIN = 11, 30, 5000
 
 
 @pytest.mark.parametrize("extra", [["--isochores=%s" % os.path.join(CLI, "isochores.bed"), "--order=track"],
-                                   ["--with-segment-tracks", "--qvalue-method=holm"]], ids=["isochores", "tracks"])
+                                   ["--with-segment-tracks", "--qvalue-method=holm"], ["--sampler=circular"]],
+                         ids=["isochores", "tracks", "circular"])
 def test_script(ctx, tmp_path, extra):
     """the printed table is the one built here: Problem.sample of the same inputs and seeds, the model's values and words"""
     from gat_amd import local, problem

@@ -363,6 +363,39 @@ def test_cli_sample_metrics_with_isochores(ctx, tmp_path):
     assert len(text.splitlines()) == 1 + 6 * 10 and words[:, :, 3].sum() > 0          # (not "wholly outside")
 
 
+def test_cli_sample_metrics_circular(ctx, tmp_path):
+    """--sampler=circular (not in the reference either): the file is the model's sums over Problem.sample of the same inputs,
+    seed and range -- the lists a rotation cuts at the workspace's borders, a contig's pieces counted one by one"""
+    import io
+    import gat_amd
+    from gat_amd import coverage, metrics
+    from gat_amd import io as IO
+    from test_metrics_host import base_argv
+    extra = ["--num-samples=6", "--random-seed=53", "--sampler=circular", "--output-stats=sample_metrics"]
+    _, pat, _ = run_cli(tmp_path, "circular", extra)
+    text = open(pat % "sample_metrics").read()
+    opts, _ = gat_amd.buildParser(samplers=gat_amd.TOOL_SAMPLERS).parse_args(base_argv(tmp_path, extra[:3])[1:])
+    segments, annotations, workspaces, isochores = IO.buildSegments(opts)
+    workspace = IO.applyIsochores(segments, annotations, workspaces, opts, isochores)
+    flat, _, _ = coverage.flatten(segments["merged"], workspace, coverage.make_sampler(opts))
+    assert flat["sampler"] == 6 and flat["merge_contigs"] == 0 and flat["n_units"] == flat["n_contigs"]
+    ws, ws_off, size = metrics.contig_workspace(workspace, flat["contig_names"])
+    P = _lib.Problem(ctx, flat)
+    try:
+        seg, off = P.sample(53, 0, 6)
+    finally:
+        P.close()
+    nc = int(flat["n_contigs"])
+    words = np.array([[M.words_of_array(seg[off[i * nc + c]:off[i * nc + c + 1]], ws[ws_off[c]:ws_off[c + 1]]) for c in range(nc)]
+                      for i in range(6)], dtype=np.int64)
+    want = io.StringIO()
+    want.write(metrics.HEADER)
+    metrics.write_rows(want, "merged", [str(i) for i in range(6)], words, size)
+    assert text == want.getvalue()
+    assert len(text.splitlines()) == 1 + 6 * 10 and words[:, :, 3].sum() > 0
+    assert len({words[i].tobytes() for i in range(6)}) > 1                       # (the samples differ: a rotation each)
+
+
 def test_cli_all_writes_the_files_it_wrote_before(tmp_path):
     """--output-stats=all: the collection summaries, neither of the two metrics files"""
     _, _, files = run_cli(tmp_path, "all", ["--num-samples=3", "--random-seed=1", "--output-stats=all"])

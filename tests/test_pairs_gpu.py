@@ -177,7 +177,7 @@ def _lib_seg(pairs):
 # ---- 2. gat_sample_pair_enrichment ----------------------------------------------------------------------------------------------------
 SEED, SAMPLES = 77, 48
 PROBLEMS = ("annotator-units", "segments-units", "shift-units", "global-permutation-units", "local-permutation-units", "brute-force-units",
-            "segments-genome", "annotator-genome-isochores")
+            "segments-genome", "annotator-genome-isochores") + CC.CIRCULAR_NAMES
 SAMPLE_TRACKS = (3, 66)
 
 
@@ -396,7 +396,8 @@ CLI_SEED, CLI_SAMPLES = 11, 30
 
 
 @pytest.mark.parametrize("extra", [["--isochores=%s" % os.path.join(CLI, "isochores.bed"), "--order=track", "--include-single"],
-                                   ["--with-segment-tracks", "--qvalue-method=holm", "--order=pvalue"]], ids=["isochores-single", "tracks"])
+                                   ["--with-segment-tracks", "--qvalue-method=holm", "--order=pvalue"], ["--sampler=circular"]],
+                         ids=["isochores-single", "tracks", "circular"])
 def test_script(ctx, tmp_path, extra):
     """the printed table is the one built here: Problem.sample of the same inputs and seeds, the model's counts and words"""
     from gat_amd import pairs, problem

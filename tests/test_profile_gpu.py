@@ -203,7 +203,7 @@ def test_list_arguments(ctx):
 
 # ---- 3. gat_sample_profile_enrichment ---------------------------------------------------------------------------------------------------
 SEED, SAMPLES, FEW, SPLIT = 77, 40, 7, 5
-PROBLEMS = ("annotator-units", "shift-units", "brute-force-units", "annotator-genome-isochores")
+PROBLEMS = ("annotator-units", "shift-units", "brute-force-units", "annotator-genome-isochores") + CC.CIRCULAR_NAMES
 BIN_SIZE, HALF_BINS = 25, 10
 
 
@@ -423,8 +423,8 @@ def anchor_file(path):
 
 @pytest.mark.parametrize("extra", [["--isochores=%s" % os.path.join(CLI, "isochores.bed"), "--order=track"],
                                    ["--with-segment-tracks", "--qvalue-method=holm", "--profile-of=midpoints", "--anchor-point=three-prime"],
-                                   ["--ignore-strand", "--annotations-label=all", "--order=annotation"]],
-                         ids=["isochores", "tracks-midpoints", "pooled"])
+                                   ["--ignore-strand", "--annotations-label=all", "--order=annotation"], ["--sampler=circular"]],
+                         ids=["isochores", "tracks-midpoints", "pooled", "circular"])
 def test_script(ctx, tmp_path, extra):
     """the printed table is the one built here: Problem.sample of the same inputs and seeds, the model's values and words"""
     from gat_amd import profile, problem

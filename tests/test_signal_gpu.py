@@ -446,8 +446,9 @@ def write_bedgraphs(tmp_path):
 
 
 @pytest.mark.parametrize("extra", [["--isochores=%s" % os.path.join(CLI, "isochores.bed")],
-                                   ["--with-segment-tracks", "--counter=signal-mean", "--counter=signal-hit"]],
-                         ids=["isochores", "tracks-two-counters"])
+                                   ["--with-segment-tracks", "--counter=signal-mean", "--counter=signal-hit"],
+                                   ["--sampler=circular", "--counter=signal-mean", "--counter=signal-hit"]],
+                         ids=["isochores", "tracks-two-counters", "circular-two-counters"])
 def test_script(ctx, tmp_path, extra):
     """the printed tables are the ones built here: Problem.sample of the same inputs and seeds, the model, engine.AnnotatorResult,
     IO.outputResults"""
