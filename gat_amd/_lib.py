@@ -38,7 +38,7 @@ SYMBOLS = [
     "gat_list_bin_overlaps", "gat_sample_bin_enrichment", "gat_count_last_launch", "gat_sampler_last_launch",
     "gat_list_pair_hits", "gat_sample_pair_enrichment", "gat_list_geneset_hits", "gat_sample_geneset_enrichment",
     "gat_list_profile", "gat_sample_profile_enrichment", "gat_list_signal", "gat_sample_signal",
-    "gat_null_fold_reset", "gat_null_fold",
+    "gat_null_fold_reset", "gat_null_fold", "gat_list_reldist", "gat_sample_reldist_enrichment",
 ]
 NULL_FOLD_WORDS = 8           # GAT_NULL_FOLD_WORDS: n, sum, sumsq_lo, sumsq_hi, n_less, n_eq, min, max
 
@@ -300,6 +300,10 @@ def lib():
     L.gat_list_profile.argtypes = [vp, vp, vp, i64, vp, vp, vp, i32, i32, i64, i32, C.c_int, vp]
     L.gat_sample_profile_enrichment.restype = C.c_int
     L.gat_sample_profile_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, vp, i32, i64, i32, C.c_int, vp, vp, C.POINTER(Stats)]
+    L.gat_list_reldist.restype = C.c_int
+    L.gat_list_reldist.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, i32, vp]
+    L.gat_sample_reldist_enrichment.restype = C.c_int
+    L.gat_sample_reldist_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, i32, vp, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -666,13 +670,32 @@ class Context(object):
                                       int(bin_size), int(half_bins), int(mode), _p(out)), self._h)
         return out
 
+    def list_reldist(self, lists, list_off, n_lists, point_pos, point_off, n_tracks, n_groups, n_bins):
+        """the relative distances of every one of n_lists x n_groups caller-provided lists (any lists: every segment counts
+        on its own) -- list l of group g is lists[list_off[l * n_groups + g]:list_off[l * n_groups + g + 1]] -- to the points
+        of n_tracks tracks, track t of group g at point_pos[point_off[t * n_groups + g]:point_off[t * n_groups + g + 1]],
+        strictly ascending (gat_list_reldist).  Returns int64 [n_lists, n_tracks, n_bins + RELDIST_EXTRA]: the bins, then
+        area (parts per million), inside, outside."""
+        lists = np.ascontiguousarray(lists, dtype=SEG)
+        list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+        n_lists, n_tracks, n_groups = int(n_lists), int(n_tracks), int(n_groups)
+        assert len(list_off) == n_lists * n_groups + 1
+        pos, point_off = _reldist_arrays(point_pos, point_off, n_tracks, n_groups)
+        out = np.zeros((n_lists, n_tracks, reldist_values(n_bins)), dtype=np.int64)
+        _check(lib().gat_list_reldist(self._h, _p(lists), _p(list_off), n_lists, _p(pos), _p(point_off), n_tracks, n_groups,
+                                      int(n_bins), _p(out)), self._h)
+        return out
+
 
 NULL_WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")      # the sampled null of one cell against obs: include/gat_mi355.h
-# GAT_LOCAL_WORDS, GAT_PAIR_WORDS, GAT_GENESET_WORDS, GAT_PROFILE_WORDS
-LOCAL_WORDS = PAIR_WORDS = GENESET_WORDS = PROFILE_WORDS = NULL_WORDS
+# GAT_LOCAL_WORDS, GAT_PAIR_WORDS, GAT_GENESET_WORDS, GAT_PROFILE_WORDS, GAT_RELDIST_WORDS
+LOCAL_WORDS = PAIR_WORDS = GENESET_WORDS = PROFILE_WORDS = RELDIST_WORDS = NULL_WORDS
 PAIR_MAX_TRACKS = 2048        # GAT_PAIR_MAX_TRACKS
 PROFILE_MAX_BINS = 1024       # GAT_PROFILE_MAX_BINS
 PROFILE_BASES, PROFILE_MIDPOINTS = 0, 1       # GAT_PROFILE_BASES, GAT_PROFILE_MIDPOINTS
+RELDIST_MAX_BINS = 1024       # GAT_RELDIST_MAX_BINS
+RELDIST_EXTRA = 3             # GAT_RELDIST_EXTRA: area, inside, outside behind the bins
+RELDIST_AREA_SCALE = 10 ** 6  # GAT_RELDIST_AREA_SCALE
 
 
 def profile_bins(half_bins):
@@ -687,6 +710,19 @@ def _profile_arrays(anchor_pos, anchor_minus, anchor_off, n_tracks, n_groups):
     anchor_off = np.ascontiguousarray(anchor_off, dtype=np.int64)
     assert len(anchor_off) == max(0, n_tracks) * max(0, n_groups) + 1 and len(pos) == len(minus)
     return pos, minus, anchor_off
+
+
+def reldist_values(n_bins):
+    """the values of a (list, track) of the relative distance calls (0 where n_bins is out of range: the library refuses the call)"""
+    return int(n_bins) + RELDIST_EXTRA if 1 <= int(n_bins) <= RELDIST_MAX_BINS else 0
+
+
+def _reldist_arrays(point_pos, point_off, n_tracks, n_groups):
+    """the point arguments of the two relative distance calls as the library takes them"""
+    pos = np.ascontiguousarray(point_pos, dtype=np.uint32)
+    point_off = np.ascontiguousarray(point_off, dtype=np.int64)
+    assert len(point_off) == max(0, n_tracks) * max(0, n_groups) + 1
+    return pos, point_off
 
 
 def pair_count(n_tracks):
@@ -1207,3 +1243,16 @@ class Problem(object):
         assert obs.shape == cells
         return self._sample_null_words(lib().gat_sample_profile_enrichment, seed, sample_begin, sample_end,
                                        (_p(pos), _p(minus), _p(anchor_off), n_tracks, int(bin_size), int(half_bins), int(mode)), obs, cells)
+
+    def sample_reldist_enrichment(self, seed, sample_begin, sample_end, point_pos, point_off, n_tracks, n_bins, obs):
+        """per (track, value) the five sums (RELDIST_WORDS; gat_sample_reldist_enrichment) over the sampled contig-level
+        lists of [sample_begin, sample_end) of the list's relative distance values -- the bins, area, inside, outside -- against
+        obs[track, value]; the points as in Context.list_reldist, the groups the problem's contigs in the problem's order.
+        Returns int64 [n_tracks, n_bins + RELDIST_EXTRA, 5]."""
+        n_tracks = int(n_tracks)
+        pos, point_off = _reldist_arrays(point_pos, point_off, n_tracks, self.n_contigs)
+        cells = (max(0, n_tracks), reldist_values(n_bins))
+        obs = np.ascontiguousarray(obs, dtype=np.int64)
+        assert obs.shape == cells
+        return self._sample_null_words(lib().gat_sample_reldist_enrichment, seed, sample_begin, sample_end,
+                                       (_p(pos), _p(point_off), n_tracks, int(n_bins)), obs, cells)

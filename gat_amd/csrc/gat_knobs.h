@@ -96,7 +96,9 @@ struct gat_ctx;
   INT(geneset_samples_per_block, "GAT_GENESET_SAMPLES_PER_BLOCK", 0) /* ... the run of lists of both kernels; default: by the launch */ \
   INT(geneset_term_tile, "GAT_GENESET_TERM_TILE", 256) /* ... terms a workgroup of k_geneset_terms owns, 1 .. 256 */           \
   INT(profile_lds_anchors, "GAT_PROFILE_LDS_ANCHORS", 1024) /* gat_*_profile*: anchor positions of a (track, group) k_profile's search finds in LDS; 0: none */ \
-  INT(profile_samples_per_block, "GAT_PROFILE_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */
+  INT(profile_samples_per_block, "GAT_PROFILE_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */ \
+  INT(reldist_lds_points, "GAT_RELDIST_LDS_POINTS", 1024) /* gat_*_reldist*: positions of a (track, group) k_reldist's search finds in LDS; 0: none */ \
+  INT(reldist_samples_per_block, "GAT_RELDIST_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */
 
 struct Knobs {
 #define GAT_KNOB_FLAG(field, name) bool field = false;

@@ -5,8 +5,8 @@
 
 // ---- the entry points that read the sampled lists where they are: gat_sample / gat_sample_units copy them out, and
 // gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_signal, gat_sample_bin_enrichment,
-// gat_sample_pair_enrichment, gat_sample_geneset_enrichment and gat_sample_profile_enrichment put a kernel (gat_coverage.h,
-// gat_metrics.h, gat_distance.h, gat_signal.h, gat_local.h, gat_pairs.h, gat_geneset.h, gat_profile.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
+// gat_sample_pair_enrichment, gat_sample_geneset_enrichment, gat_sample_profile_enrichment and gat_sample_reldist_enrichment put a kernel
+// (gat_coverage.h, gat_metrics.h, gat_distance.h, gat_signal.h, gat_local.h, gat_pairs.h, gat_geneset.h, gat_profile.h, gat_reldist.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
 
 // A synchronous call's frame: refused while a call is in flight on the problem (P == nullptr: a call over the caller's own
 // lists); the knobs are read once; body(kn, local) does the work.  Whatever the body returns, the stream is drained behind it:
@@ -165,7 +165,7 @@ static int launch_store_or_fold(gat_ctx* ctx, bool store, void (*k_store)(Args),
 }
 
 // ---- the fold of the sampled null to five words per cell (gat_null_words.h), as gat_sample_bin_enrichment,
-// gat_sample_pair_enrichment, gat_sample_geneset_enrichment and gat_sample_profile_enrichment share it: obs up and the words zeroed before the first batch,
+// gat_sample_pair_enrichment, gat_sample_geneset_enrichment, gat_sample_profile_enrichment and gat_sample_reldist_enrichment share it: obs up and the words zeroed before the first batch,
 // k_null_finish and the words down behind the last
 struct NullWordsOut {
   DevBuf<long long> d_obs;
@@ -1201,5 +1201,113 @@ extern "C" int gat_sample_profile_enrichment(gat_ctx* ctx, gat_problem* P, uint3
   if (cells > 0 && (!obs_host || !out_host)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
   if ((rc = T.check_words(ctx, S, obs_host, cells))) return rc;
   if ((rc = check_sampled_lists_normalized(ctx, who, P, "the profile needs normalized lists"))) return rc;
+  return fold_over_sampled_batches(ctx, P, stats, seed, sample_begin, S, T, obs_host, cells, out_host);
+}
+
+// gat_list_reldist / gat_sample_reldist_enrichment: k_reldist (gat_reldist.h) over caller-provided lists, or behind every batch.
+// The points go up once per call (positions, offsets from point_off[0]); the device buffers live for the call.
+struct ReldistCall {
+  const char* who;
+  const uint32_t* pos; const int64_t* off;
+  int32_t n_tracks; int32_t n_bins;
+  DevBuf<uint32_t> d_pos;
+  DevBuf<int64_t> d_off;
+  NullWordsOut out;
+  int64_t longest = 0;        // the most points of a (track, group)
+  int64_t values() const { return (int64_t)n_bins + GAT_RELDIST_EXTRA; }
+  // what both entry points ask of the bins and the points (tracks of points, not of intervals: the checks are its own)
+  int check(gat_ctx* ctx, int64_t n_groups) const {
+    if (n_bins < 1 || n_bins > GAT_RELDIST_MAX_BINS) return set_err(ctx, GAT_ERR_ARG, "%s: n_bins %d outside [1, %d]", who, n_bins, GAT_RELDIST_MAX_BINS);
+    if (n_tracks < 0 || (int64_t)n_tracks * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+      return set_err(ctx, GAT_ERR_ARG, "%s: n_tracks %d", who, n_tracks);
+    const int64_t n = (int64_t)n_tracks * n_groups;
+    int rc;
+    if ((rc = check_list_offsets(ctx, who, "point_off", "points", off, n))) return rc;
+    if (off[n] > off[0] && !pos) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+    for (int64_t t = 0; t < n_tracks; ++t)
+      for (int64_t g = 0; g < n_groups; ++g) {
+        const int64_t b = off[t * n_groups + g], e = off[t * n_groups + g + 1];
+        for (int64_t k = b + 1; k < e; ++k)
+          if (pos[k] <= pos[k - 1])
+            return set_err(ctx, GAT_ERR_ARG, "%s: point track %lld, group %lld is not strictly ascending at point %lld", who,
+                           (long long)t, (long long)g, (long long)(k - b));
+      }
+    return GAT_OK;
+  }
+  int upload(gat_ctx* ctx, const Knobs&, int32_t n_groups, int64_t) {
+    const int64_t n = (int64_t)n_tracks * n_groups, base = off[0], total = off[n] - base;
+    std::vector<int64_t> h_off((size_t)n + 1);
+    longest = 0;
+    for (int64_t l = 0; l <= n; ++l) {
+      h_off[(size_t)l] = off[l] - base;
+      if (l) longest = std::max(longest, off[l] - off[l - 1]);
+    }
+    HIPCHK(ctx, d_pos.alloc((size_t)total));
+    if (total > 0) HIPCHK(ctx, staged_h2d(ctx, d_pos.p, pos + base, (size_t)total * 4));
+    HIPCHK(ctx, d_off.upload(h_off, ctx));
+    HIPCHK(ctx, stage_flush(ctx));                    // (h_off goes away with this frame)
+    return GAT_OK;
+  }
+  // one launch over tracks x runs of n_lists lists; store: the raw values per list, else the fold into out's five words.  (A
+  // call without a point still counts its segments: outside.)
+  int launch(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists, int64_t n_lists, int32_t n_groups, bool store) const {
+    if (n_lists == 0 || n_tracks == 0 || n_groups == 0) return GAT_OK;
+    gat::ReldistArgs A;
+    memset(&A, 0, sizeof(A));
+    const int64_t L = gat::reldist_lds_points(std::max<int64_t>(0, kn.reldist_lds_points), longest, ctx->max_lds, n_bins, n_groups);
+    A.lists = lists;
+    A.n_lists = (int32_t)n_lists;
+    A.n_groups = n_groups;
+    A.n_tracks = n_tracks;
+    A.bins = n_bins;
+    A.lds_points = (int32_t)L;
+    A.pos = d_pos.p;
+    A.point_off = d_off.p;
+    A.obs = out.d_obs.p;
+    A.out = out.d_out.p;
+    // the run: the knob's where it is set, else k_profile's rule, whose layout and fixed cost per workgroup (the flush of its
+    // cells) this kernel shares: as long as leaves 8 192 workgroups, at least 8 lists, and a list for every wave in every round
+    const int64_t lpb = kn.reldist_samples_per_block > 0
+                            ? gat::run_per_block(n_lists, n_tracks, 0, kn.reldist_samples_per_block)
+                            : (gat::run_per_block(n_lists, n_tracks, 8192, gat::kNoRunCap) + gat::kReldistWaves - 1) / gat::kReldistWaves * gat::kReldistWaves;
+    A.lists_per_block = (int32_t)lpb;
+    const size_t lds = (size_t)gat::reldist_lds_bytes(n_bins, L, n_groups, store);
+    const dim3 grid((unsigned)n_tracks, (unsigned)((n_lists + lpb - 1) / lpb));
+    return launch_store_or_fold(ctx, store, gat::k_reldist<true>, gat::k_reldist<false>, grid, gat::kReldistThreads, lds, A);
+  }
+};
+
+extern "C" int gat_list_reldist(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                                const uint32_t* point_pos, const int64_t* point_off, int32_t n_tracks, int32_t n_groups,
+                                int32_t n_bins, int64_t* out_host) {
+  const char* who = "gat_list_reldist";
+  if (!ctx || !list_off || !point_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  ReldistCall T = {who, point_pos, point_off, n_tracks, n_bins};
+  int rc;
+  if ((rc = check_list_counts(ctx, who, n_lists, n_groups))) return rc;
+  if ((rc = T.check(ctx, n_groups))) return rc;
+  if ((rc = check_caller_lists(ctx, who, "segments", lists, list_off, n_lists, n_groups, nullptr))) return rc;
+  // a value is a 32-bit word on the device, and the area's route takes n < 2^31: the segments of a list over all its groups
+  for (int64_t l = 0; l < n_lists; ++l)
+    if (list_off[(l + 1) * n_groups] - list_off[l * n_groups] > (int64_t)INT32_MAX)
+      return set_err(ctx, GAT_ERR_ARG, "%s: list %lld has more than 2^31 - 1 segments over its groups", who, (long long)l);
+  return store_over_caller_lists(ctx, T, lists, list_off, n_lists, n_groups, (int64_t)n_tracks * T.values(), out_host);
+}
+
+extern "C" int gat_sample_reldist_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                             const uint32_t* point_pos, const int64_t* point_off, int32_t n_tracks, int32_t n_bins,
+                                             const int64_t* obs_host, int64_t* out_host, gat_stats* stats) {
+  const char* who = "gat_sample_reldist_enrichment";
+  if (!ctx || !P || !point_off) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (int rc = check_sample_range(ctx, sample_begin, sample_end)) return rc;
+  ReldistCall T = {who, point_pos, point_off, n_tracks, n_bins};
+  int rc;
+  if ((rc = T.check(ctx, P->n_contigs))) return rc;
+  const int64_t S = sample_end - sample_begin, cells = (int64_t)n_tracks * T.values();
+  if (cells > 0 && (!obs_host || !out_host)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  const int64_t n_max = P->slab_stride;           // the most segments one sample can hold
+  if (n_max > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_CAPACITY, "%s: a sample can hold %lld segments, more than 2^31 - 1", who, (long long)n_max);
+  // a count is at most n_max, the area at most GAT_RELDIST_AREA_SCALE
+  if ((rc = check_null_words(ctx, who, "max(10^6, n_max)", std::max<int64_t>(GAT_RELDIST_AREA_SCALE, n_max), "fewer samples per call", S, obs_host, cells))) return rc;
   return fold_over_sampled_batches(ctx, P, stats, seed, sample_begin, S, T, obs_host, cells, out_host);
 }

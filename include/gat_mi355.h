@@ -777,6 +777,66 @@ int gat_sample_profile_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                                   int32_t n_tracks, int64_t bin_size, int32_t half_bins, int mode,
                                   const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
 
+/* Where the segments of a list sit between the two points that flank them, as a fraction of the gap -- the relative distance
+ * test (bedtools reldist, GenometriCorr) -- formed on the device by k_reldist (the reference has nothing like it).  If segments
+ * and points ignore each other the fraction is spread evenly over [0, 0.5]; mass near 0 is attraction, near 0.5 avoidance.  The
+ * groups are contigs.  The reference points of track t on group g are K >= 0 positions p_0 < p_1 < ... < p_{K-1} in
+ * [0, 2^32 - 1], strictly ascending.  A segment q = [s, e), e > s, stands for m = s + (e - s) / 2 in integer division.  With j
+ * the first index with p_j > m (K: none), q is INSIDE iff 1 <= j <= K - 1, that is p_{j-1} <= m < p_j, and OUTSIDE otherwise
+ * (m < p_0, m >= p_{K-1}, K < 2).  For an inside segment d = min(m - p_{j-1}, p_j - m), gap = p_j - p_{j-1} >= 1 and
+ *     bin(q) = min(B - 1, floor(2 * d * B / gap)),      B = n_bins in [1, GAT_RELDIST_MAX_BINS]:
+ * bin b covers the relative distances [b / 2B, (b + 1) / 2B), and a relative distance of exactly 0.5 goes to the last bin.
+ * Everything is unsigned 64-bit (2 * d * B < 2^43); m <= 2^32 - 2, so m + 1 fits 32 bits and j is the first position >= m + 1.
+ * Segments with e <= s are skipped.  The lists need be neither sorted nor disjoint -- every segment counts on its own --, so
+ * SamplerSegments without isochore keys is accepted, as in gat_list_distances.  A list has at most 2^31 - 1 segments over all
+ * its groups.  Example (points 100, 200; B = 10): [138, 143) has m = 140, d = 40, bin 8; [150, 151) has d = 50 and goes to bin
+ * 9; [100, 101) has d = 0, bin 0; [200, 201) is outside.
+ * A (list L, track t) pair has W = B + GAT_RELDIST_EXTRA values, summed over all groups, in this order:
+ *     index b < B   v_b: the inside segments with bin == b
+ *     index B       area: with n = sum_b v_b, C_b = v_0 + ... + v_b and D = sum_{b < B} |B * C_b - (b + 1) * n|, 0 where n == 0,
+ *                   else floor(D * 1 000 000 / (n * B * B)) -- the area between the list's ECDF over the bins and the uniform
+ *                   one in parts per million (GAT_RELDIST_AREA_SCALE), always <= 10^6.  The 64-bit route, which the kernel
+ *                   follows: M = n * B * B < 2^51, D <= M, r = D * 1000, area = (r / M) * 1000 + ((r % M) * 1000) / M --
+ *                   exact, and no product passes 2^61
+ *     index B + 1   inside: n
+ *     index B + 2   outside
+ * point_off has n_tracks * n_groups + 1 non-decreasing entries, track t of group g at index t * n_groups + g.
+ * Over a range of S samples and against an observed value obs[t][k] >= 0 given by the caller, every (track, value index) gets
+ * five int64 words (GAT_RELDIST_WORDS) -- those of GAT_PROFILE_WORDS, in the same order and with the same meaning: n_pos, sum,
+ * sumsq (unsigned where it passes 2^63), n_less, n_eq; all S samples count in n_less / n_eq, those with a value of 0 too.  All
+ * arithmetic is integer and exact.  Every word is additive over the samples: the words of calls over [0, k) and [k, S) add up
+ * to those of the call over [0, S), and results do not depend on batches, workgroups, knobs or the run.  Context options, none
+ * of which changes a result: GAT_RELDIST_LDS_POINTS -- how many positions of a (track, group) the kernel's search finds in LDS
+ * before it goes to global memory (clamped to what a workgroup's LDS holds beside the bins; 0: none);
+ * GAT_RELDIST_SAMPLES_PER_BLOCK -- the run of lists a workgroup takes (default: by the launch).
+ *
+ * gat_list_reldist: the raw values of caller-provided lists (the observed values of the input segments with n_lists == 1).
+ * lists / list_off, n_groups: as in gat_list_distances.  out_host: [n_lists][n_tracks][W].  Synchronous.  n_lists == 0 or
+ * n_tracks == 0 writes nothing.  GAT_ERR_ARG, nothing written: a NULL ctx / list_off / point_off / out_host (lists / point_pos
+ * may be NULL where they hold nothing), negative counts, a decreasing offset, n_bins outside [1, 1024], positions of a (track,
+ * group) that are not strictly ascending (gat_last_error names the track and the group), a list of more than 2^31 - 1
+ * segments.  Never a wrong number. */
+#define GAT_RELDIST_WORDS 5
+#define GAT_RELDIST_MAX_BINS 1024
+#define GAT_RELDIST_EXTRA 3
+#define GAT_RELDIST_AREA_SCALE 1000000
+int gat_list_reldist(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                     const uint32_t* point_pos, const int64_t* point_off, int32_t n_tracks, int32_t n_groups,
+                     int32_t n_bins, int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop shared with gat_sample, k_reldist behind every batch that passed its checks,
+ * reading the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed
+ * and range (per-unit streams only), for every sampler.  The groups are the problem's contigs in the problem's order:
+ * point_off has n_tracks * n_contigs + 1 entries; obs_host: [n_tracks][W]; out_host: [n_tracks][W][5].  Synchronous, like
+ * gat_sample.  An empty sample range writes zeros; n_tracks == 0 writes nothing.  GAT_ERR_ARG, nothing written: as above, and
+ * a NULL p, a NULL obs_host / out_host with n_tracks > 0, sample_end < sample_begin, a negative obs, bound^2 * samples >= 2^64
+ * with bound = max(10^6, the most segments a sample can hold) (sumsq would not fit), a call in flight on the problem.  The
+ * sampler's errors pass through (GAT_ERR_ASSERT; SamplerBruteForce's GAT_ERR_VALUE "sampling did not converge"). */
+int gat_sample_reldist_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                                  int64_t sample_begin, int64_t sample_end,
+                                  const uint32_t* point_pos, const int64_t* point_off, int32_t n_tracks, int32_t n_bins,
+                                  const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
