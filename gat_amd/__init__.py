@@ -10,7 +10,7 @@ import numpy as np
 from . import intervals, problem, synthetic            # noqa: F401
 from . import io as IO                                   # noqa: F401
 from . import stats as Stats                             # noqa: F401
-from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerBruteForce, SamplerCircular,  # noqa: F401
+from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerBruteForce, SamplerCircular, SamplerUniverse,  # noqa: F401
                      Counter, computeCountsAll, overlap_sizes, CounterNucleotideOverlap, CounterNucleotideDensity, CounterSegmentOverlap,
                      CounterSegmentMidpointOverlap, CounterAnnotationOverlap, CounterAnnotationMidpointOverlap,
                      UnconditionalWorkspace, ConditionalWorkspaceCooccurance, ConditionalWorkspaceCentered,
@@ -647,9 +647,9 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
             seed = int(box[0])
     conditional = getattr(workspace_generator, "is_conditional", False)
     if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation,
-                                SamplerBruteForce, SamplerCircular)):
+                                SamplerBruteForce, SamplerCircular, SamplerUniverse)):
         raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation, SamplerBruteForce and SamplerCircular run on the GPU path")
+                                  "SamplerLocalPermutation, SamplerBruteForce, SamplerCircular and SamplerUniverse run on the GPU path")
     if _dist_state()[0] != 0:
         outfiles = {}                # (one writer: rank 0 computes and writes the metrics, all samples, no sharding)
     if "segment_metrics" in outfiles:
@@ -666,6 +666,8 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
         raise NotImplementedError("reference_stream: SamplerBruteForce runs on the per-unit streams only")
     if reference_stream and isinstance(sampler, SamplerCircular):
         raise NotImplementedError("reference_stream: SamplerCircular runs on the per-unit streams only")
+    if reference_stream and isinstance(sampler, SamplerUniverse):
+        raise NotImplementedError("reference_stream: SamplerUniverse runs on the per-unit streams only")
     if reference_stream:
         # the reference's own stream: numpy.random.seed(seed) once (scripts/gat-run.py:267-271), every work unit of every
         # segment track drawing from it in order -- an unpatched reference's table, number for number, at one stream's speed
@@ -861,12 +863,16 @@ CLI_SAMPLERS = ALL_SAMPLERS + ("brute-force",)
 # ... and TOOL_SAMPLERS circular, the one sampler here that the reference does not have (DESIGN §5 "k_circular"): what
 # scripts/gat-run.py and the tool scripts pass.  The tuples above stay as they were, as before.
 TOOL_SAMPLERS = CLI_SAMPLERS + ("circular",)
+# ... and UNIVERSE_SAMPLERS the subset null of a finite universe, the workspace's pieces (DESIGN §5 "k_universe"): the
+# scripts pass TOOL_SAMPLERS + UNIVERSE_SAMPLERS.  The tuples above stay as they were, as before.
+UNIVERSE_SAMPLERS = ("universe",)
 
 
 def buildParser(usage=None, samplers=SAMPLERS):
     """gat command line parser: the options of the reference's buildParser (gat/__init__.py:54-429)
     that concern the accelerated path, with the same names, destinations and defaults.  `samplers`: the choices of
-    --sampler (SAMPLERS, ALL_SAMPLERS, CLI_SAMPLERS, or TOOL_SAMPLERS as scripts/gat-run.py passes)."""
+    --sampler (SAMPLERS, ALL_SAMPLERS, CLI_SAMPLERS, TOOL_SAMPLERS, or TOOL_SAMPLERS + UNIVERSE_SAMPLERS as scripts/gat-run.py
+    passes)."""
     import optparse
     parser = optparse.OptionParser(version="%prog (gat_amd " + __version__ + ")", usage=usage)
     g = optparse.OptionGroup(parser, "Input options")
@@ -1036,6 +1042,8 @@ def fromSegments(options, args=None):
             sampler = SamplerBruteForce()                    # scripts/gat-run.py:139-140 (no bucket arguments: bucket_size 1)
         elif options.sampler == "circular":
             sampler = SamplerCircular()
+        elif options.sampler == "universe":
+            sampler = SamplerUniverse()
         else:
             raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
         counters = []

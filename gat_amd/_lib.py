@@ -47,6 +47,7 @@ MT_STATE_WORDS = 625          # GAT_MT_STATE_WORDS: 624 state words + numpy's po
 SAMPLER_ANNOTATOR, SAMPLER_SEGMENTS, SAMPLER_SHIFT, SAMPLER_GLOBAL_PERMUTATION, SAMPLER_LOCAL_PERMUTATION = 0, 1, 2, 3, 4
 SAMPLER_BRUTE_FORCE = 5
 SAMPLER_CIRCULAR = 6
+SAMPLER_UNIVERSE = 7
 
 
 def mt19937_seed(seed):

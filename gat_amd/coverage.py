@@ -19,10 +19,10 @@ import numpy as np
 
 from . import problem
 from .engine import (SamplerAnnotator, SamplerBruteForce, SamplerCircular, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerSegments,
-                     SamplerShift, get_context)
+                     SamplerShift, SamplerUniverse, get_context)
 
 SAMPLERS = (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerBruteForce,
-            SamplerCircular)
+            SamplerCircular, SamplerUniverse)
 
 
 class Coverage(object):
@@ -75,7 +75,7 @@ def sample_coverage(segs, workspace, sampler, num_samples, bin_size, random_seed
     from . import _lib
     if not isinstance(sampler, SAMPLERS):
         raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation, SamplerBruteForce and SamplerCircular run on the GPU path")
+                                  "SamplerLocalPermutation, SamplerBruteForce, SamplerCircular and SamplerUniverse run on the GPU path")
     bin_size, num_samples = int(bin_size), int(num_samples)
     if not 1 <= bin_size <= 2 ** 31:
         raise ValueError("bin_size %d outside [1, 2^31]" % bin_size)
@@ -182,4 +182,6 @@ def make_sampler(options):
         return SamplerBruteForce()
     if name == "circular":
         return SamplerCircular()
+    if name == "universe":
+        return SamplerUniverse()
     raise ValueError("sampler '%s' is outside the accelerated path" % name)

@@ -136,10 +136,10 @@ struct gat_ctx {
 inline bool count_lists_staged(const Knobs& kn, int64_t max_m) { return max_m > 0 && max_m + 4 <= kn.count_lds_entries; }
 
 // gat_problem_desc::sampler: the samplers there are; those whose kernel is a wave per work unit with its stream in LDS
-// (k_shift, k_permute, k_permute_local, k_brute_force, k_circular: no k_rng + k_place in front).  sampler_draws_lengths: gat_prep_units.h
+// (k_shift, k_permute, k_permute_local, k_brute_force, k_circular, k_universe: no k_rng + k_place in front).  sampler_draws_lengths: gat_prep_units.h
 inline bool sampler_runs_wave_per_unit(int32_t s) {
   return s == GAT_SAMPLER_SHIFT || s == GAT_SAMPLER_GLOBAL_PERMUTATION || s == GAT_SAMPLER_LOCAL_PERMUTATION || s == GAT_SAMPLER_BRUTE_FORCE ||
-         s == GAT_SAMPLER_CIRCULAR;
+         s == GAT_SAMPLER_CIRCULAR || s == GAT_SAMPLER_UNIVERSE;
 }
 inline bool sampler_is_known(int32_t s) { return s == GAT_SAMPLER_ANNOTATOR || s == GAT_SAMPLER_SEGMENTS || sampler_runs_wave_per_unit(s); }
 
@@ -410,6 +410,10 @@ struct gat_problem {
   // d_ws_cdf (cumulated - 1)
   DevBuf<uint4> d_circ_unit;
   DevBuf<uint2> d_circ_iv;
+  // GAT_SAMPLER_UNIVERSE: per unit {k, m, c, invert} (gat_prep_units.h: universe_record); the pieces are the unit's part of
+  // d_ws.  univ_table_words: the launch's mark table, universe_table_words of the most pieces an active unit has
+  DevBuf<uint4> d_univ_unit;
+  int64_t univ_table_words = 0;
   // GAT_SAMPLER_BRUTE_FORCE: SamplerBruteForce(ntries_inner, ntries_outer) (the desc's 0 replaced by the reference's 100 / 10)
   int32_t brute_ntries_inner = 100, brute_ntries_outer = 10;
   gat_annotations* anno = nullptr;       // the annotation tables: its own (made from the lists of its desc) or a shared object

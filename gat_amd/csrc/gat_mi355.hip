@@ -37,6 +37,7 @@
 #include "gat_permute.h"
 #include "gat_local_permute.h"
 #include "gat_circular.h"
+#include "gat_universe.h"
 #include "gat_brute_force.h"
 #include "gat_stats.h"
 #include "gat_null_fold.h"
@@ -651,6 +652,21 @@ static int enqueue_circular(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, ui
   H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.circ_unit = P->d_circ_unit.p; H.circ_iv = P->d_circ_iv.p;
   // (LDS for the generator's state alone: the intervals are read where they lie and the pieces go straight to the slab)
   return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_circular, H, (size_t)gat::kMtLdsWords * 4);
+}
+
+// SamplerUniverse: k_universe
+static int enqueue_universe(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
+  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerUniverse has no reference-stream mode");
+  gat::UniverseArgs H;
+  memset(&H, 0, sizeof(H));
+  H.ws = P->d_ws.p; H.univ_unit = P->d_univ_unit.p;
+  // (LDS for the generator's state and the mark table of the largest active unit, one bit per piece in whole wave steps:
+  //  the kernel is the chain of the marks' test-and-set steps, hidden by the waves a CU holds, and LDS is what bounds them.
+  //  Problem creation refused what the context's LDS does not hold)
+  H.table_words = (int32_t)P->univ_table_words;
+  const size_t lds = (size_t)gat::kUniverseFixedLdsBytes + (size_t)H.table_words * 4;
+  if ((int64_t)lds > ctx->max_lds) return set_err(ctx, GAT_ERR_CAPACITY, "SamplerUniverse: a mark table of %d words", (int)H.table_words);
+  return enqueue_list_sampler(ctx, P, B, seed, begin, gat::k_universe, H, lds);
 }
 
 // SamplerBruteForce: k_brute_force
@@ -1273,6 +1289,7 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
     else if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) rc = enqueue_permute_local(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) rc = enqueue_brute_force(ctx, P, B, seed, begin);
     else if (P->sampler == GAT_SAMPLER_CIRCULAR) rc = enqueue_circular(ctx, P, B, seed, begin);
+    else if (P->sampler == GAT_SAMPLER_UNIVERSE) rc = enqueue_universe(ctx, P, B, seed, begin);
     else rc = enqueue_placement_sampler(ctx, P, B, seed, begin, A);
     if (rc) return rc;
   }
@@ -1675,7 +1692,8 @@ extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const i
                                   : P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION ? "SamplerGlobalPermutation"
                                   : P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION ? "SamplerLocalPermutation"
                                   : P->sampler == GAT_SAMPLER_BRUTE_FORCE ? "SamplerBruteForce"
-                                  : P->sampler == GAT_SAMPLER_CIRCULAR ? "SamplerCircular" : nullptr;
+                                  : P->sampler == GAT_SAMPLER_CIRCULAR ? "SamplerCircular"
+                                  : P->sampler == GAT_SAMPLER_UNIVERSE ? "SamplerUniverse" : nullptr;
   if (per_unit_only) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: %s runs on the per-unit streams only", per_unit_only);
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
   const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state, false);

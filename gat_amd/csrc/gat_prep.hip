@@ -1031,9 +1031,10 @@ struct UnitTables {
   std::vector<uint32_t> lperm_len;
   std::vector<uint4> circ_unit;                    // GAT_SAMPLER_CIRCULAR: gat_problem::d_circ_*
   std::vector<uint2> circ_iv;
+  std::vector<uint4> univ_unit;                    // GAT_SAMPLER_UNIVERSE: gat_problem::d_univ_unit
   explicit UnitTables(size_t n)                    // (per-unit arrays: at least one element, for the upload)
       : len_cv2(n, 0.0), shift_off(n, 0), perm_unit(n, make_uint4(0u, 0u, 0u, 0u)), lperm_unit(n, make_uint4(0u, 0u, 0u, 0u)),
-        circ_unit(n, make_uint4(0u, 0u, 0u, 0u)) {}
+        circ_unit(n, make_uint4(0u, 0u, 0u, 0u)), univ_unit(n, make_uint4(0u, 0u, 0u, 0u)) {}
 };
 
 static int check_problem_desc(gat_ctx* ctx, const gat_problem_desc* d) {
@@ -1090,6 +1091,10 @@ static void append_sampler_tables(gat_problem* P, UnitTables& T, int u, const Un
     T.circ_unit[(size_t)u] = make_uint4((uint32_t)T.circ_iv.size(), (uint32_t)R.circ_iv.size(), (uint32_t)R.ws.size(), R.cdf.back() + 1u);
     T.circ_iv.insert(T.circ_iv.end(), R.circ_iv.begin(), R.circ_iv.end());
   }
+  if (P->sampler == GAT_SAMPLER_UNIVERSE) {
+    T.univ_unit[(size_t)u] = R.univ;
+    P->univ_table_words = std::max<int64_t>(P->univ_table_words, universe_table_words((int64_t)R.univ.y));
+  }
   if (P->sampler == GAT_SAMPLER_SHIFT) {
     T.shift_off[(size_t)u] = (int32_t)(T.shift.size() / 2);
     T.shift.insert(T.shift.end(), R.shift.begin(), R.shift.end());
@@ -1118,6 +1123,10 @@ static int gather_unit_tables(gat_ctx* ctx, const gat_problem_desc* d, const Kno
     }
     if (R.rc) return set_err(ctx, R.rc, "%s", R.err.c_str());
     if (!R.active) continue;
+    if (P->sampler == GAT_SAMPLER_UNIVERSE) {        // (refused, never computed: a mark table beyond the context's LDS)
+      const std::string refusal = universe_refusal(u, (int64_t)R.ws.size(), ctx->max_lds);
+      if (!refusal.empty()) return set_err(ctx, GAT_ERR_ARG, "%s", refusal.c_str());
+    }
     U.rank_off = (int32_t)T.rank_len.size();
     T.rank_len.insert(T.rank_len.end(), R.rank.begin(), R.rank.end());
     U.ws_off = (int32_t)T.ws.size();
@@ -1276,7 +1285,7 @@ static int64_t rng_rows_for_unit(const gat_problem* P, const Knobs& kn, const Un
 }
 
 static void size_rng_rows(gat_problem* P, const gat_problem_desc* d, const Knobs& kn, const UnitTables& T) {
-  // (k_shift, k_permute, k_permute_local, k_brute_force, k_circular: a wave per work unit, its stream in LDS)
+  // (k_shift, k_permute, k_permute_local, k_brute_force, k_circular, k_universe: a wave per work unit, its stream in LDS)
   if (kn.sampler_mode == "wave" || sampler_runs_wave_per_unit(P->sampler)) P->sampler_mode = 0;
   for (int32_t u : P->h_order) {
     const int64_t rows = rng_rows_for_unit(P, kn, P->h_units[(size_t)u], d->ws + d->ws_off[u], d->ws_off[u + 1] - d->ws_off[u], T.len_cv2[(size_t)u]);
@@ -1305,6 +1314,7 @@ static int upload_sampler_tables(gat_ctx* ctx, gat_problem* P, UnitTables& T) {
     HIPCHK(ctx, P->d_circ_unit.upload(T.circ_unit, ctx));
     HIPCHK(ctx, P->d_circ_iv.upload(T.circ_iv, ctx));
   }
+  if (P->sampler == GAT_SAMPLER_UNIVERSE) HIPCHK(ctx, P->d_univ_unit.upload(T.univ_unit, ctx));
   if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) {
     if (T.lperm_piece.empty()) T.lperm_piece.push_back(make_uint4(0u, 0u, 0u, 0u));
     if (T.lperm_len.empty()) T.lperm_len.push_back(0u);

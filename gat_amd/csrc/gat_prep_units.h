@@ -65,6 +65,7 @@ struct UnitPrep {
   std::vector<uint32_t> perm_cum;
   int64_t perm_free = 0;
   std::vector<uint2> circ_iv;          // GAT_SAMPLER_CIRCULAR: the working list in linear workspace coordinates {start, length}
+  uint4 univ = {0u, 0u, 0u, 0u};       // GAT_SAMPLER_UNIVERSE: {k, m, c, invert} (universe_record)
   std::vector<uint4> lperm;            // GAT_SAMPLER_LOCAL_PERMUTATION: the active pieces, the sum and maximum of their n
   int64_t lperm_sum_n = 0, lperm_max_n = 0;
   int64_t nwork = 0;
@@ -164,6 +165,40 @@ inline void circular_intervals(std::vector<uint2>& out, const gat_segment* us, i
   }
 }
 
+// SamplerUniverse (no counterpart in the reference; DESIGN.md section 5, "k_universe"): the unit's workspace pieces are the
+// candidates.  k: the pieces that share at least one base with a segment -- one merge walk of the (normalized) segments
+// against the pieces; a segment over two pieces hits two, one outside the workspace none.
+inline int64_t universe_hits(const gat_segment* us, int64_t nus, const gat_segment* uw, int64_t nuw) {
+  int64_t k = 0, j = 0;                // j: the first piece no segment so far has hit or passed
+  for (int64_t i = 0; i < nus; ++i) {
+    while (j < nuw && uw[j].end <= us[i].start) ++j;
+    for (; j < nuw && uw[j].start < us[i].end; ++j) ++k;
+  }
+  return k;
+}
+
+// ... the unit's record {k, m, c, invert}: Floyd's algorithm marks the smaller side, c = k pieces when 2k <= m, else the
+// m - k that stay out (invert)
+inline uint4 universe_record(int64_t k, int64_t m) {
+  const bool invert = 2 * k > m;
+  return make_uint4((uint32_t)k, (uint32_t)m, (uint32_t)(invert ? m - k : k), invert ? 1u : 0u);
+}
+
+// ... and the table of m mark bits k_universe keeps in LDS beside the generator's state, in whole wave steps of 64 words
+// (2 048 pieces): the words a launch needs for a unit of m pieces, and the most pieces a context's LDS limit takes
+inline int64_t universe_table_words(int64_t m) { return (m + 2047) / 2048 * 64; }
+inline int64_t universe_max_pieces(int64_t max_lds) {
+  return std::max<int64_t>(0, (max_lds - gat::kUniverseFixedLdsBytes) / 4 / 64) * 2048;
+}
+// the message of a unit that does not fit (empty: it fits)
+inline std::string universe_refusal(int u, int64_t m, int64_t max_lds) {
+  if (m <= universe_max_pieces(max_lds)) return std::string();
+  char buf[256];
+  snprintf(buf, sizeof(buf), "unit %d: SamplerUniverse: %lld workspace pieces, the mark table in LDS takes at most %lld", u,
+           (long long)m, (long long)universe_max_pieces(max_lds));
+  return buf;
+}
+
 // SamplerLocalPermutation (gat/Engine.pyx:1174-1188): per workspace piece (ws, we) the working segments are
 // getOverlappingSegments' set (gat/SegmentList.pyx:952-983) -- from the last segment with start <= ws (the first one when
 // there is none) on, every segment with start <= we, whether or not it reaches the piece --, a contiguous run of the
@@ -219,6 +254,8 @@ inline int64_t base_cap_for(int32_t sampler, const Knobs& kn, const UnitDev& U, 
     //  more working segments than LDS holds keeps its lengths and points at the top of the region)
     // (exact: an interval gives one piece and one more per border of the workspace or wrap it crosses, |W| over the list)
     case GAT_SAMPLER_CIRCULAR: return (int64_t)R.circ_iv.size() + (int64_t)R.ws.size();
+    // (exact: k whole pieces, nothing united or cut)
+    case GAT_SAMPLER_UNIVERSE: return (int64_t)R.univ.x;
     case GAT_SAMPLER_LOCAL_PERMUTATION: return 2 * R.lperm_sum_n + (R.lperm_max_n > 2048 ? 2 * R.lperm_max_n : 0);
     default: return cap_for(kn, R.nwork);
   }
@@ -433,6 +470,11 @@ inline void prepare_unit(const gat_problem_desc& d, const Knobs& kn, int u, Unit
     circular_intervals(R.circ_iv, us, nus, uw, nuw, R.cdf);
     U.hist_total = (uint32_t)R.circ_iv.size();   // (n: the intervals the kernel maps, at most the working segments' pieces)
     R.nwork = (int64_t)R.circ_iv.size();
+  }
+  if (d.sampler == GAT_SAMPLER_UNIVERSE) {
+    R.univ = universe_record(universe_hits(us, nus, uw, nuw), nuw);
+    U.hist_total = R.univ.x;                     // (k: the pieces of every list)
+    R.nwork = (int64_t)R.univ.z + nuw / 64;      // (the launch order: the marks' chain and the table's words)
   }
   R.active = true;
 }

@@ -25,6 +25,7 @@ constexpr int kPlaceWide = GAT_PLACE_WIDE_TILES;   // k_place_wide: tiles (waves
 constexpr int kPlaceWideMaxRank = 20480;  // ... whose size is bounded by the LDS beside the eight 8 KB rings (80 KB of 160)
 constexpr int kTailMaxWs = 64;        // workspace segments k_tail scans linearly (wave-uniform loop)
 constexpr int kMergedSlots = 8;       // k_count_merged: contigs are dealt to this many slots (blockIdx % 8: the XCD stride)
+constexpr int kUniverseFixedLdsBytes = 2560;   // k_universe: the generator's state (kMtLdsWords) in front of the mark table
 
 // per isochore unit, everything SamplerAnnotator.sample derives from (segments, workspace) before
 // its loop (gat/Engine.pyx:543-565), hoisted to problem creation.

@@ -1365,6 +1365,40 @@ class SamplerCircular(Sampler):
         return r
 
 
+class SamplerUniverse(Sampler):
+    """The subset null of a finite universe of candidate regions (LOLA's universe, GREAT's background set; the reference has
+    no such sampler).  The universe is the workspace: its pieces are the candidates -- all called peaks, all promoters, all CpG
+    islands -- and the segments are a chosen subset of them.  k of the m pieces share at least one base with a segment; a
+    sample is k pieces chosen uniformly without replacement, each whole and in genome order, nothing united or cut: "any
+    other subset of the same size".  The observed counts stay those of the segments as given, the sampler defines the null
+    only -- so the segments should be members of the universe (pieces of the workspace) for the test to mean what it
+    says.  Per (contig, isochore) unit one draw, so isochores stratify it.  Same per-unit stream convention as
+    SamplerAnnotator.sample (numpy's).  No parameters."""
+
+    kind = 7
+
+    def __init__(self):
+        pass
+
+    def sample(self, segments, workspace, seed=None):
+        assert workspace.isNormalized, "workspace is not normalized"
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 32))
+        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
+            return SegmentList()
+        s, w = segments.asArray(), workspace.asArray()
+        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
+                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], sampler=self.kind)
+        P = _lib.Problem(get_context(), flat)
+        try:
+            seg, _ = P.sample(seed, 0, 1)
+        finally:
+            P.close()
+        r = SegmentList(array=seg)
+        r.isNormalized = 1
+        return r
+
+
 class Counter(object):
     name = None
 

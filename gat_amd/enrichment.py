@@ -101,7 +101,7 @@ def track_start(segs, workspace, sampler, num_samples, random_seed):
     them with their offsets: contig_lists)."""
     if not isinstance(sampler, SAMPLERS):
         raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation, SamplerBruteForce and SamplerCircular run on the GPU path")
+                                  "SamplerLocalPermutation, SamplerBruteForce, SamplerCircular and SamplerUniverse run on the GPU path")
     num_samples = int(num_samples)
     if num_samples < 1:
         raise ValueError("num_samples < 1")

@@ -76,6 +76,13 @@ typedef struct gat_annotations gat_annotations;
                                   /* borders and the wrap, nothing united afterwards; a problem without tracks    */
                                   /* and isochore keys takes coordinates up to 2^32 - 1; numpy's stream; per-unit  */
                                   /* streams only                                                                 */
+#define GAT_SAMPLER_UNIVERSE 7    /* SamplerUniverse (no counterpart in the reference): the  */
+                                  /* unit's workspace pieces are the universe of candidate regions; k of the m    */
+                                  /* pieces share a base with a segment, and a sample is k pieces chosen          */
+                                  /* uniformly without replacement (Floyd's algorithm on the smaller side), each  */
+                                  /* whole, in genome order, nothing united or cut; a unit whose table of m mark  */
+                                  /* bits is beyond the context's LDS is refused at gat_problem_create with       */
+                                  /* GAT_ERR_ARG; numpy's stream; per-unit streams only                           */
 
 /*
  * Flat description of what gat.computeSample (gat/__init__.py:494-591) walks for one segment
@@ -107,7 +114,7 @@ typedef struct {
   const int64_t* cws_nseg;      /* n_contigs: len(contig_workspace[contig]) (Engine.pyx:1437)   */
   uint32_t bucket_size;         /* SamplerAnnotator(bucket_size, nbuckets): gat/Engine.pyx:498  */
   int32_t nbuckets;
-  int32_t sampler;              /* GAT_SAMPLER_ANNOTATOR (gat/Engine.pyx:445), GAT_SAMPLER_SEGMENTS (:653), GAT_SAMPLER_SHIFT (:998), GAT_SAMPLER_GLOBAL_PERMUTATION (:1234), GAT_SAMPLER_LOCAL_PERMUTATION (:1117), GAT_SAMPLER_BRUTE_FORCE (:746) or GAT_SAMPLER_CIRCULAR */
+  int32_t sampler;              /* GAT_SAMPLER_ANNOTATOR (gat/Engine.pyx:445), GAT_SAMPLER_SEGMENTS (:653), GAT_SAMPLER_SHIFT (:998), GAT_SAMPLER_GLOBAL_PERMUTATION (:1234), GAT_SAMPLER_LOCAL_PERMUTATION (:1117), GAT_SAMPLER_BRUTE_FORCE (:746), GAT_SAMPLER_CIRCULAR or GAT_SAMPLER_UNIVERSE */
   /* Optional (all 0 / NULL: annos / anno_off are the [track][contig] lists above).  With anno_group set, the caller hands
    * over the annotation lists as it holds them -- one per (track, isochore key), the `annotations` argument of
    * UnconditionalSampler.sample (gat/__init__.py:704) -- and the library forms computeSample's contig_annotations itself

@@ -37,7 +37,7 @@ from gat_amd import enrichment, geneset as Geneset  # noqa: E402
 def buildParser(usage=None):
     """gat-run.py's parser without its counters and descriptions; --genes names the gene file, -m goes from --sampler to
     --gene-sets as in the reference's script, --qvalue-method is limited to the adjustments of p-values, and --min-term-genes"""
-    parser = gat.buildParser(usage=usage, samplers=gat.TOOL_SAMPLERS)
+    parser = gat.buildParser(usage=usage, samplers=gat.TOOL_SAMPLERS + gat.UNIVERSE_SAMPLERS)
     sampler = parser.get_option("--sampler")
     for name in ("--counter", "--qvalue-method", "--descriptions", "--sampler"):
         parser.remove_option(name)

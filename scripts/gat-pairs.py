@@ -33,7 +33,7 @@ from gat_amd import enrichment, pairs as Pairs  # noqa: E402
 
 def buildParser(usage=None):
     """gat-run.py's parser without its counters, --qvalue-method limited to the adjustments of p-values, and --include-single"""
-    parser = gat.buildParser(usage=usage, samplers=gat.TOOL_SAMPLERS)
+    parser = gat.buildParser(usage=usage, samplers=gat.TOOL_SAMPLERS + gat.UNIVERSE_SAMPLERS)
     parser.remove_option("--counter")
     parser.remove_option("--qvalue-method")
     parser.add_option("-q", "--qvalue-method", dest="qvalue_method", type="choice", choices=Pairs.QVALUE_METHODS,

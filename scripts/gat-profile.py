@@ -43,7 +43,7 @@ from gat_amd import enrichment, profile as Profile  # noqa: E402
 def buildParser(usage=None):
     """gat-run.py's parser without its counters and descriptions; --anchors names the anchor files, --qvalue-method is limited
     to the adjustments of p-values, and the geometry of the profile"""
-    parser = gat.buildParser(usage=usage, samplers=gat.TOOL_SAMPLERS)
+    parser = gat.buildParser(usage=usage, samplers=gat.TOOL_SAMPLERS + gat.UNIVERSE_SAMPLERS)
     for name in ("--counter", "--qvalue-method", "--descriptions"):
         parser.remove_option(name)
     parser.add_option("--anchors", dest="annotation_files", type="string", action="append",

@@ -41,7 +41,7 @@ from gat_amd import enrichment, reldist as Reldist  # noqa: E402
 def buildParser(usage=None):
     """gat-run.py's parser without its counters and descriptions; --qvalue-method is limited to the adjustments of p-values,
     and the point of an interval and the number of bins"""
-    parser = gat.buildParser(usage=usage, samplers=gat.TOOL_SAMPLERS)
+    parser = gat.buildParser(usage=usage, samplers=gat.TOOL_SAMPLERS + gat.UNIVERSE_SAMPLERS)
     for name in ("--counter", "--qvalue-method", "--descriptions"):
         parser.remove_option(name)
     parser.add_option("--annotation-point", dest="annotation_point", type="choice", choices=Reldist.ANNOTATION_POINTS,

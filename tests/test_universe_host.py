@@ -1,0 +1,85 @@
+"""CPU: the universe sampler's host side -- its records at problem creation (tests/host/universe_check.cpp, a stand-alone
+program compiled for the host alone with the address and undefined-behaviour sanitizers), the command line, the Python
+class and the C ABI's constants."""
+import importlib.util
+import inspect
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import gat_amd
+from gat_amd import _lib, coverage, enrichment
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "gat_mi355.h")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+TOOLS = ("gat-run", "gat-coverage", "gat-distance", "gat-signal", "gat-local", "gat-pairs", "gat-geneset", "gat-profile", "gat-reldist")
+
+
+def test_universe_check(tmp_path):
+    """k of hand-made and random units, the records {k, m, c, invert}, the slab capacity k, the unit without a hit piece,
+    the mark table's size and the refusal of a unit beyond it"""
+    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
+    if not hipcc:
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "universe_check")
+    cmd = [hipcc, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined",
+           "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "gat_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host", "universe_check.cpp"), "-o", exe]
+    c = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert c.returncode == 0, "the check program does not compile:\n" + c.stderr[-4000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, "universe_check failed (exit status %d):\n%s\n%s" % (r.returncode, r.stdout[-2000:], r.stderr[-6000:])
+
+
+def test_tool_parsers_take_universe():
+    """every tool script passes TOOL_SAMPLERS + UNIVERSE_SAMPLERS, and gat-run's parser takes --sampler=universe"""
+    for tool in TOOLS:
+        src = open(os.path.join(ROOT, "scripts", tool + ".py")).read()
+        assert "gat.TOOL_SAMPLERS + gat.UNIVERSE_SAMPLERS" in src, tool
+    spec = importlib.util.spec_from_file_location("gat_run_cli_universe_host", os.path.join(ROOT, "scripts", "gat-run.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    seen = {}
+
+    class Reached(Exception):
+        pass
+
+    def stop(options, args=None):
+        seen["sampler"] = options.sampler
+        raise Reached()
+
+    old = gat_amd.fromSegments
+    gat_amd.fromSegments = stop
+    try:
+        with pytest.raises(Reached):
+            mod.main(["gat-run.py", "--sampler=universe", "--segments=s.bed", "--annotations=a.bed", "--workspace=w.bed"])
+    finally:
+        gat_amd.fromSegments = old
+    assert seen["sampler"] == "universe"
+
+
+def test_samplers_are_mapped():
+    assert '"universe"' in inspect.getsource(gat_amd.fromSegments) and "SamplerUniverse()" in inspect.getsource(gat_amd.fromSegments)
+
+    class Opt(object):
+        sampler = "universe"
+    assert isinstance(coverage.make_sampler(Opt()), gat_amd.SamplerUniverse)
+    assert gat_amd.SamplerUniverse in coverage.SAMPLERS and enrichment.SAMPLERS is coverage.SAMPLERS
+    assert "universe members" in " ".join(gat_amd.SamplerUniverse.__doc__.split()) or "members of the universe" in " ".join(gat_amd.SamplerUniverse.__doc__.split())
+
+
+def test_reference_stream_refused():
+    """run(reference_stream=True) with SamplerUniverse raises before anything reaches a device."""
+    e = gat_amd.IntervalCollection()
+    with pytest.raises(NotImplementedError, match="SamplerUniverse runs on the per-unit streams only"):
+        gat_amd.run(e, e, e, gat_amd.SamplerUniverse(), [gat_amd.CounterNucleotideOverlap()],
+                    workspace_generator=gat_amd.UnconditionalWorkspace(), num_samples=4, random_seed=1, reference_stream=True)
+
+
+def test_ctypes_constant_matches_header():
+    text = open(HEADER).read()
+    assert "#define GAT_SAMPLER_UNIVERSE %d " % _lib.SAMPLER_UNIVERSE in text
+    assert _lib.SAMPLER_UNIVERSE == 7 == gat_amd.SamplerUniverse.kind
