@@ -11,6 +11,7 @@ from . import intervals, problem, synthetic            # noqa: F401
 from . import io as IO                                   # noqa: F401
 from . import stats as Stats                             # noqa: F401
 from .engine import (SegmentList, PositionList, IntervalDictionary, IntervalCollection, Sampler, SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerBruteForce, SamplerCircular, SamplerUniverse,  # noqa: F401
+                     SAMPLER_CLASSES, sampler_from_options, check_sampler, check_reference_stream,
                      Counter, computeCountsAll, overlap_sizes, CounterNucleotideOverlap, CounterNucleotideDensity, CounterSegmentOverlap,
                      CounterSegmentMidpointOverlap, CounterAnnotationOverlap, CounterAnnotationMidpointOverlap,
                      UnconditionalWorkspace, ConditionalWorkspaceCooccurance, ConditionalWorkspaceCentered,
@@ -254,11 +255,7 @@ def _sample_start(segs, annotations, workspace, sampler, counters, num_samples, 
         flat = problem.flatten_units(segs.asArrays(), workspace.asArrays(), [(t, annotations[t].asArrays()) for t in tracks],
                                      bucket_size, nbuckets,
                                      count_workspace=None if count_workspace is None else count_workspace.asArrays())
-    flat["sampler"] = getattr(sampler, "kind", 0)
-    if flat["sampler"] == SamplerShift.kind:
-        flat["shift_radius"], flat["shift_extension"] = sampler.radius, sampler.extension
-    if flat["sampler"] == SamplerBruteForce.kind:
-        flat["brute_ntries_inner"], flat["brute_ntries_outer"] = sampler.ntries_inner, sampler.ntries_outer
+    flat.update(sampler.flat_fields())
     job.flat = flat
     names = job.names
     if null_round_size > 0:
@@ -646,28 +643,15 @@ def _run(segments, annotations, workspace, sampler, counters, workspace_generato
             dist.broadcast_object_list(box, src=0)
             seed = int(box[0])
     conditional = getattr(workspace_generator, "is_conditional", False)
-    if not isinstance(sampler, (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation,
-                                SamplerBruteForce, SamplerCircular, SamplerUniverse)):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation, SamplerBruteForce, SamplerCircular and SamplerUniverse run on the GPU path")
+    check_sampler(sampler)
     if _dist_state()[0] != 0:
         outfiles = {}                # (one writer: rank 0 computes and writes the metrics, all samples, no sharding)
     if "segment_metrics" in outfiles:
         from . import metrics
         metrics.write_segment_metrics(outfiles["segment_metrics"], segments, workspace)     # gat/__init__.py:913-925
     mt_state = None
-    if reference_stream and isinstance(sampler, SamplerShift):
-        raise NotImplementedError("reference_stream: SamplerShift runs on the per-unit streams only")
-    if reference_stream and isinstance(sampler, SamplerGlobalPermutation):
-        raise NotImplementedError("reference_stream: SamplerGlobalPermutation runs on the per-unit streams only")
-    if reference_stream and isinstance(sampler, SamplerLocalPermutation):
-        raise NotImplementedError("reference_stream: SamplerLocalPermutation runs on the per-unit streams only")
-    if reference_stream and isinstance(sampler, SamplerBruteForce):
-        raise NotImplementedError("reference_stream: SamplerBruteForce runs on the per-unit streams only")
-    if reference_stream and isinstance(sampler, SamplerCircular):
-        raise NotImplementedError("reference_stream: SamplerCircular runs on the per-unit streams only")
-    if reference_stream and isinstance(sampler, SamplerUniverse):
-        raise NotImplementedError("reference_stream: SamplerUniverse runs on the per-unit streams only")
+    if reference_stream:
+        check_reference_stream(sampler)
     if reference_stream:
         # the reference's own stream: numpy.random.seed(seed) once (scripts/gat-run.py:267-271), every work unit of every
         # segment track drawing from it in order -- an unpatched reference's table, number for number, at one stream's speed
@@ -866,6 +850,9 @@ TOOL_SAMPLERS = CLI_SAMPLERS + ("circular",)
 # ... and UNIVERSE_SAMPLERS the subset null of a finite universe, the workspace's pieces (DESIGN §5 "k_universe"): the
 # scripts pass TOOL_SAMPLERS + UNIVERSE_SAMPLERS.  The tuples above stay as they were, as before.
 UNIVERSE_SAMPLERS = ("universe",)
+# the words and the classes are one list: a sampler added to one and not the other fails here, not in a user's run
+assert tuple(cls.word for cls in SAMPLER_CLASSES) == TOOL_SAMPLERS + UNIVERSE_SAMPLERS
+assert [cls.kind for cls in SAMPLER_CLASSES] == list(range(len(SAMPLER_CLASSES)))
 
 
 def buildParser(usage=None, samplers=SAMPLERS):
@@ -1028,24 +1015,7 @@ def fromSegments(options, args=None):
                                       truncate_segments_to_workspace=options.truncate_segments_to_workspace,
                                       truncate_workspace_to_annotations=options.truncate_workspace_to_annotations,
                                       restrict_workspace=options.restrict_workspace)
-        if options.sampler == "annotator":
-            sampler = SamplerAnnotator(bucket_size=options.bucket_size, nbuckets=options.nbuckets)
-        elif options.sampler == "segments":
-            sampler = SamplerSegments()                      # scripts/gat-run.py:133 passes no bucket arguments
-        elif options.sampler == "shift":
-            sampler = SamplerShift(radius=options.shift_expansion, extension=options.shift_extension)   # scripts/gat-run.py:129-132
-        elif options.sampler == "global-permutation":
-            sampler = SamplerGlobalPermutation()             # scripts/gat-run.py:137-138
-        elif options.sampler == "local-permutation":
-            sampler = SamplerLocalPermutation()              # scripts/gat-run.py:135-136
-        elif options.sampler == "brute-force":
-            sampler = SamplerBruteForce()                    # scripts/gat-run.py:139-140 (no bucket arguments: bucket_size 1)
-        elif options.sampler == "circular":
-            sampler = SamplerCircular()
-        elif options.sampler == "universe":
-            sampler = SamplerUniverse()
-        else:
-            raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
+        sampler = sampler_from_options(options)
         counters = []
         for counter in options.counters:
             if counter not in COUNTERS:

@@ -18,11 +18,8 @@ import collections
 import numpy as np
 
 from . import problem
-from .engine import (SamplerAnnotator, SamplerBruteForce, SamplerCircular, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerSegments,
-                     SamplerShift, SamplerUniverse, get_context)
-
-SAMPLERS = (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation, SamplerBruteForce,
-            SamplerCircular, SamplerUniverse)
+from .engine import SAMPLER_CLASSES as SAMPLERS
+from .engine import check_sampler, get_context, sampler_from_options
 
 
 class Coverage(object):
@@ -61,11 +58,7 @@ def flatten(segs, workspace, sampler):
     takes none, and the coverage needs none."""
     sa, wa = segs.asArrays(), workspace.asArrays()
     flat = problem.flatten_units(sa, wa, [], getattr(sampler, "bucket_size", 0), getattr(sampler, "nbuckets", 100000))
-    flat["sampler"] = getattr(sampler, "kind", 0)
-    if flat["sampler"] == SamplerShift.kind:
-        flat["shift_radius"], flat["shift_extension"] = sampler.radius, sampler.extension
-    if flat["sampler"] == SamplerBruteForce.kind:
-        flat["brute_ntries_inner"], flat["brute_ntries_outer"] = sampler.ntries_inner, sampler.ntries_outer
+    flat.update(sampler.flat_fields())
     return flat, sa, wa
 
 
@@ -73,9 +66,7 @@ def sample_coverage(segs, workspace, sampler, num_samples, bin_size, random_seed
     """Coverage of num_samples samples of `segs` in `workspace` (IntervalDictionary, isochore level, as sample_counts takes
     them) under `sampler`.  random_seed: base of the per-unit streams (None: drawn from numpy's global RandomState)."""
     from . import _lib
-    if not isinstance(sampler, SAMPLERS):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation, SamplerBruteForce, SamplerCircular and SamplerUniverse run on the GPU path")
+    check_sampler(sampler)
     bin_size, num_samples = int(bin_size), int(num_samples)
     if not 1 <= bin_size <= 2 ** 31:
         raise ValueError("bin_size %d outside [1, 2^31]" % bin_size)
@@ -167,21 +158,4 @@ def build_inputs(options):
 
 def make_sampler(options):
     """the sampler of --sampler, built as gat.fromSegments builds it (scripts/gat-run.py:129-140 of the reference)"""
-    name = options.sampler
-    if name == "annotator":
-        return SamplerAnnotator(bucket_size=options.bucket_size, nbuckets=options.nbuckets)
-    if name == "segments":
-        return SamplerSegments()
-    if name == "shift":
-        return SamplerShift(radius=options.shift_expansion, extension=options.shift_extension)
-    if name == "global-permutation":
-        return SamplerGlobalPermutation()
-    if name == "local-permutation":
-        return SamplerLocalPermutation()
-    if name == "brute-force":
-        return SamplerBruteForce()
-    if name == "circular":
-        return SamplerCircular()
-    if name == "universe":
-        return SamplerUniverse()
-    raise ValueError("sampler '%s' is outside the accelerated path" % name)
+    return sampler_from_options(options)

@@ -22,6 +22,7 @@
 #include "../../include/gat_mi355.h"
 #include "gat_types.h"
 #include "gat_knobs.h"
+#include "gat_samplers.h"
 
 namespace gat { struct TailPatch; }
 
@@ -135,13 +136,10 @@ struct gat_ctx {
 // (build_annos: lists beyond it get the merged index) -- they had drifted apart by three entries
 inline bool count_lists_staged(const Knobs& kn, int64_t max_m) { return max_m > 0 && max_m + 4 <= kn.count_lds_entries; }
 
-// gat_problem_desc::sampler: the samplers there are; those whose kernel is a wave per work unit with its stream in LDS
-// (k_shift, k_permute, k_permute_local, k_brute_force, k_circular, k_universe: no k_rng + k_place in front).  sampler_draws_lengths: gat_prep_units.h
-inline bool sampler_runs_wave_per_unit(int32_t s) {
-  return s == GAT_SAMPLER_SHIFT || s == GAT_SAMPLER_GLOBAL_PERMUTATION || s == GAT_SAMPLER_LOCAL_PERMUTATION || s == GAT_SAMPLER_BRUTE_FORCE ||
-         s == GAT_SAMPLER_CIRCULAR || s == GAT_SAMPLER_UNIVERSE;
-}
-inline bool sampler_is_known(int32_t s) { return s == GAT_SAMPLER_ANNOTATOR || s == GAT_SAMPLER_SEGMENTS || sampler_runs_wave_per_unit(s); }
+// gat_problem_desc::sampler: the samplers there are; those whose kernel is a wave per work unit (gat_samplers.h has the
+// table).  sampler_draws_lengths: gat_prep_units.h
+inline bool sampler_is_known(int32_t s) { return sampler_info(s) != nullptr; }
+inline bool sampler_runs_wave_per_unit(int32_t s) { return sampler_is_known(s) && sampler_info(s)->wave_per_unit; }
 
 void ctx_release(gat_ctx* ctx);     // gat_mi355.hip: drops one reference, frees the context with the last
 
@@ -383,20 +381,20 @@ struct gat_problem {
   DevBuf<uint4> d_ws_rec;                // per workspace segment {start, end, previous segment's end (INT32_MIN: none), cdf}: what a
                                          // position draw needs of its segment in ONE 16-byte access (k_place_grid)
   DevBuf<int64_t> d_cws_nseg;
-  // GAT_SAMPLER_SHIFT: per working segment two records {length, first window piece (index into the unit's workspace),
+  // SamplerShift: per working segment two records {length, first window piece (index into the unit's workspace),
   // window pieces, window bases} {first piece's clipped start, last piece's clipped end, 0, 0} -- the window
   // (getOverlappingSegmentsWithRange + truncate, gat/Engine.pyx:1083-1084) does not depend on the stream; d_shift_off:
   // per unit, the index of its first record pair
   DevBuf<uint4> d_shift;
   DevBuf<int32_t> d_shift_off;
-  // GAT_SAMPLER_GLOBAL_PERMUTATION: per unit {offset into d_perm_len, offset into d_perm_w / d_perm_cum, |W|, free}; the
+  // SamplerGlobalPermutation: per unit {offset into d_perm_len, offset into d_perm_w / d_perm_cum, |W|, free}; the
   // working segments' lengths in list order; W (the unit's workspace extended by its working segments, merge(0)ed) and its
   // cumulated lengths (entry j: bases of pieces 0..j)
   DevBuf<uint4> d_perm_unit;
   DevBuf<uint32_t> d_perm_len;
   DevBuf<uint2> d_perm_w;
   DevBuf<uint32_t> d_perm_cum;
-  // GAT_SAMPLER_LOCAL_PERMUTATION: per unit {offset into d_lperm_piece, active pieces, offset into d_lperm_len, sum of the
+  // SamplerLocalPermutation: per unit {offset into d_lperm_piece, active pieces, offset into d_lperm_len, sum of the
   // pieces' n (draw groups)}; per active workspace piece, in order, {first working segment (index into the unit's list), n,
   // work_end, free} (work_start is 0: gat_local_permute.h); the lengths of the unit's segments, unfiltered, in list order --
   // a piece's working segments are a contiguous run of them
@@ -405,16 +403,16 @@ struct gat_problem {
   DevBuf<uint32_t> d_lperm_len;
   int32_t lperm_max_n = 0;               // ... the most working segments of one piece, the longest raw list (sum of 2n) of a unit
   int64_t lperm_max_out = 0;
-  // GAT_SAMPLER_CIRCULAR: per unit {offset into d_circ_iv, n, |W|, Wsum}; the working list in linear workspace coordinates
+  // SamplerCircular: per unit {offset into d_circ_iv, n, |W|, Wsum}; the working list in linear workspace coordinates
   // {linear start, length} (gat_prep_units.h: circular_intervals).  W and its cumulated lengths are the unit's part of d_ws and
   // d_ws_cdf (cumulated - 1)
   DevBuf<uint4> d_circ_unit;
   DevBuf<uint2> d_circ_iv;
-  // GAT_SAMPLER_UNIVERSE: per unit {k, m, c, invert} (gat_prep_units.h: universe_record); the pieces are the unit's part of
+  // SamplerUniverse: per unit {k, m, c, invert} (gat_prep_units.h: universe_record); the pieces are the unit's part of
   // d_ws.  univ_table_words: the launch's mark table, universe_table_words of the most pieces an active unit has
   DevBuf<uint4> d_univ_unit;
   int64_t univ_table_words = 0;
-  // GAT_SAMPLER_BRUTE_FORCE: SamplerBruteForce(ntries_inner, ntries_outer) (the desc's 0 replaced by the reference's 100 / 10)
+  // SamplerBruteForce(ntries_inner, ntries_outer) (the desc's 0 replaced by the reference's 100 / 10)
   int32_t brute_ntries_inner = 100, brute_ntries_outer = 10;
   gat_annotations* anno = nullptr;       // the annotation tables: its own (made from the lists of its desc) or a shared object
   // per-batch scratch

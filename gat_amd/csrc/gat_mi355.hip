@@ -598,7 +598,6 @@ static int enqueue_list_sampler(gat_ctx* ctx, gat_problem* P, const BatchPlan& B
 
 // SamplerShift: k_shift
 static int enqueue_shift(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
-  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerShift has no reference-stream mode");
   gat::ShiftArgs H;
   memset(&H, 0, sizeof(H));
   // (LDS for the list a unit is expected to leave -- about one piece per segment, a quarter + 64 on top -- not for its slab
@@ -612,7 +611,6 @@ static int enqueue_shift(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint3
 
 // SamplerGlobalPermutation: k_permute
 static int enqueue_permute(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
-  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerGlobalPermutation has no reference-stream mode");
   gat::PermuteArgs H;
   memset(&H, 0, sizeof(H));
   // (LDS for the lengths and the points of the longest unit, up to 2 048 working segments -- 24 KB with the generator's
@@ -625,7 +623,6 @@ static int enqueue_permute(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uin
 
 // SamplerLocalPermutation: k_permute_local
 static int enqueue_permute_local(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
-  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerLocalPermutation has no reference-stream mode");
   gat::LocalPermuteArgs H;
   memset(&H, 0, sizeof(H));
   // (LDS for the lengths and points of the largest piece, up to 2 048 working segments, and -- the same words -- for the final
@@ -646,7 +643,6 @@ static int enqueue_permute_local(gat_ctx* ctx, gat_problem* P, const BatchPlan& 
 
 // SamplerCircular: k_circular
 static int enqueue_circular(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
-  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerCircular has no reference-stream mode");
   gat::CircularArgs H;
   memset(&H, 0, sizeof(H));
   H.ws = P->d_ws.p; H.ws_cdf = P->d_ws_cdf.p; H.circ_unit = P->d_circ_unit.p; H.circ_iv = P->d_circ_iv.p;
@@ -656,7 +652,6 @@ static int enqueue_circular(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, ui
 
 // SamplerUniverse: k_universe
 static int enqueue_universe(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
-  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerUniverse has no reference-stream mode");
   gat::UniverseArgs H;
   memset(&H, 0, sizeof(H));
   H.ws = P->d_ws.p; H.univ_unit = P->d_univ_unit.p;
@@ -671,7 +666,6 @@ static int enqueue_universe(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, ui
 
 // SamplerBruteForce: k_brute_force
 static int enqueue_brute_force(gat_ctx* ctx, gat_problem* P, const BatchPlan& B, uint32_t seed, int64_t begin) {
-  if (B.o.serial_state != nullptr) return set_err(ctx, GAT_ERR_ARG, "SamplerBruteForce has no reference-stream mode");
   gat::BruteForceArgs H;
   memset(&H, 0, sizeof(H));
   // (LDS for the first kBruteLdsCap accepted segments -- the kernel is a chain of dependent draws, hidden by the waves a CU
@@ -968,6 +962,20 @@ static const sampler_fn kSerialFns[8] = {
     gat::k_serial<0, false, false, false>, gat::k_serial<0, false, true, false>, gat::k_serial<0, true, false, false>,
     gat::k_serial<0, true, true, false>, gat::k_serial<1, false, false, false>, gat::k_serial<1, false, true, false>,
     gat::k_serial<0, false, false, true>, gat::k_serial<0, false, true, true>};
+// the enqueue function of a list sampler (gat_samplers.h: wave_per_unit) by sampler id; SamplerAnnotator / SamplerSegments have
+// none: enqueue_placement_sampler
+typedef int (*list_enqueue_fn)(gat_ctx*, gat_problem*, const BatchPlan&, uint32_t, int64_t);
+static const struct ListEnqueueFns {
+  list_enqueue_fn fn[kNumSamplers] = {};
+  constexpr ListEnqueueFns() {
+    fn[GAT_SAMPLER_SHIFT] = enqueue_shift;
+    fn[GAT_SAMPLER_GLOBAL_PERMUTATION] = enqueue_permute;
+    fn[GAT_SAMPLER_LOCAL_PERMUTATION] = enqueue_permute_local;
+    fn[GAT_SAMPLER_BRUTE_FORCE] = enqueue_brute_force;
+    fn[GAT_SAMPLER_CIRCULAR] = enqueue_circular;
+    fn[GAT_SAMPLER_UNIVERSE] = enqueue_universe;
+  }
+} kListEnqueueFns;
 
 // k_sampler over what the stages in front of it left it (everything, without them) -- or k_serial: the reference's own stream
 static int enqueue_sampler(gat_ctx* ctx, const gat_problem* P, const BatchPlan& B, const gat::SamplerArgs& A) {
@@ -1284,13 +1292,10 @@ static int run_sampler_batch(gat_ctx* ctx, gat_problem* P, const Knobs& kn, uint
     P->split_ran = P->patched_contigs = P->patched_counts = false;
     const BatchPlan B = plan_batch(ctx, kn, P, nb, timed, o);
     record_plan(ctx, P, B);
-    if (P->sampler == GAT_SAMPLER_SHIFT) rc = enqueue_shift(ctx, P, B, seed, begin);
-    else if (P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION) rc = enqueue_permute(ctx, P, B, seed, begin);
-    else if (P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION) rc = enqueue_permute_local(ctx, P, B, seed, begin);
-    else if (P->sampler == GAT_SAMPLER_BRUTE_FORCE) rc = enqueue_brute_force(ctx, P, B, seed, begin);
-    else if (P->sampler == GAT_SAMPLER_CIRCULAR) rc = enqueue_circular(ctx, P, B, seed, begin);
-    else if (P->sampler == GAT_SAMPLER_UNIVERSE) rc = enqueue_universe(ctx, P, B, seed, begin);
-    else rc = enqueue_placement_sampler(ctx, P, B, seed, begin, A);
+    const list_enqueue_fn enqueue_list = kListEnqueueFns.fn[P->sampler];     // (a problem's sampler is a known one: gat_problem_create)
+    if (enqueue_list != nullptr && o.serial_state != nullptr)
+      return set_err(ctx, GAT_ERR_ARG, "%s has no reference-stream mode", sampler_info(P->sampler)->name);
+    rc = enqueue_list != nullptr ? enqueue_list(ctx, P, B, seed, begin) : enqueue_placement_sampler(ctx, P, B, seed, begin, A);
     if (rc) return rc;
   }
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[1], call_stream(ctx, P)));
@@ -1688,13 +1693,8 @@ extern "C" int gat_sample_and_count(gat_ctx* ctx, gat_problem* P, const int32_t*
 extern "C" int gat_sample_and_count_serial(gat_ctx* ctx, gat_problem* P, const int32_t* counter_ids, int n_counters,
                                            uint32_t* mt_state, int64_t n_samples, void* counts_dev, gat_stats* stats) {
   if (!mt_state) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: NULL state");
-  const char* const per_unit_only = P->sampler == GAT_SAMPLER_SHIFT ? "SamplerShift"      // (the list samplers: no k_serial)
-                                  : P->sampler == GAT_SAMPLER_GLOBAL_PERMUTATION ? "SamplerGlobalPermutation"
-                                  : P->sampler == GAT_SAMPLER_LOCAL_PERMUTATION ? "SamplerLocalPermutation"
-                                  : P->sampler == GAT_SAMPLER_BRUTE_FORCE ? "SamplerBruteForce"
-                                  : P->sampler == GAT_SAMPLER_CIRCULAR ? "SamplerCircular"
-                                  : P->sampler == GAT_SAMPLER_UNIVERSE ? "SamplerUniverse" : nullptr;
-  if (per_unit_only) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: %s runs on the per-unit streams only", per_unit_only);
+  if (sampler_runs_wave_per_unit(P->sampler))                 // (the list samplers: no k_serial)
+    return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: %s runs on the per-unit streams only", sampler_info(P->sampler)->name);
   if (mt_state[GAT_MT_STATE_WORDS - 1] > 624u) return set_err(ctx, GAT_ERR_ARG, "gat_sample_and_count_serial: position %u > 624", mt_state[GAT_MT_STATE_WORDS - 1]);
   const int rc = call_begin(ctx, P, counter_ids, n_counters, 0u, 0, n_samples, counts_dev, mt_state, false);
   return rc ? rc : call_wait(ctx, P, stats);

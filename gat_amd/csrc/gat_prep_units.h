@@ -16,13 +16,12 @@
 #include "../../include/gat_mi355.h"
 #include "gat_types.h"
 #include "gat_knobs.h"
+#include "gat_samplers.h"
 
 using gat::UnitDev;
 
 // the samplers that draw a segment's length from the unit's histogram: only they are bound by nbuckets
-inline bool sampler_draws_lengths(int32_t s) {
-  return s == GAT_SAMPLER_ANNOTATOR || s == GAT_SAMPLER_SEGMENTS || s == GAT_SAMPLER_BRUTE_FORCE;
-}
+inline bool sampler_draws_lengths(int32_t s) { return sampler_info(s) != nullptr && sampler_info(s)->draws_lengths; }
 
 // SamplerCircular computes on 64-bit linear positions and never leaves the workspace, so a problem that only samples -- no
 // annotation tracks, no isochore keys: nothing is counted or merged -- takes the whole uint32 range; whatever counts or merges

@@ -1122,7 +1122,61 @@ class Sampler(object):
     pass
 
 
-class SamplerAnnotator(Sampler):
+class _DeviceSampler(Sampler):
+    """What the samplers of SAMPLER_CLASSES share: sample(), and the facts in which they differ, as class attributes.  A
+    class says here everything the package asks about a sampler; nothing else lists them."""
+
+    kind = None                      # GAT_SAMPLER_* (include/gat_mi355.h)
+    word = None                      # its --sampler word
+    params = ()                      # (key of the flat problem, attribute) of every parameter it hands to gat_problem_desc
+    python_seed = False              # the default seed: a draw of Python's random -- else of numpy's global RandomState
+    empty_overlap_returns = True     # segments that do not reach the workspace: an empty list, without a device
+    segments_normalized = False      # sample() asserts segments.isNormalized
+    result_normalized = True         # ... and marks its result normalized
+    has_reference_stream = False     # run(reference_stream=True): the one stream of the whole run
+
+    @classmethod
+    def from_options(cls, options):
+        """the sampler of --sampler=<word>, built from parsed options as scripts/gat-run.py:129-140 of the reference builds it"""
+        return cls()
+
+    def flat_fields(self):
+        """the keys the sampler adds to a flat problem (gat_problem_desc): `sampler` and its parameters -- bucket_size / nbuckets
+        where the class has them (_lib.Problem's defaults where not), and its own"""
+        return dict([("sampler", self.kind)] + [(key, getattr(self, attr)) for key, attr in self.params])
+
+    def _sampled(self, P):
+        pass
+
+    def sample(self, segments, workspace, seed=None):
+        if self.segments_normalized:
+            assert segments.isNormalized, "segment list is not normalized"
+        assert workspace.isNormalized, "workspace is not normalized"
+        if seed is None:
+            seed = random.getrandbits(32) if self.python_seed else int(np.random.randint(0, 2 ** 32))
+        if len(segments) == 0 or len(workspace) == 0:
+            return SegmentList()
+        if self.empty_overlap_returns and len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
+            return SegmentList()
+        s, w = segments.asArray(), workspace.asArray()
+        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
+                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], **self.flat_fields())
+        P = _lib.Problem(get_context(), flat)
+        try:
+            seg, _ = P.sample(seed, 0, 1)
+            self._sampled(P)
+        finally:
+            P.close()
+        r = SegmentList(array=seg)
+        if self.result_normalized:
+            r.isNormalized = 1
+        return r
+
+
+_BUCKETS = (("bucket_size", "bucket_size"), ("nbuckets", "nbuckets"))
+
+
+class SamplerAnnotator(_DeviceSampler):
     """gat/Engine.pyx:445: the default Monte-Carlo sampler, on the GPU.
 
     sample() places one pseudo-sample.  The reference draws from numpy's process-global legacy
@@ -1132,64 +1186,41 @@ class SamplerAnnotator(Sampler):
     a script reproducible)."""
 
     kind = 0
+    word = "annotator"
+    params = _BUCKETS
+    segments_normalized = True
+    has_reference_stream = True
 
     def __init__(self, bucket_size=1, nbuckets=100000, nunsuccessful_rounds=0):
         self.bucket_size = bucket_size
         self.nbuckets = nbuckets
         self.nunsuccessful_rounds = nunsuccessful_rounds
 
-    def sample(self, segments, workspace, seed=None):
-        assert segments.isNormalized, "segment list is not normalized"
-        assert workspace.isNormalized, "workspace is not normalized"
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 32))
-        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
-            return SegmentList()
-        s, w = segments.asArray(), workspace.asArray()
-        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
-                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)],
-                    bucket_size=self.bucket_size, nbuckets=self.nbuckets)
-        P = _lib.Problem(get_context(), flat)
-        try:
-            seg, _ = P.sample(seed, 0, 1)
-            self.nunsuccessful_rounds = P.last_stats["n_unsuccessful"]
-        finally:
-            P.close()
-        r = SegmentList(array=seg)
-        r.isNormalized = 1
-        return r
+    @classmethod
+    def from_options(cls, options):
+        return cls(bucket_size=options.bucket_size, nbuckets=options.nbuckets)
+
+    def _sampled(self, P):
+        self.nunsuccessful_rounds = P.last_stats["n_unsuccessful"]
 
 
-class SamplerSegments(Sampler):
+class SamplerSegments(_DeviceSampler):
     """gat/Engine.pyx:653: places len(segments) segments drawn from the length distribution; sampled
     segments may overlap and the list is returned in placement order (not normalized), exactly as the
     reference does.  Same per-unit stream convention as SamplerAnnotator.sample."""
 
     kind = 1
+    word = "segments"                # (from_options: scripts/gat-run.py:133 passes no bucket arguments)
+    params = _BUCKETS
+    result_normalized = False
+    has_reference_stream = True
 
     def __init__(self, bucket_size=1, nbuckets=100000):
         self.bucket_size = bucket_size
         self.nbuckets = nbuckets
 
-    def sample(self, segments, workspace, seed=None):
-        assert workspace.isNormalized, "workspace is not normalized"
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 32))
-        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
-            return SegmentList()
-        s, w = segments.asArray(), workspace.asArray()
-        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
-                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)],
-                    bucket_size=self.bucket_size, nbuckets=self.nbuckets, sampler=1)
-        P = _lib.Problem(get_context(), flat)
-        try:
-            seg, _ = P.sample(seed, 0, 1)
-        finally:
-            P.close()
-        return SegmentList(array=seg)
 
-
-class SamplerShift(Sampler):
+class SamplerShift(_DeviceSampler):
     """gat/Engine.pyx:998: moves every working segment by a random amount within a window around itself -- the
     workspace within `extension // 2` of the segment's midpoint when `extension` is not 0, else within
     floor(length * radius / 2) -- wrapping what leaves the window round to its other end.  The list is normalized
@@ -1198,6 +1229,8 @@ class SamplerShift(Sampler):
     raise ValueError."""
 
     kind = 2
+    word = "shift"
+    params = (("shift_radius", "radius"), ("shift_extension", "extension"))
 
     def __init__(self, radius=2, extension=0):
         radius, extension = float(radius), int(extension)
@@ -1206,27 +1239,12 @@ class SamplerShift(Sampler):
         self.radius = radius
         self.extension = extension
 
-    def sample(self, segments, workspace, seed=None):
-        assert workspace.isNormalized, "workspace is not normalized"
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 32))
-        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
-            return SegmentList()
-        s, w = segments.asArray(), workspace.asArray()
-        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
-                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)],
-                    sampler=self.kind, shift_radius=self.radius, shift_extension=self.extension)
-        P = _lib.Problem(get_context(), flat)
-        try:
-            seg, _ = P.sample(seed, 0, 1)
-        finally:
-            P.close()
-        r = SegmentList(array=seg)
-        r.isNormalized = 1
-        return r
+    @classmethod
+    def from_options(cls, options):
+        return cls(radius=options.shift_expansion, extension=options.shift_extension)   # scripts/gat-run.py:129-132
 
 
-class SamplerGlobalPermutation(Sampler):
+class SamplerGlobalPermutation(_DeviceSampler):
     """gat/Engine.pyx:1234: keeps the lengths of the working segments (those overlapping the workspace, kept whole),
     shuffles their order and the gaps between them, and lays them into the workspace extended by them (merge(0):
     adjacent pieces united) from a random shift, wrapping round its end and splitting at its gaps.  The list is
@@ -1234,30 +1252,14 @@ class SamplerGlobalPermutation(Sampler):
     stream of a call is random.seed(seed), `seed` by default a draw of Python's random.  No parameters."""
 
     kind = 3
+    word = "global-permutation"
+    python_seed = True
 
     def __init__(self):
         pass
 
-    def sample(self, segments, workspace, seed=None):
-        assert workspace.isNormalized, "workspace is not normalized"
-        if seed is None:
-            seed = random.getrandbits(32)
-        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
-            return SegmentList()
-        s, w = segments.asArray(), workspace.asArray()
-        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
-                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], sampler=self.kind)
-        P = _lib.Problem(get_context(), flat)
-        try:
-            seg, _ = P.sample(seed, 0, 1)
-        finally:
-            P.close()
-        r = SegmentList(array=seg)
-        r.isNormalized = 1
-        return r
 
-
-class SamplerLocalPermutation(Sampler):
+class SamplerLocalPermutation(_DeviceSampler):
     """gat/Engine.pyx:1117: for every workspace piece in turn, the lengths of its working segments -- the segment in
     front of the piece and every segment starting up to the piece's end (SegmentList.getOverlappingSegments), kept
     whole -- are shuffled, random gaps drawn, and the segments laid down from a random shift, wrapping at the end.  As
@@ -1269,30 +1271,15 @@ class SamplerLocalPermutation(Sampler):
     Python's random: the stream of a call is random.seed(seed), `seed` by default a draw of Python's random."""
 
     kind = 4
+    word = "local-permutation"
+    python_seed = True
+    empty_overlap_returns = False
 
     def __init__(self):
         pass
 
-    def sample(self, segments, workspace, seed=None):
-        assert workspace.isNormalized, "workspace is not normalized"
-        if seed is None:
-            seed = random.getrandbits(32)
-        if len(segments) == 0 or len(workspace) == 0:
-            return SegmentList()
-        s, w = segments.asArray(), workspace.asArray()
-        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
-                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], sampler=self.kind)
-        P = _lib.Problem(get_context(), flat)
-        try:
-            seg, _ = P.sample(seed, 0, 1)
-        finally:
-            P.close()
-        r = SegmentList(array=seg)
-        r.isNormalized = 1
-        return r
 
-
-class SamplerBruteForce(Sampler):
+class SamplerBruteForce(_DeviceSampler):
     """gat/Engine.pyx:746: SamplerAnnotator's rejection counterpart.  A length from the working segments' histogram and
     a position in the workspace give a segment; it is kept only if its overlap with the workspace piece it was drawn
     in does not exceed the bases still to place (segments.sum() to begin with: ALL segments, whether they reach the
@@ -1303,6 +1290,8 @@ class SamplerBruteForce(Sampler):
     per-unit stream convention as SamplerAnnotator.sample."""
 
     kind = 5
+    word = "brute-force"             # (from_options: scripts/gat-run.py:139-140 passes no bucket arguments: bucket_size 1)
+    params = _BUCKETS + (("brute_ntries_inner", "ntries_inner"), ("brute_ntries_outer", "ntries_outer"))
 
     def __init__(self, bucket_size=1, nbuckets=100000, ntries_inner=100, ntries_outer=10):
         if int(ntries_inner) < 0 or int(ntries_outer) < 0:
@@ -1312,28 +1301,8 @@ class SamplerBruteForce(Sampler):
         self.ntries_inner = int(ntries_inner)
         self.ntries_outer = int(ntries_outer)
 
-    def sample(self, segments, workspace, seed=None):
-        assert workspace.isNormalized, "workspace is not normalized"
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 32))
-        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
-            return SegmentList()
-        s, w = segments.asArray(), workspace.asArray()
-        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
-                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)],
-                    bucket_size=self.bucket_size, nbuckets=self.nbuckets, sampler=self.kind,
-                    brute_ntries_inner=self.ntries_inner, brute_ntries_outer=self.ntries_outer)
-        P = _lib.Problem(get_context(), flat)
-        try:
-            seg, _ = P.sample(seed, 0, 1)
-        finally:
-            P.close()
-        r = SegmentList(array=seg)
-        r.isNormalized = 1
-        return r
 
-
-class SamplerCircular(Sampler):
+class SamplerCircular(_DeviceSampler):
     """The circular-shift null (regioneR's circularRandomizeRegions, GenometriCorr's permutations; the reference has no such
     sampler): the working list -- the segments cut to the workspace -- is rotated as a whole by one offset r = randint(0,
     workspace bases) along the workspace with its gaps taken out, wrapping at its end.  Every length and every gap between
@@ -1342,30 +1311,13 @@ class SamplerCircular(Sampler):
     touching pieces are kept apart.  Same per-unit stream convention as SamplerAnnotator.sample (numpy's).  No parameters."""
 
     kind = 6
+    word = "circular"
 
     def __init__(self):
         pass
 
-    def sample(self, segments, workspace, seed=None):
-        assert workspace.isNormalized, "workspace is not normalized"
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 32))
-        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
-            return SegmentList()
-        s, w = segments.asArray(), workspace.asArray()
-        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
-                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], sampler=self.kind)
-        P = _lib.Problem(get_context(), flat)
-        try:
-            seg, _ = P.sample(seed, 0, 1)
-        finally:
-            P.close()
-        r = SegmentList(array=seg)
-        r.isNormalized = 1
-        return r
 
-
-class SamplerUniverse(Sampler):
+class SamplerUniverse(_DeviceSampler):
     """The subset null of a finite universe of candidate regions (LOLA's universe, GREAT's background set; the reference has
     no such sampler).  The universe is the workspace: its pieces are the candidates -- all called peaks, all promoters, all CpG
     islands -- and the segments are a chosen subset of them.  k of the m pieces share at least one base with a segment; a
@@ -1376,27 +1328,37 @@ class SamplerUniverse(Sampler):
     SamplerAnnotator.sample (numpy's).  No parameters."""
 
     kind = 7
+    word = "universe"
 
     def __init__(self):
         pass
 
-    def sample(self, segments, workspace, seed=None):
-        assert workspace.isNormalized, "workspace is not normalized"
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 32))
-        if len(segments) == 0 or len(workspace) == 0 or len(iv.filter(segments.asArray(), workspace.asArray())) == 0:
-            return SegmentList()
-        s, w = segments.asArray(), workspace.asArray()
-        flat = dict(n_units=1, segs=s, seg_off=[0, len(s)], ws=w, ws_off=[0, len(w)], unit_contig=[0], n_contigs=1,
-                    merge_contigs=0, n_tracks=0, annos=iv.EMPTY, anno_off=[0], cws_nseg=[len(w)], sampler=self.kind)
-        P = _lib.Problem(get_context(), flat)
-        try:
-            seg, _ = P.sample(seed, 0, 1)
-        finally:
-            P.close()
-        r = SegmentList(array=seg)
-        r.isNormalized = 1
-        return r
+
+# The registry: every sampler there is, in the order of its `kind`.  Whatever builds, checks or names a sampler asks here.
+SAMPLER_CLASSES = (SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, SamplerLocalPermutation,
+                   SamplerBruteForce, SamplerCircular, SamplerUniverse)
+
+
+def sampler_from_options(options):
+    """the sampler of options.sampler (--sampler), built as scripts/gat-run.py:129-140 of the reference builds it"""
+    for cls in SAMPLER_CLASSES:
+        if cls.word == options.sampler:
+            return cls.from_options(options)
+    raise ValueError("sampler '%s' is outside the accelerated path" % options.sampler)
+
+
+def check_sampler(sampler):
+    """a sampler that is none of the registry's is refused"""
+    if not isinstance(sampler, SAMPLER_CLASSES):
+        names = [cls.__name__ for cls in SAMPLER_CLASSES]
+        raise NotImplementedError("only %s and %s run on the GPU path" % (", ".join(names[:-1]), names[-1]))
+
+
+def check_reference_stream(sampler):
+    """reference_stream=True with a sampler that has the per-unit streams only is refused"""
+    for cls in SAMPLER_CLASSES:
+        if isinstance(sampler, cls) and not cls.has_reference_stream:
+            raise NotImplementedError("reference_stream: %s runs on the per-unit streams only" % cls.__name__)
 
 
 class Counter(object):

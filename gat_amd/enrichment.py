@@ -13,8 +13,8 @@ import numpy as np
 from . import intervals as iv
 from . import problem
 from . import stats
-from .coverage import SAMPLERS, flatten, make_sampler
-from .engine import set_device, twoSidedPValueFromCounts
+from .coverage import SAMPLERS, flatten, make_sampler                # noqa: F401
+from .engine import check_sampler, set_device, twoSidedPValueFromCounts
 
 WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")
 QVALUE_METHODS = ("BH", "bonferroni", "holm", "hommel", "hochberg", "BY", "none")      # what stats.adjustPValues offers
@@ -99,9 +99,7 @@ def track_start(segs, workspace, sampler, num_samples, random_seed):
     takes them.  The sampler and num_samples are checked.  Returns (num_samples, the seed -- None: drawn from numpy's global
     RandomState --, the flat problem, the workspace arrays, the problem's contigs, and the segments' contig-level lists over
     them with their offsets: contig_lists)."""
-    if not isinstance(sampler, SAMPLERS):
-        raise NotImplementedError("only SamplerAnnotator, SamplerSegments, SamplerShift, SamplerGlobalPermutation, "
-                                  "SamplerLocalPermutation, SamplerBruteForce, SamplerCircular and SamplerUniverse run on the GPU path")
+    check_sampler(sampler)
     num_samples = int(num_samples)
     if num_samples < 1:
         raise ValueError("num_samples < 1")
