@@ -39,6 +39,7 @@ SYMBOLS = [
     "gat_list_pair_hits", "gat_sample_pair_enrichment", "gat_list_geneset_hits", "gat_sample_geneset_enrichment",
     "gat_list_profile", "gat_sample_profile_enrichment", "gat_list_signal", "gat_sample_signal",
     "gat_null_fold_reset", "gat_null_fold", "gat_list_reldist", "gat_sample_reldist_enrichment",
+    "gat_list_metagene", "gat_sample_metagene_enrichment",
 ]
 NULL_FOLD_WORDS = 8           # GAT_NULL_FOLD_WORDS: n, sum, sumsq_lo, sumsq_hi, n_less, n_eq, min, max
 
@@ -305,6 +306,10 @@ def lib():
     L.gat_list_reldist.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, i32, vp]
     L.gat_sample_reldist_enrichment.restype = C.c_int
     L.gat_sample_reldist_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, i32, i32, vp, vp, C.POINTER(Stats)]
+    L.gat_list_metagene.restype = C.c_int
+    L.gat_list_metagene.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i64, C.c_int, vp]
+    L.gat_sample_metagene_enrichment.restype = C.c_int
+    L.gat_sample_metagene_enrichment.argtypes = [vp, vp, u32, i64, i64, vp, vp, vp, vp, i32, i32, i32, i64, C.c_int, vp, vp, C.POINTER(Stats)]
     L.gat_count_lists.restype = C.c_int
     L.gat_count_lists.argtypes = [vp, vp, C.c_int, vp, vp, i64, vp, vp, i32, vp, i32, vp]
     L.gat_count_list_ranges.restype = C.c_int
@@ -687,16 +692,36 @@ class Context(object):
                                       int(n_bins), _p(out)), self._h)
         return out
 
+    def list_metagene(self, lists, list_off, n_lists, feat_start, feat_end, feat_minus, feat_off, n_tracks, n_groups, body_bins,
+                      flank_bins, flank_bin_size, mode=0):
+        """the metagene of every one of n_lists x n_groups caller-provided normalized lists -- list l of group g is
+        lists[list_off[l * n_groups + g]:list_off[l * n_groups + g + 1]] -- along the features of n_tracks tracks, track t of
+        group g at feat_start / feat_end / feat_minus[feat_off[t * n_groups + g]:feat_off[t * n_groups + g + 1]], ascending
+        by (start, end, minus): flank_bins bins of flank_bin_size bases upstream, body_bins scaled bins over the feature,
+        flank_bins downstream (gat_list_metagene; mode: METAGENE_BASES or METAGENE_MIDPOINTS).  Returns int64
+        [n_lists, n_tracks, 2 * flank_bins + body_bins]."""
+        lists = np.ascontiguousarray(lists, dtype=SEG)
+        list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+        n_lists, n_tracks, n_groups = int(n_lists), int(n_tracks), int(n_groups)
+        assert len(list_off) == n_lists * n_groups + 1
+        fs, fe, minus, feat_off = _metagene_arrays(feat_start, feat_end, feat_minus, feat_off, n_tracks, n_groups)
+        out = np.zeros((n_lists, n_tracks, metagene_bins(body_bins, flank_bins)), dtype=np.int64)
+        _check(lib().gat_list_metagene(self._h, _p(lists), _p(list_off), n_lists, _p(fs), _p(fe), _p(minus), _p(feat_off), n_tracks,
+                                       n_groups, int(body_bins), int(flank_bins), int(flank_bin_size), int(mode), _p(out)), self._h)
+        return out
+
 
 NULL_WORDS = ("n_pos", "sum", "sumsq", "n_less", "n_eq")      # the sampled null of one cell against obs: include/gat_mi355.h
-# GAT_LOCAL_WORDS, GAT_PAIR_WORDS, GAT_GENESET_WORDS, GAT_PROFILE_WORDS, GAT_RELDIST_WORDS
-LOCAL_WORDS = PAIR_WORDS = GENESET_WORDS = PROFILE_WORDS = RELDIST_WORDS = NULL_WORDS
+# GAT_LOCAL_WORDS, GAT_PAIR_WORDS, GAT_GENESET_WORDS, GAT_PROFILE_WORDS, GAT_RELDIST_WORDS, GAT_METAGENE_WORDS
+LOCAL_WORDS = PAIR_WORDS = GENESET_WORDS = PROFILE_WORDS = RELDIST_WORDS = METAGENE_WORDS = NULL_WORDS
 PAIR_MAX_TRACKS = 2048        # GAT_PAIR_MAX_TRACKS
 PROFILE_MAX_BINS = 1024       # GAT_PROFILE_MAX_BINS
 PROFILE_BASES, PROFILE_MIDPOINTS = 0, 1       # GAT_PROFILE_BASES, GAT_PROFILE_MIDPOINTS
 RELDIST_MAX_BINS = 1024       # GAT_RELDIST_MAX_BINS
 RELDIST_EXTRA = 3             # GAT_RELDIST_EXTRA: area, inside, outside behind the bins
 RELDIST_AREA_SCALE = 10 ** 6  # GAT_RELDIST_AREA_SCALE
+METAGENE_MAX_BINS = 1024      # GAT_METAGENE_MAX_BINS
+METAGENE_BASES, METAGENE_MIDPOINTS = 0, 1     # GAT_METAGENE_BASES, GAT_METAGENE_MIDPOINTS
 
 
 def profile_bins(half_bins):
@@ -724,6 +749,22 @@ def _reldist_arrays(point_pos, point_off, n_tracks, n_groups):
     point_off = np.ascontiguousarray(point_off, dtype=np.int64)
     assert len(point_off) == max(0, n_tracks) * max(0, n_groups) + 1
     return pos, point_off
+
+
+def metagene_bins(body_bins, flank_bins):
+    """the bins of a metagene (0 where the two are out of range: the library refuses the call)"""
+    body_bins, flank_bins = int(body_bins), int(flank_bins)
+    return 2 * flank_bins + body_bins if body_bins >= 1 and flank_bins >= 0 and 2 * flank_bins + body_bins <= METAGENE_MAX_BINS else 0
+
+
+def _metagene_arrays(feat_start, feat_end, feat_minus, feat_off, n_tracks, n_groups):
+    """the feature arguments of the two metagene calls as the library takes them"""
+    fs = np.ascontiguousarray(feat_start, dtype=np.uint32)
+    fe = np.ascontiguousarray(feat_end, dtype=np.uint32)
+    minus = np.ascontiguousarray(feat_minus, dtype=np.uint8)
+    feat_off = np.ascontiguousarray(feat_off, dtype=np.int64)
+    assert len(feat_off) == max(0, n_tracks) * max(0, n_groups) + 1 and len(fs) == len(fe) == len(minus)
+    return fs, fe, minus, feat_off
 
 
 def pair_count(n_tracks):
@@ -1257,3 +1298,19 @@ class Problem(object):
         assert obs.shape == cells
         return self._sample_null_words(lib().gat_sample_reldist_enrichment, seed, sample_begin, sample_end,
                                        (_p(pos), _p(point_off), n_tracks, int(n_bins)), obs, cells)
+
+    def sample_metagene_enrichment(self, seed, sample_begin, sample_end, feat_start, feat_end, feat_minus, feat_off, n_tracks,
+                                   body_bins, flank_bins, flank_bin_size, mode, obs):
+        """per (track, bin) the five sums (METAGENE_WORDS; gat_sample_metagene_enrichment) over the sampled contig-level lists
+        of [sample_begin, sample_end) of v = the bases (mode METAGENE_BASES) or segment midpoints (METAGENE_MIDPOINTS) of a
+        list in the bin along the track's scaled features and their flanks, against obs[track, bin] -- the features as in
+        Context.list_metagene, the groups the problem's contigs in the problem's order.  Returns int64
+        [n_tracks, 2 * flank_bins + body_bins, 5]."""
+        n_tracks = int(n_tracks)
+        fs, fe, minus, feat_off = _metagene_arrays(feat_start, feat_end, feat_minus, feat_off, n_tracks, self.n_contigs)
+        cells = (max(0, n_tracks), metagene_bins(body_bins, flank_bins))
+        obs = np.ascontiguousarray(obs, dtype=np.int64)
+        assert obs.shape == cells
+        return self._sample_null_words(lib().gat_sample_metagene_enrichment, seed, sample_begin, sample_end,
+                                       (_p(fs), _p(fe), _p(minus), _p(feat_off), n_tracks, int(body_bins), int(flank_bins),
+                                        int(flank_bin_size), int(mode)), obs, cells)

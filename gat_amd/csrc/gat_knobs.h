@@ -98,7 +98,9 @@ struct gat_ctx;
   INT(profile_lds_anchors, "GAT_PROFILE_LDS_ANCHORS", 1024) /* gat_*_profile*: anchor positions of a (track, group) k_profile's search finds in LDS; 0: none */ \
   INT(profile_samples_per_block, "GAT_PROFILE_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */ \
   INT(reldist_lds_points, "GAT_RELDIST_LDS_POINTS", 1024) /* gat_*_reldist*: positions of a (track, group) k_reldist's search finds in LDS; 0: none */ \
-  INT(reldist_samples_per_block, "GAT_RELDIST_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */
+  INT(reldist_samples_per_block, "GAT_RELDIST_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */ \
+  INT(metagene_lds_features, "GAT_METAGENE_LDS_FEATURES", 1024) /* gat_*_metagene*: prefix maxima of the ends of a (track, group) k_metagene's search finds in LDS; 0: none */ \
+  INT(metagene_samples_per_block, "GAT_METAGENE_SAMPLES_PER_BLOCK", 0) /* ... its run of lists; default: by the launch */
 
 struct Knobs {
 #define GAT_KNOB_FLAG(field, name) bool field = false;

@@ -5,8 +5,8 @@
 
 // ---- the entry points that read the sampled lists where they are: gat_sample / gat_sample_units copy them out, and
 // gat_sample_coverage, gat_sample_metrics, gat_sample_distances, gat_sample_signal, gat_sample_bin_enrichment,
-// gat_sample_pair_enrichment, gat_sample_geneset_enrichment, gat_sample_profile_enrichment and gat_sample_reldist_enrichment put a kernel
-// (gat_coverage.h, gat_metrics.h, gat_distance.h, gat_signal.h, gat_local.h, gat_pairs.h, gat_geneset.h, gat_profile.h, gat_reldist.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
+// gat_sample_pair_enrichment, gat_sample_geneset_enrichment, gat_sample_profile_enrichment, gat_sample_reldist_enrichment and gat_sample_metagene_enrichment put a kernel
+// (gat_coverage.h, gat_metrics.h, gat_distance.h, gat_signal.h, gat_local.h, gat_pairs.h, gat_geneset.h, gat_profile.h, gat_reldist.h, gat_metagene.h) behind every batch.  They share the call's frame, the batch loop and the view of a batch's lists.
 
 // A synchronous call's frame: refused while a call is in flight on the problem (P == nullptr: a call over the caller's own
 // lists); the knobs are read once; body(kn, local) does the work.  Whatever the body returns, the stream is drained behind it:
@@ -165,7 +165,7 @@ static int launch_store_or_fold(gat_ctx* ctx, bool store, void (*k_store)(Args),
 }
 
 // ---- the fold of the sampled null to five words per cell (gat_null_words.h), as gat_sample_bin_enrichment,
-// gat_sample_pair_enrichment, gat_sample_geneset_enrichment, gat_sample_profile_enrichment and gat_sample_reldist_enrichment share it: obs up and the words zeroed before the first batch,
+// gat_sample_pair_enrichment, gat_sample_geneset_enrichment, gat_sample_profile_enrichment, gat_sample_reldist_enrichment and gat_sample_metagene_enrichment share it: obs up and the words zeroed before the first batch,
 // k_null_finish and the words down behind the last
 struct NullWordsOut {
   DevBuf<long long> d_obs;
@@ -1309,5 +1309,169 @@ extern "C" int gat_sample_reldist_enrichment(gat_ctx* ctx, gat_problem* P, uint3
   if (n_max > (int64_t)INT32_MAX) return set_err(ctx, GAT_ERR_CAPACITY, "%s: a sample can hold %lld segments, more than 2^31 - 1", who, (long long)n_max);
   // a count is at most n_max, the area at most GAT_RELDIST_AREA_SCALE
   if ((rc = check_null_words(ctx, who, "max(10^6, n_max)", std::max<int64_t>(GAT_RELDIST_AREA_SCALE, n_max), "fewer samples per call", S, obs_host, cells))) return rc;
+  return fold_over_sampled_batches(ctx, P, stats, seed, sample_begin, S, T, obs_host, cells, out_host);
+}
+
+// gat_list_metagene / gat_sample_metagene_enrichment: k_metagene (gat_metagene.h) over caller-provided lists, or behind every
+// batch.  The features go up once per call (starts, ends, the prefix maximum of the ends built here, strands, offsets from
+// feat_off[0]); the device buffers live for the call.
+static const char* const kMetageneWhy = "a base counts once per feature: the metagene is formed from disjoint segments";
+struct MetageneCall {
+  const char* who;
+  const uint32_t* fs; const uint32_t* fe; const uint8_t* minus; const int64_t* off;
+  int32_t n_tracks; int32_t body_bins; int32_t flank_bins; int64_t flank_bin_size; int mode;
+  DevBuf<uint32_t> d_fs, d_fe, d_pm;
+  DevBuf<uint8_t> d_minus;
+  DevBuf<int64_t> d_off;
+  NullWordsOut out;
+  int64_t longest = 0;        // the most features of a (track, group)
+  int64_t most = 0;           // what a value can reach: the larger of K_t * w (with flanks) and sum_f ceil(len_f / Bb), over the tracks (check)
+  int64_t bins() const { return 2 * (int64_t)flank_bins + body_bins; }
+  // what both entry points ask of the bins and the features (tracks of stranded intervals that may overlap: the checks are its own)
+  int check(gat_ctx* ctx, int64_t n_groups) {
+    if (body_bins < 1) return set_err(ctx, GAT_ERR_ARG, "%s: body_bins %d is less than 1", who, body_bins);
+    if (flank_bins < 0) return set_err(ctx, GAT_ERR_ARG, "%s: flank_bins %d is negative", who, flank_bins);
+    if (bins() > GAT_METAGENE_MAX_BINS)
+      return set_err(ctx, GAT_ERR_ARG, "%s: 2 * flank_bins + body_bins = %lld is more than %d", who, (long long)bins(), GAT_METAGENE_MAX_BINS);
+    if (flank_bin_size < 1 || flank_bin_size > (int64_t)1 << 31)
+      return set_err(ctx, GAT_ERR_ARG, "%s: flank_bin_size %lld outside [1, 2^31]", who, (long long)flank_bin_size);
+    if (flank_bins * flank_bin_size > (int64_t)1 << 31)
+      return set_err(ctx, GAT_ERR_ARG, "%s: flank_bins * flank_bin_size = %d * %lld is more than 2^31", who, flank_bins, (long long)flank_bin_size);
+    if (mode != GAT_METAGENE_BASES && mode != GAT_METAGENE_MIDPOINTS)
+      return set_err(ctx, GAT_ERR_ARG, "%s: mode %d is neither GAT_METAGENE_BASES nor GAT_METAGENE_MIDPOINTS", who, mode);
+    if (n_tracks < 0 || (int64_t)n_tracks * std::max<int64_t>(1, n_groups) > (int64_t)INT32_MAX)
+      return set_err(ctx, GAT_ERR_ARG, "%s: n_tracks %d", who, n_tracks);
+    const int64_t n = (int64_t)n_tracks * n_groups;
+    int rc;
+    if ((rc = check_list_offsets(ctx, who, "feat_off", "features", off, n))) return rc;
+    if (off[n] > off[0] && (!fs || !fe || !minus)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+    most = 0;
+    for (int64_t t = 0; t < n_tracks; ++t) {
+      int64_t body = 0;       // sum_f ceil(len_f / Bb) < 2^31 * 2^32: no overflow
+      for (int64_t g = 0; g < n_groups; ++g) {
+        const int64_t b = off[t * n_groups + g], e = off[t * n_groups + g + 1];
+        for (int64_t k = b; k < e; ++k) {
+          if (fe[k] <= fs[k])
+            return set_err(ctx, GAT_ERR_ARG, "%s: feature track %lld, group %lld: feature %lld is empty (end <= start)", who,
+                           (long long)t, (long long)g, (long long)(k - b));
+          if (minus[k] > 1)
+            return set_err(ctx, GAT_ERR_ARG, "%s: feature track %lld, group %lld: feat_minus %d at feature %lld is neither 0 nor 1", who,
+                           (long long)t, (long long)g, (int)minus[k], (long long)(k - b));
+          body += ((int64_t)(fe[k] - fs[k]) + body_bins - 1) / body_bins;
+          if (k == b) continue;
+          const bool same = fs[k] == fs[k - 1] && fe[k] == fe[k - 1] && minus[k] == minus[k - 1];
+          if (same)
+            return set_err(ctx, GAT_ERR_ARG, "%s: feature track %lld, group %lld repeats a feature (start, end, strand) at feature %lld", who,
+                           (long long)t, (long long)g, (long long)(k - b));
+          const bool after = fs[k] != fs[k - 1] ? fs[k] > fs[k - 1] : fe[k] != fe[k - 1] ? fe[k] > fe[k - 1] : minus[k] > minus[k - 1];
+          if (!after)
+            return set_err(ctx, GAT_ERR_ARG, "%s: feature track %lld, group %lld is out of order at feature %lld (ascending by start, "
+                           "then end, plus before minus)", who, (long long)t, (long long)g, (long long)(k - b));
+        }
+      }
+      const int64_t flank = flank_bins > 0 ? (off[(t + 1) * n_groups] - off[t * n_groups]) * flank_bin_size : 0;
+      most = std::max<int64_t>(most, std::max(flank, body));
+    }
+    return GAT_OK;
+  }
+  // the most of a cell below 2^32 -- a value is a 32-bit word on the device -- and its square times S below 2^64
+  int check_words(gat_ctx* ctx, int64_t S, const int64_t* obs_host, int64_t cells) const {
+    if (most >= (int64_t)1 << 32)
+      return set_err(ctx, GAT_ERR_ARG, "%s: the bases one bin of a track can hold, %lld, do not fit 32 bits: fewer features per track, a "
+                     "smaller flank_bin_size or more body_bins", who, (long long)most);
+    return check_null_words(ctx, who, "bases per bin", most, "fewer features per track, a smaller flank_bin_size, more body_bins or fewer samples per call",
+                            S, obs_host, cells);
+  }
+  int upload(gat_ctx* ctx, const Knobs&, int32_t n_groups, int64_t) {
+    const int64_t n = (int64_t)n_tracks * n_groups, base = off[0], total = off[n] - base;
+    std::vector<int64_t> h_off((size_t)n + 1);
+    std::vector<uint32_t> h_pm((size_t)total);
+    longest = 0;
+    for (int64_t l = 0; l <= n; ++l) {
+      h_off[(size_t)l] = off[l] - base;
+      if (!l) continue;
+      longest = std::max(longest, off[l] - off[l - 1]);
+      uint32_t m = 0u;
+      for (int64_t k = off[l - 1]; k < off[l]; ++k) h_pm[(size_t)(k - base)] = m = std::max(m, fe[k]);
+    }
+    HIPCHK(ctx, d_fs.alloc((size_t)total));
+    HIPCHK(ctx, d_fe.alloc((size_t)total));
+    HIPCHK(ctx, d_pm.alloc((size_t)total));
+    HIPCHK(ctx, d_minus.alloc((size_t)total));
+    if (total > 0) {
+      HIPCHK(ctx, staged_h2d(ctx, d_fs.p, fs + base, (size_t)total * 4));
+      HIPCHK(ctx, staged_h2d(ctx, d_fe.p, fe + base, (size_t)total * 4));
+      HIPCHK(ctx, staged_h2d(ctx, d_pm.p, h_pm.data(), (size_t)total * 4));
+      HIPCHK(ctx, staged_h2d(ctx, d_minus.p, minus + base, (size_t)total));
+    }
+    HIPCHK(ctx, d_off.upload(h_off, ctx));
+    HIPCHK(ctx, stage_flush(ctx));                    // (h_off and h_pm go away with this frame)
+    return GAT_OK;
+  }
+  // one launch over tracks x runs of n_lists lists; store: the raw values per list, else the fold into out's five words
+  int launch(gat_ctx* ctx, const Knobs& kn, const gat::ListSet& lists, int64_t n_lists, int32_t n_groups, bool store) const {
+    if (n_lists == 0 || n_tracks == 0 || n_groups == 0 || longest == 0) return GAT_OK;
+    gat::MetageneArgs A;
+    memset(&A, 0, sizeof(A));
+    const int64_t L = gat::metagene_lds_features(std::max<int64_t>(0, kn.metagene_lds_features), longest, ctx->max_lds, bins(), n_groups);
+    A.lists = lists;
+    A.n_lists = (int32_t)n_lists;
+    A.n_groups = n_groups;
+    A.n_tracks = n_tracks;
+    A.bins = (int32_t)bins();
+    A.body_bins = body_bins;
+    A.flank_bins = flank_bins;
+    A.lds_features = (int32_t)L;
+    A.midpoints = mode == GAT_METAGENE_MIDPOINTS ? 1 : 0;
+    A.flank_bin_size = flank_bin_size;
+    A.flank = flank_bins * flank_bin_size;
+    A.fs = d_fs.p;
+    A.fe = d_fe.p;
+    A.pm = d_pm.p;
+    A.minus = d_minus.p;
+    A.feat_off = d_off.p;
+    A.obs = out.d_obs.p;
+    A.out = out.d_out.p;
+    // the run: the knob's where it is set, else k_profile's rule, whose layout and fixed cost per workgroup (the flush of its
+    // bins) this kernel shares: as long as leaves 8 192 workgroups, at least 8 lists, and a list for every wave in every round
+    const int64_t lpb = kn.metagene_samples_per_block > 0
+                            ? gat::run_per_block(n_lists, n_tracks, 0, kn.metagene_samples_per_block)
+                            : (gat::run_per_block(n_lists, n_tracks, 8192, gat::kNoRunCap) + gat::kMetageneWaves - 1) / gat::kMetageneWaves * gat::kMetageneWaves;
+    A.lists_per_block = (int32_t)lpb;
+    const size_t lds = (size_t)gat::metagene_lds_bytes(bins(), L, n_groups, store);
+    const dim3 grid((unsigned)n_tracks, (unsigned)((n_lists + lpb - 1) / lpb));
+    return launch_store_or_fold(ctx, store, gat::k_metagene<true>, gat::k_metagene<false>, grid, gat::kMetageneThreads, lds, A);
+  }
+};
+
+extern "C" int gat_list_metagene(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                                 const uint32_t* feat_start, const uint32_t* feat_end, const uint8_t* feat_minus, const int64_t* feat_off,
+                                 int32_t n_tracks, int32_t n_groups, int32_t body_bins, int32_t flank_bins, int64_t flank_bin_size,
+                                 int mode, int64_t* out_host) {
+  const char* who = "gat_list_metagene";
+  if (!ctx || !list_off || !feat_off || !out_host) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  MetageneCall T = {who, feat_start, feat_end, feat_minus, feat_off, n_tracks, body_bins, flank_bins, flank_bin_size, mode};
+  int rc;
+  if ((rc = check_list_counts(ctx, who, n_lists, n_groups))) return rc;
+  if ((rc = T.check(ctx, n_groups))) return rc;
+  if ((rc = T.check_words(ctx, 1, nullptr, 0))) return rc;
+  if ((rc = check_caller_lists(ctx, who, "intervals", lists, list_off, n_lists, n_groups, kMetageneWhy))) return rc;
+  return store_over_caller_lists(ctx, T, lists, list_off, n_lists, n_groups, (int64_t)n_tracks * T.bins(), out_host);
+}
+
+extern "C" int gat_sample_metagene_enrichment(gat_ctx* ctx, gat_problem* P, uint32_t seed, int64_t sample_begin, int64_t sample_end,
+                                              const uint32_t* feat_start, const uint32_t* feat_end, const uint8_t* feat_minus,
+                                              const int64_t* feat_off, int32_t n_tracks, int32_t body_bins, int32_t flank_bins,
+                                              int64_t flank_bin_size, int mode, const int64_t* obs_host, int64_t* out_host, gat_stats* stats) {
+  const char* who = "gat_sample_metagene_enrichment";
+  if (!ctx || !P || !feat_off) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if (int rc = check_sample_range(ctx, sample_begin, sample_end)) return rc;
+  MetageneCall T = {who, feat_start, feat_end, feat_minus, feat_off, n_tracks, body_bins, flank_bins, flank_bin_size, mode};
+  int rc;
+  if ((rc = T.check(ctx, P->n_contigs))) return rc;
+  const int64_t S = sample_end - sample_begin, cells = (int64_t)n_tracks * T.bins();
+  if (cells > 0 && (!obs_host || !out_host)) return set_err(ctx, GAT_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = T.check_words(ctx, S, obs_host, cells))) return rc;
+  if ((rc = check_sampled_lists_normalized(ctx, who, P, "the metagene needs normalized lists"))) return rc;
   return fold_over_sampled_batches(ctx, P, stats, seed, sample_begin, S, T, obs_host, cells, out_host);
 }

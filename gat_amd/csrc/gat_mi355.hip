@@ -8,7 +8,7 @@
 // In this file: the context, the scratch, the count launches, the sampler batch and the call seam (gat_sample_and_count*),
 // gat_count_lists, the RCCL entry points and the statistics.  gat_list_calls.h, included behind the call seam: gat_sample /
 // gat_sample_units and the list reductions (gat_sample_* / gat_list_* of coverage, metrics, distances, signal, gat-local,
-// gat-pairs, gat-geneset, gat-profile and gat-reldist).  One translation unit: the Makefile keeps its device assembly and checks it.
+// gat-pairs, gat-geneset, gat-profile, gat-reldist and gat-metagene).  One translation unit: the Makefile keeps its device assembly and checks it.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <link.h>            // dl_iterate_phdr: the RCCL a host process has mapped already
@@ -53,6 +53,7 @@
 #include "gat_geneset.h"
 #include "gat_profile.h"
 #include "gat_reldist.h"
+#include "gat_metagene.h"
 
 
 #include "gat_host.h"

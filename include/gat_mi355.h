@@ -844,6 +844,76 @@ int gat_sample_reldist_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
                                   const uint32_t* point_pos, const int64_t* point_off, int32_t n_tracks, int32_t n_bins,
                                   const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
 
+/* How the segments of a list are distributed along a class of SCALED features and their flanks -- the metagene, or
+ * scaled-region profile (deeptools computeMatrix scale-regions, ngs.plot) -- formed on the device by k_metagene (the reference
+ * has nothing like it).  Every feature (gene, enhancer, CpG island) is stretched to the same number of body bins, 5' to 3', with
+ * flank bins of a fixed size on both sides.  The groups are contigs.  A feature is (fs, fe, sigma): a span 0 <= fs < fe <=
+ * 2^32 - 1 with len = fe - fs, and a strand sigma in {+1, -1} (feat_minus 0 / 1).  With Bb = body_bins >= 1, Bf = flank_bins
+ * >= 0, w = flank_bin_size in [1, 2^31] (ignored with Bf == 0, but still to be in range), F = Bf * w <= 2^31 and B = 2 Bf + Bb
+ * <= GAT_METAGENE_MAX_BINS bins, the window of a feature is the bases [fs - F, fe + F) in signed 64-bit arithmetic (fs - F
+ * goes below 0 and fe + F passes 2^32).  For a base x of the window of a PLUS feature
+ *     upstream    x < fs          bin = floor((x - (fs - F)) / w)                   in [0, Bf)
+ *     body        fs <= x < fe    bin = Bf + floor((x - fs) * Bb / len)             (the product stays below 2^42)
+ *     downstream  x >= fe         bin = Bf + Bb + floor((x - fe) / w)
+ * and a MINUS feature is the mirror: bin(x; fs, fe, -) = bin(fs + fe - 1 - x; fs, fe, +).  The mirror maps the window onto
+ * itself: there is no one-base shift as in the minus window of gat_list_profile.  Body bin k holds the oriented body offsets
+ * [ceil(k * len / Bb), ceil((k + 1) * len / Bb)); a feature with len < Bb leaves some body bins without a base, which is
+ * defined behaviour.  For a normalized segment list L (per group sorted by start, pairwise disjoint, every interval with
+ * end > start; adjacent intervals allowed) and the features of track t on group g
+ *     GAT_METAGENE_BASES      v(L, t, b) = sum over g, over the features f of (t, g), over q = [s, e) in L_g of
+ *                                          #{ x in [s, e) : x in window(f), bin(x; f) = b }
+ *     GAT_METAGENE_MIDPOINTS  the same with q replaced by [m, m + 1), m = s + (e - s) / 2 in integer division
+ * A base counts once per feature whose window holds it: overlapping and nested features each get it, as an aggregate plot
+ * does.  v sums over all groups: a cell is (track, bin).  With K_t the features of track t over all groups, a flank cell is at
+ * most K_t * w, a body cell at most sum_f ceil(len_f / Bb), and most_t is the larger of the two (the flank term only with
+ * Bf > 0).  Example (Bb = 4, Bf = 1, w = 10), the feature [100, 110) -- body bins of 3, 2, 3, 2 bases: [100, 103), [103, 105),
+ * [105, 108), [108, 110) -- and the segment [95, 112): a plus feature gives v = 5, 3, 2, 3, 2, 2; a minus one gives
+ * 2, 3, 2, 3, 2, 5; the midpoint 103 lands in bin 2 of the plus feature and in bin 3 of the minus one.
+ * feat_off has n_tracks * n_groups + 1 non-decreasing entries, track t of group g at index t * n_groups + g; within a (track,
+ * group) the features ascend by (fs, fe, minus), no (fs, fe, minus) twice; they may overlap and nest.
+ * Over a range of S samples and against an observed value obs[t][b] >= 0 given by the caller, every (track, bin) gets five
+ * int64 words (GAT_METAGENE_WORDS) -- those of GAT_PROFILE_WORDS, in the same order and with the same meaning: n_pos, sum,
+ * sumsq (unsigned where it passes 2^63), n_less, n_eq; all S samples count in n_less / n_eq, those with v == 0 too.  All
+ * arithmetic is integer and exact.  Every word is additive over the samples: the words of calls over [0, k) and [k, S) add up
+ * to those of the call over [0, S), and results do not depend on batches, workgroups, knobs or the run.  Context options, none
+ * of which changes a result: GAT_METAGENE_LDS_FEATURES -- how many entries of the prefix maximum of the ends of a (track,
+ * group) the kernel's search finds in LDS before it goes to global memory (clamped to what a workgroup's LDS holds beside the
+ * bins; 0: none); GAT_METAGENE_SAMPLES_PER_BLOCK -- the run of lists a workgroup takes (default: by the launch).
+ *
+ * gat_list_metagene: the raw v of caller-provided lists (the observed values of the input segments with n_lists == 1).
+ * lists / list_off, n_groups: as in gat_list_distances.  out_host: [n_lists][n_tracks][B].  Synchronous.  n_lists == 0 or
+ * n_tracks == 0 writes nothing.  GAT_ERR_ARG, nothing written: a NULL ctx / list_off / feat_off / out_host (lists /
+ * feat_start / feat_end / feat_minus may be NULL where they hold nothing), negative counts, a decreasing offset,
+ * body_bins < 1, flank_bins < 0, B > 1024, flank_bin_size outside [1, 2^31], F > 2^31, a mode that is neither of the two, a
+ * feature with fe <= fs (fe > 2^32 - 1 has no representation in the argument's type), a feat_minus other than 0 or 1, features
+ * that are out of order or repeated (gat_last_error names the track and the group), most_t >= 2^32 for some track (a value is
+ * a 32-bit word on the device), a segment list that is not normalized (it names the list and the group).  Never a wrong
+ * number. */
+#define GAT_METAGENE_WORDS 5
+#define GAT_METAGENE_MAX_BINS 1024
+#define GAT_METAGENE_BASES 0
+#define GAT_METAGENE_MIDPOINTS 1
+int gat_list_metagene(gat_ctx* ctx, const gat_segment* lists, const int64_t* list_off, int64_t n_lists,
+                      const uint32_t* feat_start, const uint32_t* feat_end, const uint8_t* feat_minus, const int64_t* feat_off,
+                      int32_t n_tracks, int32_t n_groups, int32_t body_bins, int32_t flank_bins, int64_t flank_bin_size,
+                      int mode, int64_t* out_host);
+
+/* ... of the sampled lists: the batch loop shared with gat_sample, k_metagene behind every batch that passed its checks,
+ * reading the contig-level lists where gat_sample copies them out -- exactly the lists gat_sample returns for the same seed
+ * and range (per-unit streams only).  The groups are the problem's contigs in the problem's order: feat_off has n_tracks *
+ * n_contigs + 1 entries; obs_host: [n_tracks][B]; out_host: [n_tracks][B][5].  Synchronous, like gat_sample.  An empty sample
+ * range writes zeros; n_tracks == 0 writes nothing.  GAT_ERR_ARG, nothing written: as above, and a NULL p, a NULL obs_host /
+ * out_host with n_tracks > 0, sample_end < sample_begin, a negative obs, most_t^2 * samples >= 2^64 for some track (sumsq
+ * would not fit), a sampler whose lists are not normalized (SamplerSegments on a problem without isochore keys; the message
+ * says so), a call in flight on the problem.  The sampler's errors pass through (GAT_ERR_ASSERT; SamplerBruteForce's
+ * GAT_ERR_VALUE "sampling did not converge"). */
+int gat_sample_metagene_enrichment(gat_ctx* ctx, gat_problem* p, uint32_t seed,
+                                   int64_t sample_begin, int64_t sample_end,
+                                   const uint32_t* feat_start, const uint32_t* feat_end, const uint8_t* feat_minus,
+                                   const int64_t* feat_off, int32_t n_tracks, int32_t body_bins, int32_t flank_bins,
+                                   int64_t flank_bin_size, int mode,
+                                   const int64_t* obs_host, int64_t* out_host, gat_stats* stats /* nullable */);
+
 /* Counters only, on caller-provided lists: replaces Engine.computeCounts
  * (gat/Engine.pyx:2164-2204; observed counts) and counter(segments, annotations, workspace)
  * (gat/Engine.pyx:1417-1472).  lists: n_lists*n_groups segment lists (HOST, CSR via list_off),
